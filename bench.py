@@ -13,10 +13,18 @@ fixed); spatial rows are all-gathered, the temporal update does one RCCL all-red
 
 `python bench.py --gpus N` without a launcher's WORLD_SIZE spawns the N ranks itself (one per GPU, nccl = RCCL; it refuses to run when fewer than
 N GPUs are visible); under `python -m torch.distributed.run` it takes RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment.
-At N = 1 the default run also times configs[3] (`c4`: the same video as 16 patches on this one GPU) in a child process and reports it as `c4_n1`,
-the N = 1 point of the strong-scaling curve the N > 1 runs continue.
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs when --dump-outputs DIR is given, and prints its line: the
+headline figure and nothing else.  --full adds what the headline does not need: the per-kernel event timing of the warm-up, the timed region
+and two extra steps, the separate ring-sweep launches, the rooflines (with in-run PMC passes over a child run), the CPU baseline and, at N = 1,
+configs[3] (`c4`: the same video as 16 patches on this one GPU) timed in a child process and reported as `c4_n1`, the N = 1 point of the
+strong-scaling curve the N > 1 runs continue.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+--dump-outputs DIR: after the timed steps, what the last one computed goes to DIR/<name>.npy (float32; b0_new float64), 64 MiB at most --
+`C` (with --deconv also `C_raw`, `S`) for a fixed, seeded sample of neurons when the K x T traces exceed their share, `A` as dense columns
+(neurons x pixels) of another fixed sample, `b0_new` whole, `W` the ring weights of a fixed sample of pixel rows (nonzeros in column order,
+zero-padded to the widest row).  The inputs are seeded: two builds run with the same arguments can be compared array by array.
+
+Prints ONE JSON line on rank 0 (contract in the task statement); `roofline` and `cpu_baseline` are null unless --full.
 """
 import argparse
 import json
@@ -199,6 +207,53 @@ def spawn_ranks(n, argv):
     print(lines[-1], flush=True)
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_TRACE_BYTES = 30 << 20      # shared by C (and C_raw, S with --deconv)
+DUMP_A_BYTES = 20 << 20
+DUMP_W_ROWS = 4096
+DUMP_SEED = 7
+
+
+def dump_outputs(dirname, s, video, deconv, write):
+    """the timed path's outputs after its last step as DIR/<name>.npy (module docstring).  Every rank calls it at the same point (reading b0_new
+    may be a collective); only the rank with `write` fetches the ring weights and writes."""
+    rng = np.random.default_rng(DUMP_SEED)
+    b0_new = np.asarray(s.b0_new)
+    if not write:
+        return
+    K, T = np.asarray(s.C).shape
+    d = video.d1 * video.d2
+    out = {}
+    names = ("C", "C_raw", "S") if deconv and getattr(s, "S", None) is not None else ("C",)
+    nt = min(K, DUMP_TRACE_BYTES // len(names) // (4 * T))
+    rows = np.arange(K) if nt == K else np.sort(rng.choice(K, nt, replace=False))
+    for name in names:
+        out[name] = np.ascontiguousarray(np.asarray(getattr(s, name), dtype=np.float32)[rows])
+    na = min(K, DUMP_A_BYTES // (4 * d))
+    cols = np.arange(K) if na == K else np.sort(rng.choice(K, na, replace=False))
+    out["A"] = np.ascontiguousarray(s.A[:, cols].toarray().T, dtype=np.float32)
+    out["b0_new"] = np.ascontiguousarray(b0_new, dtype=np.float64)
+    per_patch = max(1, DUMP_W_ROWS // len(video.owned))
+    Ws = []
+    for idx in video.owned:
+        W = s.get_W(idx).tocsr()
+        W.sort_indices()
+        nnz_row = np.diff(W.indptr)
+        sel = np.sort(rng.choice(W.shape[0], min(per_patch, W.shape[0]), replace=False))
+        Wp = np.zeros((sel.size, int(nnz_row.max()) if nnz_row.size else 0), dtype=np.float32)
+        for i, r_ in enumerate(sel):
+            Wp[i, :nnz_row[r_]] = W.data[W.indptr[r_]:W.indptr[r_ + 1]]
+        Ws.append(Wp)
+    width = max(w.shape[1] for w in Ws)
+    out["W"] = np.concatenate([np.pad(w, ((0, 0), (0, width - w.shape[1]))) for w in Ws])
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes, more than %d" % (total, DUMP_MAX_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), v)
+
+
 def emit(obj):
     """the ONE JSON line, as the last thing on stdout: what C libraries still hold in stdio's buffer (RCCL's banner under NCCL_DEBUG=VERSION, written when the communicator
     was made and otherwise flushed at exit, BEHIND the line) goes out first"""
@@ -226,7 +281,12 @@ def main():
                                                             "pixel sample of the background regression; minutes of host work, no GPU step) | none")
     ap.add_argument("--no-extras", action="store_true", help="skip the c4_n1 child run and the in-run PMC traffic passes (what the child runs pass)")
     ap.add_argument("--bg-ssub", type=int, default=1, help="options.bg_ssub (the shipped demo uses 2; the headline metric is quoted at 1)")
+    ap.add_argument("--full", action="store_true", help="also the per-kernel timing, rooflines (PMC child runs), c4_n1 and the CPU baseline; "
+                                                         "without it a run times the steps and prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (module docstring)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.cpu_baseline == "full":
         which = tuple(a.config.split(",")) if a.config else ("c2", "c3")
         print(json.dumps(cpu_baseline_full(which, os.environ.get("CNMFE_CPU_BASELINE_OUT"))))
@@ -255,7 +315,7 @@ def main():
     if world > 1:
         import torch.distributed as td
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        if one_dev or (dry and not torch.cuda.is_available()):
+        if one_dev or (dry and torch.cuda.device_count() < world):     # (the launcher test on a box with fewer GPUs than ranks: gloo, not a rank on a missing device)
             one_dev = True
             td.init_process_group(backend="gloo")
         else:
@@ -324,7 +384,8 @@ def main():
     if force_coll:
         s.force_collectives = True
         comm["forced_collectives"] = True
-    eng.profile(True)
+    if a.full or a.demo_sequence:
+        eng.profile(True)
 
     last = {}
     def step():
@@ -372,30 +433,35 @@ def main():
         step()
         fence()
         warm_steps_ms.append(1e3 * (time.perf_counter() - tw0))
-        if first_tab is None:
+        if first_tab is None and a.full:
             first_tab = eng.profile_table()
-    warm_tab = eng.profile_table()
-    # timed region: HIP events only around the kernels a roofline is quoted for (an event pair around EVERY launch costs host and device time per
-    # launch -- 8 ms per iteration with the ~2000 small launches of c4, ~1 % at c3); the per-kernel breakdown comes from EXTRA steps after it
-    eng.profile(2)
-    eng.profile_reset()
+    warm_tab = eng.profile_table() if a.full else {}
+    # timed region: with --full, HIP events only around the kernels a roofline is quoted for (an event pair around EVERY launch costs host and device time
+    # per launch -- 8 ms per iteration with the ~2000 small launches of c4, ~1 % at c3); the per-kernel breakdown comes from EXTRA steps after it.  A plain
+    # run records no events.
+    if a.full:
+        eng.profile(2)
+        eng.profile_reset()
     fence()
     t0 = time.perf_counter()
     for _ in range(a.steps):
         step()
     fence()
     dt = time.perf_counter() - t0
-    tab_timed = eng.profile_table()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, s, video, a.deconv, rank == 0)
+    tab_timed = eng.profile_table() if a.full else {}
     XSTEPS = 2
-    eng.profile(1)
-    eng.profile_reset()
-    for _ in range(XSTEPS):                                     # (every rank: the steps hold the collectives)
-        step()
-    fence()
+    if a.full:
+        eng.profile(1)
+        eng.profile_reset()
+        for _ in range(XSTEPS):                                 # (every rank: the steps hold the collectives)
+            step()
+        fence()
     # The iteration no longer runs the ring sweep (sweep-free residual): the kernel the north star names is timed on its own, in this
     # run, on this video -- a few separate launches per owned patch with the engine switched to the swept residual, HIP events on the engine's stream.
     r1_sep = None
-    if a.bg_ssub == 1 and os.environ.get("CNMFE_BENCH_R1", "1") != "0":
+    if a.full and a.bg_ssub == 1 and os.environ.get("CNMFE_BENCH_R1", "1") != "0":
         before = {k: dict(v) for k, v in eng.profile_table().items()}
         prev_opts = {k: eng.get_option(k, 1) for k in ("r1_virtual", "r1_delta")}       # (a CNMFE_OPTS preset survives this block)
         eng.set_option("r1_virtual", 0); eng.set_option("r1_delta", 0)
@@ -424,6 +490,40 @@ def main():
         return
     n_patches = video.nr_patch * video.nc_patch
     value = (n_patches if a.weak else 1) * a.steps / dt          # whole-FOV iterations/s (weak mode: patch-iterations/s, every patch a full 512 x 512 FOV)
+    out = {
+        "metric": "cnmfe_iters_per_sec" if not shard_of else "cnmfe_rank_share_iters_per_sec", "value": value, "unit": "iter/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": 1e3 * dt / a.steps, "higher_is_better": True, "scaling": "weak" if a.weak else "strong", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": ("%s: %dx%dx%d fp32 video, K=%d, ring_radius=%d, %dx%d patches of distribute_data.m (%d resident blocks per GPU), "
+                                "spatial=%s, deconv_flag=%s, bg_ssub=%d" % (a.config, d1, d2, T, K, r, video.nr_patch, video.nc_patch, len(video.owned), a.alg, "true" if a.deconv else "false", a.bg_ssub))
+                               if not a.weak else
+                               ("%s (weak): %dx%dx%d fp32 video per GPU, K=%d per GPU, ring_radius=%d, 1 patch per GPU (%d patches), "
+                                "spatial=%s, deconv_flag=%s, bg_ssub=%d" % (a.config, d1, d2p, T, Kp, r, n_patches, a.alg, "true" if a.deconv else "false", a.bg_ssub)),
+                   "iteration": "update_background_parallel + update_spatial_parallel + update_temporal_parallel",
+                   "formulation": ("sweep-free residual through the resampling maps (option ssub_virtual = 1, the default): Ysig*C' = P_F - up(W_L*P_L) with P_F the video rows "
+                                   "under the masks and P_L the table of the low-resolution video, A'*Ysig = A'*Yc - B_L'*(down Yc), B_L = W_L'*up'*A; same values as the swept "
+                                   "residual (tests/test_gpu_ssub_virtual.py)" if a.bg_ssub != 1 and os.environ.get("CNMFE_OPTS", "").find("ssub_virtual=0") < 0 and os.environ.get("CNMFE_OPTS", "").find("r1_virtual=0") < 0 else
+                                  ("sweep-free residual (option r1_virtual = 1, the default): the spatial update reads Ysig*C' = P - W*P out of the fit's table "
+                                   "P = Yc*Cc', the temporal update projects the centred video through B = A - W'*A; same values as the swept residual "
+                                   "(tests/test_gpu_virtual.py); with --full the ring sweep itself is timed separately for `roofline_r1`")
+                                  if os.environ.get("CNMFE_OPTS", "").find("r1_virtual=0") < 0 and a.bg_ssub == 1 else "swept residual (r1_virtual = 0 / ssub_virtual = 0): one ring sweep per iteration"),
+                   "lanes_per_rank": lanes,
+                   "parallelism": ("patches round-robin over %d rank(s)" % world) if not shard_of else
+                                  ("rank 0 of %d: this rank's %d of the %d patches on ONE GPU, no collectives (a per-rank load figure, not a scaling point); "
+                                   "the video is uploaded as fp16 and widened on the device" % (shard_of, len(video.owned), len(video.order))),
+                   **({"note": "strong scaling of the 4 x 4-patch decomposition (BASELINE configs[3]); its own N = 1 point is the `c4_n1` object of the N = 1 line "
+                               "(16 patches on one GPU) -- the N = 1 `value` is configs[2], the same video as ONE patch, which has no halo re-reads and 16x larger launches"}
+                      if (world > 1 and a.config == "c4" and not a.weak) else {})},
+        **comm,
+        "first_iteration": {"ms": warm_steps_ms[0] if warm_steps_ms else None, "warmup_steps_ms": [round(x, 3) for x in warm_steps_ms]},
+        # a recording gets TWO background updates (demos/demo_large_data_1p.m:142,199): the mean of the first two steps from a fresh upload
+        "ms_per_step_incl_cold": (sum(warm_steps_ms[:2]) / 2.0) if len(warm_steps_ms) >= 2 else None,
+        "full": a.full, "roofline": None, "cpu_baseline": None,
+    }
+    if not a.full:
+        eng.close()
+        emit(out)
+        return
     tab_x = eng.profile_table()
     if r1_sep:                                                  # the separate sweep launches are not part of the extra steps
         for k, v in r1_sep.items():
@@ -544,7 +644,7 @@ def main():
             tmp = tempfile.mkdtemp(prefix="cnmfe_pmc_", dir="/tmp")
             try:
                 subprocess.run(["rocprofv3", "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", tmp, "-o", "x", "--",
-                                sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--alg", a.alg, "--no-cpu-baseline", "--no-extras"],
+                                sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--alg", a.alg, "--full", "--no-cpu-baseline", "--no-extras"],
                                cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=300, check=True)
                 vals = {k: [] for k in keys}
                 for fn in glob.glob(os.path.join(tmp, "**", "*counter_collection.csv"), recursive=True):
@@ -680,44 +780,12 @@ def main():
         by = 2 * 4.0 * d * T + 4.0 * Kp * T
         dlr = {"bound": "hbm", "achieved": by / ms / 1e6, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": by / ms / 1e6 / HBM_PEAK_GBS,
                "traffic": pmc_traffic("k_residual_delta"), "kernel": "residual_delta", "ms_per_launch": ms, "algorithmic_bytes_per_launch": by}
-    out = {
-        "metric": "cnmfe_iters_per_sec" if not shard_of else "cnmfe_rank_share_iters_per_sec", "value": value, "unit": "iter/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": 1e3 * dt / a.steps, "higher_is_better": True, "scaling": "weak" if a.weak else "strong", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": ("%s: %dx%dx%d fp32 video, K=%d, ring_radius=%d, %dx%d patches of distribute_data.m (%d resident blocks per GPU), "
-                                "spatial=%s, deconv_flag=%s, bg_ssub=%d" % (a.config, d1, d2, T, K, r, video.nr_patch, video.nc_patch, len(video.owned), a.alg, "true" if a.deconv else "false", a.bg_ssub))
-                               if not a.weak else
-                               ("%s (weak): %dx%dx%d fp32 video per GPU, K=%d per GPU, ring_radius=%d, 1 patch per GPU (%d patches), "
-                                "spatial=%s, deconv_flag=%s, bg_ssub=%d" % (a.config, d1, d2p, T, Kp, r, n_patches, a.alg, "true" if a.deconv else "false", a.bg_ssub)),
-                   "iteration": "update_background_parallel + update_spatial_parallel + update_temporal_parallel",
-                   "formulation": ("sweep-free residual through the resampling maps (option ssub_virtual = 1, the default): Ysig*C' = P_F - up(W_L*P_L) with P_F the video rows "
-                                   "under the masks and P_L the table of the low-resolution video, A'*Ysig = A'*Yc - B_L'*(down Yc), B_L = W_L'*up'*A; same values as the swept "
-                                   "residual (tests/test_gpu_ssub_virtual.py)" if a.bg_ssub != 1 and os.environ.get("CNMFE_OPTS", "").find("ssub_virtual=0") < 0 and os.environ.get("CNMFE_OPTS", "").find("r1_virtual=0") < 0 else
-                                  ("sweep-free residual (option r1_virtual = 1, the default): the spatial update reads Ysig*C' = P - W*P out of the fit's table "
-                                   "P = Yc*Cc', the temporal update projects the centred video through B = A - W'*A; same values as the swept residual "
-                                   "(tests/test_gpu_virtual.py); the ring sweep itself is timed separately for `roofline_r1`")
-                                  if os.environ.get("CNMFE_OPTS", "").find("r1_virtual=0") < 0 and a.bg_ssub == 1 else "swept residual (r1_virtual = 0 / ssub_virtual = 0): one ring sweep per iteration"),
-                   "lanes_per_rank": lanes,
-                   "parallelism": ("patches round-robin over %d rank(s)" % world) if not shard_of else
-                                  ("rank 0 of %d: this rank's %d of the %d patches on ONE GPU, no collectives (a per-rank load figure, not a scaling point); "
-                                   "the video is uploaded as fp16 and widened on the device" % (shard_of, len(video.owned), len(video.order))),
-                   **({"note": "strong scaling of the 4 x 4-patch decomposition (BASELINE configs[3]); its own N = 1 point is the `c4_n1` object of the N = 1 line "
-                               "(16 patches on one GPU) -- the N = 1 `value` is configs[2], the same video as ONE patch, which has no halo re-reads and 16x larger launches"}
-                      if (world > 1 and a.config == "c4" and not a.weak) else {})},
+    out.update({
         "roofline": roof,
         "roofline_r1": r1r,
         "roofline_solve": solve_roof(),
         "roofline_r1_delta": dlr,
         "roofline_projections": with_pmc(proj_roofs()),
-        **comm,
-        "first_iteration": {"ms": warm_steps_ms[0] if warm_steps_ms else None, "warmup_steps_ms": [round(x, 3) for x in warm_steps_ms],
-                            "one_off_kernels_ms": {k: round(v["total_ms"], 3) for k, v in warm_tab.items() if k in ("bg_gram_i8", "bg_gram_f64", "bg_build_dig", "bg_dig_scale", "bg_build_bf", "bg_rowsum", "bg_sys_pack") and v["calls"]},
-                            "kernels_ms": None if first_tab is None else {k: round(v["total_ms"], 3) for k, v in sorted(first_tab.items(), key=lambda kv: -kv[1]["total_ms"])[:14] if v["calls"]},
-                            "kernel_sum_ms": None if first_tab is None else round(sum(v["total_ms"] for v in first_tab.values()), 3),
-                            "note": "the FIRST step after the upload (timed on its own): its background fit also builds the block-pair covariance table of the video on "
-                                    "the fp64 matrix pipe (kept until the video or the frame stride changes); `--warmup 0` puts it inside the timed region"},
-        # a recording gets TWO background updates (demos/demo_large_data_1p.m:142,199): the mean of the first two steps from a fresh upload
-        "ms_per_step_incl_cold": (sum(warm_steps_ms[:2]) / 2.0) if len(warm_steps_ms) >= 2 else None,
         "kernel_timing": {"timed_region": sorted(k for k, v in kern.items() if v["from"] == "timed region"),
                           "note": "HIP events on the engine's stream.  Inside the timed region only the kernels a roofline is quoted for are bracketed "
                                   "(cnmfe_profile_enable(ctx, 2)); every other row of kernels_ms_per_step is the average of %d extra steps run after it with "
@@ -725,7 +793,13 @@ def main():
         "kernel_sum_ms_per_step": round(sum(v["ms_per_step"] for v in kern.values()), 3),
         "kernels_ms_per_step": {k: round(v["ms_per_step"], 4) for k, v in sorted(kern.items(), key=lambda kv: -kv[1]["ms_per_step"])},
         "kernel_calls_per_step": {k: round(v["calls_per_step"], 2) for k, v in sorted(kern.items(), key=lambda kv: -kv[1]["ms_per_step"]) if v["ms_per_step"] > 0.5},
-    }
+    })
+    out["first_iteration"].update({
+        "one_off_kernels_ms": {k: round(v["total_ms"], 3) for k, v in warm_tab.items() if k in ("bg_gram_i8", "bg_gram_f64", "bg_build_dig", "bg_dig_scale", "bg_build_bf", "bg_rowsum", "bg_sys_pack") and v["calls"]},
+        "kernels_ms": None if first_tab is None else {k: round(v["total_ms"], 3) for k, v in sorted(first_tab.items(), key=lambda kv: -kv[1]["total_ms"])[:14] if v["calls"]},
+        "kernel_sum_ms": None if first_tab is None else round(sum(v["total_ms"] for v in first_tab.values()), 3),
+        "note": "the FIRST step after the upload (timed on its own): its background fit also builds the block-pair covariance table of the video on "
+                "the fp64 matrix pipe (kept until the video or the frame stride changes); `--warmup 0` puts it inside the timed region"})
     # the driver's record keeps `roofline`, `config` and `cpu_baseline` whole and only the NAMES of the other keys: the iteration's other large kernels, the share of
     # the step the kernels fill and the cold figure ride along inside `roofline` (verdict r4 #8)
     if out["roofline"] is not None:
@@ -750,7 +824,7 @@ def main():
     if world == 1 and a.config == "c3" and not a.no_extras and not a.weak and a.bg_ssub == 1 and not a.deconv and a.alg == "hals":
         # the N = 1 point of the strong-scaling curve (`--gpus N` runs configs[3] = this video in 4 x 4 patches): all 16 patches on this one GPU
         try:
-            r_ = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", "c4", "--steps", "6", "--warmup", "5", "--no-cpu-baseline", "--no-extras"],
+            r_ = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", "c4", "--steps", "6", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-extras"],
                                 stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=600, check=True)
             c4 = json.loads(r_.stdout.decode().strip().splitlines()[-1])
             out["c4_n1"] = {k: c4[k] for k in ("value", "unit", "ms_per_step", "steps", "warmup", "n_gpus", "kernel_sum_ms_per_step")}

@@ -2,8 +2,8 @@
 # Round-3 record: bench lines of every configuration DESIGN.md section 4 quotes + the rocprofv3 kernel statistics and PMC passes of the bench command.
 # On the GPU box: bash scripts/gpu_r3_profiles.sh <ver>   -> gpurun_out/r03/*_<ver>.json, gpurun_out/prof_r03<ver>/
 ver=${1:-v1}; o=gpurun_out/r03; mkdir -p $o
-python bench.py > $o/bench_c3_$ver.json 2> $o/bench_c3_$ver.err
-X="--no-extras --no-cpu-baseline"
+python bench.py --full > $o/bench_c3_$ver.json 2> $o/bench_c3_$ver.err
+X="--full --no-extras --no-cpu-baseline"
 python bench.py $X --alg hals_thresh > $o/bench_c3_hals_thresh_$ver.json 2>/dev/null
 python bench.py $X --alg nnls > $o/bench_c3_nnls_$ver.json 2>/dev/null
 python bench.py $X --bg-ssub 2 > $o/bench_c3_bg_ssub2_$ver.json 2>/dev/null

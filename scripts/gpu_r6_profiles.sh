@@ -4,8 +4,8 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 ver=${1:-v1}; o=gpurun_out/r06; mkdir -p $o
 export PYTHONUNBUFFERED=1
-python bench.py > $o/bench_c3_$ver.json 2> $o/bench_c3_$ver.err
-X="--no-extras --no-cpu-baseline"
+python bench.py --full > $o/bench_c3_$ver.json 2> $o/bench_c3_$ver.err
+X="--full --no-extras --no-cpu-baseline"
 export CNMFE_BENCH_R1=0
 python bench.py $X --alg hals_thresh > $o/bench_c3_hals_thresh_$ver.json 2>/dev/null
 python bench.py $X --alg nnls > $o/bench_c3_nnls_$ver.json 2>/dev/null

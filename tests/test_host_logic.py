@@ -252,6 +252,46 @@ def test_bench_line_contract_of_the_committed_profile():
     assert c["kind"] in ("port", "reference") and c["cores"] >= 1
 
 
+def test_bench_dump_outputs_is_seeded_and_bounded(tmp_path):
+    """bench.py --dump-outputs: float arrays only, at most 64 MiB at the headline sizes (traces and footprints sampled), the same samples on every call"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    d1, d2, T, K, p = 512, 512, 10000, 500, 96
+    rng = np.random.default_rng(0)
+
+    class Video:
+        pass
+
+    class Src:
+        pass
+
+    video = Video(); video.d1, video.d2, video.owned = d1, d2, [0]
+    s = Src()
+    s.C = rng.random((K, T), dtype=np.float32); s.C_raw = s.C + 1; s.S = s.C + 2
+    s.A = sp.random(d1 * d2, K, density=1e-3, format="csc", dtype=np.float32, random_state=1)
+    s.b0_new = rng.random((d1, d2))
+    n = d1 * d2
+    W = sp.csr_matrix((rng.random(n * p, dtype=np.float32), np.tile(np.arange(p), n), np.arange(0, n * p + 1, p)), shape=(n, n))
+    s.get_W = lambda idx: W
+    for deconv in (False, True):
+        outs = []
+        for k in range(2):
+            dd = tmp_path / ("%d_%d" % (deconv, k))
+            bench.dump_outputs(str(dd), s, video, deconv, True)
+            outs.append({f.name: np.load(f) for f in dd.iterdir()})
+        names = {"A.npy", "C.npy", "b0_new.npy", "W.npy"} | ({"C_raw.npy", "S.npy"} if deconv else set())
+        assert set(outs[0]) == names
+        assert sum(v.nbytes for v in outs[0].values()) <= 64 << 20
+        for name, v in outs[0].items():
+            assert v.dtype in (np.float32, np.float64) and np.array_equal(v, outs[1][name]), name
+        assert outs[0]["W.npy"].shape[1] == p and outs[0]["A.npy"].shape[1] == n
+        if not deconv:
+            assert np.array_equal(outs[0]["C.npy"], s.C)
+        else:
+            assert np.array_equal(outs[0]["C_raw.npy"], outs[0]["C.npy"] + 1)
+
+
 def test_noise_image_bookkeeping_and_nearest_rows_match_the_oracle():
     """host pieces of round 2: the storage-block bookkeeping of Sources2D.m:361-376 applied to per-pixel estimates == the oracle's literal block
     loop, on several geometries; and the rows imresize(., 1/s, 'nearest') keeps == the oracle's box-kernel weights"""
