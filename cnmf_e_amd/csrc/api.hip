@@ -964,6 +964,26 @@ int cnmfe_estimate_noise(cnmfe_ctx *ctx, int patch_id, int64_t nframes, float *s
     return sn_video_run(ctx, P, nframes, sn_block_out);
 }
 
+int cnmfe_seed_images(cnmfe_ctx *ctx, int patch_id, const float *psf, int32_t psf_n, int64_t frame0, int64_t nframes, const double *Q, int32_t M, float sig,
+                      float *Cn_block, float *PNR_block) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    Patch *P = get_patch(ctx, patch_id);
+    if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
+    if (!Cn_block || !PNR_block) return fail(CNMFE_EINVAL, "null Cn_block / PNR_block");
+    if (psf_n < 0 || M < 0 || frame0 < 0 || !(sig == sig) || std::isinf(sig)) return fail(CNMFE_EINVAL, "seed images: psf_n = %d, M = %d, frame0 = %lld, sig = %g", psf_n, M, (long long)frame0, (double)sig);
+    if (!psf) psf_n = 0;
+    if (!Q) M = 0;
+    if (P->derived) return fail(CNMFE_EUNSUPPORTED, "seed images of a derived (bg_ssub) patch are not built: patch %d", patch_id);
+    if (psf_n > 0 && (psf_n % 2 == 0 || psf_n > 25)) return fail(CNMFE_EUNSUPPORTED, "seed images: the filter must be odd-sized and at most 25 x 25 (got %d; pad an even kernel)", psf_n);
+    if (M > 16) return fail(CNMFE_EUNSUPPORTED, "seed images: at most 16 detrend basis columns (got %d)", M);
+    if (frame0 != 0) return fail(CNMFE_EUNSUPPORTED, "seed images read the frames from the first one on (frame0 = %lld)", (long long)frame0);
+    if (nframes < 64 || nframes > std::min<int64_t>(P->T, 20400))
+        return fail(CNMFE_EUNSUPPORTED, "seed images support 64 <= nframes <= min(T, 20400) (got %lld of %lld)", (long long)nframes, (long long)P->T);
+    CK(hipSetDevice(ctx->device));
+    RET(ensure_ymean(ctx, P));
+    return seed_images_run(ctx, P, psf, psf_n, nframes, Q, M, sig, Cn_block, PNR_block);
+}
+
 int cnmfe_update_spatial(cnmfe_ctx *ctx, int patch_id, int algorithm, int32_t K, const int64_t *A_colptr,
                          const int32_t *A_rowidx, const float *A_val, const float *C, int c_order,
                          const int64_t *IND_colptr, const int32_t *IND_rowidx, const float *sn, int32_t param, float *A_out) {

@@ -484,6 +484,8 @@ int postproc_run(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_
                  const float *A_val, uint8_t *keep);
 int ensure_ymean(cnmfe_ctx *ctx, Patch *P);
 int sn_video_run(cnmfe_ctx *ctx, Patch *P, int64_t nframes, float *sn_out);
+int seed_images_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, int64_t nframes, const double *Q, int32_t M, float sig,
+                    float *Cn_out, float *PNR_out);   // seed.hpp (deconv.hip)
 int spatial_fetch(cnmfe_ctx *ctx, float *A_out, int64_t nnz);
 int spatial_fetch_connected(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *IND_colptr, const int32_t *IND_rowidx, float *A_out, uint8_t *keep, bool wait = true);
 int ring_first_run(cnmfe_ctx *ctx, Patch *P, bool *first);

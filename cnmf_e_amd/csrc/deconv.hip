@@ -1030,6 +1030,10 @@ int sn_video_run(cnmfe_ctx *ctx, Patch *P, int64_t nframes, float *sn_out) {
     return 0;
 }
 
+}  // namespace cnmfe
+#include "seed.hpp"       // (f) seed images: Cn and PNR of the spatially filtered block (its noise is get_sn above)
+namespace cnmfe {
+
 // ---- host side -------------------------------------------------------------------------------------------
 
 int deconv_setup(const cnmfe_deconv_opts *o, int64_t T, int in_sweep, DeconvCfg &c, size_t &shmem) {

@@ -43,6 +43,9 @@
 //   job = cnmfe_mex('temporal_job', h, pid, A_patch, C_or_rows, maxIter)   everything of 'temporal' up to the Gauss-Seidel sweeps; 'temporal_jobs_sweep' then runs
 //   cnmfe_mex('temporal_jobs_sweep', h)                                    level l of EVERY job in one launch; cnmfe_mex('stitch_add_job', h, job, ind) adds a job
 //   cnmfe_mex('stitch_finish_async', h, subtract_min, K, T)                :279-286 + bind on one context without waiting; C_raw = cnmfe_mex('stitch_collect', h)
+// Seed images (correlation_pnr_parallel.m:70-104 per patch):
+//   [Cn_block, PNR_block] = cnmfe_mex('seed_images', h, pid, psf, nframes, Q)   psf: odd n x n (or []), Q: nframes x M orthonormal detrend basis (or [] / omitted);
+//                                                                          nr_b x nc_b double images of the block (its size is remembered from 'patch')
 #include "mex.h"
 #include "matrix.h"
 #include <string.h>
@@ -59,7 +62,13 @@ static Pending g_pend[MAX_PEND];
 // the asynchronous stitch of a context ('stitch_finish_async' ... 'stitch_collect'): K x T floats, row-major, pinned
 typedef struct { float *pinned; size_t K, T; } StitchOut;
 static StitchOut g_stitch[MAX_CTX];
+// block sizes by (context, patch id), noted by 'patch': what 'seed_images' shapes its outputs with
+#define MAX_DIMS 4096
+typedef struct { cnmfe_ctx *c; int pid; int32_t nr_b, nc_b; } BlockDims;
+static BlockDims g_dims[MAX_DIMS];
+static int g_ndims = 0;
 static void at_exit(void) {
+    g_ndims = 0;
     for (int i = 0; i < MAX_PEND; ++i) if (g_pend[i].used) { if (g_pend[i].pinned) cnmfe_host_free(g_pend[i].pinned); if (g_pend[i].ind) mxDestroyArray(g_pend[i].ind); g_pend[i].used = 0; }
     for (int i = 0; i < MAX_CTX; ++i) if (g_stitch[i].pinned) { cnmfe_host_free(g_stitch[i].pinned); g_stitch[i].pinned = NULL; }
     for (int i = 0; i < g_nctx; ++i) if (g_ctx[i]) { cnmfe_destroy(g_ctx[i]); g_ctx[i] = NULL; }
@@ -168,7 +177,13 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
         return;
     }
     cnmfe_ctx *c = ctx_of(pin[1]);
-    if (!strcmp(cmd, "destroy")) { const int i = (int)mxGetScalar(pin[1]); cnmfe_destroy(c); g_ctx[i - 1] = NULL; return; }
+    if (!strcmp(cmd, "destroy")) {
+        const int i = (int)mxGetScalar(pin[1]);
+        int keep = 0;                                               // the block sizes noted for this context go with it (its address may be handed out again)
+        for (int k = 0; k < g_ndims; ++k) if (g_dims[k].c != c) g_dims[keep++] = g_dims[k];
+        g_ndims = keep;
+        cnmfe_destroy(c); g_ctx[i - 1] = NULL; return;
+    }
     if (!strcmp(cmd, "bind_traces")) {
         if (nin != 3) FAIL("bind_traces: 3 inputs required");
         if (mxIsEmpty(pin[2])) { CHECK(cnmfe_traces_bind(c, 0, 0, NULL, CNMFE_COLMAJOR)); return; }
@@ -292,7 +307,12 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
         if (mxGetNumberOfElements(pin[3]) != 4 || mxGetNumberOfElements(pin[4]) != 4) FAIL("patch: positions are [r0 r1 c0 c1]");
         int32_t pr[4], br[4];
         for (int i = 0; i < 4; ++i) { pr[i] = (int32_t)mxGetPr(pin[3])[i]; br[i] = (int32_t)mxGetPr(pin[4])[i]; }
+        int slot = 0;
+        while (slot < g_ndims && !(g_dims[slot].c == c && g_dims[slot].pid == pid)) ++slot;
+        if (slot >= MAX_DIMS) FAIL("patch: this gateway keeps the block sizes of at most %d patches", MAX_DIMS);
         CHECK(cnmfe_patch_create(c, pid, pr, br, (int32_t)mxGetScalar(pin[5]), (int32_t)mxGetScalar(pin[6]), (int64_t)mxGetScalar(pin[7])));
+        g_dims[slot].c = c; g_dims[slot].pid = pid; g_dims[slot].nr_b = br[1] - br[0] + 1; g_dims[slot].nc_b = br[3] - br[2] + 1;
+        if (slot == g_ndims) ++g_ndims;
     } else if (!strcmp(cmd, "upload")) {
         if (nin != 5) FAIL("upload: 5 inputs required");
         const mxArray *Y = pin[3];
@@ -430,6 +450,26 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
         float *sn = (float *)mxMalloc((db + 1) * sizeof(float));
         CHECK(cnmfe_estimate_noise(c, pid, (int64_t)mxGetScalar(pin[4]), sn));
         pout[0] = to_double(sn, db, 1);
+    } else if (!strcmp(cmd, "seed_images")) {                  // [Cn_block, PNR_block] = cnmfe_mex('seed_images', h, pid, psf, nframes, Q)   correlation_image_endoscope.m:36-96
+        if (nin != 5 && nin != 6) FAIL("seed_images: 5 or 6 inputs required");
+        int slot = 0;
+        while (slot < g_ndims && !(g_dims[slot].c == c && g_dims[slot].pid == pid)) ++slot;
+        if (slot == g_ndims) FAIL("seed_images: patch %d was not created through this gateway", pid);
+        const size_t nrb = (size_t)g_dims[slot].nr_b, ncb = (size_t)g_dims[slot].nc_b;
+        const mxArray *F = pin[3];
+        if (!mxIsEmpty(F) && mxGetM(F) != mxGetN(F)) FAIL("seed_images: psf must be square");
+        const int32_t pn = mxIsEmpty(F) ? 0 : (int32_t)mxGetM(F);
+        const float *psf = pn ? f32_of(F, NULL) : NULL;
+        const int64_t nf = (int64_t)mxGetScalar(pin[4]);
+        const double *Q = NULL; int32_t M = 0;
+        if (nin == 6 && !mxIsEmpty(pin[5])) {
+            if (!mxIsDouble(pin[5]) || mxIsSparse(pin[5]) || (int64_t)mxGetM(pin[5]) != nf) FAIL("seed_images: Q must be a full double nframes x M matrix");
+            Q = mxGetPr(pin[5]); M = (int32_t)mxGetN(pin[5]);
+        }
+        float *cn = (float *)mxMalloc((nrb * ncb + 1) * sizeof(float)), *pnr = (float *)mxMalloc((nrb * ncb + 1) * sizeof(float));
+        CHECK(cnmfe_seed_images(c, pid, psf, pn, 0, nf, Q, M, 3.0f, cn, pnr));
+        pout[0] = to_double(cn, nrb, ncb);
+        if (nout > 1) pout[1] = to_double(pnr, nrb, ncb);
     } else if (!strcmp(cmd, "background_ssub")) {              // cnmfe_mex('background_ssub', h, pid, fit_pid, bg_ssub, A_prev_block, C_or_rows, b0_block)
         if (nin != 8) FAIL("background_ssub: 8 inputs required");
         Csc A = csc_of(pin[5]);

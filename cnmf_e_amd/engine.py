@@ -332,6 +332,31 @@ class Engine:
         L.check(L.lib.cnmfe_estimate_noise(self._ctx, pid, n, _p(out, L.f32p)))
         return out
 
+    def seed_images(self, pid, psf, nframes=None, Q=None, sig=3.0, frame0=0):
+        """[Cn, PNR] = correlation_image_endoscope(Ypatch, options) of the BLOCK of a patch (correlation_image_endoscope.m:36-96) over the first `nframes`
+        frames (default all): psf = the spatial filter (sources2d.seed_psf; None = no filter), Q = nframes x M orthonormal detrend basis (None = none),
+        sig = the threshold factor.  Two float32 arrays of d_b pixels, column-major in the block."""
+        info = self._patch[pid]
+        n = info["T"] if nframes is None else int(nframes)
+        psf_a, psf_n = None, 0
+        if psf is not None and np.size(psf):
+            psf = np.asarray(psf, dtype=np.float32)
+            if psf.ndim != 2 or psf.shape[0] != psf.shape[1]:
+                raise ValueError("psf must be square, got %s" % (psf.shape,))
+            psf_n = int(psf.shape[0])
+            psf_a = np.ascontiguousarray(psf.T)                            # column-major
+        Q_a, M = None, 0
+        if Q is not None and np.size(Q):
+            Q = np.asarray(Q, dtype=np.float64)
+            if Q.ndim != 2 or Q.shape[0] != n:
+                raise ValueError("Q must be (%d, M), got %s" % (n, Q.shape))
+            M = int(Q.shape[1])
+            Q_a = np.ascontiguousarray(Q.T)                                # column-major
+        Cn = np.empty(info["d_b"], dtype=np.float32); PNR = np.empty(info["d_b"], dtype=np.float32)
+        L.check(L.lib.cnmfe_seed_images(self._ctx, pid, _p(psf_a, L.f32p), psf_n, int(frame0), n, _p(Q_a, L.f64p), M, float(sig),
+                                        _p(Cn, L.f32p), _p(PNR, L.f32p)))
+        return Cn, PNR
+
     def set_noise(self, pid, sn_block):
         """sn of the block pixels (update_background_parallel.m:131,137); read by the outlier branch of fit_ring_model only"""
         sn_block = np.ascontiguousarray(sn_block, dtype=np.float32).ravel()

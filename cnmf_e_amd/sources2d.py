@@ -28,7 +28,7 @@ import scipy.sparse as sp
 from . import _lib as L
 from .engine import BoundRows, DeviceTraces, Engine
 
-__all__ = ["Options", "PatchedVideo", "Sources2D", "distribute_geometry", "determine_search_location"]
+__all__ = ["Options", "PatchedVideo", "Sources2D", "distribute_geometry", "determine_search_location", "seed_psf", "bspline_basis"]
 
 
 # --------------------------------------------------------------------------------------
@@ -58,6 +58,14 @@ class Options:
     deconv_options: dict = field(default_factory=lambda: {"type": "ar1", "method": "foopsi", "smin": -5.0,
                                                           "optimize_pars": True, "optimize_b": True, "max_tau": 100.0})   # demo_large_data_1p.m:38-43
     spatial_constraints: dict = field(default_factory=lambda: {"circular": False, "connected": True})   # :116
+    # the seed images (correlation_pnr_parallel): demo_large_data_1p.m:16-17,45-47,76 and the reference's defaults for the rest
+    gSig: float = 3.0                # width of the Gaussian kernel that approximates one neuron; <= 0: no spatial filter
+    gSiz: float = 13.0               # neuron diameter
+    center_psf: bool = True          # subtract the kernel's mean over its support (1p data)
+    nk: int = 1                      # knots of the detrending spline basis; 1 = no detrending
+    detrend_method: str = "spline"   # 'spline' | 'local_min' (only 'spline' is built)
+    ssub: int = 1                    # spatial / temporal downsampling of the initialisation (only 1 is built)
+    tsub: int = 1
 
 
 def _mround(x):
@@ -120,6 +128,68 @@ def estimate_noise_image(sn_pix, block_idx_r, block_idx_c):
     for b in np.asarray(block_idx_c)[1:-1]:
         out[:, b - 2] = out[:, b - 1]
     return out
+
+
+def _fspecial_gaussian(n, sigma):
+    """fspecial('gaussian', n, sigma) (MathWorks documentation): exp(-(x^2 + y^2) / (2 sigma^2)) on the n x n grid centred on 0, entries below eps * max
+    zeroed, normalised to sum 1"""
+    x = np.arange(n, dtype=np.float64) - (n - 1) / 2.0
+    h = np.exp(-(x[:, None] ** 2 + x[None, :] ** 2) / (2.0 * sigma * sigma))
+    h[h < np.finfo(np.float64).eps * h.max()] = 0.0
+    return h / h.sum()
+
+
+def seed_psf(gSig, gSiz, center_psf=True):
+    """The spatial filter of the seed images (correlation_image_endoscope.m:36-47), float64, odd-sized; None for gSig <= 0 (no filter).
+    center_psf: the Gaussian of ceil(4 gSig + 1) pixels, its mean over the support {psf >= max of its first column} subtracted, 0 outside the support.
+    Otherwise the plain Gaussian of round(gSiz) pixels; an even-sized one gets a leading zero row and column, which keeps imfilter's origin
+    floor((n + 1) / 2) of the even kernel at the centre of the odd one (the engine filters with odd kernels only)."""
+    if gSig <= 0:
+        return None
+    if center_psf:
+        psf = _fspecial_gaussian(int(np.ceil(gSig * 4 + 1)), gSig)
+        ind = psf >= psf[:, 0].max()
+        psf = psf - psf[ind].mean()
+        psf[~ind] = 0.0
+        n = psf.shape[0]
+    else:
+        n = int(_mround(gSiz))
+        psf = _fspecial_gaussian(n, gSig)
+    if n % 2 == 0:
+        pad = np.zeros((n + 1, n + 1))
+        pad[1:, 1:] = psf
+        psf = pad
+    return psf
+
+
+def bspline_basis(T, nk, order=4):
+    """X = bsplineM((1:T)', linspace(1, T, nk), 4) of detrend_data.m:23: the nk + order - 2 B-splines of that order on the breaks with order-fold end knots,
+    evaluated at the frames 1..T (T x (nk + order - 2), float64; rows sum to 1).  Plain de Boor recursion over the knot interval of every frame."""
+    T, nk, k = int(T), int(nk), int(order)
+    if nk < 2:
+        raise ValueError("a spline basis needs at least 2 knots")
+    x = np.arange(1, T + 1, dtype=np.float64)
+    breaks = np.linspace(1.0, float(T), nk)
+    knots = np.concatenate([np.full(k - 1, breaks[0]), breaks, np.full(k - 1, breaks[-1])])
+    nbasis = knots.size - k
+    # knots[left] <= x < knots[left + 1], the last frame in the last non-empty interval
+    left = np.clip(np.searchsorted(knots, x, side="right") - 1, k - 1, nbasis - 1)
+    b = np.zeros((T, k))
+    b[:, 0] = 1.0
+    for j in range(1, k):
+        saved = np.zeros(T)
+        for r in range(j):
+            tr = knots[left + r + 1] - x
+            tl = x - knots[left + r + 1 - j]
+            term = b[:, r] / (tr + tl)
+            b[:, r] = saved + tr * term
+            saved = tl * term
+        b[:, j] = saved
+    X = np.zeros((T, nbasis))
+    rows = np.arange(T)
+    for r in range(k):
+        X[rows, left - (k - 1) + r] = b[:, r]
+    return X
 
 
 def _rect_pixels(rect, d1):
@@ -806,6 +876,33 @@ class Sources2D:
         sn = estimate_noise_image(out, storage_block_index(v.d1, pr, v.w_overlap), storage_block_index(v.d2, pc, v.w_overlap))
         self.P["sn"] = sn.reshape(-1, order="F").astype(np.float32)
         return sn
+
+    def correlation_pnr_parallel(self, frame_range=None):
+        """[Cn, PNR] = obj.correlation_pnr_parallel(frame_range)  (@Sources2D/correlation_pnr_parallel.m:1-128): the local-correlation and peak-to-noise images
+        of the spatially filtered video, d1 x d2 float64 each.  Every owned patch evaluates its block on the device (Engine.seed_images) and keeps the patch
+        interior (:117-127: the interiors are disjoint, so the reference's max merge is a scatter; sharded runs sum them).  frame_range = (1, n), 1-based
+        inclusive and clipped to the recording as in :40-45."""
+        self._need_data()
+        v, o = self.video, self.options
+        if int(o.ssub) != 1 or int(o.tsub) != 1:
+            raise NotImplementedError("correlation_pnr_parallel: ssub / tsub other than 1 are not built")
+        nk = int(o.nk)
+        if nk > 1 and str(o.detrend_method).lower() != "spline":
+            raise NotImplementedError("correlation_pnr_parallel: detrend_method %r is not built (only 'spline')" % (o.detrend_method,))
+        f0, f1 = (1, v.T) if frame_range is None or len(frame_range) == 0 else (int(frame_range[0]), int(frame_range[1]))
+        f0, f1 = min(max(f0, 1), v.T), min(max(f1, 1), v.T)
+        if f0 != 1:
+            raise NotImplementedError("correlation_pnr_parallel reads the frames from the first one on (frame_range = [%d, %d])" % (f0, f1))
+        n = f1 - f0 + 1
+        psf = seed_psf(float(o.gSig), float(o.gSiz), bool(o.center_psf))
+        Q = np.linalg.qr(bspline_basis(n, nk))[0] if nk > 1 else None     # detrend_data.m:23-29: the projection only needs the span
+        Cn = np.zeros(v.d1 * v.d2, dtype=np.float64); PNR = np.zeros(v.d1 * v.d2, dtype=np.float64)
+        for idx in v.owned:
+            cn_b, pnr_b = self.engine.seed_images(v.pid[idx], psf, n, Q, 3.0)
+            Cn[v.patch_pix[idx]] = cn_b[v.ind_patch[idx]]
+            PNR[v.patch_pix[idx]] = pnr_b[v.ind_patch[idx]]
+        both = self._allreduce(np.stack([Cn, PNR]))
+        return both[0].reshape(v.d1, v.d2, order="F"), both[1].reshape(v.d1, v.d2, order="F")
 
     def reconstruct_b0(self):
         """Sources2D.m:1153-1190: stitch b0{m} into a d1 x d2 image (owned patches; all-reduced if sharded)."""

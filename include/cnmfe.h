@@ -139,6 +139,22 @@ int cnmfe_fit_reserve(cnmfe_ctx *ctx, int patch_id);
  * last is dropped) is index arithmetic on the assembled image and stays with the host (sources2d.estimate_noise_image). */
 int cnmfe_estimate_noise(cnmfe_ctx *ctx, int patch_id, int64_t nframes, float *sn_block_out /* d_b */);
 
+/* ---- (f) seed images: [Cn, PNR] = correlation_image_endoscope(Ypatch, options) of the block of one patch
+ * @Sources2D/correlation_pnr_parallel.m:70-104 -> endoscope/correlation_image_endoscope.m:36-96 -> utilities/correlation_image.m:31-77:
+ *   HY = imfilter(Y, psf, 'replicate') (border replicated at the BLOCK edge);  HY -= median(HY, 2);  PNR = max(HY, [], 2) ./ GetSn(HY);
+ *   HY(HY < sig * Sn) = 0;  Cn = the mean correlation of every pixel's trace with its 8 neighbours inside the block.
+ * psf: psf_n x psf_n, column-major, psf_n odd and <= 25 (an even kernel is zero-padded by the caller: sources2d.seed_psf); NULL / 0 = no filter (gSig <= 0).
+ * Q: nframes x M orthonormal columns (column-major, M <= 16) spanning the detrend basis of detrend_data.m:23 (nk > 1, method 'spline'): the filtered trace
+ * loses its projection on them first; NULL / 0 = no detrending.  sig: the threshold factor (the reference's is 3).
+ * Frames [frame0, frame0 + nframes) with frame0 == 0 and 64 <= nframes <= min(T, 20400) (the LDS-resident GetSn); anything else, and a derived (bg_ssub) patch,
+ * is CNMFE_EUNSUPPORTED.  The block is filtered whole (the reference's 500^3-sample sub-patch split of :50-59 is a memory workaround and is not reproduced).
+ * Scratch: the filtered block, 16 * ceil(nframes / 4) * d_b bytes, allocated for the call and released before it returns (CNMFE_ENOMEM names the bytes);
+ * no resident state of the patch is read or written except the centred video.  Two calls return bit-identical images.  A pixel without a neighbour inside the
+ * block (a 1 x 1 block) has Cn = 0 / 0 = NaN, as in the reference; a constant trace (Sn = 0) has PNR = NaN likewise.  Outputs: d_b floats each, the patch's
+ * caller keeps the patch interior (:108-128). */
+int cnmfe_seed_images(cnmfe_ctx *ctx, int patch_id, const float *psf, int32_t psf_n, int64_t frame0, int64_t nframes,
+                      const double *Q, int32_t M, float sig, float *Cn_block /* d_b */, float *PNR_block /* d_b */);
+
 /* sn of the BLOCK pixels of a patch (obj.P.sn(logical(mask)), update_background_parallel.m:131; for a low-resolution fit patch of
  * bg_ssub > 1 the resized values of :137).  Only the outlier branch of the ring fit reads them. */
 int cnmfe_set_noise(cnmfe_ctx *ctx, int patch_id, const float *sn_block /* d_b */);
