@@ -76,6 +76,10 @@ PROTOTYPES = {
     "cnmfe_compute_rss_ssub": (C.c_int, [c_ctx, C.c_int, C.c_int32, i64p, i32p, f32p, f32p, C.c_int, f32p, C.POINTER(C.c_double)]),
     "cnmfe_estimate_noise": (C.c_int, [c_ctx, C.c_int, C.c_int64, f32p]),
     "cnmfe_seed_images": (C.c_int, [c_ctx, C.c_int, f32p, C.c_int32, C.c_int64, C.c_int64, f64p, C.c_int32, C.c_float, f32p, f32p]),
+    "cnmfe_peel_open": (C.c_int, [c_ctx, C.c_int, f32p, C.c_int32, C.c_int64, C.c_int64, f64p, C.c_int32, C.c_float, f32p, f32p, f32p]),
+    "cnmfe_peel_extract": (C.c_int, [c_ctx, C.c_int, C.c_int32, C.c_int32, C.c_int32, f64p, f64p, f64p, f64p]),
+    "cnmfe_peel_apply": (C.c_int, [c_ctx, C.c_int, C.c_int32, C.c_int32, C.c_int32, f64p, f64p, f64p, C.c_double, C.c_double, C.c_double, f32p, f32p]),
+    "cnmfe_peel_close": (C.c_int, [c_ctx, C.c_int]),
     "cnmfe_stitch_finish_async": (C.c_int, [c_ctx, C.c_int, f32p]),
     "cnmfe_update_spatial_fetch": (C.c_int, [c_ctx, f32p, C.c_int64]),
     "cnmfe_update_spatial_fetch_connected": (C.c_int, [c_ctx, C.c_int32, C.c_int32, C.c_int32, i64p, i32p, f32p, u8p]),

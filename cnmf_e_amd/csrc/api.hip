@@ -964,10 +964,11 @@ int cnmfe_estimate_noise(cnmfe_ctx *ctx, int patch_id, int64_t nframes, float *s
     return sn_video_run(ctx, P, nframes, sn_block_out);
 }
 
-int cnmfe_seed_images(cnmfe_ctx *ctx, int patch_id, const float *psf, int32_t psf_n, int64_t frame0, int64_t nframes, const double *Q, int32_t M, float sig,
-                      float *Cn_block, float *PNR_block) {
+// the argument checks cnmfe_seed_images and cnmfe_peel_open share (the same refusals); psf_n and M come back normalised
+static int seed_args(cnmfe_ctx *ctx, int patch_id, const float *psf, int32_t &psf_n, int64_t frame0, int64_t nframes, const double *Q, int32_t &M, float sig,
+                     const float *Cn_block, const float *PNR_block, Patch *&P) {
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
-    Patch *P = get_patch(ctx, patch_id);
+    P = get_patch(ctx, patch_id);
     if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
     if (!Cn_block || !PNR_block) return fail(CNMFE_EINVAL, "null Cn_block / PNR_block");
     if (psf_n < 0 || M < 0 || frame0 < 0 || !(sig == sig) || std::isinf(sig)) return fail(CNMFE_EINVAL, "seed images: psf_n = %d, M = %d, frame0 = %lld, sig = %g", psf_n, M, (long long)frame0, (double)sig);
@@ -979,9 +980,70 @@ int cnmfe_seed_images(cnmfe_ctx *ctx, int patch_id, const float *psf, int32_t ps
     if (frame0 != 0) return fail(CNMFE_EUNSUPPORTED, "seed images read the frames from the first one on (frame0 = %lld)", (long long)frame0);
     if (nframes < 64 || nframes > std::min<int64_t>(P->T, 20400))
         return fail(CNMFE_EUNSUPPORTED, "seed images support 64 <= nframes <= min(T, 20400) (got %lld of %lld)", (long long)nframes, (long long)P->T);
+    return 0;
+}
+
+int cnmfe_seed_images(cnmfe_ctx *ctx, int patch_id, const float *psf, int32_t psf_n, int64_t frame0, int64_t nframes, const double *Q, int32_t M, float sig,
+                      float *Cn_block, float *PNR_block) {
+    Patch *P = nullptr;
+    RET(seed_args(ctx, patch_id, psf, psf_n, frame0, nframes, Q, M, sig, Cn_block, PNR_block, P));
     CK(hipSetDevice(ctx->device));
     RET(ensure_ymean(ctx, P));
     return seed_images_run(ctx, P, psf, psf_n, nframes, Q, M, sig, Cn_block, PNR_block);
+}
+
+// ---- greedy initialisation: a peel session per patch (peel.hpp) ----
+int cnmfe_peel_open(cnmfe_ctx *ctx, int patch_id, const float *psf, int32_t psf_n, int64_t frame0, int64_t nframes, const double *Q, int32_t M, float sig,
+                    float *Cn_block, float *PNR_block, float *Sn_block) {
+    Patch *P = nullptr;
+    RET(seed_args(ctx, patch_id, psf, psf_n, frame0, nframes, Q, M, sig, Cn_block, PNR_block, P));
+    if (P->peel) return fail(CNMFE_ESTATE, "patch %d already has an open peel session", patch_id);
+    CK(hipSetDevice(ctx->device));
+    RET(ensure_ymean(ctx, P));
+    P->peel = new PeelSession();
+    const int rc = peel_open_run(ctx, P, psf, psf_n, nframes, Q, M, sig, Cn_block, PNR_block, Sn_block);
+    if (rc != 0) { (void)hipStreamSynchronize(ctx->st()); delete P->peel; P->peel = nullptr; }
+    return rc;
+}
+
+static int peel_args(cnmfe_ctx *ctx, int patch_id, int32_t r, int32_t c, int32_t gSiz, Patch *&P) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    P = get_patch(ctx, patch_id);
+    if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
+    if (!P->peel) return fail(CNMFE_ESTATE, "patch %d has no open peel session (cnmfe_peel_open)", patch_id);
+    if (gSiz < 1) return fail(CNMFE_EINVAL, "peel: gSiz = %d", gSiz);
+    if (gSiz > 20) return fail(CNMFE_EUNSUPPORTED, "peel: gSiz <= 20 is built (got %d)", gSiz);
+    if (r < 0 || r >= P->nr_b || c < 0 || c >= P->nc_b) return fail(CNMFE_EINVAL, "peel: the seed (%d, %d) lies outside the %d x %d block", r, c, P->nr_b, P->nc_b);
+    return 0;
+}
+
+int cnmfe_peel_extract(cnmfe_ctx *ctx, int patch_id, int32_t r, int32_t c, int32_t gSiz, double *corr_box, double *ai_box, double *ci, double *stats) {
+    Patch *P = nullptr;
+    RET(peel_args(ctx, patch_id, r, c, gSiz, P));
+    if (!corr_box || !ai_box || !ci || !stats) return fail(CNMFE_EINVAL, "null corr_box / ai_box / ci / stats");
+    CK(hipSetDevice(ctx->device));
+    return peel_extract_run(ctx, P, r, c, gSiz, corr_box, ai_box, ci, stats);
+}
+
+int cnmfe_peel_apply(cnmfe_ctx *ctx, int patch_id, int32_t r, int32_t c, int32_t gSiz, const double *ai_box, const double *Hai_box2, const double *ci,
+                     double sig, double min_pnr, double min_corr, float *PNR_box2, float *Cn_box2) {
+    Patch *P = nullptr;
+    RET(peel_args(ctx, patch_id, r, c, gSiz, P));
+    if (!ai_box || !Hai_box2 || !ci || !PNR_box2 || !Cn_box2) return fail(CNMFE_EINVAL, "null ai_box / Hai_box2 / ci / PNR_box2 / Cn_box2");
+    if (!(sig == sig) || std::isinf(sig)) return fail(CNMFE_EINVAL, "peel: sig = %g", sig);
+    CK(hipSetDevice(ctx->device));
+    return peel_apply_run(ctx, P, r, c, gSiz, ai_box, Hai_box2, ci, sig, min_pnr, min_corr, PNR_box2, Cn_box2);
+}
+
+int cnmfe_peel_close(cnmfe_ctx *ctx, int patch_id) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    Patch *P = get_patch(ctx, patch_id);
+    if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
+    if (!P->peel) return fail(CNMFE_ESTATE, "patch %d has no open peel session", patch_id);
+    CK(hipSetDevice(ctx->device));
+    CK(hipStreamSynchronize(ctx->st()));
+    delete P->peel; P->peel = nullptr;
+    return 0;
 }
 
 int cnmfe_update_spatial(cnmfe_ctx *ctx, int patch_id, int algorithm, int32_t K, const int64_t *A_colptr,

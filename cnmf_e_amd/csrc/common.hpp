@@ -133,6 +133,10 @@ inline void csc_to_csr(int64_t nrow, int32_t ncol, const int64_t *colptr, const 
         }
 }
 
+// a greedy-initialisation session of one patch (peel.hpp, cnmfe_peel_open .. cnmfe_peel_close): the filtered block HY, the working copy Yw of the video (both
+// [ceil(n / 4)][d_b] float4), GetSn of HY per block pixel (fp64), the detrend basis, ci | y_bg (fp64, n each) and the box kernels' scratch
+struct PeelSession { DevBuf hy, yw, sn, q, ci, scr; int64_t n = 0, nq = 0; int M = 0; };
+
 // ---- per-patch resident state ----------------------------------------------------
 struct Patch {
     int32_t prect[4], brect[4];        // 1-based inclusive [r0 r1 c0 c1]
@@ -213,7 +217,8 @@ struct Patch {
     // pinned memory behind the fit that produced W: the next fit reads it without draining the stream (ring_stats_*, api.hip)
     DevBuf stat_dev; void *stat_host = nullptr; hipEvent_t stat_ev = nullptr; bool stat_valid = false;
     int lane = 0;                                          // the execution lane (stream + scratch set) of this patch's calls: cnmfe_ctx::activate, option "lanes"
-    ~Patch() { if (stat_host) (void)hipHostFree(stat_host); if (stat_ev) (void)hipEventDestroy(stat_ev); }
+    PeelSession *peel = nullptr;                           // an open greedy-initialisation session (cnmfe_peel_open)
+    ~Patch() { delete peel; if (stat_host) (void)hipHostFree(stat_host); if (stat_ev) (void)hipEventDestroy(stat_ev); }
 };
 
 // device scratch of the OASIS kernels (deconv.hip): pool / task tables, grown on demand and kept with the context
@@ -485,7 +490,12 @@ int postproc_run(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_
 int ensure_ymean(cnmfe_ctx *ctx, Patch *P);
 int sn_video_run(cnmfe_ctx *ctx, Patch *P, int64_t nframes, float *sn_out);
 int seed_images_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, int64_t nframes, const double *Q, int32_t M, float sig,
-                    float *Cn_out, float *PNR_out);   // seed.hpp (deconv.hip)
+                    float *Cn_out, float *PNR_out, PeelSession *keep = nullptr);   // seed.hpp (deconv.hip)
+int peel_open_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, int64_t nframes, const double *Q, int32_t M, float sig,
+                  float *Cn_out, float *PNR_out, float *Sn_out);   // peel.hpp (deconv.hip)
+int peel_extract_run(cnmfe_ctx *ctx, Patch *P, int r, int c, int gSiz, double *corr_box, double *ai_box, double *ci_out, double *stats);
+int peel_apply_run(cnmfe_ctx *ctx, Patch *P, int r, int c, int gSiz, const double *ai_box, const double *Hai_box2, const double *ci, double sig, double min_pnr,
+                   double min_corr, float *PNR_box2, float *Cn_box2);
 int spatial_fetch(cnmfe_ctx *ctx, float *A_out, int64_t nnz);
 int spatial_fetch_connected(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *IND_colptr, const int32_t *IND_rowidx, float *A_out, uint8_t *keep, bool wait = true);
 int ring_first_run(cnmfe_ctx *ctx, Patch *P, bool *first);

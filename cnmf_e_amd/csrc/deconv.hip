@@ -1032,6 +1032,7 @@ int sn_video_run(cnmfe_ctx *ctx, Patch *P, int64_t nframes, float *sn_out) {
 
 }  // namespace cnmfe
 #include "seed.hpp"       // (f) seed images: Cn and PNR of the spatially filtered block (its noise is get_sn above)
+#include "peel.hpp"       // (g) greedy initialisation: the peel-off session over those images (its kernels need get_sn, select_pair and seed.hpp's)
 namespace cnmfe {
 
 // ---- host side -------------------------------------------------------------------------------------------

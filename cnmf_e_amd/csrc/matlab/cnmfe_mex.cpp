@@ -46,6 +46,12 @@
 // Seed images (correlation_pnr_parallel.m:70-104 per patch):
 //   [Cn_block, PNR_block] = cnmfe_mex('seed_images', h, pid, psf, nframes, Q)   psf: odd n x n (or []), Q: nframes x M orthonormal detrend basis (or [] / omitted);
 //                                                                          nr_b x nc_b double images of the block (its size is remembered from 'patch')
+// Greedy initialisation, a peel session per patch (greedyROI_endoscope.m:119-145, 287-311, 378-402; the search loop is the host's):
+//   [Cn_block, PNR_block, Sn_block] = cnmfe_mex('peel_open', h, pid, psf, nframes, Q)          the arguments and images of 'seed_images' (+ GetSn of the filtered traces)
+//   [corr, ai, ci, stats] = cnmfe_mex('peel_extract', h, pid, r, c, gSiz)                       (r, c): the seed, 1-BASED in the block; corr, ai: the clipped
+//                                                                          (2 gSiz + 1)^2 box; ci: 1 x nframes; stats: [max(diff(y0)) std(diff(y0)) norm(ci) GetSn(ci) n_hi n_lo]
+//   [PNR_box2, Cn_box2] = cnmfe_mex('peel_apply', h, pid, r, c, gSiz, ai, Hai, ci, sig, min_pnr, min_corr)   Hai: the clipped (4 gSiz + 1)^2 box
+//   cnmfe_mex('peel_close', h, pid)
 #include "mex.h"
 #include "matrix.h"
 #include <string.h>
@@ -64,7 +70,7 @@ typedef struct { float *pinned; size_t K, T; } StitchOut;
 static StitchOut g_stitch[MAX_CTX];
 // block sizes by (context, patch id), noted by 'patch': what 'seed_images' shapes its outputs with
 #define MAX_DIMS 4096
-typedef struct { cnmfe_ctx *c; int pid; int32_t nr_b, nc_b; } BlockDims;
+typedef struct { cnmfe_ctx *c; int pid; int32_t nr_b, nc_b; int64_t peel_n; } BlockDims;   // peel_n: frames of the open peel session ('peel_open')
 static BlockDims g_dims[MAX_DIMS];
 static int g_ndims = 0;
 static void at_exit(void) {
@@ -311,7 +317,7 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
         while (slot < g_ndims && !(g_dims[slot].c == c && g_dims[slot].pid == pid)) ++slot;
         if (slot >= MAX_DIMS) FAIL("patch: this gateway keeps the block sizes of at most %d patches", MAX_DIMS);
         CHECK(cnmfe_patch_create(c, pid, pr, br, (int32_t)mxGetScalar(pin[5]), (int32_t)mxGetScalar(pin[6]), (int64_t)mxGetScalar(pin[7])));
-        g_dims[slot].c = c; g_dims[slot].pid = pid; g_dims[slot].nr_b = br[1] - br[0] + 1; g_dims[slot].nc_b = br[3] - br[2] + 1;
+        g_dims[slot].c = c; g_dims[slot].pid = pid; g_dims[slot].nr_b = br[1] - br[0] + 1; g_dims[slot].nc_b = br[3] - br[2] + 1; g_dims[slot].peel_n = 0;
         if (slot == g_ndims) ++g_ndims;
     } else if (!strcmp(cmd, "upload")) {
         if (nin != 5) FAIL("upload: 5 inputs required");
@@ -470,6 +476,66 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
         CHECK(cnmfe_seed_images(c, pid, psf, pn, 0, nf, Q, M, 3.0f, cn, pnr));
         pout[0] = to_double(cn, nrb, ncb);
         if (nout > 1) pout[1] = to_double(pnr, nrb, ncb);
+    } else if (!strcmp(cmd, "peel_open") || !strcmp(cmd, "peel_extract") || !strcmp(cmd, "peel_apply") || !strcmp(cmd, "peel_close")) {
+        int slot = 0;
+        while (slot < g_ndims && !(g_dims[slot].c == c && g_dims[slot].pid == pid)) ++slot;
+        if (slot == g_ndims) FAIL("%s: patch %d was not created through this gateway", cmd, pid);
+        const int nrb = g_dims[slot].nr_b, ncb = g_dims[slot].nc_b;
+        if (!strcmp(cmd, "peel_open")) {                       // [Cn_block, PNR_block, Sn_block] = cnmfe_mex('peel_open', h, pid, psf, nframes, Q)
+            if (nin != 5 && nin != 6) FAIL("peel_open: 5 or 6 inputs required");
+            const mxArray *F = pin[3];
+            if (!mxIsEmpty(F) && mxGetM(F) != mxGetN(F)) FAIL("peel_open: psf must be square");
+            const int32_t pn = mxIsEmpty(F) ? 0 : (int32_t)mxGetM(F);
+            const float *psf = pn ? f32_of(F, NULL) : NULL;
+            const int64_t nf = (int64_t)mxGetScalar(pin[4]);
+            const double *Q = NULL; int32_t M = 0;
+            if (nin == 6 && !mxIsEmpty(pin[5])) {
+                if (!mxIsDouble(pin[5]) || mxIsSparse(pin[5]) || (int64_t)mxGetM(pin[5]) != nf) FAIL("peel_open: Q must be a full double nframes x M matrix");
+                Q = mxGetPr(pin[5]); M = (int32_t)mxGetN(pin[5]);
+            }
+            const size_t db = (size_t)nrb * (size_t)ncb;
+            float *cn = (float *)mxMalloc((db + 1) * sizeof(float)), *pnr = (float *)mxMalloc((db + 1) * sizeof(float)), *sn = (float *)mxMalloc((db + 1) * sizeof(float));
+            CHECK(cnmfe_peel_open(c, pid, psf, pn, 0, nf, Q, M, 3.0f, cn, pnr, sn));
+            g_dims[slot].peel_n = nf;
+            pout[0] = to_double(cn, (size_t)nrb, (size_t)ncb);
+            if (nout > 1) pout[1] = to_double(pnr, (size_t)nrb, (size_t)ncb);
+            if (nout > 2) pout[2] = to_double(sn, (size_t)nrb, (size_t)ncb);
+        } else if (!strcmp(cmd, "peel_close")) {               // cnmfe_mex('peel_close', h, pid)
+            if (nin != 3) FAIL("peel_close: 3 inputs required");
+            CHECK(cnmfe_peel_close(c, pid));
+            g_dims[slot].peel_n = 0;
+        } else {
+            if (nin < 6) FAIL("%s: the seed (r, c) and gSiz are required", cmd);
+            const int r = (int)mxGetScalar(pin[3]) - 1, cc = (int)mxGetScalar(pin[4]) - 1, g = (int)mxGetScalar(pin[5]);
+            const int64_t nf = g_dims[slot].peel_n;
+            if (nf <= 0) FAIL("%s: patch %d has no open peel session ('peel_open')", cmd, pid);
+            if (r < 0 || r >= nrb || cc < 0 || cc >= ncb || g < 1) FAIL("%s: the seed (%d, %d) lies outside the %d x %d block, or gSiz = %d", cmd, r + 1, cc + 1, nrb, ncb, g);
+#define PEEL_LO(x, reach) ((x) - (reach) < 0 ? 0 : (x) - (reach))
+#define PEEL_HI(x, reach, n) ((x) + (reach) > (n) - 1 ? (n) - 1 : (x) + (reach))
+            const size_t nr1 = (size_t)(PEEL_HI(r, g, nrb) - PEEL_LO(r, g) + 1), nc1 = (size_t)(PEEL_HI(cc, g, ncb) - PEEL_LO(cc, g) + 1);
+            const size_t nr2 = (size_t)(PEEL_HI(r, 2 * g, nrb) - PEEL_LO(r, 2 * g) + 1), nc2 = (size_t)(PEEL_HI(cc, 2 * g, ncb) - PEEL_LO(cc, 2 * g) + 1);
+            if (!strcmp(cmd, "peel_extract")) {                // [corr, ai, ci, stats] = cnmfe_mex('peel_extract', h, pid, r, c, gSiz)   extract_ac.m:19-58
+                if (nin != 6) FAIL("peel_extract: 6 inputs required");
+                mxArray *corr = mxCreateDoubleMatrix(nr1, nc1, mxREAL), *ai = mxCreateDoubleMatrix(nr1, nc1, mxREAL);
+                mxArray *ci = mxCreateDoubleMatrix(1, (size_t)nf, mxREAL), *st = mxCreateDoubleMatrix(1, 6, mxREAL);
+                CHECK(cnmfe_peel_extract(c, pid, r, cc, g, mxGetPr(corr), mxGetPr(ai), mxGetPr(ci), mxGetPr(st)));
+                pout[0] = corr;
+                if (nout > 1) pout[1] = ai; else mxDestroyArray(ai);
+                if (nout > 2) pout[2] = ci; else mxDestroyArray(ci);
+                if (nout > 3) pout[3] = st; else mxDestroyArray(st);
+            } else {                                           // [PNR_box2, Cn_box2] = cnmfe_mex('peel_apply', h, pid, r, c, gSiz, ai, Hai, ci, sig, min_pnr, min_corr)
+                if (nin != 12) FAIL("peel_apply: 12 inputs required");
+                for (int k = 6; k < 9; ++k) if (!mxIsDouble(pin[k]) || mxIsSparse(pin[k])) FAIL("peel_apply: ai, Hai and ci must be full double arrays");
+                if (mxGetNumberOfElements(pin[6]) != nr1 * nc1 || mxGetNumberOfElements(pin[7]) != nr2 * nc2 || (int64_t)mxGetNumberOfElements(pin[8]) != nf)
+                    FAIL("peel_apply: ai must have %d, Hai %d and ci %d elements", (int)(nr1 * nc1), (int)(nr2 * nc2), (int)nf);
+                float *pnr = (float *)mxMalloc((nr2 * nc2 + 1) * sizeof(float)), *cn = (float *)mxMalloc((nr2 * nc2 + 1) * sizeof(float));
+                CHECK(cnmfe_peel_apply(c, pid, r, cc, g, mxGetPr(pin[6]), mxGetPr(pin[7]), mxGetPr(pin[8]), mxGetScalar(pin[9]), mxGetScalar(pin[10]), mxGetScalar(pin[11]), pnr, cn));
+                pout[0] = to_double(pnr, nr2, nc2);
+                if (nout > 1) pout[1] = to_double(cn, nr2, nc2);
+            }
+#undef PEEL_LO
+#undef PEEL_HI
+        }
     } else if (!strcmp(cmd, "background_ssub")) {              // cnmfe_mex('background_ssub', h, pid, fit_pid, bg_ssub, A_prev_block, C_or_rows, b0_block)
         if (nin != 8) FAIL("background_ssub: 8 inputs required");
         Csc A = csc_of(pin[5]);

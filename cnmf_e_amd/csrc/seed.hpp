@@ -67,7 +67,7 @@ __device__ __forceinline__ float seed_block_max(float v, double *red) {
 // One workgroup per block pixel, the LDS layout of k_sn_video: the filtered trace of frames [0, n) | the Welch transform.  Only t < n is ever read: the padding
 // frames of the last quad enter nothing.
 __global__ void __launch_bounds__(256) k_seed_stats(DeconvCfg c, const float4 *__restrict__ hy4, int64_t d_b, const double *__restrict__ Q, int M, double sig,
-                                                    double *__restrict__ rec, float *__restrict__ pnr) {
+                                                    double *__restrict__ rec, float *__restrict__ pnr, double *__restrict__ sn_keep) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ double red[4];
     const int64_t p = blockIdx.x;
@@ -110,6 +110,7 @@ __global__ void __launch_bounds__(256) k_seed_stats(DeconvCfg c, const float4 *_
     if (tid == 0) {
         orec[0] = thr; orec[1] = mean; orec[2] = rms == 0.0 ? 1.0 : 1.0 / rms; orec[3] = (double)med;
         pnr[p] = (float)((double)mx / sn);                   // :88
+        if (sn_keep) sn_keep[p] = sn;                        // (a peel session keeps Ysig, greedyROI_endoscope.m:132)
     }
 }
 
@@ -180,8 +181,26 @@ __global__ void __launch_bounds__(256) k_seed_cn(const double *__restrict__ part
     cn[p] = (float)(s / (double)n / (double)cnt);
 }
 
+// HY as greedyROI_endoscope.m:130 holds it, in place; the padding frames of the last quad become 0
+__global__ void __launch_bounds__(256) k_peel_hy_final(float4 *__restrict__ hy4, int64_t d_b, int n, const double *__restrict__ Q, int M,
+                                                       const double *__restrict__ rec) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= d_b) return;
+    const int q = (int)blockIdx.y;
+    const double *o = rec + p * (int64_t)(SEED_REC + M);
+    const float med = (float)o[3];
+    const float4 v4 = hy4[(int64_t)q * d_b + p];
+    float v[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int t = 4 * q + j;
+        v[j] = t < n ? (M > 0 ? seed_detrend(v[j], o + SEED_REC, Q + t, n, M) : v[j]) - med : 0.f;
+    }
+    hy4[(int64_t)q * d_b + p] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
 int seed_images_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, int64_t nframes, const double *Q, int32_t M, float sig,
-                    float *Cn_out, float *PNR_out) {
+                    float *Cn_out, float *PNR_out, PeelSession *keep) {
     const int64_t n = nframes, d_b = P->d_b;
     const int nr_b = P->nr_b, nc_b = P->nc_b;
     const int64_t nq = (n + 3) / 4;
@@ -194,7 +213,9 @@ int seed_images_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, i
     if (sh_stats > 160 * 1024 - 256) return fail(CNMFE_EUNSUPPORTED, "%lld frames do not fit the seed statistics kernel's LDS (trace + Welch transform in 160 KB: <= 20400)", (long long)n);
     // everything the call allocates lives in these two and is released when it returns (seeding runs once per recording, the fits want the room): the filtered
     // block, and ONE allocation for all the small arrays -- every hipFree drains the device, and a patched run makes this call once per patch
-    DevBuf hy, small;
+    // (a peel session -- peel.hpp -- keeps the filtered block and the noise levels: `keep`)
+    DevBuf hy_call, small;
+    DevBuf &hy = keep ? keep->hy : hy_call;
     const int ntr = (nr_b + SEED_TILE - 1) / SEED_TILE, ntc = (nc_b + SEED_TILE - 1) / SEED_TILE;
     const int ntile = ntr * ntc;
     const bool filt = psf && psf_n > 0;
@@ -235,11 +256,16 @@ int seed_images_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, i
         hy4 = hy.as<float4>();
     }
     if (sh_stats > 64 * 1024) CK(hipFuncSetAttribute((const void *)k_seed_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_stats));
-    LAUNCH(ctx, "seed_stats", k_seed_stats, dim3((unsigned)d_b), dim3(256), sh_stats, c, hy4, d_b, dQ, (int)M, (double)sig, dRec, dPnr);
+    LAUNCH(ctx, "seed_stats", k_seed_stats, dim3((unsigned)d_b), dim3(256), sh_stats, c, hy4, d_b, dQ, (int)M, (double)sig, dRec, dPnr,
+           keep ? keep->sn.as<double>() : (double *)nullptr);
     const size_t sh_corr = ((size_t)4 * SEED_HN + (size_t)SEED_HN * recw) * sizeof(double);
     LAUNCH(ctx, "seed_corr", k_seed_corr, dim3((unsigned)ntile, (unsigned)nsplit), dim3(256), sh_corr, hy4, d_b, nr_b, nc_b, ntr, (int)n, qchunk,
            dQ, (int)M, dRec, dPart);
     LAUNCH(ctx, "seed_cn", k_seed_cn, dim3((unsigned)((d_b + 255) / 256)), dim3(256), 0, dPart, d_b, nr_b, nc_b, nsplit, (int)n, dCn);
+    if (keep) {                                                              // HY of greedyROI_endoscope.m:130 in place, by the arithmetic of the two kernels above
+        if (!filt) CK(hipMemcpyAsync(hy.p, P->Yc4.p, (size_t)nq * (size_t)d_b * sizeof(float4), hipMemcpyDeviceToDevice, ctx->st()));
+        LAUNCH(ctx, "peel_hy_final", k_peel_hy_final, dim3((unsigned)((d_b + 255) / 256), (unsigned)nq), dim3(256), 0, hy.as<float4>(), d_b, (int)n, dQ, (int)M, dRec);
+    }
     CK(hipMemcpyAsync(Cn_out, dCn, (size_t)d_b * sizeof(float), hipMemcpyDeviceToHost, ctx->st()));
     CK(hipMemcpyAsync(PNR_out, dPnr, (size_t)d_b * sizeof(float), hipMemcpyDeviceToHost, ctx->st()));
     CK(hipStreamSynchronize(ctx->st()));

@@ -243,6 +243,7 @@ class Engine:
             raise L.CnmfeError("cnmfe_create failed: " + L.lib.cnmfe_last_error().decode())
         self.device = device
         self._patch = {}
+        self._peel = {}                     # patch id -> frames of its open peel session
 
     def close(self):
         if getattr(self, "_ctx", None):
@@ -356,6 +357,77 @@ class Engine:
         L.check(L.lib.cnmfe_seed_images(self._ctx, pid, _p(psf_a, L.f32p), psf_n, int(frame0), n, _p(Q_a, L.f64p), M, float(sig),
                                         _p(Cn, L.f32p), _p(PNR, L.f32p)))
         return Cn, PNR
+
+    # ---- greedy initialisation: a peel session per patch (cnmfe_peel_* in include/cnmfe.h) ----
+    def _seed_args(self, pid, psf, nframes, Q):
+        info = self._patch[pid]
+        n = info["T"] if nframes is None else int(nframes)
+        psf_a, psf_n = None, 0
+        if psf is not None and np.size(psf):
+            psf = np.asarray(psf, dtype=np.float32)
+            if psf.ndim != 2 or psf.shape[0] != psf.shape[1]:
+                raise ValueError("psf must be square, got %s" % (psf.shape,))
+            psf_n = int(psf.shape[0])
+            psf_a = np.ascontiguousarray(psf.T)                            # column-major
+        Q_a, M = None, 0
+        if Q is not None and np.size(Q):
+            Q = np.asarray(Q, dtype=np.float64)
+            if Q.ndim != 2 or Q.shape[0] != n:
+                raise ValueError("Q must be (%d, M), got %s" % (n, Q.shape))
+            M = int(Q.shape[1])
+            Q_a = np.ascontiguousarray(Q.T)                                # column-major
+        return info, n, psf_a, psf_n, Q_a, M
+
+    @staticmethod
+    def peel_box(nr_b, nc_b, r, c, reach):
+        """(r0, r1, c0, c1), 0-based half-open, of the box of `reach` around the 0-based block pixel (r, c) (greedyROI_endoscope.m:299-300,310-311)"""
+        return max(0, r - reach), min(nr_b, r + reach + 1), max(0, c - reach), min(nc_b, c + reach + 1)
+
+    def peel_open(self, pid, psf, nframes=None, Q=None, sig=3.0, frame0=0):
+        """open the peel session of a patch: (Cn, PNR, Sn) of its block as seed_images gives them (+ GetSn of the filtered traces), d_b float32 each"""
+        info, n, psf_a, psf_n, Q_a, M = self._seed_args(pid, psf, nframes, Q)
+        Cn = np.empty(info["d_b"], dtype=np.float32); PNR = np.empty(info["d_b"], dtype=np.float32); Sn = np.empty(info["d_b"], dtype=np.float32)
+        L.check(L.lib.cnmfe_peel_open(self._ctx, pid, _p(psf_a, L.f32p), psf_n, int(frame0), n, _p(Q_a, L.f64p), M, float(sig),
+                                      _p(Cn, L.f32p), _p(PNR, L.f32p), _p(Sn, L.f32p)))
+        self._peel[pid] = n
+        return Cn, PNR, Sn
+
+    def peel_extract(self, pid, r, c, gSiz):
+        """extract_ac.m:19-58 around the 0-based block pixel (r, c): (corr, ai) as nr x nc float64 images of the box, ci (nframes float64), stats = dict of
+        max_diff, std_diff (greedyROI_endoscope.m:287-293), norm_ci, sn_ci (GetSn(ci)), n_hi, n_lo (the sizes of {corr > 0.9}, {corr < 0.3})"""
+        info = self._patch[pid]
+        nr_b, nc_b = info["nr_b"], info["nc_b"]
+        r0, r1, c0, c1 = self.peel_box(nr_b, nc_b, int(r), int(c), int(gSiz))
+        npix = max(r1 - r0, 0) * max(c1 - c0, 0)
+        n = self._peel.get(pid, info["T"])
+        corr = np.empty(max(npix, 1), dtype=np.float64); ai = np.empty(max(npix, 1), dtype=np.float64)
+        ci = np.empty(n, dtype=np.float64); st = np.empty(6, dtype=np.float64)
+        L.check(L.lib.cnmfe_peel_extract(self._ctx, pid, int(r), int(c), int(gSiz), _p(corr, L.f64p), _p(ai, L.f64p), _p(ci, L.f64p), _p(st, L.f64p)))
+        sh = (r1 - r0, c1 - c0)
+        stats = dict(max_diff=st[0], std_diff=st[1], norm_ci=st[2], sn_ci=st[3], n_hi=int(st[4]), n_lo=int(st[5]))
+        return corr[:npix].reshape(sh, order="F"), ai[:npix].reshape(sh, order="F"), ci, stats
+
+    def peel_apply(self, pid, r, c, gSiz, ai_box, Hai_box2, ci, sig, min_pnr, min_corr):
+        """greedyROI_endoscope.m:378-402: subtract ai ci from the working video and Hai ci from HY, return (PNR, Cn) of the (4 gSiz + 1)^2 box as float32 images"""
+        info = self._patch[pid]
+        nr_b, nc_b = info["nr_b"], info["nc_b"]
+        r0, r1, c0, c1 = self.peel_box(nr_b, nc_b, int(r), int(c), int(gSiz))
+        s0, s1, t0, t1 = self.peel_box(nr_b, nc_b, int(r), int(c), 2 * int(gSiz))
+        ai = np.ascontiguousarray(np.asarray(ai_box, dtype=np.float64).reshape(-1, order="F"))
+        hai = np.ascontiguousarray(np.asarray(Hai_box2, dtype=np.float64).reshape(-1, order="F"))
+        ci = np.ascontiguousarray(ci, dtype=np.float64)
+        n = self._peel.get(pid, info["T"])
+        if ai.size != (r1 - r0) * (c1 - c0) or hai.size != (s1 - s0) * (t1 - t0) or ci.size != n:
+            raise ValueError("peel_apply: ai %d, Hai %d, ci %d do not match the boxes %d, %d and %d frames" % (ai.size, hai.size, ci.size, (r1 - r0) * (c1 - c0), (s1 - s0) * (t1 - t0), n))
+        pnr = np.empty(max(hai.size, 1), dtype=np.float32); cn = np.empty(max(hai.size, 1), dtype=np.float32)
+        L.check(L.lib.cnmfe_peel_apply(self._ctx, pid, int(r), int(c), int(gSiz), _p(ai, L.f64p), _p(hai, L.f64p), _p(ci, L.f64p), float(sig), float(min_pnr),
+                                       float(min_corr), _p(pnr, L.f32p), _p(cn, L.f32p)))
+        sh = (s1 - s0, t1 - t0)
+        return pnr[:hai.size].reshape(sh, order="F"), cn[:hai.size].reshape(sh, order="F")
+
+    def peel_close(self, pid):
+        self._peel.pop(pid, None)
+        L.check(L.lib.cnmfe_peel_close(self._ctx, pid))
 
     def set_noise(self, pid, sn_block):
         """sn of the block pixels (update_background_parallel.m:131,137); read by the outlier branch of fit_ring_model only"""

@@ -136,3 +136,235 @@ def circular_constraints_columns(A, d1, d2):
     out = sp.csc_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=A.shape)
     out.sort_indices()
     return out
+
+
+# --------------------------------------------------------------------------------------
+# greedy initialisation (Sources2D.initComponents_parallel): the work on single block images and single traces around the device's peel session
+#   endoscope/greedyROI_endoscope.m:62-164,193-216,262-311,339-410,447-463   the search loop
+#   endoscope/extract_ac.m:60-107                                             constraints, minimum size, baseline
+#   endoscope/connectivity_constraint.m, endoscope/remove_baseline.m, OASIS_matlab/functions/estimate_baseline_noise.m, fit_gauss1.m
+# Everything is float64.  Toolbox rules used: ordfilt2 pads with zeros and centres an even domain at floor((n + 1) / 2); quantile places the sorted samples at
+# the probabilities (i - 0.5) / n and interpolates linearly, clamped to the extremes; hist(y, centres) counts between the mid-points of the centres with open
+# outer bins (a value on a mid-point goes to the lower bin); imopen erodes with +Inf and dilates with -Inf outside the image.
+# --------------------------------------------------------------------------------------
+def matlab_quantile(x, p):
+    x = np.sort(np.asarray(x, dtype=np.float64).ravel())
+    n = x.size
+    pos = np.clip(np.asarray(p, dtype=np.float64) * n + 0.5, 1.0, float(n))   # 1-based position among the sorted samples
+    lo = np.floor(pos).astype(np.int64)
+    hi = np.minimum(lo + 1, n)
+    return x[lo - 1] + (pos - lo) * (x[hi - 1] - x[lo - 1])
+
+
+def hist_centres(y, centres):
+    """nums = hist(y, centres)"""
+    centres = np.asarray(centres, dtype=np.float64)
+    mids = 0.5 * (centres[:-1] + centres[1:])
+    return np.bincount(np.searchsorted(mids, np.asarray(y, dtype=np.float64).ravel(), side="left"), minlength=centres.size).astype(np.float64)
+
+
+def fit_gauss1(x, y, thr=0.1, maxIter=5, mu_fix=False):
+    """[mu, sig, A] = fit_gauss1(x, y, thr, maxIter, mu_fix) (fit_gauss1.m:21-87): iteratively re-weighted least squares on log y = p0 + p1 x + p2 x^2
+    over the points above thr * max(y) (Guo 2011)"""
+    x = np.asarray(x, dtype=np.float64).ravel(); y = np.asarray(y, dtype=np.float64).ravel()
+    ind = y > y.max() * thr                                                # :35
+    x = x[ind]; y = y[ind]
+    x2 = x * x; x3 = x2 * x; x4 = x2 * x2
+    y2 = y * y; logy = np.log(y); y2logy = y2 * logy
+    with np.errstate(all="ignore"):
+        for _ in range(int(maxIter)):
+            if mu_fix:                                                     # :50-64
+                M = np.array([[y2.sum(), x2 @ y2], [x2 @ y2, x4 @ y2]])
+                b = np.array([y2logy.sum(), x2 @ y2logy])
+            else:                                                          # :66-77
+                M = np.array([[y2.sum(), x @ y2, x2 @ y2], [x @ y2, x2 @ y2, x3 @ y2], [x2 @ y2, x3 @ y2, x4 @ y2]])
+                b = np.array([y2logy.sum(), x @ y2logy, x2 @ y2logy])
+            try:
+                p = np.linalg.solve(M, b)
+            except np.linalg.LinAlgError:
+                p = np.full(b.size, np.nan)
+            logy = p[0] + p[1] * x2 if mu_fix else p[0] + p[1] * x + p[2] * x2
+            y = np.exp(logy); y2 = y * y; y2logy = y2 * logy
+        if mu_fix:
+            return 0.0, float(np.sqrt(-0.5 / p[1])), float(np.exp(p[0]))
+        return float(-p[1] / 2 / p[2]), float(abs(np.sqrt(-0.5 / p[2] + 0j))), float(np.exp(p[0] - 0.25 * p[1] ** 2 / p[2]))
+
+
+def estimate_baseline_noise(y, bmin=-np.inf):
+    """[b, sn] = estimate_baseline_noise(y, bmin) (estimate_baseline_noise.m:18-35): a Gaussian fitted to the histogram of the trace around its mode"""
+    y = np.asarray(y, dtype=np.float64).ravel()
+    temp = matlab_quantile(y, np.arange(11) / 10.0)                        # :18
+    dbin = max(np.diff(temp).min() / 3.0, (temp.max() - temp.min()) / 1000.0)   # :19
+    if not dbin > 0:                                                       # :24-28 (an empty colon range)
+        return float(y.mean()), 0.0
+    bins = temp[0] + dbin * np.arange(int(np.floor((temp[-1] - temp[0]) / dbin + 1e-10)) + 1)   # :20
+    nums = hist_centres(y, bins)                                           # :21
+    b, sn, _ = fit_gauss1(bins, nums, 0.3, 3)                              # :29
+    if b < bmin:                                                           # :31-34
+        b = bmin
+        sn = fit_gauss1(bins - bmin, nums, 0.3, 3, True)[1]
+    return b, sn
+
+
+def remove_baseline(y, sn):
+    """[y, b] = remove_baseline(y, sn) (remove_baseline.m:6-10)"""
+    y = np.asarray(y, dtype=np.float64).ravel()
+    y_diff = np.r_[-1.0, np.diff(y)]
+    sel = y[(y_diff >= 0) & (y_diff < sn)]
+    b = np.median(sel) if sel.size else np.nan
+    return y - b, b
+
+
+def ordfilt2_max(v, n):
+    """ordfilt2(v, n^2, true(n)): the maximum of the n x n neighbourhood, zeros outside the image, an even n centred at floor((n + 1) / 2)"""
+    v = np.asarray(v, dtype=np.float64)
+    c0 = (n + 1) // 2 - 1
+    vp = np.pad(v, ((c0, n - 1 - c0), (c0, n - 1 - c0)))
+    out = np.full(v.shape, -np.inf)
+    for i in range(n):
+        for j in range(n):
+            np.maximum(out, vp[i:i + v.shape[0], j:j + v.shape[1]], out=out)
+    return out
+
+
+def connectivity_constraint(img, thr=0.01, sz=5):
+    """img = connectivity_constraint(img) (connectivity_constraint.m:12-18) of one small image: open with a sz x sz square, threshold at thr * max(img), keep
+    the 4-connected component that holds the maximum of img"""
+    img = np.array(img, dtype=np.float64)
+    ind_max = int(np.argmax(img.reshape(-1, order="F")))
+    er = ndi.minimum_filter(img, size=sz, mode="constant", cval=np.inf)
+    ai_open = ndi.maximum_filter(er, size=sz, mode="constant", cval=-np.inf)
+    lab, _ = ndi.label(ai_open > img.max() * thr, structure=CROSS4)
+    img[lab != lab[ind_max % img.shape[0], ind_max // img.shape[0]]] = 0
+    return img
+
+
+def imfilter_replicate(img, psf):
+    """imfilter(img, psf, 'replicate') of one image: correlation about the origin floor((n + 1) / 2) of the kernel"""
+    img = np.asarray(img, dtype=np.float64); psf = np.asarray(psf, dtype=np.float64)
+    n0, n1 = psf.shape
+    cr, cc = (n0 + 1) // 2 - 1, (n1 + 1) // 2 - 1
+    ip = np.pad(img, ((cr, n0 - 1 - cr), (cc, n1 - 1 - cc)), mode="edge")
+    out = np.zeros_like(img)
+    for i, j in zip(*np.nonzero(psf)):
+        out += psf[i, j] * ip[i:i + img.shape[0], j:j + img.shape[1]]
+    return out
+
+
+def refine_ac(ai_img, ci, sn_ci, connected=True, min_pixels=5):
+    """extract_ac.m:60-107 after the regression: (ai image, ci, success).  sn_ci = GetSn(ci) (:89)."""
+    ai = circular_constraints(ai_img)                                      # :61
+    if connected:
+        ai = connectivity_constraint(ai)                                   # :64-66
+    if np.count_nonzero(ai > 0) < min_pixels:                              # :75-78
+        return ai, ci, False
+    b, sn = estimate_baseline_noise(ci)                                    # :88
+    if sn > sn_ci:                                                         # :90-95
+        ci = remove_baseline(ci, sn_ci)[0]
+    else:
+        ci = ci - b
+    return ai, ci, bool(np.linalg.norm(ai) != 0)                           # :103-107
+
+
+def box_of(nr, nc, r, c, reach):
+    """0-based half-open (r0, r1, c0, c1) of rsub x csub (greedyROI_endoscope.m:299-300,310-311) around the 0-based pixel (r, c)"""
+    return max(0, r - reach), min(nr, r + reach + 1), max(0, c - reach), min(nc, c + reach + 1)
+
+
+def greedy_roi_block(sess, Cn, PNR, gSiz, psf, min_corr, min_pnr, min_pixel, bd, K=None, connected=True, deconv=None, seeds=None, sig=3.0, on_step=None):
+    """[results, center] = greedyROI_endoscope(Y, K, options) (greedyROI_endoscope.m:62-164,193-216,262-311,339-410,447-463) on one block, the video behind
+    `sess`: sess.extract(r, c) -> (corr, ai, ci, stats) and sess.apply(r, c, ai, Hai, ci, sig, min_pnr, min_corr) -> (PNR, Cn) of the (4 gSiz + 1)^2 box,
+    0-based block pixels (Engine.peel_extract / peel_apply).  Cn, PNR: the block's seed images.  bd = the four margins [top, bottom, left, right].
+    deconv(ci_raw) -> (ci, ci_raw - b, si, pars) or None.  seeds: 0-based block pixels tried once, in the given order, under the halved thresholds of
+    seed_method = 'manual' (:66-69); None = the automatic search.  on_step(kind, data): observer of every extract / apply (tests).
+    Returns dict(A = list of ((r0, r1, c0, c1), ai image), C, C_raw, S, kernel_pars, center (k x 2, 1-based block coordinates))."""
+    gSiz = int(gSiz)
+    Cn = np.array(Cn, dtype=np.float64); PNR = np.array(PNR, dtype=np.float64)
+    d1, d2 = Cn.shape
+    min_v_search = min_corr * min_pnr                                      # :64
+    if seeds is not None:                                                  # :66-69
+        min_corr, min_pnr = min_corr / 2.0, min_pnr / 2.0
+    with np.errstate(invalid="ignore"):
+        PNR[PNR < min_pnr] = 0                                             # :135
+        Cn[np.isnan(Cn)] = 0                                               # :147
+        v_search = Cn * PNR                                                # :151
+        v_search[(Cn < min_corr) | (PNR < min_pnr)] = 0                    # :152
+    v_search[~np.isfinite(v_search)] = 0                                   # (a constant pixel, Sn = 0: never a seed; the reference leaves a NaN to medfilt2)
+    ind_search = v_search == 0                                             # :153-154
+    ind_bd = np.zeros((d1, d2), dtype=bool)                                # :160-164
+    bd = [int(b) for b in bd]
+    ind_bd[:bd[0], :] = True
+    if bd[1] > 0: ind_bd[d1 - bd[1]:, :] = True
+    ind_bd[:, :bd[2]] = True
+    if bd[3] > 0: ind_bd[:, d2 - bd[3]:] = True
+    nseed = int(np.count_nonzero(v_search > 0)) // 10                      # :194-198
+    K = nseed if K is None else min(nseed, int(K))
+    jj, ii = np.mgrid[1:d1 + 1, 1:d2 + 1]
+    pixel_v = (ii * 10 + jj) * 1e-10                                       # :209-210
+    tmp_d = max(3, int(np.floor(gSiz / 4.0 + 0.5)))                        # :215
+    out_A, out_C, out_Craw, out_S, out_kp, center = [], [], [], [], [], []
+    k = 0
+    searching = True
+    while searching and K > 0:
+        v_search = medfilt2(v_search) + pixel_v                            # :216
+        v_search[ind_search] = 0                                           # :217
+        v_max = ordfilt2_max(v_search, tmp_d)                              # :218
+        v_search[ind_bd] = 0                                               # :220
+        if seeds is not None:                                              # :243-260: the clicks; an invalid one ends the list
+            loc = []
+            for (r, c) in seeds:
+                if not (0 <= r < d1 and 0 <= c < d2) or v_search[r, c] == 0:
+                    break
+                loc.append((int(r), int(c)))
+            searching = False                                              # (one round: the given pixels are tried once, in the given order)
+        else:
+            ind_search[v_search < min_v_search] = True                     # :263
+            vf, mf = v_search.reshape(-1, order="F"), v_max.reshape(-1, order="F")
+            ind = np.nonzero((vf == mf) & (mf > 0))[0]                     # :264
+            ind = ind[np.argsort(-vf[ind], kind="stable")]                 # :267-268
+            loc = [(int(i % d1), int(i // d1)) for i in ind]
+        if not loc:
+            break
+        for (r, c) in loc:                                                 # :272
+            max_v = v_search[r, c]
+            ind_search[r, c] = True                                        # :280
+            if max_v < min_v_search:                                       # :281-283
+                continue
+            corr, ai0, ci_raw, st = sess.extract(r, c)
+            if on_step is not None:
+                on_step("extract", dict(r=r, c=c, corr=corr, ai=ai0, ci=ci_raw, stats=st))
+            if st["max_diff"] < 3 * st["std_diff"]:                        # :293
+                continue
+            ok = st["n_lo"] > 0 and np.isfinite(st["norm_ci"]) and st["norm_ci"] != 0      # extract_ac.m:29-33; an empty background set: y_bg = NaN
+            if ok:
+                ai, ci_raw, ok = refine_ac(ai0, ci_raw, st["sn_ci"], connected)
+            if ok and (np.isnan(ai).any() or np.isnan(ci_raw).any()):      # :346
+                ok = False
+            if ok and (ai.sum() <= min_pixel or np.count_nonzero(ai > 0) < min_pixel):     # :347,351
+                ok = False
+            if not ok:
+                continue
+            k += 1
+            if deconv is not None:                                         # :355-364
+                ci, ci_keep, si, pars = deconv(ci_raw)
+            else:                                                          # :366-369
+                ci, ci_keep, si, pars = ci_raw, ci_raw, None, None
+            ci = np.asarray(ci, dtype=np.float64)
+            r0, r1, c0, c1 = box_of(d1, d2, r, c, gSiz)
+            s0, s1, t0, t1 = box_of(d1, d2, r, c, 2 * gSiz)
+            out_A.append(((r0, r1, c0, c1), ai)); out_C.append(ci); out_Craw.append(np.asarray(ci_keep, dtype=np.float64)); out_S.append(si); out_kp.append(pars)
+            center.append((r + 1, c + 1))                                  # :372
+            ind_search[r0:r1, c0:c1] |= ai > ai.max() * 0.5                # :375
+            big = np.zeros((s1 - s0, t1 - t0))
+            big[r0 - s0:r1 - s0, c0 - t0:c1 - t0] = ai
+            Hai = imfilter_replicate(big, psf) if psf is not None else big     # :380-384
+            pnr2, cn2 = sess.apply(r, c, ai, Hai, ci, sig, min_pnr, min_corr)  # :378,385-401
+            if on_step is not None:
+                on_step("apply", dict(r=r, c=c, ai=ai, ci=ci, Hai=Hai, pnr=pnr2, cn=cn2))
+            PNR[s0:s1, t0:t1] = pnr2; Cn[s0:s1, t0:t1] = cn2               # :394,402
+            v_search[s0:s1, t0:t1] = Cn[s0:s1, t0:t1] * PNR[s0:s1, t0:t1]  # :405
+            v_search[ind_bd] = 0; v_search[ind_search] = 0                 # :406-407
+            if k == K:                                                     # :447-450
+                searching = False
+                break
+    return dict(A=out_A, C=out_C, C_raw=out_Craw, S=out_S, kernel_pars=out_kp, center=np.asarray(center, dtype=np.int64).reshape(-1, 2))

@@ -66,6 +66,13 @@ class Options:
     detrend_method: str = "spline"   # 'spline' | 'local_min' (only 'spline' is built)
     ssub: int = 1                    # spatial / temporal downsampling of the initialisation (only 1 is built)
     tsub: int = 1
+    # the greedy initialisation (initComponents_parallel): CNMFSetParms.m names at :19,97-100, their defaults at :209,286-289
+    min_corr: float = 0.3            # :19 / :209   minimum local correlation of a seed pixel
+    min_pnr: float = 10.0            # :97 / :286   minimum peak-to-noise ratio of a seed pixel
+    seed_method: str = "auto"        # :98 / :287   'auto' | 'manual' (manual = the `seeds` argument of initComponents_parallel)
+    min_pixel: float = 5.0           # :99 / :288   minimum number of non-zero pixels of a neuron
+    bd: int | None = 3               # :100 / :289  margin of the FOV without seed pixels; None = [] -> gSiz (initComponents_parallel.m:200-203)
+    K: int | None = None             # maximum number of neurons per patch (initComponents_parallel's argument; None = [] -> as many as are found)
 
 
 def _mround(x):
@@ -686,6 +693,19 @@ _LazyRow.__hash__ = object.__hash__
 _UNSET = object()
 
 
+class _PeelSession:
+    """the device's peel session of one patch as hostops.greedy_roi_block sees it"""
+    def __init__(self, engine, pid, gSiz):
+        self.engine, self.pid, self.gSiz = engine, pid, gSiz
+
+    def extract(self, r, c):
+        return self.engine.peel_extract(self.pid, r, c, self.gSiz)
+
+    def apply(self, r, c, ai, Hai, ci, sig, min_pnr, min_corr):
+        pnr, cn = self.engine.peel_apply(self.pid, r, c, self.gSiz, ai, Hai, ci, sig, min_pnr, min_corr)
+        return pnr.astype(np.float64), cn.astype(np.float64)
+
+
 class Sources2D:
     """State and the three update methods of the reference's handle class (Sources2D.m:10-57):
     A (d x K sparse), A_prev, C, C_prev, C_raw (K x T), W{.}/b0{.} (resident on the GPU per patch,
@@ -903,6 +923,122 @@ class Sources2D:
             PNR[v.patch_pix[idx]] = pnr_b[v.ind_patch[idx]]
         both = self._allreduce(np.stack([Cn, PNR]))
         return both[0].reshape(v.d1, v.d2, order="F"), both[1].reshape(v.d1, v.d2, order="F")
+
+    def initComponents_parallel(self, K=None, frame_range=None, seeds=None, use_prev=False, save_avi=False, debug_on=False):
+        """[center, Cn, PNR] = obj.initComponents_parallel(K, frame_range, save_avi, use_parallel, use_prev)  (@Sources2D/initComponents_parallel.m:200-203,
+        308-352,410-484 -> endoscope/greedyROI_endoscope.m): the greedy initialisation of every owned patch on the device's peel session of its block
+        (Engine.peel_open / peel_extract / peel_apply), the search loop and the single-image / single-trace work on the host in float64
+        (hostops.greedy_roi_block).  Sets A, C, C_raw, S, P.kernel_pars (deconv_flag), Cn, ids, tags, P.Ymean and returns (center, Cn, PNR) in FOV coordinates
+        (1-based).  K: the maximum number of neurons PER PATCH (None: options.K).  frame_range = (1, n).
+        seeds: a list of 1-based FOV pixels (r, c), the counterpart of seed_method = 'manual': min_corr and min_pnr are halved (:66-69), and every patch tries
+        the given pixels of its block ONCE, in the given order -- the one deviation: the reference asks for another round of clicks until none is valid.
+        Not built (NotImplementedError): ssub / tsub other than 1, detrend_method 'local_min', a frame range that does not start at 1, use_prev, save_avi /
+        debug_on."""
+        from . import hostops
+        self._need_data()
+        v, o = self.video, self.options
+        if int(o.ssub) != 1 or int(o.tsub) != 1:
+            raise NotImplementedError("initComponents_parallel: ssub / tsub other than 1 are not built")
+        nk = int(o.nk)
+        if str(o.detrend_method).lower() != "spline":
+            raise NotImplementedError("initComponents_parallel: detrend_method %r is not built (only 'spline')" % (o.detrend_method,))
+        if use_prev:
+            raise NotImplementedError("initComponents_parallel: use_prev is not built")
+        if save_avi or debug_on:
+            raise NotImplementedError("initComponents_parallel: save_avi / debug mode are not built")
+        f0, f1 = (1, v.T) if frame_range is None or len(frame_range) == 0 else (int(frame_range[0]), int(frame_range[1]))
+        f0, f1 = min(max(f0, 1), v.T), min(max(f1, 1), v.T)
+        if f0 != 1:
+            raise NotImplementedError("initComponents_parallel reads the frames from the first one on (frame_range = [%d, %d])" % (f0, f1))
+        if seeds is None and str(o.seed_method).lower() == "manual":
+            raise ValueError("seed_method = 'manual' needs the seed pixels: initComponents_parallel(seeds=[(r, c), ...])")
+        n = f1 - f0 + 1
+        K = o.K if K is None else K
+        gSiz = int(_mround(float(o.gSiz)))
+        bd = gSiz if o.bd is None else int(o.bd)                          # initComponents_parallel.m:200-203
+        psf = seed_psf(float(o.gSig), float(o.gSiz), bool(o.center_psf))
+        Q = np.linalg.qr(bspline_basis(n, nk))[0] if nk > 1 else None
+        connected = bool(o.spatial_constraints.get("connected", True))
+        deconv = None
+        if o.deconv_flag:                                                 # greedyROI_endoscope.m:355-364
+            def deconv(ci_raw):
+                c_, r_, s_, kp_, _sn = self.engine.deconv_temporal(np.asarray(ci_raw, dtype=np.float32)[None, :], o.deconv_options)
+                return c_[0].astype(np.float64), r_[0].astype(np.float64), s_[0].astype(np.float64), float(kp_[0])
+        d = v.d1 * v.d2
+        Cn = np.zeros(d, dtype=np.float64); PNR = np.zeros(d, dtype=np.float64)
+        per_patch = {}
+        observer = getattr(self, "_init_observer", None)                  # tests: called with (patch idx, kind, data) at every extract / apply
+        for idx in v.owned:
+            pid = v.pid[idx]
+            pp, bp = v.patch_pos[idx], v.block_pos[idx]
+            nr_b, nc_b = int(bp[1] - bp[0] + 1), int(bp[3] - bp[2] + 1)
+            cn_b, pnr_b, _sn_b = self.engine.peel_open(pid, psf, n, Q, 3.0)
+            try:
+                Cn[v.patch_pix[idx]] = cn_b[v.ind_patch[idx]]
+                PNR[v.patch_pix[idx]] = pnr_b[v.ind_patch[idx]]
+                bd4 = [bd if int(pp[j]) == int(bp[j]) else 0 for j in range(4)]      # initComponents_parallel.m:318
+                loc = None
+                if seeds is not None:
+                    loc = [(int(r) - int(bp[0]), int(c) - int(bp[2])) for (r, c) in seeds
+                           if int(bp[0]) <= int(r) <= int(bp[1]) and int(bp[2]) <= int(c) <= int(bp[3])]
+                sess = _PeelSession(self.engine, pid, gSiz)
+                res = hostops.greedy_roi_block(sess, cn_b.astype(np.float64).reshape(nr_b, nc_b, order="F"), pnr_b.astype(np.float64).reshape(nr_b, nc_b, order="F"),
+                                               gSiz, psf, float(o.min_corr), float(o.min_pnr), float(o.min_pixel), bd4, K, connected, deconv, loc, 3.0,
+                                               None if observer is None else (lambda kind, data, idx=idx: observer(idx, kind, data)))
+            finally:
+                self.engine.peel_close(pid)
+            # initComponents_parallel.m:428-431: the neurons whose seed pixel lies in the patch interior
+            ctr = res["center"]
+            keep = [k for k in range(ctr.shape[0]) if int(pp[0]) <= ctr[k, 0] + int(bp[0]) - 1 <= int(pp[1]) and int(pp[2]) <= ctr[k, 1] + int(bp[2]) - 1 <= int(pp[3])]
+            per_patch[idx] = (res, keep, (int(bp[0]), int(bp[2])))
+        sharded = self.dist is not None and (v.world_size > 1 or self.force_collectives)
+        counts = np.zeros(len(v.order), dtype=np.int64)
+        for i, idx in enumerate(v.order):
+            if idx in per_patch:
+                counts[i] = len(per_patch[idx][1])
+        if sharded:
+            counts = np.rint(self._allreduce(counts.astype(np.float64))).astype(np.int64)
+        first = np.concatenate([[0], np.cumsum(counts)])                  # :466-469: patches in column-major order, neurons by discovery
+        Ktot = int(first[-1])
+        rows, cols, vals = [], [], []
+        Cm = np.zeros((Ktot, n), dtype=np.float32); Craw = np.zeros((Ktot, n), dtype=np.float32); Sm = np.zeros((Ktot, n), dtype=np.float32)
+        kp = np.zeros(Ktot, dtype=np.float64); center = np.zeros((Ktot, 2), dtype=np.float64)
+        for i, idx in enumerate(v.order):
+            if idx not in per_patch:
+                continue
+            res, keep, (br0, bc0) = per_patch[idx]
+            for j, k in enumerate(keep):
+                col = int(first[i]) + j
+                (r0, r1, c0, c1), ai = res["A"][k]
+                rr, cc = np.nonzero(ai)
+                rows.append((cc + c0 + bc0 - 1) * v.d1 + (rr + r0 + br0 - 1)); cols.append(np.full(rr.size, col)); vals.append(ai[rr, cc])
+                Cm[col] = res["C"][k]; Craw[col] = res["C_raw"][k]
+                if o.deconv_flag:
+                    Sm[col] = res["S"][k]; kp[col] = res["kernel_pars"][k]
+                center[col] = (res["center"][k, 0] + br0 - 1, res["center"][k, 1] + bc0 - 1)      # :461
+        A = (sp.csc_matrix((np.concatenate(vals).astype(np.float32), (np.concatenate(rows), np.concatenate(cols))), shape=(d, Ktot)) if rows
+             else sp.csc_matrix((d, Ktot), dtype=np.float32))
+        if sharded:
+            A = sp.csc_matrix(self._gather_sparse(A), dtype=np.float32)
+            pack = self._allreduce(np.concatenate([Cm, Craw, Sm, kp[:, None].astype(np.float32), center.astype(np.float32)], axis=1))
+            Cm, Craw, Sm = (np.ascontiguousarray(pack[:, i * n:(i + 1) * n]) for i in range(3))
+            kp, center = pack[:, 3 * n].astype(np.float64), pack[:, 3 * n + 1:3 * n + 3].astype(np.float64)
+        both = self._allreduce(np.stack([Cn, PNR]))
+        Cn, PNR = both[0].reshape(v.d1, v.d2, order="F"), both[1].reshape(v.d1, v.d2, order="F")
+        A.sort_indices()
+        if n == v.T:
+            self.set_components(A, Cm, Craw)                              # :470-472
+        else:                                                             # (traces of the first n frames only: kept, but not bound for the updates)
+            self.A, self.C, self.C_raw = A, Cm, Craw
+            if hasattr(self.engine, "bind_traces"):
+                self.engine.bind_traces(None)
+        if o.deconv_flag:                                                 # :473-480
+            self.S = Sm; self.P["kernel_pars"] = kp
+        else:
+            self.S = np.zeros_like(Cm)
+        self.Cn = Cn                                                      # :481
+        self.ids = np.arange(1, Ktot + 1); self.tags = np.zeros(Ktot, dtype=np.uint16); self.P["k_ids"] = Ktot      # :482-485
+        return center, Cn, PNR
 
     def reconstruct_b0(self):
         """Sources2D.m:1153-1190: stitch b0{m} into a d1 x d2 image (owned patches; all-reduced if sharded)."""

@@ -155,6 +155,37 @@ int cnmfe_estimate_noise(cnmfe_ctx *ctx, int patch_id, int64_t nframes, float *s
 int cnmfe_seed_images(cnmfe_ctx *ctx, int patch_id, const float *psf, int32_t psf_n, int64_t frame0, int64_t nframes,
                       const double *Q, int32_t M, float sig, float *Cn_block /* d_b */, float *PNR_block /* d_b */);
 
+/* ---- (g) greedy initialisation: the peel-off of greedyROI_endoscope as a session per patch
+ * endoscope/greedyROI_endoscope.m:119-145 (open), :287-311 + endoscope/extract_ac.m:19-58 (extract), :378-402 (apply).  The loop over the seed pixels, the
+ * images v_search / ind_search, the shape constraints and the baseline fit are the host's (sources2d.Sources2D.initComponents_parallel); one step's work over
+ * a pixel box times all frames is the device's.
+ *
+ * cnmfe_peel_open: the arguments, refusals and the images Cn_block / PNR_block of cnmfe_seed_images (bit-identical), plus Sn_block = GetSn of the filtered
+ * traces (d_b floats, may be NULL).  The session keeps HY (the filtered block, trend and median subtracted: :130), Sn in fp64 (:132) and Yw, a working copy of the
+ * centred video (M > 0: of the detrended video), 2 x 16 * ceil(nframes / 4) * d_b bytes; CNMFE_ENOMEM if they do not fit, CNMFE_ESTATE if the patch already
+ * has a session.  The resident video and all fit state stay untouched.
+ *
+ * cnmfe_peel_extract: the seed (r, c), 0-BASED in the block; box = rows max(0, r - gSiz) .. min(nr_b - 1, r + gSiz), columns likewise (:299-300), nr x nc
+ * pixels column-major.  corr_box = Pearson's r of every box pixel's HY trace with the seed's (NaN for a constant trace); ci = mean of HY over {corr > 0.9}
+ * (nframes doubles); y_bg(t) = the exact median over {corr < 0.3} of Yw + the pixel mean (M > 0: of Yw), NaN for an empty set; ai_box = row 3 of
+ * ([1, y_bg, ci]' [1, y_bg, ci]) \ ([1, y_bg, ci]' Y') clipped at 0 (max(0, NaN) = 0), before any constraint.  stats[6] = max(diff(y0)), std(diff(y0)),
+ * norm(ci), GetSn(ci), |{corr > 0.9}|, |{corr < 0.3}|.  Nothing of the session changes.
+ *
+ * cnmfe_peel_apply: Yw(box) -= ai_box ci (:378); HY(box2) -= Hai_box2 ci (:385-387) on box2 = the box of reach 2 gSiz (:310-311); then per box2 pixel
+ * PNR_box2 = max(HY) / Sn (NaN or < min_pnr -> 0, :391-393) and Cn_box2 = the 8-neighbour correlation image of HY(box2) thresholded at sig Sn, the box
+ * taken as a whole image (:396-401; NaN or < min_corr -> 0).
+ *
+ * gSiz > 20 is CNMFE_EUNSUPPORTED; extract / apply / close without a session are CNMFE_ESTATE.  Every reduction runs in a fixed order: two identical
+ * sessions are bit-identical.  The calls run on the patch's lane. */
+int cnmfe_peel_open(cnmfe_ctx *ctx, int patch_id, const float *psf, int32_t psf_n, int64_t frame0, int64_t nframes,
+                    const double *Q, int32_t M, float sig, float *Cn_block /* d_b */, float *PNR_block /* d_b */, float *Sn_block /* d_b or NULL */);
+int cnmfe_peel_extract(cnmfe_ctx *ctx, int patch_id, int32_t r, int32_t c, int32_t gSiz, double *corr_box /* nr * nc */, double *ai_box /* nr * nc */,
+                       double *ci /* nframes */, double *stats /* 6 */);
+int cnmfe_peel_apply(cnmfe_ctx *ctx, int patch_id, int32_t r, int32_t c, int32_t gSiz, const double *ai_box /* nr * nc */,
+                     const double *Hai_box2 /* nr2 * nc2 */, const double *ci /* nframes */, double sig, double min_pnr, double min_corr,
+                     float *PNR_box2 /* nr2 * nc2 */, float *Cn_box2 /* nr2 * nc2 */);
+int cnmfe_peel_close(cnmfe_ctx *ctx, int patch_id);
+
 /* sn of the BLOCK pixels of a patch (obj.P.sn(logical(mask)), update_background_parallel.m:131; for a low-resolution fit patch of
  * bg_ssub > 1 the resized values of :137).  Only the outlier branch of the ring fit reads them. */
 int cnmfe_set_noise(cnmfe_ctx *ctx, int patch_id, const float *sn_block /* d_b */);
