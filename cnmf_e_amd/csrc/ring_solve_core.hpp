@@ -93,8 +93,10 @@ template <int N, bool NOP> __device__ __forceinline__ void rs_fmac_bc_self(doubl
 template <int J, int C> __device__ __forceinline__ void rs_chol_col(double (&a)[16]) {       // a[c] -= L(i, J) L(c, J) for c = C .. 15
     if constexpr (C < 16) { rs_fmac_bc<C, C == J + 1>(a[C], a[J], a[J]); rs_chol_col<J, C + 1>(a); }
 }
-template <int J, int CC> __device__ __forceinline__ void rs_inv_row(double (&a)[16], const double &lij) {   // E(i, cc) -= lij E(J, cc) for cc = CC .. J-1
-    if constexpr (CC < J) { rs_fmac_bc_self<J, CC == 0>(a[CC], lij); rs_inv_row<J, CC + 1>(a, lij); }
+// The inverse half keeps column cc of E in DPP row cc & 3 only (the four rows used to update all sixteen columns in replica): slot s of a lane
+// in row g is column 4 s + g, so step J is ceil(J / 4) FMAs instead of J, each reading lane J of its OWN row -- which holds that row's column.
+template <int J, int S> __device__ __forceinline__ void rs_inv_slots(double (&a)[16], const double &lij) {  // E(i, 4 s + g) -= lij E(J, 4 s + g) for the slots s = S .. with 4 s < J
+    if constexpr (4 * S < J) { rs_fmac_bc_self<J, S == 0>(a[S], lij); rs_inv_slots<J, S + 1>(a, lij); }
 }
 // `inv` = 1 / sqrt(pivot J), handed in by the previous column: the NEXT pivot is final as soon as column J's first update (C = J + 1) has landed, so its
 // broadcast and reciprocal square root (v_rsq_f64 + two Newton steps: a ~70-clock dependent chain) are started there and run under the remaining 14 - J updates
@@ -113,23 +115,26 @@ template <int J> __device__ __forceinline__ void rs_chol(double (&a)[16], double
     }
 }
 // in place: E(i, c) = -sum_{j = c .. i-1} L(i, j) Y(j, c),  Y(j, c) = E(j, c) / L(j, j),  Y(j, j) = 1 / L(j, j)
-template <int J> __device__ __forceinline__ void rs_inv(double (&a)[16], const double &mydinv, int i) {
+// Slot s lives in the register of a[s]: L(i, s) is last read at step s, the slot is first written at step 4 s -- there the rows that do not own column 4 s
+// get 0.0 instead of the stale L(i, s), and a slot whose column has not started stays 0.0 under the updates (-lij * 0).  A column enters its slot at its own
+// step J, in row J & 3; every element then sees the updates J' = cc + 1 .. 15 in the same order with the same operands as in the replicated form: the same bits.
+template <int J> __device__ __forceinline__ void rs_inv(double (&a)[16], const double &mydinv, int i, int g) {
     if constexpr (J < 16) {
         const double dj = rs_bc<J>(mydinv);                 // (its own statement: inside the conditional below it would run under an exec mask that switches lane J off)
-        const double lij = i > J ? a[J] * dj : 0.0;
-        rs_inv_row<J, 0>(a, lij);
-        a[J] = i > J ? -lij : a[J];
-        // Round 5: a[J] is next read THROUGH DPP -- rs_inv_row<J + 1, J>, an asm statement without wait states of its own -- and the scheduler is free to sink
-        // this select to right in front of that read (VALU write -> DPP read needs two wait states; the compiler's hazard recogniser does not look into asm).
-        // scripts/isa_stats.py found exactly that in the NT = 4, 5, 7, 8 instantiations (at J = 15, where the stale value is multiplied by lij = 0: harmless by
-        // luck) and, in this round's fused variant of the step, at J = 14 (wrong weights).  The pin keeps the select in front of the next step's asm sequence.
-        asm volatile("s_nop 0" : "+v"(a[J]));
-        rs_inv<J + 1>(a, mydinv, i);
+        const double lij = i > J ? a[J] * dj : 0.0;         // (L(i, J): replicated in the four rows; a[J] is still the Cholesky half's for every J -- slot s = J needs 4 s <= J - 1 or s = J = 0, read here first)
+        rs_inv_slots<J, 0>(a, lij);
+        constexpr int S = J >> 2;
+        const double keep = (J & 3) == 0 ? 0.0 : a[S];
+        a[S] = (g == (J & 3) && i > J) ? -lij : keep;
+        // a[S] is next read THROUGH DPP by the next step's asm sequence, which the compiler's hazard recogniser does not look into: the pin keeps this select
+        // in front of it (VALU write -> DPP read needs two wait states, which the first statement of that sequence carries)
+        asm volatile("s_nop 0" : "+v"(a[S]));
+        rs_inv<J + 1>(a, mydinv, i, g);
     }
 }
 // 16x16 diagonal step: sb holds the (symmetric) block, row i at sb[i * RS_DS]; on return it holds inv(L), L = chol(block), lower
-// triangular with zeros above the diagonal.  Lane = row, the four 16-lane DPP rows of the wave work in replica (lane l: row l & 15);
-// a column / row broadcast is the DPP source of the consuming fp64 FMA: 120 + 120 FMAs carry the whole step.
+// triangular with zeros above the diagonal.  Lane = row, the four 16-lane DPP rows of the wave run the Cholesky half in replica (lane l: row l & 15)
+// and share the columns of the inverse half; a column / row broadcast is the DPP source of the consuming fp64 FMA: 120 + 36 FMAs carry the whole step.
 __device__ __forceinline__ void rs_diag_block(double *sb, int lane) {
     const int i = lane & 15;
     double a[16];
@@ -137,16 +142,17 @@ __device__ __forceinline__ void rs_diag_block(double *sb, int lane) {
     for (int c = 0; c < 16; c += 2) { const double2 v = *reinterpret_cast<const double2 *>(sb + i * RS_DS + c); a[c] = v.x; a[c + 1] = v.y; }
     double mydinv = 0.0;
     rs_chol<0>(a, mydinv, i, rs_rsqrt(rs_bc<0>(a[0])));
-    rs_inv<0>(a, mydinv, i);
+    // the DPP row, opaque to the optimiser: the masks `g == J & 3` and the store's `i > 4 s + g` would otherwise be computed once for all the diagonal steps of a
+    // kernel and kept in scalar registers throughout -- together with the masks `i > J`, `i == J` that the Cholesky half shares that way, more than there are
+    // scalar registers: the NT = 6 kernels then moved 85 of them through VGPR lanes and spilled 44 VGPRs instead of 24
+    int g = lane >> 4;
+    asm volatile("" : "+v"(g));
+    rs_inv<0>(a, mydinv, i, g);
     __syncthreads();                                        // every lane has read its row
-    if (lane < 16) {
 #pragma unroll
-        for (int c = 0; c < 16; c += 2) {
-            double2 v;
-            v.x = i > c ? a[c] * mydinv : (i == c ? mydinv : 0.0);
-            v.y = i > c + 1 ? a[c + 1] * mydinv : (i == c + 1 ? mydinv : 0.0);
-            *reinterpret_cast<double2 *>(sb + i * RS_DS + c) = v;
-        }
+    for (int s = 0; s < 4; ++s) {                           // every lane its four entries of inv(L)
+        const int c = 4 * s + g;
+        sb[i * RS_DS + c] = i > c ? a[s] * mydinv : (i == c ? mydinv : 0.0);
     }
     __syncthreads();
 }

@@ -114,6 +114,7 @@ class _PinnedBlock:
         self.eng = weakref.ref(eng); self.nbytes = nbytes; self.ready = False
         self.gen = None                                   # the download batch that fills the buffer (Engine._mark_batch): what wait() waits for
         self.ptr = eng._pinned_take(nbytes)
+        self._free = L.lib.cnmfe_host_free                # the library that allocated the buffer frees it, whatever `L` is when the last view dies
     def _wait_ctx(self, ctx, check):
         # this block's batch only: the copy stream may already hold the NEXT iteration's downloads, which a release of this buffer must not wait for
         rc = L.lib.cnmfe_stitch_wait(ctx) if self.gen is None else L.lib.cnmfe_copy_wait(ctx, self.gen)
@@ -133,7 +134,7 @@ class _PinnedBlock:
                     self._wait_ctx(eng._ctx, False)              # the copy may still be writing into the buffer
                 eng._pinned_give(self.ptr, self.nbytes)
             else:
-                L.lib.cnmfe_host_free(self.ptr)
+                self._free(self.ptr)
         except Exception:
             pass
 

@@ -60,6 +60,58 @@ def diag_block(sblk):
     return out
 
 
+def diag_block_rows(sblk):
+    """The diagonal step as rs_diag_block runs it on the 64 lanes: lane l is row i = l & 15 of the block in DPP row g = l >> 4.  The Cholesky half is
+    replicated in the four DPP rows; the inverse half keeps column cc of E in DPP row cc & 3 only -- slot s of a lane in row g is column 4 s + g and lives in the
+    register of a[s] (L(i, s) is dead after step s, the slot is first written at step 4 s, where the rows that do not own column 4 s get 0.0).  A row broadcast
+    (row_newbcast:J) reads lane J of the reader's OWN DPP row.  Returns the 16 x DS exchange tile as the 64 lanes write it (every lane four entries)."""
+    i, g = C, RQ                                                                  # row of the block, DPP row
+    a = np.array([[sblk[ii * DS + c] for c in range(16)] for ii in i])            # a[lane][c]
+    bc = lambda v, j: v[(L & 48) + j]                                             # lane j of the own DPP row -> all 16 lanes of the row
+    mydinv = np.zeros(64)
+    for j in range(16):
+        inv = 1.0 / np.sqrt(bc(a[:, j], j))
+        a[:, j] *= inv
+        mydinv = np.where(i == j, inv, mydinv)
+        for c in range(j + 1, 16):
+            a[:, c] = a[:, c] - a[:, j] * bc(a[:, j], c)
+    nfma = 0
+    for j in range(16):
+        dj = bc(mydinv, j)
+        lij = np.where(i > j, a[:, j] * dj, 0.0)                                  # a[j] is still L(:, j): slot s = j would need 4 s < j
+        for s in range(4):
+            if 4 * s < j:
+                a[:, s] = a[:, s] - lij * bc(a[:, s], j)
+                nfma += 1
+        s = j >> 2
+        keep = 0.0 if (j & 3) == 0 else a[:, s]
+        a[:, s] = np.where((g == (j & 3)) & (i > j), -lij, keep)
+    assert nfma == 36
+    out = np.full(16 * DS, np.nan)
+    for s in range(4):
+        c = 4 * s + g
+        out[i * DS + c] = np.where(i > c, a[:, s] * mydinv, np.where(i == c, mydinv, 0.0))
+    return out
+
+
+def check_diag_block_rows(rng, n=8):
+    """the 64-lane layout against the one-row model (bit for bit: the same operations on the same values) and against NumPy's Cholesky and inverse"""
+    worst = 0.0
+    for _ in range(n):
+        X = rng.standard_normal((16, 40))
+        S = X @ X.T + 1e-3 * np.eye(16)
+        sblk = np.zeros(16 * DS)
+        for ii in range(16):
+            sblk[ii * DS:ii * DS + 16] = S[ii]
+        ref = diag_block(sblk)
+        got = diag_block_rows(sblk).reshape(16, DS)
+        assert np.all(np.isnan(got[:, 16:])) and not np.any(np.isnan(got[:, :16]))        # every entry written exactly where it belongs, nothing else
+        assert np.array_equal(got[:, :16].view(np.uint64), ref.view(np.uint64))
+        Linv = np.linalg.inv(np.linalg.cholesky(S))
+        worst = max(worst, np.abs(got[:, :16] - Linv).max() / np.abs(Linv).max())
+    return worst
+
+
 def solve_pixel(G, u, g, s, Tp, p):
     """G: p x p Gram of the real ring rows (identity rows for missing neighbours already in place), u, g: p vectors"""
     NT = (p + 15) // 16
@@ -157,6 +209,7 @@ def main():
         err = np.abs(w[:p] - ref[:p]).max() / np.abs(ref[:p]).max()
         print("p=%3d NT=%d  max rel err %.2e  w0 err %.2e  pad %.1e" % (p, NT, err, abs(w0 - ref[p]), np.abs(w[p:]).max() if N > p else 0))
         assert err < 1e-9
+    print("diagonal step on four DPP rows: max rel err against numpy %.2e" % check_diag_block_rows(rng))
 
 
 if __name__ == "__main__":
