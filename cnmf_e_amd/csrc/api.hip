@@ -989,7 +989,7 @@ int cnmfe_seed_images(cnmfe_ctx *ctx, int patch_id, const float *psf, int32_t ps
     RET(seed_args(ctx, patch_id, psf, psf_n, frame0, nframes, Q, M, sig, Cn_block, PNR_block, P));
     CK(hipSetDevice(ctx->device));
     RET(ensure_ymean(ctx, P));
-    return seed_images_run(ctx, P, psf, psf_n, nframes, Q, M, sig, Cn_block, PNR_block);
+    return seed_images_run(ctx, SeedSrc{P->Yc4.as<float4>(), P->d_b, P->nr_b, P->nc_b}, psf, psf_n, nframes, Q, M, sig, Cn_block, PNR_block);
 }
 
 // ---- greedy initialisation: a peel session per patch (peel.hpp) ----
@@ -1006,6 +1006,34 @@ int cnmfe_peel_open(cnmfe_ctx *ctx, int patch_id, const float *psf, int32_t psf_
     return rc;
 }
 
+// The second pass (@Sources2D/initComponents_residual_parallel.m:186-220): the session on the PATCH, its source video Yres = Ysig - A(patch, ind) C(ind, :) built
+// off the resident residual (peel.hpp, k_peel_yres).  Ysig is only read; the residual REQUEST is the session's: cnmfe_peel_close drops it (as a fit does), so the
+// next update requests its own and finds the patch as it would have without the session
+int cnmfe_peel_open_residual(cnmfe_ctx *ctx, int patch_id, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const float *C,
+                             int c_order, const float *psf, int32_t psf_n, float sig, float *Cn_patch, float *PNR_patch, float *Sn_patch, float *Yres_out,
+                             int out_memspace) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    Patch *P = get_patch(ctx, patch_id);
+    if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
+    if (!Cn_patch || !PNR_patch) return fail(CNMFE_EINVAL, "null Cn_patch / PNR_patch");
+    if (psf_n < 0 || Ksel < 0 || !(sig == sig) || std::isinf(sig)) return fail(CNMFE_EINVAL, "residual peel session: psf_n = %d, Ksel = %d, sig = %g", psf_n, Ksel, (double)sig);
+    if (!psf) psf_n = 0;
+    if (P->derived) return fail(CNMFE_EUNSUPPORTED, "a peel session of a derived (bg_ssub) patch is not built: patch %d", patch_id);
+    if (psf_n > 0 && (psf_n % 2 == 0 || psf_n > 25)) return fail(CNMFE_EUNSUPPORTED, "seed images: the filter must be odd-sized and at most 25 x 25 (got %d; pad an even kernel)", psf_n);
+    if (P->T < 64 || P->T > 20400) return fail(CNMFE_EUNSUPPORTED, "seed images support 64 <= nframes <= 20400 (the residual session reads all %lld frames)", (long long)P->T);
+    if (!P->ysig_valid) return fail(CNMFE_ESTATE, "cnmfe_residual has not been run for patch %d", patch_id);
+    if (P->peel) return fail(CNMFE_ESTATE, "patch %d already has an open peel session", patch_id);
+    RET(check_csc("A", Ksel, P->d, A_colptr, A_rowidx));
+    if (Ksel > 0 && ((!A_val && A_colptr[Ksel] > 0) || (!C && c_order != CNMFE_BOUND))) return fail(CNMFE_EINVAL, "null A_val / C");
+    CK(hipSetDevice(ctx->device));
+    RET(residual_materialize(ctx, P));                       // a virtual or pending residual: Ysig itself is about to be read
+    P->peel = new PeelSession();
+    const int rc = peel_open_residual_run(ctx, P, Ksel, A_colptr, A_rowidx, A_val, C, c_order, psf, psf_n, sig, Cn_patch, PNR_patch, Sn_patch, Yres_out, out_memspace);
+    // a failed open (CNMFE_ENOMEM ...) has realised the residual all the same: it is dropped as a close would drop it, so that the next update requests its own
+    if (rc != 0) { (void)hipStreamSynchronize(ctx->st()); delete P->peel; P->peel = nullptr; P->ysig_valid = false; }
+    return rc;
+}
+
 static int peel_args(cnmfe_ctx *ctx, int patch_id, int32_t r, int32_t c, int32_t gSiz, Patch *&P) {
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
     P = get_patch(ctx, patch_id);
@@ -1013,7 +1041,8 @@ static int peel_args(cnmfe_ctx *ctx, int patch_id, int32_t r, int32_t c, int32_t
     if (!P->peel) return fail(CNMFE_ESTATE, "patch %d has no open peel session (cnmfe_peel_open)", patch_id);
     if (gSiz < 1) return fail(CNMFE_EINVAL, "peel: gSiz = %d", gSiz);
     if (gSiz > 20) return fail(CNMFE_EUNSUPPORTED, "peel: gSiz <= 20 is built (got %d)", gSiz);
-    if (r < 0 || r >= P->nr_b || c < 0 || c >= P->nc_b) return fail(CNMFE_EINVAL, "peel: the seed (%d, %d) lies outside the %d x %d block", r, c, P->nr_b, P->nc_b);
+    if (r < 0 || r >= P->peel->nr || c < 0 || c >= P->peel->nc)
+        return fail(CNMFE_EINVAL, "peel: the seed (%d, %d) lies outside the %d x %d %s", r, c, P->peel->nr, P->peel->nc, P->peel->residual ? "patch" : "block");
     return 0;
 }
 
@@ -1042,6 +1071,7 @@ int cnmfe_peel_close(cnmfe_ctx *ctx, int patch_id) {
     if (!P->peel) return fail(CNMFE_ESTATE, "patch %d has no open peel session", patch_id);
     CK(hipSetDevice(ctx->device));
     CK(hipStreamSynchronize(ctx->st()));
+    if (P->peel->residual) P->ysig_valid = false;            // the residual was requested for the session and goes with it
     delete P->peel; P->peel = nullptr;
     return 0;
 }

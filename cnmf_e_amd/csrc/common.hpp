@@ -135,7 +135,11 @@ inline void csc_to_csr(int64_t nrow, int32_t ncol, const int64_t *colptr, const 
 
 // a greedy-initialisation session of one patch (peel.hpp, cnmfe_peel_open .. cnmfe_peel_close): the filtered block HY, the working copy Yw of the video (both
 // [ceil(n / 4)][d_b] float4), GetSn of HY per block pixel (fp64), the detrend basis, ci | y_bg (fp64, n each) and the box kernels' scratch
-struct PeelSession { DevBuf hy, yw, sn, q, ci, scr; int64_t n = 0, nq = 0; int M = 0; };
+// The session runs on the geometry of its SOURCE video: the centred block (cnmfe_peel_open: d = d_b, nr_b x nc_b, y_bg adds the pixel mean back) or the
+// residual video of the patch (cnmfe_peel_open_residual: Yw starts as Yres = Ysig - A C, d x nr x nc of the patch, no pixel mean -- the residual carries its own)
+struct PeelSession { DevBuf hy, yw, sn, q, ci, scr; int64_t n = 0, nq = 0; int M = 0; int64_t d = 0; int nr = 0, nc = 0; bool residual = false; };
+// the video a seed / peel pass reads: [ceil(n / 4)][d] float4, nr x nc pixels column-major
+struct SeedSrc { const float4 *y4; int64_t d; int nr, nc; };
 
 // ---- per-patch resident state ----------------------------------------------------
 struct Patch {
@@ -489,8 +493,10 @@ int postproc_run(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_
                  const float *A_val, uint8_t *keep);
 int ensure_ymean(cnmfe_ctx *ctx, Patch *P);
 int sn_video_run(cnmfe_ctx *ctx, Patch *P, int64_t nframes, float *sn_out);
-int seed_images_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, int64_t nframes, const double *Q, int32_t M, float sig,
+int seed_images_run(cnmfe_ctx *ctx, const SeedSrc &src, const float *psf, int32_t psf_n, int64_t nframes, const double *Q, int32_t M, float sig,
                     float *Cn_out, float *PNR_out, PeelSession *keep = nullptr);   // seed.hpp (deconv.hip)
+int peel_open_residual_run(cnmfe_ctx *ctx, Patch *P, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const float *C, int c_order,
+                           const float *psf, int32_t psf_n, float sig, float *Cn_out, float *PNR_out, float *Sn_out, float *Yres_out, int out_memspace);   // peel.hpp (deconv.hip)
 int peel_open_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, int64_t nframes, const double *Q, int32_t M, float sig,
                   float *Cn_out, float *PNR_out, float *Sn_out);   // peel.hpp (deconv.hip)
 int peel_extract_run(cnmfe_ctx *ctx, Patch *P, int r, int c, int gSiz, double *corr_box, double *ai_box, double *ci_out, double *stats);

@@ -52,6 +52,9 @@
 //                                                                          (2 gSiz + 1)^2 box; ci: 1 x nframes; stats: [max(diff(y0)) std(diff(y0)) norm(ci) GetSn(ci) n_hi n_lo]
 //   [PNR_box2, Cn_box2] = cnmfe_mex('peel_apply', h, pid, r, c, gSiz, ai, Hai, ci, sig, min_pnr, min_corr)   Hai: the clipped (4 gSiz + 1)^2 box
 //   cnmfe_mex('peel_close', h, pid)
+//   [Cn_patch, PNR_patch, Sn_patch, Yres] = cnmfe_mex('peel_open_residual', h, pid, A_patch, C_or_rows, psf)   the second pass (initComponents_residual_parallel.m:186-220):
+//                                                                          the session on the PATCH and on Ysig - A_patch C, after 'residual' / 'residual_ssub'; the images are
+//                                                                          nr x nc of the patch, Yres (asked for as 4th output) d x T single; extract / apply then take the seed in the patch
 #include "mex.h"
 #include "matrix.h"
 #include <string.h>
@@ -70,7 +73,7 @@ typedef struct { float *pinned; size_t K, T; } StitchOut;
 static StitchOut g_stitch[MAX_CTX];
 // block sizes by (context, patch id), noted by 'patch': what 'seed_images' shapes its outputs with
 #define MAX_DIMS 4096
-typedef struct { cnmfe_ctx *c; int pid; int32_t nr_b, nc_b; int64_t peel_n; } BlockDims;   // peel_n: frames of the open peel session ('peel_open')
+typedef struct { cnmfe_ctx *c; int pid; int32_t nr_b, nc_b, nr_p, nc_p, peel_nr, peel_nc; int64_t T, peel_n; } BlockDims;   // peel_n, peel_nr, peel_nc: frames and geometry of the open peel session ('peel_open': the block, 'peel_open_residual': the patch)
 static BlockDims g_dims[MAX_DIMS];
 static int g_ndims = 0;
 static void at_exit(void) {
@@ -318,6 +321,7 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
         if (slot >= MAX_DIMS) FAIL("patch: this gateway keeps the block sizes of at most %d patches", MAX_DIMS);
         CHECK(cnmfe_patch_create(c, pid, pr, br, (int32_t)mxGetScalar(pin[5]), (int32_t)mxGetScalar(pin[6]), (int64_t)mxGetScalar(pin[7])));
         g_dims[slot].c = c; g_dims[slot].pid = pid; g_dims[slot].nr_b = br[1] - br[0] + 1; g_dims[slot].nc_b = br[3] - br[2] + 1; g_dims[slot].peel_n = 0;
+        g_dims[slot].nr_p = pr[1] - pr[0] + 1; g_dims[slot].nc_p = pr[3] - pr[2] + 1; g_dims[slot].T = (int64_t)mxGetScalar(pin[7]); g_dims[slot].peel_nr = g_dims[slot].peel_nc = 0;
         if (slot == g_ndims) ++g_ndims;
     } else if (!strcmp(cmd, "upload")) {
         if (nin != 5) FAIL("upload: 5 inputs required");
@@ -476,12 +480,29 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
         CHECK(cnmfe_seed_images(c, pid, psf, pn, 0, nf, Q, M, 3.0f, cn, pnr));
         pout[0] = to_double(cn, nrb, ncb);
         if (nout > 1) pout[1] = to_double(pnr, nrb, ncb);
-    } else if (!strcmp(cmd, "peel_open") || !strcmp(cmd, "peel_extract") || !strcmp(cmd, "peel_apply") || !strcmp(cmd, "peel_close")) {
+    } else if (!strcmp(cmd, "peel_open") || !strcmp(cmd, "peel_open_residual") || !strcmp(cmd, "peel_extract") || !strcmp(cmd, "peel_apply") || !strcmp(cmd, "peel_close")) {
         int slot = 0;
         while (slot < g_ndims && !(g_dims[slot].c == c && g_dims[slot].pid == pid)) ++slot;
         if (slot == g_ndims) FAIL("%s: patch %d was not created through this gateway", cmd, pid);
-        const int nrb = g_dims[slot].nr_b, ncb = g_dims[slot].nc_b;
-        if (!strcmp(cmd, "peel_open")) {                       // [Cn_block, PNR_block, Sn_block] = cnmfe_mex('peel_open', h, pid, psf, nframes, Q)
+        int nrb = g_dims[slot].nr_b, ncb = g_dims[slot].nc_b;
+        if (!strcmp(cmd, "peel_open_residual")) {              // [Cn_patch, PNR_patch, Sn_patch, Yres] = cnmfe_mex('peel_open_residual', h, pid, A_patch, C_or_rows, psf)
+            if (nin != 6) FAIL("peel_open_residual: 6 inputs required");
+            const mxArray *F = pin[5];
+            if (!mxIsEmpty(F) && mxGetM(F) != mxGetN(F)) FAIL("peel_open_residual: psf must be square");
+            const int32_t pn = mxIsEmpty(F) ? 0 : (int32_t)mxGetM(F);
+            const float *psf = pn ? f32_of(F, NULL) : NULL;
+            Csc A = csc_of(pin[3]);
+            Traces Cm = traces_of(pin[4], A.K);
+            const size_t nrp = (size_t)g_dims[slot].nr_p, ncp = (size_t)g_dims[slot].nc_p, dp = nrp * ncp;
+            float *cn = (float *)mxMalloc((dp + 1) * sizeof(float)), *pnr = (float *)mxMalloc((dp + 1) * sizeof(float)), *sn = (float *)mxMalloc((dp + 1) * sizeof(float));
+            mxArray *yres = nout > 3 ? mxCreateNumericMatrix(dp, (size_t)g_dims[slot].T, mxSINGLE_CLASS, mxREAL) : NULL;
+            CHECK(cnmfe_peel_open_residual(c, pid, A.K, A.cp, A.ri, A.v, Cm.ptr, Cm.order, psf, pn, 3.0f, cn, pnr, sn, yres ? (float *)mxGetData(yres) : NULL, CNMFE_HOST));
+            g_dims[slot].peel_n = g_dims[slot].T; g_dims[slot].peel_nr = (int32_t)nrp; g_dims[slot].peel_nc = (int32_t)ncp;
+            pout[0] = to_double(cn, nrp, ncp);
+            if (nout > 1) pout[1] = to_double(pnr, nrp, ncp);
+            if (nout > 2) pout[2] = to_double(sn, nrp, ncp);
+            if (nout > 3) pout[3] = yres;
+        } else if (!strcmp(cmd, "peel_open")) {                       // [Cn_block, PNR_block, Sn_block] = cnmfe_mex('peel_open', h, pid, psf, nframes, Q)
             if (nin != 5 && nin != 6) FAIL("peel_open: 5 or 6 inputs required");
             const mxArray *F = pin[3];
             if (!mxIsEmpty(F) && mxGetM(F) != mxGetN(F)) FAIL("peel_open: psf must be square");
@@ -496,7 +517,7 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
             const size_t db = (size_t)nrb * (size_t)ncb;
             float *cn = (float *)mxMalloc((db + 1) * sizeof(float)), *pnr = (float *)mxMalloc((db + 1) * sizeof(float)), *sn = (float *)mxMalloc((db + 1) * sizeof(float));
             CHECK(cnmfe_peel_open(c, pid, psf, pn, 0, nf, Q, M, 3.0f, cn, pnr, sn));
-            g_dims[slot].peel_n = nf;
+            g_dims[slot].peel_n = nf; g_dims[slot].peel_nr = nrb; g_dims[slot].peel_nc = ncb;
             pout[0] = to_double(cn, (size_t)nrb, (size_t)ncb);
             if (nout > 1) pout[1] = to_double(pnr, (size_t)nrb, (size_t)ncb);
             if (nout > 2) pout[2] = to_double(sn, (size_t)nrb, (size_t)ncb);
@@ -509,7 +530,8 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
             const int r = (int)mxGetScalar(pin[3]) - 1, cc = (int)mxGetScalar(pin[4]) - 1, g = (int)mxGetScalar(pin[5]);
             const int64_t nf = g_dims[slot].peel_n;
             if (nf <= 0) FAIL("%s: patch %d has no open peel session ('peel_open')", cmd, pid);
-            if (r < 0 || r >= nrb || cc < 0 || cc >= ncb || g < 1) FAIL("%s: the seed (%d, %d) lies outside the %d x %d block, or gSiz = %d", cmd, r + 1, cc + 1, nrb, ncb, g);
+            nrb = g_dims[slot].peel_nr; ncb = g_dims[slot].peel_nc;          // the session's geometry: the block, or the patch of a residual session
+            if (r < 0 || r >= nrb || cc < 0 || cc >= ncb || g < 1) FAIL("%s: the seed (%d, %d) lies outside the %d x %d session, or gSiz = %d", cmd, r + 1, cc + 1, nrb, ncb, g);
 #define PEEL_LO(x, reach) ((x) - (reach) < 0 ? 0 : (x) - (reach))
 #define PEEL_HI(x, reach, n) ((x) + (reach) > (n) - 1 ? (n) - 1 : (x) + (reach))
             const size_t nr1 = (size_t)(PEEL_HI(r, g, nrb) - PEEL_LO(r, g) + 1), nc1 = (size_t)(PEEL_HI(cc, g, ncb) - PEEL_LO(cc, g) + 1);

@@ -8,6 +8,8 @@
 // by d_b float4s and a box column is the contiguous run, so the box kernels put 64 lanes on the box rows and one wave on each of 4 interleaved frame quads:
 // workgroup = (box column, frame chunk).  Every sum is a per-lane fp64 partial, and the partials are added in ascending (chunk, wave) order by a second small
 // kernel: two identical sessions are bit-identical.  Only frames t < n enter anything (the last quad's padding does not).
+// A session runs on the geometry of its source video (PeelSession::d / nr / nc): the block for cnmfe_peel_open, the PATCH and its residual video
+// Yres = Ysig - A C (k_peel_yres) for cnmfe_peel_open_residual, the second pass of @Sources2D/initComponents_residual_parallel.m:186-220.
 #pragma once
 
 namespace cnmfe {
@@ -46,6 +48,33 @@ __global__ void __launch_bounds__(256) k_peel_yw_detrend(const float4 *__restric
         float v[4] = {v4.x, v4.y, v4.z, v4.w};
         for (int j = 0; j < 4; ++j) { const int t = 4 * q + j; v[j] = t < n ? seed_detrend(v[j], coef, Q + t, n, M) : 0.f; }
         yw4[(int64_t)q * d_b + p] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+
+// The source video of a residual session (@Sources2D/initComponents_residual_parallel.m:199,206): Yres = Ysig - A(patch, ind) C(ind, :) off the resident residual,
+// which is only read.  One thread per patch pixel and frame quad: the pixel's stored neurons (CSR row, ascending column) are summed in fp64 and the difference
+// is rounded once; the padding frames of the last quad become 0.  The result IS the session's working copy Yw: until the first apply Yw equals Yres bit for
+// bit, so the seed pipeline and the export of the open read it there and no third video is kept.  16 bytes read, 16 written per (pixel, quad), coalesced
+// over pixels; the trace quads C(k, 4q..) of a wave's few neurons come from L2.  rowptr == nullptr: no footprint in the patch, a copy.
+__global__ void __launch_bounds__(256) k_peel_yres(const float4 *__restrict__ ysig4, int64_t d, int n, int qchunk, const int *__restrict__ rowptr,
+                                                   const int *__restrict__ col, const float *__restrict__ val, const float *__restrict__ C, int64_t ldc,
+                                                   float4 *__restrict__ yw4) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= d) return;
+    const int nq = (n + 3) / 4, q0 = (int)blockIdx.y * qchunk, q1 = min(nq, q0 + qchunk);
+    const int e0 = rowptr ? rowptr[p] : 0, e1 = rowptr ? rowptr[p + 1] : 0;
+    for (int q = q0; q < q1; ++q) {
+        const float4 y4 = ysig4[(int64_t)q * d + p];
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int e = e0; e < e1; ++e) {
+            const double a = (double)val[e];
+            const float4 c4 = *reinterpret_cast<const float4 *>(C + (int64_t)col[e] * ldc + 4 * (int64_t)q);
+            s[0] = fma(a, (double)c4.x, s[0]); s[1] = fma(a, (double)c4.y, s[1]); s[2] = fma(a, (double)c4.z, s[2]); s[3] = fma(a, (double)c4.w, s[3]);
+        }
+        float v[4] = {(float)((double)y4.x - s[0]), (float)((double)y4.y - s[1]), (float)((double)y4.z - s[2]), (float)((double)y4.w - s[3])};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (4 * q + j >= n) v[j] = 0.f;
+        yw4[(int64_t)q * d + p] = make_float4(v[0], v[1], v[2], v[3]);
     }
 }
 
@@ -361,10 +390,10 @@ __global__ void __launch_bounds__(256) k_peel_cn(const double *__restrict__ part
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------------------------
-static inline PeelBox peel_box(const Patch *P, int r, int c, int reach) {
+static inline PeelBox peel_box(const PeelSession *S, int r, int c, int reach) {
     PeelBox b;
     b.r0 = std::max(0, r - reach); b.c0 = std::max(0, c - reach);
-    b.nr = std::min(P->nr_b - 1, r + reach) - b.r0 + 1; b.nc = std::min(P->nc_b - 1, c + reach) - b.c0 + 1;
+    b.nr = std::min(S->nr - 1, r + reach) - b.r0 + 1; b.nc = std::min(S->nc - 1, c + reach) - b.c0 + 1;
     return b;
 }
 static inline void peel_chunks(int64_t nq, int &nch, int &qchunk) {
@@ -378,7 +407,7 @@ int peel_open_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, int
                   float *Cn_out, float *PNR_out, float *Sn_out) {
     PeelSession *S = P->peel;
     const int64_t n = nframes, d_b = P->d_b, nq = (n + 3) / 4;
-    S->n = n; S->nq = nq; S->M = M;
+    S->n = n; S->nq = nq; S->M = M; S->d = d_b; S->nr = P->nr_b; S->nc = P->nc_b; S->residual = false;
     const size_t vid = (size_t)nq * (size_t)d_b * sizeof(float4);
     if (S->hy.ensure(vid) != 0 || S->yw.ensure(vid) != 0) {
         (void)hipGetLastError();
@@ -386,7 +415,7 @@ int peel_open_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, int
     }
     RET(S->sn.ensure((size_t)d_b * sizeof(double)));
     RET(S->ci.ensure(peel_al((size_t)n * sizeof(double)) * 2));
-    RET(seed_images_run(ctx, P, psf, psf_n, nframes, Q, M, sig, Cn_out, PNR_out, S));
+    RET(seed_images_run(ctx, SeedSrc{P->Yc4.as<float4>(), d_b, P->nr_b, P->nc_b}, psf, psf_n, nframes, Q, M, sig, Cn_out, PNR_out, S));
     if (M > 0) {
         RET(S->q.ensure((size_t)n * M * sizeof(double)));
         CK(hipMemcpyAsync(S->q.p, Q, (size_t)n * M * sizeof(double), hipMemcpyHostToDevice, ctx->st()));
@@ -404,11 +433,55 @@ int peel_open_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, int
     return 0;
 }
 
+// cnmfe_peel_open_residual: the session on the PATCH and its residual video (all frames, no detrending: initComponents_residual_parallel.m:176-177,220).
+// The caller has made sure that P->ysig holds the residual itself (residual_materialize).
+int peel_open_residual_run(cnmfe_ctx *ctx, Patch *P, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const float *C, int c_order,
+                           const float *psf, int32_t psf_n, float sig, float *Cn_out, float *PNR_out, float *Sn_out, float *Yres_out, int out_memspace) {
+    PeelSession *S = P->peel;
+    const int64_t n = P->T, d = P->d, nq = (n + 3) / 4;
+    S->n = n; S->nq = nq; S->M = 0; S->d = d; S->nr = P->nr; S->nc = P->nc; S->residual = true;
+    const size_t vid = (size_t)nq * (size_t)d * sizeof(float4);
+    if (S->hy.ensure(vid) != 0 || S->yw.ensure(vid) != 0) {
+        (void)hipGetLastError();
+        return fail(CNMFE_ENOMEM, "residual peel session: no room for the filtered residual video and the working copy, 2 x %zu bytes (16 x ceil(T / 4) x d)", vid);
+    }
+    RET(S->sn.ensure((size_t)d * sizeof(double)));
+    RET(S->ci.ensure(peel_al((size_t)n * sizeof(double)) * 2));
+    // (buffers of this call: released when it returns, behind the stream's last wait)
+    DevBuf dC, dRow, dCol, dVal;
+    int64_t ldc = 4;
+    const bool has_ac = Ksel > 0 && A_colptr[Ksel] > 0;
+    if (has_ac) {
+        RET(upload_traces(ctx, dC, C, Ksel, n, c_order, &ldc));
+        HostCSR csr; csc_to_csr(d, Ksel, A_colptr, A_rowidx, A_val, csr);
+        RET(to_dev(ctx, dRow, csr.rowptr.data(), csr.rowptr.size()));
+        RET(to_dev(ctx, dCol, csr.col.data(), csr.col.size()));
+        RET(to_dev(ctx, dVal, csr.val.data(), csr.val.size()));
+    }
+    // a patch of few pixels splits its frames over workgroups (some thousands wanted); every (pixel, quad) is written by exactly one thread
+    const int64_t nblk = (d + 255) / 256;
+    int64_t nseg = std::max<int64_t>(1, std::min<int64_t>(nq, (4096 + nblk - 1) / nblk));
+    const int qchunk = (int)((nq + nseg - 1) / nseg);
+    nseg = (nq + qchunk - 1) / qchunk;
+    LAUNCH(ctx, "peel_yres", k_peel_yres, dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, P->ysig.as<float4>(), d, (int)n, qchunk,
+           has_ac ? dRow.as<int>() : (const int *)nullptr, dCol.as<int>(), dVal.as<float>(), dC.as<float>(), ldc, S->yw.as<float4>());
+    RET(seed_images_run(ctx, SeedSrc{S->yw.as<float4>(), d, P->nr, P->nc}, psf, psf_n, n, nullptr, 0, sig, Cn_out, PNR_out, S));
+    if (Sn_out) {
+        std::vector<double> sn((size_t)d);
+        CK(hipMemcpyAsync(sn.data(), S->sn.p, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, ctx->st()));
+        CK(hipStreamSynchronize(ctx->st()));
+        for (int64_t i = 0; i < d; ++i) Sn_out[i] = (float)sn[(size_t)i];
+    }
+    if (Yres_out) RET(ysig_export(ctx, P, S->yw, Yres_out, out_memspace));      // (nothing has been peeled yet: Yw is Yres) exactly the fp32 video the session searches, frame-major like cnmfe_residual's output
+    CK(hipStreamSynchronize(ctx->st()));
+    return 0;
+}
+
 int peel_extract_run(cnmfe_ctx *ctx, Patch *P, int r, int c, int gSiz, double *corr_box, double *ai_box, double *ci_out, double *stats) {
     PeelSession *S = P->peel;
-    const int64_t n = S->n, d_b = P->d_b, nq = S->nq;
-    const int nr_b = P->nr_b;
-    const PeelBox b = peel_box(P, r, c, gSiz);
+    const int64_t n = S->n, d_b = S->d, nq = S->nq;
+    const int nr_b = S->nr;
+    const PeelBox b = peel_box(S, r, c, gSiz);
     const int npix = b.nr * b.nc, ictr = (c - b.c0) * b.nr + (r - b.r0);
     const int64_t pctr = (int64_t)c * nr_b + r;
     int nch, qchunk;
@@ -433,7 +506,7 @@ int peel_extract_run(cnmfe_ctx *ctx, Patch *P, int r, int c, int gSiz, double *c
     LAUNCH(ctx, "peel_corr_part", k_peel_corr_part, dim3((unsigned)b.nc, (unsigned)nch), dim3(256), 0, hy4, d_b, nr_b, b, pctr, (int)n, qchunk, dPart);
     LAUNCH(ctx, "peel_corr_fin", k_peel_corr_fin, dim3(1), dim3(256), 0, dPart, npart, npix, ictr, (int)n, dCorr, dHi, dLo, dCnt);
     const size_t sh_tr = (size_t)4 * npix * sizeof(double) + 264 * sizeof(int);
-    LAUNCH(ctx, "peel_traces", k_peel_traces, dim3((unsigned)nq), dim3(256), sh_tr, hy4, yw4, S->M > 0 ? (const double *)nullptr : P->ymean_d.as<double>(), d_b, nr_b, b,
+    LAUNCH(ctx, "peel_traces", k_peel_traces, dim3((unsigned)nq), dim3(256), sh_tr, hy4, yw4, (S->M > 0 || S->residual) ? (const double *)nullptr : P->ymean_d.as<double>(), d_b, nr_b, b,
            dHi, dLo, dCnt, (int)n, dCi, dBg);
     if (sh_stats > 64 * 1024) CK(hipFuncSetAttribute((const void *)k_peel_trace_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_stats));
     LAUNCH(ctx, "peel_trace_stats", k_peel_trace_stats, dim3(1), dim3(256), sh_stats, cfg, hy4, d_b, pctr, dCi, dBg, dCnt, dMom, dSt);
@@ -450,9 +523,9 @@ int peel_extract_run(cnmfe_ctx *ctx, Patch *P, int r, int c, int gSiz, double *c
 int peel_apply_run(cnmfe_ctx *ctx, Patch *P, int r, int c, int gSiz, const double *ai_box, const double *Hai_box2, const double *ci, double sig, double min_pnr,
                    double min_corr, float *PNR_box2, float *Cn_box2) {
     PeelSession *S = P->peel;
-    const int64_t n = S->n, d_b = P->d_b, nq = S->nq;
-    const int nr_b = P->nr_b;
-    const PeelBox b = peel_box(P, r, c, gSiz), b2 = peel_box(P, r, c, 2 * gSiz);
+    const int64_t n = S->n, d_b = S->d, nq = S->nq;
+    const int nr_b = S->nr;
+    const PeelBox b = peel_box(S, r, c, gSiz), b2 = peel_box(S, r, c, 2 * gSiz);
     const int npix = b.nr * b.nc, npix2 = b2.nr * b2.nc;
     int nch, qchunk;
     peel_chunks(nq, nch, qchunk);

@@ -199,10 +199,11 @@ __global__ void __launch_bounds__(256) k_peel_hy_final(float4 *__restrict__ hy4,
     hy4[(int64_t)q * d_b + p] = make_float4(v[0], v[1], v[2], v[3]);
 }
 
-int seed_images_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, int64_t nframes, const double *Q, int32_t M, float sig,
+// src: the video and its geometry -- the centred block of a patch (cnmfe_seed_images, cnmfe_peel_open) or the residual video of a patch (cnmfe_peel_open_residual)
+int seed_images_run(cnmfe_ctx *ctx, const SeedSrc &src, const float *psf, int32_t psf_n, int64_t nframes, const double *Q, int32_t M, float sig,
                     float *Cn_out, float *PNR_out, PeelSession *keep) {
-    const int64_t n = nframes, d_b = P->d_b;
-    const int nr_b = P->nr_b, nc_b = P->nc_b;
+    const int64_t n = nframes, d_b = src.d;
+    const int nr_b = src.nr, nc_b = src.nc;
     const int64_t nq = (n + 3) / 4;
     DeconvCfg c{};
     c.T = (int)n; c.P2 = 1; while (c.P2 < n) c.P2 <<= 1;
@@ -242,7 +243,7 @@ int seed_images_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, i
     int2 *dTaps = reinterpret_cast<int2 *>(sb + o_taps);
     float *dPnr = reinterpret_cast<float *>(sb + o_pnr), *dCn = reinterpret_cast<float *>(sb + o_cn);
     if (M > 0) CK(hipMemcpyAsync(dQ, Q, (size_t)n * M * sizeof(double), hipMemcpyHostToDevice, ctx->st()));
-    const float4 *hy4 = P->Yc4.as<float4>();                                 // gSig <= 0: psf = [] (correlation_image_endoscope.m:45-47,80-82), the video itself
+    const float4 *hy4 = src.y4;                                 // gSig <= 0: psf = [] (correlation_image_endoscope.m:45-47,80-82), the video itself
     if (filt) {
         const size_t need = (size_t)nq * (size_t)d_b * sizeof(float4);
         if (hy.ensure(need) != 0) {
@@ -252,7 +253,7 @@ int seed_images_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, i
         if (!taps.empty()) CK(hipMemcpyAsync(dTaps, taps.data(), taps.size() * sizeof(int2), hipMemcpyHostToDevice, ctx->st()));
         CK(hipStreamSynchronize(ctx->st()));                                 // (`taps` is pageable host memory of this frame)
         LAUNCH(ctx, "seed_filter", k_seed_filter, dim3((unsigned)ntile, (unsigned)nq), dim3(256), (size_t)W * W * sizeof(float4),
-               P->Yc4.as<float4>(), d_b, nr_b, nc_b, ntr, R, dTaps, (int)taps.size(), hy.as<float4>());
+               src.y4, d_b, nr_b, nc_b, ntr, R, dTaps, (int)taps.size(), hy.as<float4>());
         hy4 = hy.as<float4>();
     }
     if (sh_stats > 64 * 1024) CK(hipFuncSetAttribute((const void *)k_seed_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_stats));
@@ -263,7 +264,7 @@ int seed_images_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, i
            dQ, (int)M, dRec, dPart);
     LAUNCH(ctx, "seed_cn", k_seed_cn, dim3((unsigned)((d_b + 255) / 256)), dim3(256), 0, dPart, d_b, nr_b, nc_b, nsplit, (int)n, dCn);
     if (keep) {                                                              // HY of greedyROI_endoscope.m:130 in place, by the arithmetic of the two kernels above
-        if (!filt) CK(hipMemcpyAsync(hy.p, P->Yc4.p, (size_t)nq * (size_t)d_b * sizeof(float4), hipMemcpyDeviceToDevice, ctx->st()));
+        if (!filt) CK(hipMemcpyAsync(hy.p, src.y4, (size_t)nq * (size_t)d_b * sizeof(float4), hipMemcpyDeviceToDevice, ctx->st()));
         LAUNCH(ctx, "peel_hy_final", k_peel_hy_final, dim3((unsigned)((d_b + 255) / 256), (unsigned)nq), dim3(256), 0, hy.as<float4>(), d_b, (int)n, dQ, (int)M, dRec);
     }
     CK(hipMemcpyAsync(Cn_out, dCn, (size_t)d_b * sizeof(float), hipMemcpyDeviceToHost, ctx->st()));

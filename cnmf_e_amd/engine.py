@@ -244,7 +244,7 @@ class Engine:
             raise L.CnmfeError("cnmfe_create failed: " + L.lib.cnmfe_last_error().decode())
         self.device = device
         self._patch = {}
-        self._peel = {}                     # patch id -> frames of its open peel session
+        self._peel = {}                     # patch id -> (frames, rows, columns) of its open peel session: the block, or the patch of a residual session
 
     def close(self):
         if getattr(self, "_ctx", None):
@@ -390,17 +390,33 @@ class Engine:
         Cn = np.empty(info["d_b"], dtype=np.float32); PNR = np.empty(info["d_b"], dtype=np.float32); Sn = np.empty(info["d_b"], dtype=np.float32)
         L.check(L.lib.cnmfe_peel_open(self._ctx, pid, _p(psf_a, L.f32p), psf_n, int(frame0), n, _p(Q_a, L.f64p), M, float(sig),
                                       _p(Cn, L.f32p), _p(PNR, L.f32p), _p(Sn, L.f32p)))
-        self._peel[pid] = n
+        self._peel[pid] = (n, info["nr_b"], info["nc_b"])
         return Cn, PNR, Sn
+
+    def peel_open_residual(self, pid, A_patch, C, psf, sig=3.0, want_video=False):
+        """open the peel session of the SECOND pass on a patch (initComponents_residual_parallel.m:186-220): the session runs on the patch and on
+        Yres = Ysig - A_patch C, Ysig the resident residual (residual() / residual_ssub() first, with the block's current neurons).  A_patch: d x K sparse over the
+        patch rows (None: no neuron), C: their K x T traces.  Returns (Cn, PNR, Sn, Yres): d float32 each, column-major in the patch; Yres (want_video) is the
+        (T, d) float32 video the session searches, else None.  extract / apply then take seeds 0-based in the PATCH.  Closing the session drops the residual."""
+        info = self._patch[pid]
+        _i, n, psf_a, psf_n, _q, _m = self._seed_args(pid, psf, None, None)
+        K, cp, ri, va = _csc(A_patch, info["d"]) if A_patch is not None and A_patch.shape[1] else (0, None, None, None)
+        cptr, cord, _keep = self._targs(C, K, info["T"])
+        Cn = np.empty(info["d"], dtype=np.float32); PNR = np.empty(info["d"], dtype=np.float32); Sn = np.empty(info["d"], dtype=np.float32)
+        out = np.empty((info["T"], info["d"]), dtype=np.float32) if want_video else None
+        dst = out.ctypes.data_as(L.C.c_void_p) if want_video else L.C.c_void_p(None)      # (C is the trace matrix here)
+        L.check(L.lib.cnmfe_peel_open_residual(self._ctx, pid, K, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p), cptr, cord, _p(psf_a, L.f32p), psf_n, float(sig),
+                                               _p(Cn, L.f32p), _p(PNR, L.f32p), _p(Sn, L.f32p), dst, L.HOST))
+        self._peel[pid] = (n, info["nr"], info["nc"])
+        return Cn, PNR, Sn, out
 
     def peel_extract(self, pid, r, c, gSiz):
         """extract_ac.m:19-58 around the 0-based block pixel (r, c): (corr, ai) as nr x nc float64 images of the box, ci (nframes float64), stats = dict of
         max_diff, std_diff (greedyROI_endoscope.m:287-293), norm_ci, sn_ci (GetSn(ci)), n_hi, n_lo (the sizes of {corr > 0.9}, {corr < 0.3})"""
         info = self._patch[pid]
-        nr_b, nc_b = info["nr_b"], info["nc_b"]
+        n, nr_b, nc_b = self._peel.get(pid, (info["T"], info["nr_b"], info["nc_b"]))      # the session's geometry
         r0, r1, c0, c1 = self.peel_box(nr_b, nc_b, int(r), int(c), int(gSiz))
         npix = max(r1 - r0, 0) * max(c1 - c0, 0)
-        n = self._peel.get(pid, info["T"])
         corr = np.empty(max(npix, 1), dtype=np.float64); ai = np.empty(max(npix, 1), dtype=np.float64)
         ci = np.empty(n, dtype=np.float64); st = np.empty(6, dtype=np.float64)
         L.check(L.lib.cnmfe_peel_extract(self._ctx, pid, int(r), int(c), int(gSiz), _p(corr, L.f64p), _p(ai, L.f64p), _p(ci, L.f64p), _p(st, L.f64p)))
@@ -411,13 +427,12 @@ class Engine:
     def peel_apply(self, pid, r, c, gSiz, ai_box, Hai_box2, ci, sig, min_pnr, min_corr):
         """greedyROI_endoscope.m:378-402: subtract ai ci from the working video and Hai ci from HY, return (PNR, Cn) of the (4 gSiz + 1)^2 box as float32 images"""
         info = self._patch[pid]
-        nr_b, nc_b = info["nr_b"], info["nc_b"]
+        n, nr_b, nc_b = self._peel.get(pid, (info["T"], info["nr_b"], info["nc_b"]))      # the session's geometry
         r0, r1, c0, c1 = self.peel_box(nr_b, nc_b, int(r), int(c), int(gSiz))
         s0, s1, t0, t1 = self.peel_box(nr_b, nc_b, int(r), int(c), 2 * int(gSiz))
         ai = np.ascontiguousarray(np.asarray(ai_box, dtype=np.float64).reshape(-1, order="F"))
         hai = np.ascontiguousarray(np.asarray(Hai_box2, dtype=np.float64).reshape(-1, order="F"))
         ci = np.ascontiguousarray(ci, dtype=np.float64)
-        n = self._peel.get(pid, info["T"])
         if ai.size != (r1 - r0) * (c1 - c0) or hai.size != (s1 - s0) * (t1 - t0) or ci.size != n:
             raise ValueError("peel_apply: ai %d, Hai %d, ci %d do not match the boxes %d, %d and %d frames" % (ai.size, hai.size, ci.size, (r1 - r0) * (c1 - c0), (s1 - s0) * (t1 - t0), n))
         pnr = np.empty(max(hai.size, 1), dtype=np.float32); cn = np.empty(max(hai.size, 1), dtype=np.float32)

@@ -924,6 +924,59 @@ class Sources2D:
         both = self._allreduce(np.stack([Cn, PNR]))
         return both[0].reshape(v.d1, v.d2, order="F"), both[1].reshape(v.d1, v.d2, order="F")
 
+    def _init_deconv(self):
+        """the deconvolution of one accepted trace (greedyROI_endoscope.m:355-364) both initialisations hand to hostops.greedy_roi_block: ci_raw -> (ci, ci_raw - b,
+        si, kernel parameter), or None without deconv_flag"""
+        o = self.options
+        if not o.deconv_flag:
+            return None
+
+        def deconv(ci_raw):
+            c_, r_, s_, kp_, _sn = self.engine.deconv_temporal(np.asarray(ci_raw, dtype=np.float32)[None, :], o.deconv_options)
+            return c_[0].astype(np.float64), r_[0].astype(np.float64), s_[0].astype(np.float64), float(kp_[0])
+        return deconv
+
+    def _stitch_init(self, per_patch, n):
+        """the collection both initialisations share (initComponents_parallel.m:410-469, initComponents_residual_parallel.m:345-398): per_patch[idx] = (the
+        result of hostops.greedy_roi_block, the neurons of it that are kept, the 1-based FOV position (r0, c0) of the rectangle the result's coordinates refer to);
+        patches in column-major order, neurons by discovery.  Sharded: one all-reduce of the counts, the all-gather of A, one all-reduce of the packed rows.
+        Returns (A d x K csc, C, C_raw, S (K x n float32), kernel_pars, center (K x 2, 1-based FOV))."""
+        v, o = self.video, self.options
+        d = v.d1 * v.d2
+        sharded = self.dist is not None and (v.world_size > 1 or self.force_collectives)
+        counts = np.zeros(len(v.order), dtype=np.int64)
+        for i, idx in enumerate(v.order):
+            if idx in per_patch:
+                counts[i] = len(per_patch[idx][1])
+        if sharded:
+            counts = np.rint(self._allreduce(counts.astype(np.float64))).astype(np.int64)
+        first = np.concatenate([[0], np.cumsum(counts)])                  # :466-469: patches in column-major order, neurons by discovery
+        Ktot = int(first[-1])
+        rows, cols, vals = [], [], []
+        Cm = np.zeros((Ktot, n), dtype=np.float32); Craw = np.zeros((Ktot, n), dtype=np.float32); Sm = np.zeros((Ktot, n), dtype=np.float32)
+        kp = np.zeros(Ktot, dtype=np.float64); center = np.zeros((Ktot, 2), dtype=np.float64)
+        for i, idx in enumerate(v.order):
+            if idx not in per_patch:
+                continue
+            res, keep, (br0, bc0) = per_patch[idx]
+            for j, k in enumerate(keep):
+                col = int(first[i]) + j
+                (r0, r1, c0, c1), ai = res["A"][k]
+                rr, cc = np.nonzero(ai)
+                rows.append((cc + c0 + bc0 - 1) * v.d1 + (rr + r0 + br0 - 1)); cols.append(np.full(rr.size, col)); vals.append(ai[rr, cc])
+                Cm[col] = res["C"][k]; Craw[col] = res["C_raw"][k]
+                if o.deconv_flag:
+                    Sm[col] = res["S"][k]; kp[col] = res["kernel_pars"][k]
+                center[col] = (res["center"][k, 0] + br0 - 1, res["center"][k, 1] + bc0 - 1)      # :461
+        A = (sp.csc_matrix((np.concatenate(vals).astype(np.float32), (np.concatenate(rows), np.concatenate(cols))), shape=(d, Ktot)) if rows
+             else sp.csc_matrix((d, Ktot), dtype=np.float32))
+        if sharded:
+            A = sp.csc_matrix(self._gather_sparse(A), dtype=np.float32)
+            pack = self._allreduce(np.concatenate([Cm, Craw, Sm, kp[:, None].astype(np.float32), center.astype(np.float32)], axis=1))
+            Cm, Craw, Sm = (np.ascontiguousarray(pack[:, i * n:(i + 1) * n]) for i in range(3))
+            kp, center = pack[:, 3 * n].astype(np.float64), pack[:, 3 * n + 1:3 * n + 3].astype(np.float64)
+        return A, Cm, Craw, Sm, kp, center
+
     def initComponents_parallel(self, K=None, frame_range=None, seeds=None, use_prev=False, save_avi=False, debug_on=False):
         """[center, Cn, PNR] = obj.initComponents_parallel(K, frame_range, save_avi, use_parallel, use_prev)  (@Sources2D/initComponents_parallel.m:200-203,
         308-352,410-484 -> endoscope/greedyROI_endoscope.m): the greedy initialisation of every owned patch on the device's peel session of its block
@@ -959,11 +1012,7 @@ class Sources2D:
         psf = seed_psf(float(o.gSig), float(o.gSiz), bool(o.center_psf))
         Q = np.linalg.qr(bspline_basis(n, nk))[0] if nk > 1 else None
         connected = bool(o.spatial_constraints.get("connected", True))
-        deconv = None
-        if o.deconv_flag:                                                 # greedyROI_endoscope.m:355-364
-            def deconv(ci_raw):
-                c_, r_, s_, kp_, _sn = self.engine.deconv_temporal(np.asarray(ci_raw, dtype=np.float32)[None, :], o.deconv_options)
-                return c_[0].astype(np.float64), r_[0].astype(np.float64), s_[0].astype(np.float64), float(kp_[0])
+        deconv = self._init_deconv()
         d = v.d1 * v.d2
         Cn = np.zeros(d, dtype=np.float64); PNR = np.zeros(d, dtype=np.float64)
         per_patch = {}
@@ -991,38 +1040,8 @@ class Sources2D:
             ctr = res["center"]
             keep = [k for k in range(ctr.shape[0]) if int(pp[0]) <= ctr[k, 0] + int(bp[0]) - 1 <= int(pp[1]) and int(pp[2]) <= ctr[k, 1] + int(bp[2]) - 1 <= int(pp[3])]
             per_patch[idx] = (res, keep, (int(bp[0]), int(bp[2])))
-        sharded = self.dist is not None and (v.world_size > 1 or self.force_collectives)
-        counts = np.zeros(len(v.order), dtype=np.int64)
-        for i, idx in enumerate(v.order):
-            if idx in per_patch:
-                counts[i] = len(per_patch[idx][1])
-        if sharded:
-            counts = np.rint(self._allreduce(counts.astype(np.float64))).astype(np.int64)
-        first = np.concatenate([[0], np.cumsum(counts)])                  # :466-469: patches in column-major order, neurons by discovery
-        Ktot = int(first[-1])
-        rows, cols, vals = [], [], []
-        Cm = np.zeros((Ktot, n), dtype=np.float32); Craw = np.zeros((Ktot, n), dtype=np.float32); Sm = np.zeros((Ktot, n), dtype=np.float32)
-        kp = np.zeros(Ktot, dtype=np.float64); center = np.zeros((Ktot, 2), dtype=np.float64)
-        for i, idx in enumerate(v.order):
-            if idx not in per_patch:
-                continue
-            res, keep, (br0, bc0) = per_patch[idx]
-            for j, k in enumerate(keep):
-                col = int(first[i]) + j
-                (r0, r1, c0, c1), ai = res["A"][k]
-                rr, cc = np.nonzero(ai)
-                rows.append((cc + c0 + bc0 - 1) * v.d1 + (rr + r0 + br0 - 1)); cols.append(np.full(rr.size, col)); vals.append(ai[rr, cc])
-                Cm[col] = res["C"][k]; Craw[col] = res["C_raw"][k]
-                if o.deconv_flag:
-                    Sm[col] = res["S"][k]; kp[col] = res["kernel_pars"][k]
-                center[col] = (res["center"][k, 0] + br0 - 1, res["center"][k, 1] + bc0 - 1)      # :461
-        A = (sp.csc_matrix((np.concatenate(vals).astype(np.float32), (np.concatenate(rows), np.concatenate(cols))), shape=(d, Ktot)) if rows
-             else sp.csc_matrix((d, Ktot), dtype=np.float32))
-        if sharded:
-            A = sp.csc_matrix(self._gather_sparse(A), dtype=np.float32)
-            pack = self._allreduce(np.concatenate([Cm, Craw, Sm, kp[:, None].astype(np.float32), center.astype(np.float32)], axis=1))
-            Cm, Craw, Sm = (np.ascontiguousarray(pack[:, i * n:(i + 1) * n]) for i in range(3))
-            kp, center = pack[:, 3 * n].astype(np.float64), pack[:, 3 * n + 1:3 * n + 3].astype(np.float64)
+        A, Cm, Craw, Sm, kp, center = self._stitch_init(per_patch, n)
+        Ktot = A.shape[1]
         both = self._allreduce(np.stack([Cn, PNR]))
         Cn, PNR = both[0].reshape(v.d1, v.d2, order="F"), both[1].reshape(v.d1, v.d2, order="F")
         A.sort_indices()
@@ -1038,6 +1057,96 @@ class Sources2D:
             self.S = np.zeros_like(Cm)
         self.Cn = Cn                                                      # :481
         self.ids = np.arange(1, Ktot + 1); self.tags = np.zeros(Ktot, dtype=np.uint16); self.P["k_ids"] = Ktot      # :482-485
+        return center, Cn, PNR
+
+    def initComponents_residual_parallel(self, K=None, min_corr=None, min_pnr=None, seed_method=None, seeds=None, save_avi=False):
+        """[center, Cn, PNR] = obj.initComponents_residual_parallel(K, save_avi, use_parallel, min_corr, min_pnr, seed_method)
+        (@Sources2D/initComponents_residual_parallel.m:47-64,106-121,165-220,345-412, ring model): the second pass that picks the neurons the first one missed.
+        Per owned patch the residual of the block's current neurons is requested (cnmfe_residual[_ssub]), the device's peel session is opened on the PATCH and on
+        Yres = Ysig - A(patch, ind) C(ind, :) (Engine.peel_open_residual), and the greedy search runs as in initComponents_parallel (hostops.greedy_roi_block)
+        with bd = options.bd * [first row, last row, first column, last column of the patch grid] (:173), all frames and no detrending.  Every neuron found is
+        kept (patches do not overlap); the new columns and rows are APPENDED to A, C, C_raw, S, P.kernel_pars (deconv_flag), ids continue from P.k_ids, tags
+        grow by zeros (:393-412); obj.Cn, A_prev, C_prev, W and b0 stay.  Returns (center of the new neurons, Cn, PNR) in FOV coordinates (1-based), the images
+        being the sessions' opening images placed by patch.  K: the maximum number of new neurons PER PATCH (None: the patch's pixel count, :61-64).
+        min_corr, min_pnr, seed_method: when given they overwrite the options and stay overwritten (:47-55) -- first of all, as in the reference, so a call that is
+        then refused (seed_method = 'manual' without seeds) has changed them all the same.  seeds: as in initComponents_parallel, tried by the
+        patch that holds them.  Not built (NotImplementedError): ssub / tsub other than 1, save_avi."""
+        from . import hostops
+        self._need_data()
+        v, o = self.video, self.options
+        if int(o.ssub) != 1 or int(o.tsub) != 1:
+            raise NotImplementedError("initComponents_residual_parallel: ssub / tsub other than 1 are not built")
+        if save_avi:
+            raise NotImplementedError("initComponents_residual_parallel: save_avi is not built")
+        if min_corr is not None:                                          # :47-55
+            o.min_corr = float(min_corr)
+        if min_pnr is not None:
+            o.min_pnr = float(min_pnr)
+        if seed_method is not None:
+            o.seed_method = seed_method
+        if seeds is None and str(o.seed_method).lower() == "manual":
+            raise ValueError("seed_method = 'manual' needs the seed pixels: initComponents_residual_parallel(seeds=[(r, c), ...])")
+        n = v.T
+        gSiz = int(_mround(float(o.gSiz)))
+        bd = gSiz if o.bd is None else int(o.bd)                          # :80-83
+        psf = seed_psf(float(o.gSig), float(o.gSiz), bool(o.center_psf))
+        connected = bool(o.spatial_constraints.get("connected", True))
+        deconv = self._init_deconv()
+        d = v.d1 * v.d2
+        Cn = np.zeros(d, dtype=np.float64); PNR = np.zeros(d, dtype=np.float64)
+        per_patch = {}
+        observer = getattr(self, "_init_observer", None)                  # tests (the hook of initComponents_parallel): (patch idx, kind, data) at every open /
+        want_video = observer is not None                                 # extract / apply; an observer is also handed the video every session was opened on
+        for idx in v.owned:
+            pid = v.pid[idx]
+            pp = [int(x) for x in v.patch_pos[idx]]
+            nr, nc = pp[1] - pp[0] + 1, pp[3] - pp[2] + 1
+            ind, A_blk = self._slice(self.A, idx, "block")                # :116-117
+            C_blk = self._rows(self.C, ind) if ind.size else None         # :120
+            self._residual(idx, A_blk if ind.size else None, C_blk)       # :199-217 without A(patch, ind) C: the resident Ysig (it goes with the session: tag None)
+            A_pp = self._slice(self.A, idx, "patch", cols=ind)[1] if ind.size else None
+            cn_p, pnr_p, _sn_p, yres = self.engine.peel_open_residual(pid, A_pp, C_blk, psf, 3.0, want_video=want_video)
+            try:
+                if observer is not None:
+                    observer(idx, "open", dict(Cn=cn_p, PNR=pnr_p, Yres=yres))
+                Cn[v.patch_pix[idx]] = cn_p
+                PNR[v.patch_pix[idx]] = pnr_p
+                bd4 = [bd * int(f) for f in (idx[0] == 0, idx[0] == v.nr_patch - 1, idx[1] == 0, idx[1] == v.nc_patch - 1)]      # :173
+                loc = None
+                if seeds is not None:
+                    loc = [(int(r) - pp[0], int(c) - pp[2]) for (r, c) in seeds if pp[0] <= int(r) <= pp[1] and pp[2] <= int(c) <= pp[3]]
+                sess = _PeelSession(self.engine, pid, gSiz)
+                res = hostops.greedy_roi_block(sess, cn_p.astype(np.float64).reshape(nr, nc, order="F"), pnr_p.astype(np.float64).reshape(nr, nc, order="F"),
+                                               gSiz, psf, float(o.min_corr), float(o.min_pnr), float(o.min_pixel), bd4, nr * nc if K is None else K, connected,
+                                               deconv, loc, 3.0, None if observer is None else (lambda kind, data, idx=idx: observer(idx, kind, data)))
+            finally:
+                self.engine.peel_close(pid)
+            keep = [k for k in range(res["center"].shape[0]) if np.any(res["A"][k][1])]      # :362-363
+            per_patch[idx] = (res, keep, (pp[0], pp[2]))
+        A_new, Cm, Craw, Sm, kp, center = self._stitch_init(per_patch, n)
+        both = self._allreduce(np.stack([Cn, PNR]))
+        Cn, PNR = both[0].reshape(v.d1, v.d2, order="F"), both[1].reshape(v.d1, v.d2, order="F")
+        A_new.sort_indices()
+        K_old, K_new = self.A.shape[1], A_new.shape[1]
+        C_old = np.asarray(self.C, dtype=np.float32)
+        Craw_old = C_old if self.C_raw is self.C else np.asarray(self.C_raw, dtype=np.float32)
+        S_old = getattr(self, "S", None)
+        S_old = np.asarray(S_old, dtype=np.float32) if S_old is not None and np.shape(S_old) == (K_old, n) else np.zeros((K_old, n), dtype=np.float32)
+        if K_new:
+            A_all = sp.hstack([sp.csc_matrix(self.A), A_new], format="csc", dtype=np.float32)                   # :393
+            self.set_components(A_all, np.concatenate([C_old, Cm]), np.concatenate([Craw_old, Craw]))          # :394-395
+        self.S = np.concatenate([S_old, Sm if o.deconv_flag else np.zeros_like(Cm)])                          # :396-403
+        if o.deconv_flag:
+            kp_old = self.P.get("kernel_pars")
+            kp_old = np.asarray(kp_old, dtype=np.float64).reshape(-1) if kp_old is not None and len(kp_old) == K_old else np.zeros(K_old, dtype=np.float64)
+            self.P["kernel_pars"] = np.concatenate([kp_old, kp])
+        k_ids = int(self.P.get("k_ids", K_old))                           # :404-408
+        ids_old = getattr(self, "ids", None)
+        ids_old = np.asarray(ids_old) if ids_old is not None and len(ids_old) == K_old else np.arange(1, K_old + 1)
+        tags_old = getattr(self, "tags", None)
+        tags_old = np.asarray(tags_old, dtype=np.uint16) if tags_old is not None and len(tags_old) == K_old else np.zeros(K_old, dtype=np.uint16)
+        self.ids = np.concatenate([ids_old, k_ids + np.arange(1, K_new + 1)]); self.tags = np.concatenate([tags_old, np.zeros(K_new, dtype=np.uint16)])
+        self.P["k_ids"] = k_ids + K_new
         return center, Cn, PNR
 
     def reconstruct_b0(self):

@@ -175,10 +175,26 @@ int cnmfe_seed_images(cnmfe_ctx *ctx, int patch_id, const float *psf, int32_t ps
  * PNR_box2 = max(HY) / Sn (NaN or < min_pnr -> 0, :391-393) and Cn_box2 = the 8-neighbour correlation image of HY(box2) thresholded at sig Sn, the box
  * taken as a whole image (:396-401; NaN or < min_corr -> 0).
  *
- * gSiz > 20 is CNMFE_EUNSUPPORTED; extract / apply / close without a session are CNMFE_ESTATE.  Every reduction runs in a fixed order: two identical
+ * cnmfe_peel_open_residual: the session of the SECOND pass (@Sources2D/initComponents_residual_parallel.m:186-220), on the PATCH (nr x nc, d pixels) and on
+ *   Yres = Ysig - A(patch, ind) C(ind, :)                                                   (:199 on the patch rows, after :206 / :209-217)
+ * with Ysig the resident residual of cnmfe_residual / cnmfe_residual_ssub (called with the block's current neurons; CNMFE_ESTATE without one, a recorded or
+ * pending one is realised first, as for cnmfe_get_sn).  A: d x Ksel CSC over the PATCH rows (empty columns are legal: a neuron that only touches the halo), C as
+ * for cnmfe_residual; Ksel = 0 searches Ysig itself.  Per pixel the stored neurons are summed in fp64 in ascending column order and the difference is rounded
+ * once to fp32; Ysig is only read.  All T frames are used (64 <= T <= 20400), there is no detrending (M = 0), y_bg takes no pixel mean (the residual carries its
+ * own), and extract / apply take the seed 0-BASED in the PATCH and clip their boxes at the patch (tmp_options.d1 / d2, :176-177).  Cn_patch / PNR_patch /
+ * Sn_patch: d floats (Sn may be NULL); Yres_out (may be NULL): exactly the fp32 video the session searches, d x T frame-major like cnmfe_residual's output, to
+ * host or device memory (out_memspace).  The session keeps 2 x 16 * ceil(T / 4) * d bytes (HY and Yw, which starts as Yres; CNMFE_ENOMEM names them).  The
+ * residual request belongs to the session: cnmfe_peel_close -- and an open that fails after the residual was realised -- drops it as a background fit does
+ * (a NEW side effect of cnmfe_peel_close, for residual sessions only), so the next update requests its own and sees the patch as it would have without the
+ * session; W, b0 and every table of the fit stay untouched.
+ *
+ * gSiz > 20 is CNMFE_EUNSUPPORTED; extract / apply / close without a session are CNMFE_ESTATE, a seed outside the session's geometry is CNMFE_EINVAL.  Every reduction runs in a fixed order: two identical
  * sessions are bit-identical.  The calls run on the patch's lane. */
 int cnmfe_peel_open(cnmfe_ctx *ctx, int patch_id, const float *psf, int32_t psf_n, int64_t frame0, int64_t nframes,
                     const double *Q, int32_t M, float sig, float *Cn_block /* d_b */, float *PNR_block /* d_b */, float *Sn_block /* d_b or NULL */);
+int cnmfe_peel_open_residual(cnmfe_ctx *ctx, int patch_id, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx /* in [0, d) */, const float *A_val,
+                             const float *C, int c_order, const float *psf, int32_t psf_n, float sig, float *Cn_patch /* d */, float *PNR_patch /* d */,
+                             float *Sn_patch /* d or NULL */, float *Yres_out /* d x T or NULL */, int out_memspace);
 int cnmfe_peel_extract(cnmfe_ctx *ctx, int patch_id, int32_t r, int32_t c, int32_t gSiz, double *corr_box /* nr * nc */, double *ai_box /* nr * nc */,
                        double *ci /* nframes */, double *stats /* 6 */);
 int cnmfe_peel_apply(cnmfe_ctx *ctx, int patch_id, int32_t r, int32_t c, int32_t gSiz, const double *ai_box /* nr * nc */,
