@@ -26,6 +26,8 @@ class _Lib:
                 "Run `python -m cnmf_e_amd.build` (needs hipcc)." % LIB_PATH)
         dll = C.CDLL(LIB_PATH)
         for name, (res, args) in PROTOTYPES.items():
+            if name in OPTIONAL and not hasattr(dll, name):
+                continue                     # (an older build of the ABI behind CNMFE_LIB: the engine asks with hasattr and leaves the feature off)
             fn = getattr(dll, name)          # AttributeError here == missing export
             fn.restype = res
             fn.argtypes = args
@@ -138,7 +140,12 @@ PROTOTYPES = {
     "cnmfe_profile_get": (C.c_int, [c_ctx, C.c_int, C.c_char_p, C.c_int, f64p, i64p]),
     "cnmfe_synchronize": (C.c_int, [c_ctx]),
     "cnmfe_set_option": (C.c_int, [c_ctx, C.c_char_p, C.c_int64]),
+    "cnmfe_get_option": (C.c_int, [c_ctx, C.c_char_p, C.POINTER(C.c_int64)]),
+    "cnmfe_temporal_early_project": (C.c_int, [c_ctx, C.c_int32, i64p, i32p, C.POINTER(C.c_int64)]),
+    "cnmfe_temporal_early_claim": (C.c_int, [c_ctx, C.c_int64]),
 }
+# exports younger than the oldest build CNMFE_LIB is used with (A/B runs against the parent commit's library)
+OPTIONAL = {"cnmfe_get_option", "cnmfe_temporal_early_project", "cnmfe_temporal_early_claim"}
 
 # enums of include/cnmfe.h
 F32, F64, U16, U8, F16 = 0, 1, 2, 3, 4

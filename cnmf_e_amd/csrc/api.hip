@@ -347,6 +347,7 @@ static int errflag_raise(cnmfe_ctx *ctx, int h, bool taken = false) {
     // be trusted by a later call -- the next residual sweeps again, the next spatial update builds its own table
     for (auto &kv : ctx->patches) { Patch *q = kv.second; q->ysig_valid = false; q->ysig_virtual = false; q->pend = false; q->res_ac = false; q->res_kind = 0; q->pt_valid = false; }
     ctx->bgs_patch = -1;
+    if (h & 8) return fail(CNMFE_EHIP, "temporal update: the device's aa = diag(A'A) disagrees with the host-side test of a column (flag %d)", h);
     if (h & 2) return fail(CNMFE_EUNSUPPORTED, "a pixel's ring touches more than 256 footprints of A_prev (flag %d)", h);
     if (h & 4) return fail(CNMFE_EUNSUPPORTED, "bg_ssub > 1: a pixel's interpolation window meets more than 64 footprints of A_prev (flag %d)", h);
     return fail(CNMFE_ESTATE, "a kernel met an inconsistent table (flag %d): the ring regression needed a block pair the covariance table does not hold", h);
@@ -634,11 +635,23 @@ int cnmfe_synchronize(cnmfe_ctx *ctx) {
 int cnmfe_set_option(cnmfe_ctx *ctx, const char *name, int64_t value) {
     if (!ctx || !name) return fail(CNMFE_EINVAL, "null argument");
     // behaviour switches (include/cnmfe.h) and, behind them, the probes of scripts/ (diagnostics: solve_probe, r1_probe, deconv_trace, host_trace, debug)
-    static const char *known[] = {"r1_variant", "r1_delta", "r1_lazy", "r1_defer", "r1_virtual", "gram_incremental", "prealloc", "solve_packed", "sweep_dag", "win_i8_planes", "solve_staged", "solve_inv", "solve_inv_terms", "gram_i8", "win_i8", "proj_tiled", "proj_i8", "proj_i8_planes", "ssub_virtual",
+    static const char *known[] = {"r1_variant", "r1_delta", "r1_lazy", "r1_defer", "r1_virtual", "gram_incremental", "prealloc", "solve_packed", "sweep_dag", "win_i8_planes", "solve_staged", "solve_inv", "solve_inv_terms", "gram_i8", "win_i8", "proj_tiled", "proj_i8", "proj_i8_planes", "ssub_virtual", "temporal_early",
                                   "solve_probe", "r1_probe", "deconv_trace", "host_trace", "debug", nullptr};
     if (!strcmp(name, "lanes")) { RET(lanes_set(ctx, value)); ctx->opts[name] = value; return 0; }
     for (int i = 0; known[i]; ++i) if (!strcmp(known[i], name)) { ctx->opts[name] = value; if (!strcmp(name, "host_trace")) ctx->trace_level = (int)value; return 0; }
     return fail(CNMFE_EINVAL, "unknown option '%s'", name);
+}
+
+// what cnmfe_set_option gave an option last (CNMFE_OPTS included), and the read-only counters of the hand-over between the spatial and the temporal update
+int cnmfe_get_option(cnmfe_ctx *ctx, const char *name, int64_t *value) {
+    if (!ctx || !name || !value) return fail(CNMFE_EINVAL, "null argument");
+    const struct { const char *n; int64_t v; } counters[] = {{"temporal_early_hits", ctx->early_hits}, {"temporal_early_drops", ctx->early_drops}, {"temporal_early_declined", ctx->early_declined},
+                                                              {"temporal_early_entries", ctx->early_nent}, {"temporal_proj_entries", ctx->last_nent}, {"temporal_nowait", ctx->sweep_nowait}};
+    for (const auto &c : counters) if (!strcmp(c.n, name)) { *value = c.v; return 0; }
+    auto it = ctx->opts.find(name);
+    if (it == ctx->opts.end()) return fail(CNMFE_EINVAL, "option '%s' is unknown or was never set (its default holds)", name);
+    *value = it->second;
+    return 0;
 }
 
 int cnmfe_patch_create(cnmfe_ctx *ctx, int patch_id, const int32_t pr[4], const int32_t br[4], int32_t d1, int32_t d2, int64_t T) {
@@ -650,6 +663,7 @@ int cnmfe_patch_create(cnmfe_ctx *ctx, int patch_id, const int32_t pr[4], const 
                     pr[0], pr[1], pr[2], pr[3], br[0], br[1], br[2], br[3], d1, d2);
     CK(hipSetDevice(ctx->device));
     if (ctx->patches.count(patch_id)) { delete ctx->patches[patch_id]; ctx->patches.erase(patch_id); }
+    ctx->early.valid = false; ctx->spatial_patch = nullptr;  // (they may name the patch that just went)
     Patch *P = new Patch();
     P->lane = ctx->lanes.empty() ? 0 : (ctx->patches_created++ % (int)ctx->lanes.size());
     memcpy(P->prect, pr, sizeof(P->prect)); memcpy(P->brect, br, sizeof(P->brect));
@@ -1180,6 +1194,21 @@ int cnmfe_update_spatial_fetch_connected_async(cnmfe_ctx *ctx, int32_t d1, int32
     RET(ctx->activate(ctx->spatial_lane));
     RET(spatial_fetch_connected(ctx, d1, d2, K, IND_colptr, IND_rowidx, A_out_pinned, keep_out_pinned, false));
     return ticket_record(ctx, ticket);
+}
+
+int cnmfe_temporal_early_project(cnmfe_ctx *ctx, int32_t K, const int64_t *IND_colptr, const int32_t *IND_rowidx, int64_t *token) {
+    if (!ctx || !token) return fail(CNMFE_EINVAL, "null context / token");
+    *token = 0;
+    if (K <= 0 || !IND_colptr || !IND_rowidx) return fail(CNMFE_EINVAL, "bad K / null IND");
+    if (!ctx->lanes.empty()) return 0;                       // (declined: the result of a lane's spatial update lies in that lane's scratch)
+    CK(hipSetDevice(ctx->device));
+    return temporal_early_project(ctx, K, IND_colptr, IND_rowidx, token);
+}
+
+int cnmfe_temporal_early_claim(cnmfe_ctx *ctx, int64_t token) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    if (token > 0 && ctx->early.valid && ctx->early.token == token) ctx->early.claimed = token;
+    return 0;
 }
 
 int cnmfe_hals_temporal(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx,

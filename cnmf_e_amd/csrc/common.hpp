@@ -181,6 +181,7 @@ struct Patch {
     DevBuf pt_tab, pt_lp, pt_slot;
     bool pt_valid = false; int32_t pt_K = 0; int64_t pt_gen = -1;
     std::vector<int32_t> pt_rows; std::vector<int> pt_lp_h; std::vector<short> pt_slot_h;
+    int64_t res_gen = 0;               // counts the residual requests of this patch (residual_run, ssub_residual): what a projection queued ahead of its consumer is valid for
     bool res_ac = false; int res_kind = 0; int64_t res_ldc = 0;    // res_kind: who wrote Ysig and the term beside it: 1 = cnmfe_residual, 2 = cnmfe_residual_ssub (0: no term kept)
     DevBuf resCnt, resK, resV, resCc, resCm;              // resCm: the means the centred traces were taken about (fp64, per trace)
     // a footprint term asked for by the last cnmfe_residual but not yet folded into Ysig: cnmfe_hals_temporal only needs A' Ysig and adds
@@ -362,6 +363,19 @@ struct cnmfe_ctx {
     // the traces the last cnmfe_hals_temporal[_deconv] / cnmfe_fast_temporal left on the device (C_raw rows, row stride last_t_ldc, and aa): what
     // cnmfe_stitch_add folds into the stitch accumulator without a host round trip
     cnmfe::DevBuf last_craw, last_aa;
+    // The temporal projection queued behind the connectivity kernel (option temporal_early, factor.hip: temporal_early_project; DESIGN.md section 3, "the hand-over").
+    // early_a: keep ? value : 0 on the mask's pattern; early_u: U = B' Yc of exactly those values.  Nothing else writes either.  The tag says what early_u is valid
+    // for; temporal_run takes it only when the caller claimed the token (its A IS that spatial result) and every field still holds, and drops it otherwise.
+    struct EarlyU {
+        bool valid = false; int64_t token = 0, claimed = 0;
+        cnmfe::Patch *P = nullptr; int32_t K = 0; int64_t ldc = 0, T = 0, spatial_gen = 0, res_gen = 0;      // res_gen: W, b0 and the video only change in front of a new residual request
+        int64_t proj_i8 = 0, proj_i8_planes = 0, proj_tiled = 0;                                             // the options that select the projection kernel
+    } early;
+    cnmfe::DevBuf early_a, early_u;
+    cnmfe::Patch *spatial_patch = nullptr; int32_t spatial_K = 0;        // what spatial_run recorded: the patch and K of the result in scr[6]
+    int64_t spatial_gen = 0, conn_gen = -1;                              // spatial results so far; the one whose keep flags lie in scr[14] with its pattern still in scr[0], scr[1] (-1: none)
+    int64_t last_nent = 0;                                               // (block, neuron) entries of the last vproj_temporal
+    int64_t early_seq = 0, early_hits = 0, early_drops = 0, early_declined = 0, early_nent = 0, sweep_nowait = 0;   // counters (cnmfe_get_option)
     std::vector<cnmfe::TemporalJob *> tjobs; int tjobs_used = 0;          // cnmfe_hals_temporal_job: kept (with their buffers) from update to update, counted from cnmfe_stitch_begin
     cnmfe::DevBuf dcv_c, dcv_s, dcv_pars, dcv_sn;          // cnmfe_deconv_temporal_bound: C_raw - b (after the swap with `bound`), S, kernel_pars, sn -- read by the copy stream, so not shared scratch
     int32_t last_t_K = 0; int64_t last_t_ldc = 0, last_t_T = 0; bool last_t_valid = false;
@@ -504,6 +518,7 @@ int peel_apply_run(cnmfe_ctx *ctx, Patch *P, int r, int c, int gSiz, const doubl
                    double min_corr, float *PNR_box2, float *Cn_box2);
 int spatial_fetch(cnmfe_ctx *ctx, float *A_out, int64_t nnz);
 int spatial_fetch_connected(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *IND_colptr, const int32_t *IND_rowidx, float *A_out, uint8_t *keep, bool wait = true);
+int temporal_early_project(cnmfe_ctx *ctx, int32_t K, const int64_t *IND_colptr, const int32_t *IND_rowidx, int64_t *token);   // factor.hip; *token = 0: declined
 int ring_first_run(cnmfe_ctx *ctx, Patch *P, bool *first);
 int ring_stats_enqueue(cnmfe_ctx *ctx, Patch *P);                    // after W changed on the stream: count + row 1 to pinned memory, event
 int ring_stats_get(cnmfe_ctx *ctx, Patch *P, int *pmax, bool *first); // waits for that event only (falls back to a fresh evaluation)

@@ -221,6 +221,23 @@ __global__ void __launch_bounds__(256) k_ata_pairs(const int64_t *__restrict__ c
     if (lane == 0) nval[i] = (float)s;
 }
 
+// aa(k) = V(k,k) = nval[diag[k]], taken on the device so that the levels can be queued without a wait for A'A.  code[k] = diag[k] when the host's test of the
+// column (some stored value squares to a non-zero float) says the neuron is updated, ~diag[k] when not: a disagreement raises bit 8 of the context's error word
+__global__ void __launch_bounds__(256) k_aa_gather(const float *__restrict__ nval, const int *__restrict__ code, int K, float *__restrict__ aa, int *__restrict__ err) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= K) return;
+    const int c = code[k];
+    const bool upd = c >= 0;
+    const float a = nval[upd ? c : ~c];
+    aa[k] = a;
+    if ((a > 0.f) != upd) atomicOr(err, 8);
+}
+// keep ? value : 0 on the mask's pattern: the post-processed footprints where the spatial update left them, in a buffer of their own
+__global__ void __launch_bounds__(256) k_keep_values(const float *__restrict__ aval, const unsigned char *__restrict__ keep, int64_t nnz, float *__restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < nnz) out[e] = keep[e] ? aval[e] : 0.f;
+}
+
 // ---- T3: one Gauss-Seidel level of HALS_temporal (no-deconvolution branch :62-68) --------------------
 constexpr int HT_NB = 64;        // neighbours of a neuron staged in LDS (more: read from the lists in global memory)
 constexpr int HT_NR = 12;        // frames per thread kept in registers
@@ -509,6 +526,7 @@ int spatial_run(cnmfe_ctx *ctx, Patch *P, int algorithm, int32_t K, const int64_
                 const float *sn, int32_t param, float *A_out) {
     const int64_t T = P->T, d = P->d, nnz = IND_colptr[K];
     ctx->spatial_nnz = nnz == 0 ? 0 : -1;
+    ++ctx->spatial_gen; ctx->spatial_patch = P; ctx->spatial_K = K; ctx->conn_gen = -1; ctx->early.valid = false;      // (a new result: what was queued ahead for the last one is void)
     if (nnz == 0) return 0;
     if (nnz >= (int64_t(1) << 31)) return fail(CNMFE_EUNSUPPORTED, "nnz(IND) too large");
     DevBuf &dC = ctx->tmp[0], &dCc = ctx->tmp[1], &dCm = ctx->tmp[2];
@@ -659,6 +677,7 @@ int fast_temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colp
     }
     DevBuf *S_ = ctx->scr;
     DevBuf &dColptr = S_[0], &dErow = S_[1], &dAval = S_[6], &dU = ctx->last_craw, &dInv = S_[13];
+    ctx->conn_gen = -1;                                      // (scr[0], scr[1], scr[6] change hands)
     const int64_t ldc = (T + 3) & ~int64_t(3);
     RET(to_dev(ctx, dColptr, A_colptr, (size_t)K + 1));
     RET(to_dev(ctx, dErow, A_rowidx, (size_t)nnz));
@@ -688,19 +707,36 @@ int temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, c
     // a job (cnmfe_hals_temporal_job) works in buffers of its own and stops in front of the sweeps: temporal_sweep_jobs runs them for all jobs together
     DevBuf *S_ = ctx->scr;
     DevBuf &dC = job ? job->dC : ctx->tmp[0];
-    DevBuf &dColptr = job ? job->dColptr : S_[0], &dErow = job ? job->dErow : S_[1], &dAval = job ? job->dAval : S_[6], &dU = job ? job->dU : S_[7],
+    DevBuf &dColptr = job ? job->dColptr : S_[0], &dErow = job ? job->dErow : S_[1], &dAval = job ? job->dAval : S_[6], &dU_scr = job ? job->dU : S_[7],
            &dCraw = job ? job->dCraw : ctx->last_craw, &dNk = job ? job->dNk : S_[14], &dNidx = job ? job->dNidx : S_[15], &dNval = job ? job->dNval : S_[16],
            &dNptr = job ? job->dNptr : S_[17], &dAa = job ? job->dAa : ctx->last_aa, &dLvl = S_[12], &dOvf = job ? job->dOvf : S_[18];
     if (!job) ctx->last_t_valid = false;
     HostTrace ht(ctx, "temporal");
     int64_t ldc;
     RET(upload_traces(ctx, dC, C_in, K, T, c_order, &ldc));
+    // the hand-over (option temporal_early): U = B' Yc of exactly this A may already be queued behind the spatial update's connectivity kernel
+    // (temporal_early_project).  Taken only when the caller claimed it and the whole tag still holds; dropped otherwise -- never a different value
+    const int64_t te_mode = ctx->opt("temporal_early", 1);
+    bool early_hit = false;
+    if (!job) {
+        cnmfe_ctx::EarlyU &E = ctx->early;
+        if (E.valid) {
+            early_hit = (te_mode == 1 || te_mode == 2) && E.claimed == E.token && E.P == P && E.K == K && E.ldc == ldc && E.T == T && E.spatial_gen == ctx->spatial_gen
+                        && E.res_gen == P->res_gen && nnz > 0 && P->ysig_virtual && P->res_kind == 1 && ctx->lanes.empty()
+                        && !(P->pend && (P->pend_ldc != ldc || (P->res_ac && P->res_ldc != ldc)))                       // (the term would be folded into Ysig below: no virtual residual then)
+                        && E.proj_i8 == ctx->opt("proj_i8", 1) && E.proj_i8_planes == ctx->opt("proj_i8_planes", 3) && E.proj_tiled == ctx->opt("proj_tiled", 1);
+            E.valid = false;                                 // consumed either way
+            ++(early_hit ? ctx->early_hits : ctx->early_drops);
+        }
+        ctx->conn_gen = -1;                                  // (scr[0], scr[1], scr[6], scr[14] change hands below)
+    }
+    DevBuf &dU = early_hit ? ctx->early_u : dU_scr;
     RET(to_dev(ctx, dColptr, A_colptr, (size_t)K + 1));
     RET(to_dev(ctx, dErow, A_rowidx, (size_t)nnz));
     RET(to_dev(ctx, dAval, A_val, (size_t)nnz));
     RET(dU.ensure((size_t)K * ldc * sizeof(float)));
     RET(dCraw.ensure((size_t)K * ldc * sizeof(float)));
-    CK(hipMemsetAsync(dU.p, 0, (size_t)K * ldc * sizeof(float), ctx->st()));
+    if (!early_hit) CK(hipMemsetAsync(dU.p, 0, (size_t)K * ldc * sizeof(float), ctx->st()));
     CK(hipMemsetAsync(dCraw.p, 0, (size_t)K * ldc * sizeof(float), ctx->st()));             // C_raw = zeros(K,T)  (:45)
     // T1
     const int64_t Tc = (T + 3) / 4;
@@ -719,7 +755,7 @@ int temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, c
         if (P->pend && (P->pend_ldc != ldc || (P->res_ac && P->res_ldc != ldc))) RET(residual_materialize(ctx, P));
         // a virtual residual: A' Ysig = B' Yc + A' (Ymean - b0), B = A - W'A, one block-tiled pass over the centred video (vproj.hip)
         bool virt = P->ysig_virtual;
-        if (virt) {
+        if (virt && !early_hit) {
             const int rcv = P->res_kind == 2 ? vproj_temporal_ssub(ctx, P, K, A_colptr, A_rowidx, A_val, dColptr.as<int64_t>(), dErow.as<int>(), dAval.as<float>(), dU.as<float>(), ldc)
                                              : vproj_temporal(ctx, P, K, A_colptr, A_rowidx, A_val, dColptr.as<int64_t>(), dErow.as<int>(), dAval.as<float>(), dU.as<float>(), ldc);
             if (rcv < 0) return rcv;
@@ -735,7 +771,7 @@ int temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, c
         if (rc_ > 0) RET(reproject());
         else term_applied = P->pend;
     }
-    ht.mark("uploads + projection launch");
+    ht.mark(early_hit ? "uploads (projection queued ahead)" : "uploads + projection launch");
     // T2: overlap graph + V values (neighbour lists include k itself: V(k,k) = aa(k))
     HostCSR csr; csc_to_csr(d, K, A_colptr, A_rowidx, A_val, csr);
     std::vector<char> nonempty(K, 0);
@@ -795,6 +831,25 @@ int temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, c
         ht.mark("job queued");
         return 0;
     }
+    // No host wait in front of the levels (temporal_early 1 or 3, no deconvolution): aa and its test against `upd` are taken on the device (k_aa_gather).  The one
+    // thing left that needs a host decision is the overflow word of the term projection: k_term_project lists the traces near a footprint in lst[512] and
+    // raises it when a 513th turns up -- impossible when the term has at most 512 traces (pend_K / res_K), so the wait is kept exactly when a term was
+    // applied that has more
+    const bool ovf_possible = term_applied && ((P->pend_ac && P->pend_K > 512) || (P->res_ac && P->res_K > 512));
+    const bool nowait = (te_mode == 1 || te_mode == 3) && !dopts && !ovf_possible;
+    std::vector<float> aa(K);
+    if (nowait) {
+        std::vector<int> code(K);
+        for (int k = 0; k < K; ++k) code[k] = upd[k] ? diag[k] : ~diag[k];
+        DevBuf &dCode = S_[13];
+        RET(to_dev(ctx, dCode, code.data(), code.size()));
+        RET(dAa.ensure((size_t)K * sizeof(float)));
+        int *dErr = nullptr;
+        RET(ctx_errflag(ctx, &dErr));
+        LAUNCH(ctx, "temporal_aa", k_aa_gather, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, dNval.as<float>(), dCode.as<int>(), (int)K, dAa.as<float>(), dErr);
+        ++ctx->sweep_nowait;
+        ht.mark("level schedule (no wait)");
+    } else {
     std::vector<float> nval(nn);
     int ovf = 0;
     CK(hipMemcpyAsync(nval.data(), dNval.p, (size_t)nn * sizeof(float), hipMemcpyDeviceToHost, ctx->st()));
@@ -802,13 +857,13 @@ int temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, c
     RET(ctx_check_errflag(ctx));                                // the wait for A'A; also what the residual's kernels had to report
     ht.mark("wait for A'A (sync)");
     if (ovf) RET(reproject());                                  // a footprint near more than 512 traces: the list kernel gave up
-    std::vector<float> aa(K);
     for (int k = 0; k < K; ++k) {
         aa[k] = nval[diag[k]];
         if ((aa[k] > 0.f) != (upd[k] != 0)) return fail(CNMFE_EHIP, "temporal update: aa(%d) = %g disagrees with the host-side test of its column", k, (double)aa[k]);
     }
     RET(to_dev(ctx, dAa, aa.data(), aa.size()));
     ht.mark("level schedule");
+    }
     if (!dopts) {
         for (int it = 0; it < (dag_on ? 1 : maxIter); ++it)
             for (size_t l = 0; l < g.levels.size(); ++l)
@@ -836,6 +891,10 @@ int temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, c
     ctx->last_t_K = K; ctx->last_t_ldc = ldc; ctx->last_t_T = T; ctx->last_t_valid = true;      // C_raw rows + aa stay on the device for cnmfe_stitch_add
     RET(download_traces(ctx, dC.as<float>(), ldc, C_out, K, T, c_order));
     RET(download_traces(ctx, dCraw.as<float>(), ldc, C_raw_out, K, T, c_order));
+    if (aa_out && nowait) {                                     // (a caller that wants aa on the host waits for it here, behind the queued levels)
+        CK(hipMemcpyAsync(aa_out, dAa.p, (size_t)K * sizeof(float), hipMemcpyDeviceToHost, ctx->st()));
+        return ctx_check_errflag(ctx);
+    }
     if (aa_out) memcpy(aa_out, aa.data(), (size_t)K * sizeof(float));
     if (C_out || C_raw_out) CK(hipStreamSynchronize(ctx->st()));
     return 0;
@@ -936,7 +995,43 @@ int spatial_fetch_connected(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, c
            dBox.as<int4>(), d1, d2, dKeep.as<unsigned char>());
     CK(hipMemcpyAsync(A_out, dAval.p, (size_t)nnz * sizeof(float), hipMemcpyDeviceToHost, ctx->st()));
     CK(hipMemcpyAsync(keep, dKeep.p, (size_t)nnz, hipMemcpyDeviceToHost, ctx->st()));
+    ctx->conn_gen = ctx->spatial_gen;                        // (pattern, values and keep flags of this result lie in scr[0], scr[1], scr[6], scr[14]: temporal_early_project)
     return wait ? ctx_check_errflag(ctx) : 0;                // (no wait: the caller records a ticket behind the copies, cnmfe_update_spatial_fetch_connected_async)
+}
+
+// The hand-over (option temporal_early): the temporal update's projection U = B' Yc, B = A - W'A, queued on the stream right behind the
+// connectivity kernel, before the host has seen the new A.  Everything it needs is on the device: the mask's CSC pattern (scr[0], scr[1]), the new values
+// (scr[6]) and the keep flags (scr[14]); the block lists come from the mask's host pattern, a superset of A's whose extra entries are stored zeros.  The result
+// waits in ctx->early_u under a tag; *token = 0 when the request is declined (several lanes, a patch that is not the field of view, no virtual residual,
+// bg_ssub > 1, a projection that cannot serve it).  Same stream, no event.
+int temporal_early_project(cnmfe_ctx *ctx, int32_t K, const int64_t *IND_colptr, const int32_t *IND_rowidx, int64_t *token) {
+    *token = 0;
+    ctx->early.valid = false;
+    const int64_t mode = ctx->opt("temporal_early", 1);
+    if ((mode != 1 && mode != 2) || !ctx->lanes.empty()) return 0;
+    Patch *P = ctx->spatial_patch;
+    const int64_t nnz = IND_colptr[K];
+    // (no virtual residual: also what a spatial update leaves whose own table lists were too long -- they are the lists of the masks grown by the ring, the
+    //  very lists built below, so vproj_temporal's own limit of 64 masks over a block is met there first and the residual realised)
+    if (!P || ctx->spatial_K != K || nnz == 0 || ctx->spatial_nnz != nnz || ctx->conn_gen != ctx->spatial_gen
+        || P->d != (int64_t)P->d1 * P->d2 || !P->ysig_valid || !P->ysig_virtual || P->res_kind != 1) { ++ctx->early_declined; return 0; }
+    HostTrace ht(ctx, "temporal_early");
+    const int64_t T = P->T, ldc = (T + 3) & ~int64_t(3);    // (the row stride upload_traces gives the traces of this T)
+    DevBuf *S_ = ctx->scr;
+    RET(ctx->early_a.ensure((size_t)nnz * sizeof(float)));
+    RET(ctx->early_u.ensure((size_t)K * ldc * sizeof(float)));
+    LAUNCH(ctx, "temporal_early_values", k_keep_values, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, S_[6].as<float>(), S_[14].as<unsigned char>(), nnz, ctx->early_a.as<float>());
+    // (k_vp_reduce writes every column of every row of U, the padded tail included: no memset)
+    const int rcv = vproj_temporal(ctx, P, K, IND_colptr, IND_rowidx, nullptr, S_[0].as<int64_t>(), S_[1].as<int>(), ctx->early_a.as<float>(), ctx->early_u.as<float>(), ldc);
+    if (rcv < 0) return rcv;
+    if (rcv > 0) { ++ctx->early_declined; return 0; }        // more than 64 masks over one block, too large a partial buffer: the temporal update projects as before
+    cnmfe_ctx::EarlyU &E = ctx->early;
+    E.P = P; E.K = K; E.ldc = ldc; E.T = T; E.spatial_gen = ctx->spatial_gen; E.res_gen = P->res_gen;
+    E.proj_i8 = ctx->opt("proj_i8", 1); E.proj_i8_planes = ctx->opt("proj_i8_planes", 3); E.proj_tiled = ctx->opt("proj_tiled", 1);
+    E.token = ++ctx->early_seq; E.claimed = 0; E.valid = true;
+    ctx->early_nent = ctx->last_nent;
+    *token = E.token;
+    return 0;
 }
 
 static int postproc_boxes(int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, std::vector<int4> &box) {
@@ -975,6 +1070,7 @@ int postproc_run(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_
     }
     DevBuf *S_ = ctx->scr;
     DevBuf &dColptr = S_[0], &dErow = S_[1], &dAval = S_[6], &dBox = S_[13], &dKeep = S_[14];
+    ctx->conn_gen = -1;                                      // (scr[0], scr[1], scr[6], scr[14] change hands)
     RET(to_dev(ctx, dColptr, A_colptr, (size_t)K + 1));
     RET(to_dev(ctx, dErow, A_rowidx, (size_t)nnz));
     RET(to_dev(ctx, dAval, A_val, (size_t)nnz));

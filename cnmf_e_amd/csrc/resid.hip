@@ -1114,6 +1114,7 @@ int residual_realize(cnmfe_ctx *ctx, Patch *P) {
 int residual_run(cnmfe_ctx *ctx, Patch *P, int pid, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx,
                  const float *A_val, const float *C, int c_order, float *Ysig_out, int out_memspace, DevBuf *outbuf, int tables_only) {
     const int64_t T = P->T;
+    ++P->res_gen;
     DevBuf &ysig = outbuf ? *outbuf : P->ysig;               // bg_ssub > 1 sweeps the low-resolution patch into its own buffer
     // the resident Ysig of this patch is still the residual under the current video, W and b0: only the footprint term changes
     const bool delta = !outbuf && P->ysig_valid && P->res_kind == 1 && (P->ysig.p || P->ysig_virtual) && ctx->opt("r1_delta", 1) != 0;

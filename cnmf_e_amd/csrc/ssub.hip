@@ -246,6 +246,7 @@ int ssub_derive(cnmfe_ctx *ctx, Patch *S, int dst_id, int ssub, int mode) {
     RET(ensure_ymean(ctx, S));
     int d1s, d2s; low_dims(S, ssub, d1s, d2s);
     if (ctx->patches.count(dst_id)) { delete ctx->patches[dst_id]; ctx->patches.erase(dst_id); }
+    ctx->early.valid = false; ctx->spatial_patch = nullptr;
     Patch *P = new Patch();
     P->derived = true; P->lane = S->lane;                   // (the low-resolution patches run on their source's lane: the calls that name two of them see one scratch set)
     const int32_t rect[4] = {1, d1s, 1, d2s};
@@ -515,6 +516,7 @@ int ssub_residual(cnmfe_ctx *ctx, Patch *M, int pid, Patch *R, int res_id, int s
                   const float *va, const float *C, int c_order, float *Ysig_out, int out_memspace) {
     int d1s, d2s; low_dims(M, ssub, d1s, d2s);
     if (R->d1 != d1s || R->d2 != d2s || R->T != M->T) return fail(CNMFE_ESTATE, "patch %d is not the low-resolution residual patch of patch %d", res_id, pid);
+    ++M->res_gen;
     std::vector<int64_t> ocp; std::vector<int32_t> ori; std::vector<float> ova;
     const bool has_a = K > 0 && cp[K] > 0;
     HostTrace ht(ctx, "residual_ssub");

@@ -484,6 +484,7 @@ int vproj_temporal(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr,
     VpLists L;
     if (vp_make_lists(need_ptr, need, nblk, K, false, L)) return 1;
     const int64_t nent = L.nent;
+    ctx->last_nent = nent;
     const int64_t ldp = ldu;                               // partial sums: one row of ldu doubles per entry
     if (nent * ldp * 8 > (int64_t(24) << 30)) return 1;    // (a partial buffer beyond 24 GB: not what this path is for)
     ht.mark("lists");

@@ -605,21 +605,31 @@ class Engine:
                 A_raw = sp.csc_matrix((out, iri.copy(), icp.copy()), shape=(info["d"], K))
                 A_pp = sp.csc_matrix((out * keep, iri.copy(), icp.copy()), shape=(info["d"], K))
                 return A_raw, A_pp
+            def temporal_early():
+                """behind start_connected: queue the temporal update's projection of the post-processed result where it lies (cnmfe_temporal_early_project).
+                Returns a token for temporal_early_claim, 0 when the engine declines"""
+                if "c" not in pend or not hasattr(L.lib, "cnmfe_temporal_early_project"):
+                    return 0
+                tk = C.c_int64(0)
+                L.check(L.lib.cnmfe_temporal_early_project(self._ctx, K, _p(icp, L.i64p), _p(iri, L.i32p), C.byref(tk)))
+                return tk.value
             fetch.start = start
             fetch.start_connected = start_connected
+            fetch.temporal_early = temporal_early
             return fetch
         return sp.csc_matrix((out, iri.copy(), icp.copy()), shape=(info["d"], K))
 
-    def hals_temporal(self, pid, A_patch, C_patch, maxIter=5, want_C=True, want_raw=True):
+    def hals_temporal(self, pid, A_patch, C_patch, maxIter=5, want_C=True, want_raw=True, want_aa=True):
         """[C, C_raw] = HALS_temporal(Ysig, A, C, maxIter); want_C=False skips the download of C (the caller of
-        update_temporal_parallel.m:180 only keeps C_raw), want_raw=False that of C_raw too: it stays on the device for stitch_add."""
+        update_temporal_parallel.m:180 only keeps C_raw), want_raw=False that of C_raw too: it stays on the device for stitch_add.
+        want_aa=False: aa stays there as well (returned as None) and the call does not wait for it."""
         info = self._patch[pid]
         K, cp, ri, va = _csc(A_patch, info["d"])
         T = info["T"]
         cptr, cord, _keep = self._targs(C_patch, K, T)
         Cout = np.empty((K, T), dtype=np.float32) if want_C else None
         Craw = np.empty((K, T), dtype=np.float32) if want_raw else None
-        aa = np.empty(K, dtype=np.float32)
+        aa = np.empty(K, dtype=np.float32) if want_aa else None
         L.check(L.lib.cnmfe_hals_temporal(self._ctx, pid, K, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p), cptr, cord,
                                           int(maxIter), _p(Cout, L.f32p), _p(Craw, L.f32p), _p(aa, L.f32p)))
         return Cout, Craw, aa
@@ -877,6 +887,17 @@ class Engine:
     def set_option(self, name, value):
         L.check(L.lib.cnmfe_set_option(self._ctx, name.encode(), int(value)))
         self._opts_set[name] = int(value)
+
+    def temporal_early_claim(self, token):
+        """the A of the next hals_temporal IS the spatial result `token` was given for: it may start from the projection queued then"""
+        if token and hasattr(L.lib, "cnmfe_temporal_early_claim"):
+            L.check(L.lib.cnmfe_temporal_early_claim(self._ctx, int(token)))
+
+    def counter(self, name):
+        """a read-only counter of the library (cnmfe_get_option: temporal_early_hits, temporal_early_drops, temporal_nowait, ...)"""
+        v = C.c_int64(0)
+        L.check(L.lib.cnmfe_get_option(self._ctx, name.encode(), C.byref(v)))
+        return v.value
 
     def get_option(self, name, default):
         """the value this engine's option has: what set_option gave it last, else what CNMFE_OPTS preset at cnmfe_create, else `default` (the library's own)"""

@@ -1451,12 +1451,20 @@ class Sources2D:
                     # starts on the device (the deferred half of the ring solve, the W*A_prev tables) runs behind them, under the host's assembly of A
                     fetch.start_connected((v.d1, v.d2))
                 self._temporal_residual_early(idx)                       # host work under the sweeps
+                self._early_u = None
+                if (whole_conn and hasattr(fetch, "temporal_early") and not update_sn and not o.spatial_constraints.get("circular", False)
+                        and not o.deconv_flag and self.ssub == 1 and len(v.owned) == 1):
+                    # the hand-over: the temporal update's projection of this result, queued behind the connectivity kernel and the residual request above,
+                    # before the host has seen the values (engine option temporal_early); update_temporal_parallel claims it when self.A is still this result
+                    self._early_u = fetch.temporal_early()
                 if nxt is not None:
                     ahead = (prev_of(nxt), masks_of(nxt))                # ... and the slices of the next patch
                 if whole_conn:
                     # one patch = the field of view: post_process_spatial's connectivity constraint (:341) runs on the result where it lies
                     # (the engine's fetch: A without stored zeros, rows sorted, and the raw update as a recipe -- see the early return below)
                     Anew, whole_pp = fetch(connected_fov=(v.d1, v.d2), **({"compact": True} if hasattr(fetch, "start") else {}))
+                    if getattr(self, "_early_u", None):
+                        self._early_u = (self._early_u, whole_pp)
                 elif late:
                     in_flight.append((fetch, pp, ind))
                     while len(in_flight) > self.spatial_lag:
@@ -1742,7 +1750,12 @@ class Sources2D:
                 eng.hals_temporal_deconv(v.pid[idx], A_pp, C_patch, o.maxIter, o.deconv_options, want_all=None)
             else:
                 self._start_wanted_prefetch()
-                eng.hals_temporal(v.pid[idx], A_pp, C_patch, o.maxIter, want_C=False, want_raw=False)  # :180-181
+                early, self._early_u = getattr(self, "_early_u", None), None
+                if (isinstance(early, tuple) and whole and A_pp is early[1] and self.A is early[1] and ind.size == K and not sharded and len(v.owned) == 1
+                        and hasattr(eng, "temporal_early_claim")):
+                    eng.temporal_early_claim(early[0])       # (A is exactly the spatial result the projection was queued for: hand-over)
+                eng.hals_temporal(v.pid[idx], A_pp, C_patch, o.maxIter, want_C=False, want_raw=False,
+                                  **({"want_aa": False} if hasattr(eng, "temporal_early_claim") else {}))  # :180-181
             eng.stitch_add(ind)                                                                       # :274-275
         if jobs:
             self._start_wanted_prefetch()                                  # host thread under the (GIL-free) sweep / stitch / fit calls that follow

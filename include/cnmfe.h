@@ -509,6 +509,10 @@ int cnmfe_synchronize(cnmfe_ctx *ctx);
  *   sweep_dag         default 1: the maxIter Gauss-Seidel sweeps of a HALS update (HALS_spatial.m:36-44, HALS_temporal.m:59-68, with or without the in-sweep
  *                     deconvolution) are launched level by level of ONE dependency graph over (sweep, neuron) items -- the same reads and writes per item, equal results,
  *                     fewer and fuller launches (512 x 512, K = 500: 21 instead of 25); 0: sweep after sweep, level by level (rounds 1-5)
+ *   temporal_early    default 1: the hand-over from the spatial to the temporal update without device idle time -- the temporal projection is queued behind the
+ *                     spatial update's connectivity kernel (cnmfe_temporal_early_project, below) and the Gauss-Seidel levels are queued without the host wait for
+ *                     A'A (aa and its check are taken on the device; the wait stays when a footprint term over more than 512 traces was applied, whose list kernel
+ *                     may overflow).  2: the projection only, 3: the levels only, 0: neither.  Results are bit-equal (tests/test_gpu_handover.py)
  *   prealloc          default 1: cnmfe_fit_reserve may allocate the fit's large buffers ahead of the first fit
  * A deployment short of HBM sets win_i8 = proj_tiled = 0 (and solve_packed = 0) or leaves it to the engine, which falls back by itself.
  * Diagnostics (scripts/): solve_probe, r1_probe (phase probes: results are NOT the product's), deconv_trace, host_trace (1: host-side phase times of every call on
@@ -517,6 +521,20 @@ int cnmfe_synchronize(cnmfe_ctx *ctx);
  * r1_arc_bias, r1_duo_ord) and the experiment switches tile_order, gram_probe, r1_nseg.
  * Every option can be preset for a process with CNMFE_OPTS="name=value,..." (logged once on stderr). */
 int cnmfe_set_option(cnmfe_ctx *ctx, const char *name, int64_t value);
+/* The value cnmfe_set_option (or CNMFE_OPTS) gave an option last; an option that was never set reports CNMFE_EINVAL (its default, above, holds).  Also the
+ * read-only counters of the hand-over: temporal_early_hits / _drops (early projections a temporal update took / found but could not take), temporal_early_declined
+ * (requests the projection could not serve), temporal_early_entries / temporal_proj_entries ((block, neuron) entries of the last early / of the last projection),
+ * temporal_nowait (temporal updates whose levels were queued without the host wait). */
+int cnmfe_get_option(cnmfe_ctx *ctx, const char *name, int64_t *value);
+
+/* The hand-over between the spatial and the temporal update (option temporal_early).  After cnmfe_update_spatial_fetch_connected[_async] of a patch that is the
+ * whole field of view, cnmfe_temporal_early_project queues the temporal update's projection of the post-processed result where it lies on the device (IND: the
+ * mask pattern of that spatial update) and returns a token, 0 when it declines.  A caller whose next cnmfe_hals_temporal passes EXACTLY that result -- the fetched
+ * values where the keep flag is set, stored zeros dropped, every column non-empty -- says so with cnmfe_temporal_early_claim(token) right before the call; the
+ * update then starts from the queued projection.  Unclaimed, or stale in any way (another K, patch, T, residual request, spatial update, projection option), the
+ * early result is dropped and the update projects as before: the values are the same either way. */
+int cnmfe_temporal_early_project(cnmfe_ctx *ctx, int32_t K, const int64_t *IND_colptr, const int32_t *IND_rowidx, int64_t *token);
+int cnmfe_temporal_early_claim(cnmfe_ctx *ctx, int64_t token);
 
 #ifdef __cplusplus
 }
