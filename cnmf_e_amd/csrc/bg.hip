@@ -477,9 +477,6 @@ struct CovTab {
     int nbr, nbc;
     int maxd, nrel;                          // largest block displacement between two ring pixels of one centre (2: radius <= 16, 3: <= 24); nrel_of(maxd)
 };
-// canonical displacement index: dC in 0..maxd; dC == 0 -> dR in 0..maxd (0..maxd); dC >= 1 -> dR in -maxd..maxd.  maxd = 2: 13 classes (0..2, 3..7, 8..12)
-__host__ __device__ __forceinline__ int rel_index(int dR, int dC, int maxd) { return dC == 0 ? dR : (maxd + 1) + (dC - 1) * (2 * maxd + 1) + dR + maxd; }
-__host__ __device__ __forceinline__ int nrel_of(int maxd) { return (maxd + 1) + maxd * (2 * maxd + 1); }
 
 // The block-pair codes of a pixel's 4 x 4-block window depend on the window's origin only, so they are tabulated once per fit instead of being
 // re-derived (25 integer operations and a dependent load per entry, 256 entries) by every pixel's wave.
@@ -605,722 +602,567 @@ static double matlab_quantile(std::vector<int> x, double q) {
     return x[lo - 1] + (r - (double)lo) * (double)(x[lo] - x[lo - 1]);
 }
 
+// ---- one NT dispatch: f(integral_constant<NT>) for nt in 1..MAX register tiles of 16 ring neighbours; any other nt launches nothing ----
+template <int MAX, class F> static int nt_dispatch(int nt, F &&f) {
+#define NT_CASE(N_) case N_: if constexpr (N_ <= MAX) return f(std::integral_constant<int, N_>{}); else return 0;
+    switch (nt) { NT_CASE(1) NT_CASE(2) NT_CASE(3) NT_CASE(4) NT_CASE(5) NT_CASE(6) NT_CASE(7) NT_CASE(8) default: return 0; }
+#undef NT_CASE
+}
+#define NT_OF(c) decltype(c)::value
+
 static int solve_launch(cnmfe_ctx *ctx, Patch *P, const CovTab &tab, const BgGeom &g, const double *rowsum, const unsigned char *act, int nt, int probe, const double *fill) {
-    const unsigned ngrid = (unsigned)P->d;
-    const int *pix = nullptr;
     int *dErr = nullptr;
     RET(ctx_errflag(ctx, &dErr));
     // one wave per pixel, the matrix in MFMA accumulator tiles (ring_solve.hpp).  Measured and removed (profiles/r02/solve_ab_c3.txt): the
     // panel-blocked LDS solver (22.5 ms against 8.0) and the looped-block-column variant (10.6 ms: it spills ~200 tile registers)
-#define RS5_CASE(NT_) case NT_: LAUNCH(ctx, "bg_ring_solve", (k_ring_solve5<NT_>), dim3(ngrid), dim3(64), 0, tab, g, P->ring_dr.as<int>(), \
-                                        P->ring_dc.as<int>(), rowsum, act, P->W.as<float>(), dErr, probe, pix, fill); break;
-    switch (nt) { RS5_CASE(1) RS5_CASE(2) RS5_CASE(3) RS5_CASE(4) RS5_CASE(5) RS5_CASE(6) RS5_CASE(7) RS5_CASE(8) default: break; }
-#undef RS5_CASE
+    return nt_dispatch<8>(nt, [&](auto c) -> int {
+        LAUNCH(ctx, "bg_ring_solve", (k_ring_solve5<NT_OF(c)>), dim3((unsigned)P->d), dim3(64), 0, tab, g, P->ring_dr.as<int>(), P->ring_dc.as<int>(), rowsum, act, P->W.as<float>(), dErr, probe, (const int *)nullptr, fill);
+        return 0; });
+}
+
+// ---- the rules the fit, bg_reserve and vproj.hip share: one copy each ----
+int fits_leaving(const DevBuf &b, size_t bytes, bool *fits, bool quarter) {
+    *fits = true;
+    if (b.cap >= bytes) return 0;
+    size_t fr = 0, tot = 0; CK(hipMemGetInfo(&fr, &tot));
+    *fits = fr >= bytes + std::max((size_t)8 << 30, quarter ? tot / 4 : (size_t)0);
+    return 0;
+}
+// the frame stride of a fit with projection (fit_ring_model.m:84-87): k = floor(T / min(T, 100 pmax)); pmax starts at p and only grows
+static int fit_stride(int64_t T, int pmax) { return (int)std::max<int64_t>(1, T / std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)pmax * 100))); }
+// round 5 (gram_i8.hpp): a Gram over Tp frames on the int8 matrix pipe, exact up to a 32-bit quantisation of the data (option gram_i8, default 1; int32 range)
+static bool gram_i8_ok(cnmfe_ctx *ctx, int64_t Tp) { return ctx->opt("gram_i8", 1) != 0 && Tp <= 24576; }
+// the digit planes of the video stay resident with a patch whose fits use every frame (win_proj_i8.hpp) ...
+static bool planes_wanted(cnmfe_ctx *ctx, const Patch *P, int kstride) { return kstride == 1 && !P->derived && ctx->opt("win_i8", 1) != 0; }
+// ... and such a fit's window projection runs out of them (a strided fit keeps the fp64 window kernel)
+static bool win_i8_applies(cnmfe_ctx *ctx, const Patch *P, int kstride) { return P->dig_valid && kstride == 1 && P->T <= 24576 && ctx->opt("win_i8", 1) != 0; }
+// the packed systems of the ring solve (ring_solve_packed.hpp): 43 KB per pixel at p = 96
+static bool pack_wanted(cnmfe_ctx *ctx, int nt) { return ctx->opt("solve_packed", 1) != 0 && nt >= 1 && nt <= 8; }
+static size_t sys_bytes_of(int64_t d, int nt) { return (size_t)d * ((size_t)(nt * (nt + 1) / 2) * 256 + 16 * nt) * sizeof(double); }
+
+// ---- launch helpers: the fit and win_i8_table go through them ----
+// digits of the centred traces for the int8 window projection (gram: and their K x K Gram matrix, which k_win_fix then takes G from)
+static int trace_digits(cnmfe_ctx *ctx, const char *name, const float *dCc, int64_t ldc, int K, int64_t T, int64_t T16, bool gram) {
+    RET(ctx->tdig.ensure((size_t)K * T16 * 4 * sizeof(uint4))); RET(ctx->tscale.ensure((size_t)K * sizeof(double)));
+    if (gram) RET(ctx->gk.ensure((size_t)K * K * sizeof(double)));
+    LAUNCH(ctx, name, k_trace_dig, dim3(K), dim3(256), 0, dCc, ldc, T, T16, ctx->tdig.as<uint4>(), ctx->tscale.as<double>());
+    if (gram) LAUNCH(ctx, "bg_trace_gram", k_trace_gram, dim3((unsigned)(((K + 15) >> 4) * (((K + 15) >> 4) + 1) / 2)), dim3(64 * TG_W), 0, dCc, ldc, T, K, ctx->gk.as<double>());
+    return 0;
+}
+// round 5 (win_proj_i8.hpp): the window projection on the int8 matrix pipe out of the resident digit planes, one work item per (block, pair of trace groups)
+static int win_proj_i8_launch(cnmfe_ctx *ctx, Patch *P, const char *name, const std::vector<int> &lst_ptr, const std::vector<int> &blall, const int *dLp, const int *dLk, int nsg,
+                              double *dUt, int64_t ut_stride) {
+    static thread_local std::vector<int> items;
+    plan::win_i8_items(blall, lst_ptr, items);
+    RET(to_dev(ctx, ctx->win_items, items));
+    if (items.empty()) return 0;
+    const int64_t T16 = P->dig_T16;
+#define WPI8_GO(V0_) LAUNCH(ctx, name, k_win_proj_i8<V0_>, dim3((unsigned)(items.size() * nsg)), dim3(512), 0, P->dig.as<uint4>(), T16, P->dig_sc.as<double>(), ctx->tdig.as<uint4>(), \
+                            ctx->tscale.as<double>(), dLp, dLk, ctx->win_items.as<int>(), nsg, dUt, ut_stride)
+    if (win_planes3(ctx, T16)) WPI8_GO(1); else WPI8_GO(0);
+#undef WPI8_GO
+    return 0;
+}
+// the digit planes of g's frames (gram_i8.hpp): the resident video minus da's footprints -> scales digs, planes digp; nchunk != nullptr: and the row sums per frame
+// chunk in dig_rspart (*nchunk of them, reduced by k_rs_reduce)
+static int build_digits(cnmfe_ctx *ctx, Patch *P, const BgGeom &g, const DigA &da, double *digs, uint4 *digp, int *nchunk) {
+    const int nblk = g.nbr * g.nbc;
+    RET(ctx->dig_smax.ensure((size_t)nblk * BLKPX * sizeof(unsigned)));
+    CK(hipMemsetAsync(ctx->dig_smax.p, 0, (size_t)nblk * BLKPX * sizeof(unsigned), ctx->st()));
+    const int tchunk16 = (int)((std::max<int64_t>(64, (g.Tpad + 15) / 16) + 15) & ~int64_t(15));
+    const dim3 gd(nblk, (unsigned)((g.Tpad + tchunk16 - 1) / tchunk16));
+    LAUNCH(ctx, "bg_dig_scale", k_dig_scale, gd, dim3(256), 0, P->Yc4.as<float4>(), P->Tc, g, da, tchunk16, ctx->dig_smax.as<unsigned>());
+    if (nchunk) { RET(ctx->dig_rspart.ensure((size_t)gd.y * nblk * BLKPX * sizeof(double))); *nchunk = (int)gd.y; }
+    LAUNCH(ctx, "bg_build_dig", k_build_dig, gd, dim3(256), 0, P->Yc4.as<float4>(), P->Tc, g, da, ctx->dig_smax.as<unsigned>(), digs, digp, tchunk16,
+           nchunk ? ctx->dig_rspart.as<double>() : (double *)nullptr);
     return 0;
 }
 
 // The large buffers of the ring fit, allocated when the ring is set (cnmfe_ring_init: once per patch, after the upload) instead of inside the first fit: the
 // video's covariance table, the context's working table, the tiled Bf and the window projection's partial sums -- 18 GB at the headline size.  A fit then
 // queues its kernels without a hipMalloc in between (tens of milliseconds of the first iteration, and on some boxes the dispatch behind a fresh multi-GB
-// allocation stalled for 0.5-0.8 s, profiles/r03/README.md).  Sizes follow the geometry only; a buffer that is already large enough is left alone.
+// allocation stalled for 0.5-0.8 s, profiles/r03/README.md).  Sizes follow the geometry only -- by the functions the fit itself decides with; a buffer that is
+// already large enough is left alone.
 int bg_reserve(cnmfe_ctx *ctx, Patch *P) {
     if (ctx->opt("gram_incremental", 1) == 0 || P->p <= 0) return 0;
-    int p_radius = 0;
-    for (int i = 0; i < P->p; ++i) p_radius = std::max(p_radius, std::max(std::abs(P->dr[i]), std::abs(P->dc[i])));
-    const int maxd = (2 * p_radius + 15) >> 4;
-    if (maxd > 3) return 0;
-    const int nbr = (P->nr_b + BLK - 1) / BLK, nbc = (P->nc_b + BLK - 1) / BLK, nblk = nbr * nbc;
-    const int pi0 = std::max(0, P->roff - p_radius) / BLK, pi1 = std::min(P->nr_b - 1, P->roff + P->nr - 1 + p_radius) / BLK;
-    const int pj0 = std::max(0, P->coff - p_radius) / BLK, pj1 = std::min(P->nc_b - 1, P->coff + P->nc - 1 + p_radius) / BLK;
-    int64_t npairs = 0;                                      // as the pair list of bg_fit_ring counts them: touched blocks, canonical displacements within maxd
-    for (int j = pj0; j <= pj1; ++j)
-        for (int i = pi0; i <= pi1; ++i)
-            for (int dC = 0; dC <= maxd; ++dC)
-                for (int dR = (dC == 0 ? 0 : -maxd); dR <= maxd; ++dR) {
-                    const int i2 = i + dR, j2 = j + dC;
-                    if (i2 >= pi0 && i2 <= pi1 && j2 >= pj0 && j2 <= pj1) ++npairs;
-                }
-    const bool i8 = ctx->opt("gram_i8", 1) != 0 && P->T <= 24576;                   // (as bg_fit_ring decides for a stride-1 build: steps of four 16-frame stages)
-    const int64_t Tpad = i8 ? (P->T + 4 * GK - 1) / (4 * GK) * (4 * GK) : (P->T + GK - 1) / GK * GK;
-    const size_t tab = (size_t)npairs * BLKPX * BLKPX * sizeof(double);
-    RET(P->cov_base.ensure(tab));
-    RET(P->rowsum_base.ensure((size_t)nblk * BLKPX * sizeof(double)));
-    RET(ctx->cov.ensure(tab));
-    RET(ctx->rowsum.ensure((size_t)nblk * BLKPX * sizeof(double)));
-    RET(ctx->bf.ensure((size_t)nblk * Tpad * BLKPX * sizeof(float)));
-    const int nsg = nblk >= 512 ? std::max(1, std::min(8, (2048 + nblk - 1) / nblk)) : std::max(1, std::min(16, (4096 + nblk - 1) / std::max(1, nblk)));
-    RET(ctx->inc[6].ensure((size_t)nsg * nblk * WIN_NLB * WIN_NLB * sizeof(double)));
-    // the packed systems of the ring solve (ring_solve_packed.hpp), under the same conditions as the fit applies
-    const int nt = (P->p + 15) / 16;
-    if (ctx->opt("solve_packed", 1) != 0 && nt >= 1 && nt <= 8) {
-        const size_t sys_bytes = (size_t)P->d * ((size_t)(nt * (nt + 1) / 2) * 256 + 16 * nt) * sizeof(double);
-        if (P->sys.cap < sys_bytes) {
-            size_t fr = 0, tot = 0;
-            CK(hipMemGetInfo(&fr, &tot));
-            if (fr >= sys_bytes + ((size_t)8 << 30)) { P->sys_valid = false; P->kinv_valid = false; P->kinv_lam_valid = false; P->kinv_fits = 0; RET(P->sys.ensure(sys_bytes)); }
-        }
+    const plan::Reach reach = plan::ring_reach(P->dr.data(), P->dc.data(), P->p);
+    if (!reach.ok) return 0;
+    const bool i8 = gram_i8_ok(ctx, P->T);                   // (a stride-1 build: the first fit of most recordings)
+    const BgGeom g = bg_geom(P, 1, i8);
+    const int nblk = g.nbr * g.nbc, nt = (P->p + 15) / 16;
+    const size_t tab = (size_t)plan::ring_pairs(P->nr_b, P->nc_b, P->roff, P->coff, P->nr, P->nc, reach.p_radius, reach.maxd, nullptr, nullptr) * BLKPX * BLKPX * sizeof(double);
+    RET(P->cov_base.ensure(tab)); RET(P->rowsum_base.ensure((size_t)nblk * BLKPX * sizeof(double))); RET(ctx->cov.ensure(tab));
+    RET(ctx->rowsum.ensure((size_t)nblk * BLKPX * sizeof(double))); RET(ctx->bf.ensure((size_t)nblk * g.Tpad * BLKPX * sizeof(float)));
+    RET(ctx->inc[6].ensure((size_t)plan::win_segments(nblk) * nblk * WIN_NLB * WIN_NLB * sizeof(double)));      // (the segments of a fit with every block on a list; one with fewer listed blocks takes more and grows it)
+    bool fits = false;
+    if (pack_wanted(ctx, nt) && P->sys.cap < sys_bytes_of(P->d, nt)) {
+        RET(fits_leaving(P->sys, sys_bytes_of(P->d, nt), &fits));
+        if (fits) { P->drop_systems(); RET(P->sys.ensure(sys_bytes_of(P->d, nt))); }
     }
     // round 5: the two further copies of the video (digit planes of the window projection, the temporal projection's read-order copy) under the rule their builders
     // apply -- one more video's worth each, only if that leaves 8 GB free.  Allocated HERE, while the caller sets its patches up: a fresh 10 GB hipMalloc takes 0.3 ms
     // on most leases and 1-3 SECONDS on some (profiles/r05/first_iteration_stall.txt: one run in five, inside the first iteration's temporal projection)
     // (AHEAD of time only while a quarter of the device stays free: the buffers every patch's fit and updates must have are allocated later, and 64 patches
     //  reserving down to the builders' 8 GB left none for them -- tests/test_gpu_zconfigs.py::test_c5_whole_on_one_gpu; below that the builders decide as before)
-    auto reserve = [&](DevBuf &b, size_t bytes) -> int {
-        if (b.cap >= bytes) return 0;
-        size_t fr = 0, tot = 0;
-        CK(hipMemGetInfo(&fr, &tot));
-        if (fr >= bytes + std::max((size_t)8 << 30, tot / 4)) RET(b.ensure(bytes));
-        return 0;
-    };
-    // (only a recording whose fits use every frame keeps digit planes: the stride floor(T / min(T, 100 pmax)) of fit_ring_model.m:84-87 starts at pmax = p and only grows)
-    const bool stride1 = P->T / std::max<int64_t>(1, std::min<int64_t>(P->T, (int64_t)P->p * 100)) <= 1;
-    if (!P->derived) {
-        const bool planes = i8 && stride1 && ctx->opt("win_i8", 1) != 0;
-        const bool pi8 = planes && ctx->opt("proj_i8", 1) != 0;      // the temporal projection on the int8 pipe reads pixel-major planes instead of the read-order copy
-        if (planes) { RET(reserve(P->dig, (size_t)nblk * Tpad * BLKPX * sizeof(float))); RET(P->dig_sc.ensure((size_t)nblk * BLKPX * sizeof(double))); }
-        if (ctx->opt("r1_virtual", 1) != 0) {
-            if (pi8) RET(reserve(P->digp, (size_t)nblk * Tpad * BLKPX * sizeof(float)));
-            else if (ctx->opt("proj_tiled", 1) != 0) RET(reserve(P->yt4, (size_t)nblk * ((P->Tc + 15) >> 4) * 64 * 64 * sizeof(float4)));
-        }
+    auto reserve = [&](DevBuf &b, size_t bytes) -> int { RET(fits_leaving(b, bytes, &fits, true)); return fits ? b.ensure(bytes) : 0; };
+    if (P->derived) return 0;
+    // (only a recording whose fits use every frame keeps digit planes)
+    const bool planes = i8 && planes_wanted(ctx, P, fit_stride(P->T, P->p));
+    if (planes) { RET(reserve(P->dig, (size_t)nblk * g.Tpad * BLKPX * sizeof(float))); RET(P->dig_sc.ensure((size_t)nblk * BLKPX * sizeof(double))); }
+    if (ctx->opt("r1_virtual", 1) != 0) {
+        // the temporal projection on the int8 pipe reads pixel-major planes instead of the read-order copy
+        if (planes && ctx->opt("proj_i8", 1) != 0) RET(reserve(P->digp, (size_t)nblk * g.Tpad * BLKPX * sizeof(float)));
+        else if (ctx->opt("proj_tiled", 1) != 0) RET(reserve(P->yt4, (size_t)nblk * ((P->Tc + 15) >> 4) * 64 * 64 * sizeof(float4)));
     }
     return 0;
 }
 
-int bg_fit_ring(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
-                const float *C, int c_order, int with_projection, float *b0_out, int64_t info[4], int b0_only, double thresh_outlier) {
-    HostTrace ht(ctx, "fit_ring");
-    const bool outl = thresh_outlier == thresh_outlier;      // ~isnan(thresh_outlier), :50
-    if (outl && !P->sn_ready && !(b0_only & 1)) return fail(CNMFE_ESTATE, "fit_ring_model with thresh_outlier needs the noise levels of the block (cnmfe_set_noise)");
-    const int64_t T = P->T;
-    const int p = P->p;
-    DevBuf &dC = ctx->tmp[0], &dCc = ctx->tmp[1], &dCm = ctx->tmp[2], &dArow = ctx->tmp[3], &dAcol = ctx->tmp[4], &dAval = ctx->tmp[5],
-           &dMisc = ctx->tmp[6], &dAsum = ctx->tmp[7], &dActive = ctx->tmp[8], &dPairs = ctx->tmp[9], &dPairOf = ctx->tmp[10];
-    // isempty(A) -> A = ones(d,1), C = zeros(1,T)  (fit_ring_model.m:15-17): Bf = Y - Ymean, b0 = Ymean
-    const bool has_a = K > 0 && A_colptr[K] > 0;
-    const bool a_empty = K == 0;
-    int64_t ldc = 4;
+// ---- bg_fit_ring: the state its phases share, then the phases in the order they run ----
+struct RingFit {
+    cnmfe_ctx *ctx; Patch *P; int32_t K; const int64_t *A_colptr; const int32_t *A_rowidx; const float *A_val; const float *C; int c_order, b0_only; double thresh_outlier;
+    HostTrace ht;
+    bool outl, has_a, a_empty;                                 // ~isnan(thresh_outlier), :50; A has entries; isempty(A) -> A = ones(d,1), C = zeros(1,T) (:15-17): Bf = Y - Ymean, b0 = Ymean
+    int64_t T, ldc = 4, nactive = 0;
     HostCSR csr;
-    bool trace_i8_done = false;                                // the int8 window projection's trace digits and K x K Gram are already queued
-    if (has_a) {
-        RET(upload_centered(ctx, dC, C, K, T, c_order, dCc, dCm, &ldc));
-        // win_proj_i8.hpp: what depends on the traces alone goes out NOW -- the host's footprint block lists (0.2 ms at the headline size) are built underneath it
-        // instead of in front of an idle GPU (a fit that turns out to use a frame stride > 1 has queued 0.1 ms for nothing)
-        if (P->dig_valid && !outl && T <= 24576 && ctx->opt("win_i8", 1) != 0 && ctx->opt("gram_incremental", 1) != 0 && !(P->base_valid && P->base_kstride > 1)) {      // (a strided fit keeps the fp64 window kernel)
-            const int64_t T16 = P->dig_T16;
-            RET(ctx->tdig.ensure((size_t)K * T16 * 4 * sizeof(uint4)));
-            RET(ctx->tscale.ensure((size_t)K * sizeof(double)));
-            RET(ctx->gk.ensure((size_t)K * K * sizeof(double)));
-            LAUNCH(ctx, "bg_trace_dig", k_trace_dig, dim3(K), dim3(256), 0, dCc.as<float>(), ldc, (int64_t)T, T16, ctx->tdig.as<uint4>(), ctx->tscale.as<double>());
-            const int ntk = ((int)K + 15) >> 4;
-            LAUNCH(ctx, "bg_trace_gram", k_trace_gram, dim3((unsigned)(ntk * (ntk + 1) / 2)), dim3(64 * TG_W), 0, dCc.as<float>(), ldc, (int64_t)T, (int)K, ctx->gk.as<double>());
-            trace_i8_done = true;
-        }
+    bool first_run = false; int pmax = 0, kstride = 1;
+    BgGeom g; plan::Reach reach; int nblk = 0, nt = 0;
+    // the plan (ring_plan.hpp)
+    plan::BlockLists L; std::vector<plan::Pair> pairs; std::vector<int> pair_of; plan::Tables tabs; int npairs = 0, nwork = 0;
+    // the path verdicts, each decided in one place.  fit_lists: incr = the incremental Gram (the video's table kept with the patch + this fit's corrections), build_base = this
+    // fit builds that table, use_i8 = this fit's Gram (that table, or the direct Gram of Bf) runs on the int8 pipe, keep_pt = the window projection is the P = Yc Cc' table
+    // the next spatial update wants.  fit_traces_up: trace_i8_done = the int8 window projection's trace digits and K x K Gram are queued.  fit_queue_projection: proj_queued;
+    // win_i8 = it ran on the int8 pipe (k_win_fix takes G from the K x K matrix).  fit_pack: packed = the solve reads the packed systems.  fit_stage_windows: stage_ok
+    bool incr = false, build_base = false, use_i8 = false, keep_pt = false, trace_i8_done = false, proj_queued = false, win_i8 = false, packed = false, stage_ok = false;
+    int nsg = 1; int64_t ut_stride = 0, gb_stride = 0;
+    uint4 *digp = nullptr; double *digs = nullptr;             // where the digit planes of this build live
+    // device views
+    DevBuf &dC, &dCc, &dCm, &dArow, &dAcol, &dAval, &dMisc, &dAsum, &dActive, &dPairs, &dPairOf, &dWork, &dNeed, &dTcnt, &dTl, &dLk, &dBl, &dUt, &dCsum, &dGb, *dLp, *dSlot;
+    RingFit(cnmfe_ctx *c, Patch *p_) : ctx(c), P(p_), ht(c, "fit_ring"), dC(c->tmp[0]), dCc(c->tmp[1]), dCm(c->tmp[2]), dArow(c->tmp[3]), dAcol(c->tmp[4]), dAval(c->tmp[5]), dMisc(c->tmp[6]),
+        dAsum(c->tmp[7]), dActive(c->tmp[8]), dPairs(c->tmp[9]), dPairOf(c->tmp[10]), dWork(c->tmp[11]), dNeed(c->tmp[7]), dTcnt(c->tmp[12]), dTl(c->tmp[13]), dLk(c->inc[1]),
+        dBl(c->inc[3]), dUt(c->inc[4]), dCsum(c->inc[5]), dGb(c->inc[6]), dLp(&c->inc[0]), dSlot(&c->inc[2]) {}
+    const int *arow() const { return has_a ? dArow.as<int>() : nullptr; }
+    CovTab covtab() const { CovTab t{}; t.cov = ctx->cov.as<double>(); t.pair_of = dPairOf.as<int>(); t.nbr = g.nbr; t.nbc = g.nbc; t.maxd = reach.maxd; t.nrel = reach.nrel; return t; }
+};
+static thread_local std::vector<int> fit_nbox;                 // 4 per neuron: first / last row, first / last column of its footprint in the block region
+
+static int fit_traces_up(RingFit &f) {
+    cnmfe_ctx *ctx = f.ctx; Patch *P = f.P;
+    if (!f.has_a) return 0;
+    RET(upload_centered(ctx, f.dC, f.C, f.K, f.T, f.c_order, f.dCc, f.dCm, &f.ldc));
+    // win_proj_i8.hpp: what depends on the traces alone goes out NOW -- the host's footprint block lists (0.2 ms at the headline size) are built underneath it
+    // instead of in front of an idle GPU (the stride is not known yet: a fit that turns out to use another than the table in place has queued 0.1 ms for nothing)
+    if (!f.outl && ctx->opt("gram_incremental", 1) != 0 && win_i8_applies(ctx, P, P->base_valid ? P->base_kstride : 1)) {
+        RET(trace_digits(ctx, "bg_trace_dig", f.dCc.as<float>(), f.ldc, f.K, f.T, P->dig_T16, true));
+        f.trace_i8_done = true;
     }
-    // the CSR rows of A (b0, ind_active, the table corrections): built AFTER the window projection is queued when that can go first (below)
-    auto upload_csr = [&]() -> int {
-        if (!has_a) return 0;
-        csc_to_csr(P->d_b, K, A_colptr, A_rowidx, A_val, csr);
-        RET(to_dev(ctx, dArow, csr.rowptr.data(), csr.rowptr.size()));
-        RET(to_dev(ctx, dAcol, csr.col.data(), csr.col.size()));
-        RET(to_dev(ctx, dAval, csr.val.data(), csr.val.size()));
-        return 0;
-    };
-    ht.mark("traces");
-    if (b0_only & 1) {
-        RET(upload_csr());                                    // bg_ssub > 1: b0 = mean(Y - A*C, 2) on the patch (update_background_parallel.m:222-223)
-        BgGeom g0{};
-        g0.nr = P->nr; g0.nc = P->nc; g0.nr_b = P->nr_b; g0.nc_b = P->nc_b; g0.roff = P->roff; g0.coff = P->coff; g0.d = P->d; g0.d_b = P->d_b;
-        LAUNCH(ctx, "bg_b0", k_b0, dim3((unsigned)((P->d + 255) / 256)), dim3(256), 0, P->ymean_d.as<double>(), g0,
-               has_a ? dArow.as<int>() : nullptr, dAcol.as<int>(), dAval.as<float>(), dCm.as<double>(), P->b0.as<double>());
-        // (no drain: every upload above went through the pinned arena -- or, too large for it, waited itself -- and what reads b0 is stream-ordered behind this)
-        P->ysig_valid = false;
-        return 0;
+    return 0;
+}
+// the CSR rows of A (b0, ind_active, the table corrections): built AFTER the window projection is queued when that can go first
+static int fit_upload_csr(RingFit &f) {
+    if (!f.has_a) return 0;
+    csc_to_csr(f.P->d_b, f.K, f.A_colptr, f.A_rowidx, f.A_val, f.csr);
+    RET(to_dev(f.ctx, f.dArow, f.csr.rowptr)); RET(to_dev(f.ctx, f.dAcol, f.csr.col)); RET(to_dev(f.ctx, f.dAval, f.csr.val));
+    return 0;
+}
+// ---- b0 (:44) ----
+static int fit_b0(RingFit &f, const BgGeom &g) {
+    LAUNCH(f.ctx, "bg_b0", k_b0, dim3((unsigned)((f.P->d + 255) / 256)), dim3(256), 0, f.P->ymean_d.as<double>(), g, f.arow(), f.dAcol.as<int>(), f.dAval.as<float>(), f.dCm.as<double>(),
+           f.P->b0.as<double>());
+    return 0;
+}
+// ---- first-run test (:25), frame stride (:84-87), geometry ----
+static int fit_geometry(RingFit &f, int with_projection) {
+    // first run: row 1 of W_old has exactly two distinct values (0 and 1/count).  Both questions about W_old were answered behind the call that produced it
+    // (ring_stats_enqueue): no drain of the stream here, so with several patches per context the host sets up patch m + 1 while the GPU still solves patch m.
+    RET(ring_stats_get(f.ctx, f.P, &f.pmax, &f.first_run));
+    RET(f.dMisc.ensure(64));
+    f.ht.mark("first_run + pmax");
+    // with a threshold the frames are SELECTED instead (:62-67) and nmax = nnz(ind_frames) = size(Bf, 2) makes k = 1 at :84-85 (also when nmax >= T, where nk = min(T, nmax) = T)
+    f.kstride = with_projection && !f.outl ? fit_stride(f.T, f.pmax) : 1;
+    f.g = bg_geom(f.P, f.kstride);
+    f.reach = plan::ring_reach(f.P->dr.data(), f.P->dc.data(), f.P->p);
+    f.nblk = f.g.nbr * f.g.nbc; f.nt = (f.P->p + 15) / 16;
+    if (!f.reach.ok) return fail(CNMFE_EUNSUPPORTED, "fit_ring_model: ring offsets up to %d pixels (the block-pair table covers <= 24)", f.reach.p_radius);
+    return 0;
+}
+// ---- incremental Gram (k_win_proj / k_cov_correct): per 16x16 block the footprints with a pixel within maxd blocks of it; which table this fit uses or builds ----
+static void fit_lists(RingFit &f) {
+    cnmfe_ctx *ctx = f.ctx; Patch *P = f.P;
+    static thread_local std::vector<int> pair_blk, k_ptr;
+    f.incr = !f.outl && ctx->opt("gram_incremental", 1) != 0 && f.K < 32768;   // the clipped Bf is not linear in the video: direct Gram   // (derived low-resolution patches of bg_ssub included: their video is built once)
+    if (f.incr) {
+        plan::footprint_blocks(f.K, f.A_colptr, f.A_rowidx, P->nr_b, f.g.nbr, f.g.nbc, f.reach.maxd, pair_blk, k_ptr, fit_nbox);
+        f.incr = plan::block_lists(f.nblk, f.K, pair_blk.data(), k_ptr.data(), f.L);            // (denser than the window kernel is built for: direct Gram)
     }
-    // ---- first-run test (:25): row 1 of W_old has exactly two distinct values (0 and 1/count) ----
-    // Both questions about W_old were answered behind the call that produced it (ring_stats_enqueue): no drain of the stream here, so with
-    // several patches per context the host sets up patch m + 1 while the GPU still solves patch m.
-    bool first_run = false;
-    int pmax = 0;
-    RET(ring_stats_get(ctx, P, &pmax, &first_run));
-    RET(dMisc.ensure(64));
-    ht.mark("first_run + pmax");
-    int kstride = 1;
-    if (with_projection) {                                // :84-87
-        int64_t nk = std::min<int64_t>(T, (int64_t)pmax * 100);
-        if (nk < 1) nk = 1;
-        kstride = (int)(T / nk);
-        if (kstride < 1) kstride = 1;
-    }
-    // with a threshold the frames are SELECTED instead (:62-67) and nmax = nnz(ind_frames) = size(Bf, 2) makes k = 1 at :84-85
-    // (also when nmax >= T, where nk = min(T, nmax) = T)
-    if (outl) kstride = 1;
-    BgGeom g;
-    g.nr = P->nr; g.nc = P->nc; g.nr_b = P->nr_b; g.nc_b = P->nc_b; g.roff = P->roff; g.coff = P->coff;
-    g.r0_abs = P->brect[0]; g.c0_abs = P->brect[2]; g.d1 = P->d1; g.d2 = P->d2;
-    g.nbr = (P->nr_b + BLK - 1) / BLK; g.nbc = (P->nc_b + BLK - 1) / BLK;
-    g.d = P->d; g.d_b = P->d_b; g.T = T; g.kstride = kstride;
-    g.Tp = (T + kstride - 1) / kstride;                   // numel(1:k:T)
-    g.nbr = (P->nr_b + BLK - 1) / BLK; g.nbc = (P->nc_b + BLK - 1) / BLK;
-    // ---- incremental Gram (k_win_proj / k_cov_correct above): per 16x16 block, the footprints with a pixel within two blocks of it ----
-    g.p_radius = 0;
-    for (int i = 0; i < P->p; ++i) g.p_radius = std::max(g.p_radius, std::max(std::abs(P->dr[i]), std::abs(P->dc[i])));
-    g.nbw = ((2 * g.p_radius) >> 4) + 2;
-    g.p = p;
-    // two ring pixels of one centre are up to 2*p_radius apart along an axis: their 16x16 blocks up to maxd apart (2 for radius <= 16, 3 up to 24)
-    const int maxd = (2 * g.p_radius + 15) >> 4, nrel = nrel_of(maxd);
-    if (maxd > 3 || g.nbw > 4) return fail(CNMFE_EUNSUPPORTED, "fit_ring_model: ring offsets up to %d pixels (the block-pair table covers <= 24)", g.p_radius);
-    bool incr = !outl && ctx->opt("gram_incremental", 1) != 0 && K < 32768;   // the clipped Bf is not linear in the video: direct Gram   // (derived low-resolution patches of bg_ssub included: their video is built once)
-    std::vector<int> lst_ptr, lst_k, blk_nt[4];
-    std::vector<short> slot_of;
-    static thread_local std::vector<int> nbox;               // 4 per neuron: first / last row, first / last column of its footprint in the block region
-    if (incr) {
-        // (flat arrays, two passes: a vector of vectors cost 0.4 ms of allocator churn per fit at the headline size, in front of the window projection)
-        const int nblk_ = g.nbr * g.nbc;
-        static thread_local std::vector<int> own, seen, cnt, pairs_b, pairs_k, mark;
-        own.assign(nblk_, -1); seen.assign(nblk_, -1); cnt.assign(nblk_ + 1, 0);
-        pairs_b.clear(); pairs_k.clear();
-        nbox.assign((size_t)4 * std::max(1, K), 0);
-        for (int k = 0; k < K && has_a; ++k) {
-            mark.clear();
-            int bx[4] = {1 << 30, -1, 1 << 30, -1};                                 // the footprint's bounding box in the block region: rows, columns
-            // (the entries of a column ascend with the pixel index: one step per run of an image column of the block region, not per entry -- this list
-            //  building sits in front of the window projection's launch)
-            for (int64_t e = A_colptr[k]; e < A_colptr[k + 1];) {
-                const int q0 = A_rowidx[e], cb = q0 / P->nr_b, col_end = (cb + 1) * P->nr_b;
-                int qlast = q0;
-                ++e;
-                while (e < A_colptr[k + 1] && A_rowidx[e] < col_end && A_rowidx[e] >= qlast) { qlast = A_rowidx[e]; ++e; }
-                bx[0] = std::min(bx[0], q0 - cb * P->nr_b); bx[1] = std::max(bx[1], qlast - cb * P->nr_b); bx[2] = std::min(bx[2], cb); bx[3] = std::max(bx[3], cb);
-                for (int bi = (q0 - cb * P->nr_b) >> 4; bi <= (qlast - cb * P->nr_b) >> 4; ++bi) {
-                    const int b_ = (cb >> 4) * g.nbr + bi;
-                    if (own[b_] != k) { own[b_] = k; mark.push_back(b_); }
-                }
-            }
-            for (int i = 0; i < 4; ++i) nbox[(size_t)4 * k + i] = bx[i];
-            for (int b_ : mark)
-                for (int dj = -maxd; dj <= maxd; ++dj)
-                    for (int di = -maxd; di <= maxd; ++di) {
-                        const int i2 = b_ % g.nbr + di, j2 = b_ / g.nbr + dj;
-                        if (i2 < 0 || i2 >= g.nbr || j2 < 0 || j2 >= g.nbc) continue;
-                        const int nb_ = j2 * g.nbr + i2;
-                        if (seen[nb_] != k) { seen[nb_] = k; pairs_b.push_back(nb_); pairs_k.push_back(k); ++cnt[nb_ + 1]; }
-                    }
-        }
-        lst_ptr.assign(nblk_ + 1, 0);
-        for (int b_ = 0; b_ < nblk_; ++b_) {
-            if (cnt[b_ + 1] > WIN_NLB) { incr = false; break; }                     // denser than the window kernel is built for: direct Gram
-            lst_ptr[b_ + 1] = lst_ptr[b_] + cnt[b_ + 1];
-        }
-        if (incr) {
-            lst_k.resize(pairs_k.size());
-            slot_of.assign((size_t)nblk_ * std::max(1, K), (short)-1);
-            std::vector<int> &fill = cnt;                                           // next free slot per block
-            for (int b_ = 0; b_ < nblk_; ++b_) fill[b_] = 0;
-            for (size_t i = 0; i < pairs_k.size(); ++i) {                           // pairs are k-major: every list comes out in ascending k, as before
-                const int b_ = pairs_b[i], k = pairs_k[i], s_ = fill[b_]++;
-                lst_k[lst_ptr[b_] + s_] = k; slot_of[(size_t)b_ * K + k] = (short)s_;
-            }
-            for (int b_ = 0; b_ < nblk_; ++b_) { const int n = lst_ptr[b_ + 1] - lst_ptr[b_]; if (n) blk_nt[(n - 1) >> 4].push_back(b_); }
-        }
-    }
-    if (incr && P->base_valid && P->base_kstride != kstride) {
+    if (f.incr && P->base_valid && P->base_kstride != f.kstride) {
         // the table in place is of another stride: it moves to the second slot, and what that slot held -- the table of THIS stride, if the recording
         // alternates -- comes forward (otherwise its memory is where the new table is built)
         P->cov_base.swap(P->cov_base_alt); P->rowsum_base.swap(P->rowsum_base_alt);
         std::swap(P->base_valid, P->base_alt_valid); std::swap(P->base_kstride, P->base_alt_kstride);
         P->sys.swap(P->sys_alt); std::swap(P->sys_valid, P->sys_alt_valid);          // (the packed systems belong to their table)
-        P->kinv_valid = false; P->kinv_lam_valid = false; P->kinv_fits = 0;          // (and the inverses to the packed systems)
+        P->drop_inverses();                                                          // (and the inverses to the packed systems)
     }
-    const bool build_base = incr && !(P->base_valid && P->base_kstride == kstride);
-    if (build_base) { P->sys_valid = false; P->kinv_valid = false; P->kinv_lam_valid = false; P->kinv_fits = 0; }
-    ht.mark("footprint block lists");
-    g.bf4 = 1;
-    // round 5 (gram_i8.hpp): the Gram -- the VIDEO's table of the incremental path, or the direct Gram of Bf where that path does not apply -- on the int8 matrix
-    // pipe, exact up to a 32-bit quantisation of the data (option gram_i8, default 1; int32 range: <= 24576 used frames).  The outlier branch (a clipped,
-    // frame-selected Bf) keeps the fp64 kernel.
-    const bool use_i8 = (build_base || !incr) && !outl && ctx->opt("gram_i8", 1) != 0 && g.Tp <= 24576;
-    if (use_i8) g.bf4 = 3;
-    g.Tpad = g.bf4 == 3 ? (g.Tp + 4 * GK - 1) / (4 * GK) * (4 * GK) : (g.Tp + GK - 1) / GK * GK;   // int8: steps of four 16-frame stages
-    const int nblk = g.nbr * g.nbc;
-
-    // ---- the window projection first: it needs the footprint lists and the traces, nothing else, and takes 5 ms at the headline size -- the host
-    // builds the CSR rows of A, ind_active and the pair tables underneath it (a later fit of a patch: the video's table exists)
-    // keep_pt: this fit's window projection is the P = Yc Cc' table the next spatial update wants (all frames, the block's neurons, the same centred traces):
-    // the raw sums are kept with the patch, and so are the lists that index them (then the fit works out of the patch's copies)
-    const bool keep_pt = incr && has_a && kstride == 1 && !P->derived && !(b0_only & 2) && ctx->opt("r1_virtual", 1) != 0;
-    DevBuf &dLp = keep_pt ? P->pt_lp : ctx->inc[0], &dLk = ctx->inc[1], &dSlot = keep_pt ? P->pt_slot : ctx->inc[2], &dBl = ctx->inc[3], &dUt = ctx->inc[4], &dCsum = ctx->inc[5], &dGb = ctx->inc[6];
-    if (keep_pt) P->pt_valid = false;                        // (until the new table is queued)
-    std::vector<int> blall;
-    int nsg = 1; int64_t ut_stride = 0, gb_stride = 0;
-    bool proj_queued = false;
-    bool stage_ok = false;                                     // ring_solve_staged.hpp: this fit's neuron windows are built
-    bool win_i8 = false;                                       // the window projection ran on the int8 pipe: k_win_fix takes G from the K x K matrix
-    auto queue_projection = [&]() -> int {
-        for (int t = 3; t >= 0; --t) blall.insert(blall.end(), blk_nt[t].begin(), blk_nt[t].end());      // longest lists first
-        RET(to_dev(ctx, dLp, lst_ptr.data(), lst_ptr.size()));
-        RET(to_dev(ctx, dLk, lst_k.data(), lst_k.size()));
-        RET(to_dev(ctx, dBl, blall.data(), blall.size()));
-        RET(dCsum.ensure((size_t)K * sizeof(double)));
-        LAUNCH(ctx, "bg_trace_subsum", k_trace_subsum, dim3(K), dim3(256), 0, dCc.as<float>(), ldc, g.Tp, g.kstride, dCsum.as<double>());
-        const int nb_ = (int)blall.size();
-        // frame segments per block: enough workgroups to fill the chip; small patches (few blocks) get more, shorter segments
-        nsg = nb_ >= 512 ? std::max(1, std::min(8, (2048 + nb_ - 1) / nb_)) : std::max(1, std::min(16, (4096 + nb_ - 1) / std::max(1, nb_)));
-        ut_stride = (int64_t)std::max<size_t>(1, lst_k.size()) * BLKPX; gb_stride = (int64_t)nblk * WIN_NLB * WIN_NLB;
-        RET(dUt.ensure((size_t)nsg * ut_stride * sizeof(double)));
-        RET(dGb.ensure((size_t)nsg * gb_stride * sizeof(double)));
-        if (P->dig_valid && g.kstride == 1 && g.Tp <= 24576 && ctx->opt("win_i8", 1) != 0 && K > 0) {
-            // round 5 (win_proj_i8.hpp): the same sums on the int8 matrix pipe out of the resident digit planes; G = Cc Cc' once, K x K
-            // (round 6 ran a strided fit here too -- planes of every frame, trace digits zeroed on the skipped frames: correct, and no faster than the fp64 kernel on
-            //  patches of 128 x 128, which reads its 2 GB at 5.5 TB/s already, while the K x K trace Gram became a kernel of its own: profiles/r06/c5shard_i8.txt)
-            const int64_t T16 = P->dig_T16;
-            if (!trace_i8_done) {                                // (the first fit of a patch: the digit planes did not exist when the traces went up)
-                RET(ctx->tdig.ensure((size_t)K * T16 * 4 * sizeof(uint4)));
-                RET(ctx->tscale.ensure((size_t)K * sizeof(double)));
-                RET(ctx->gk.ensure((size_t)K * K * sizeof(double)));
-                LAUNCH(ctx, "bg_trace_dig", k_trace_dig, dim3(K), dim3(256), 0, dCc.as<float>(), ldc, (int64_t)T, T16, ctx->tdig.as<uint4>(), ctx->tscale.as<double>());
-                const int ntk = ((int)K + 15) >> 4;
-                LAUNCH(ctx, "bg_trace_gram", k_trace_gram, dim3((unsigned)(ntk * (ntk + 1) / 2)), dim3(64 * TG_W), 0, dCc.as<float>(), ldc, (int64_t)T, (int)K, ctx->gk.as<double>());
-            }
-            std::vector<int> items;
-            for (int b_ : blall) {
-                const int ntl = (lst_ptr[b_ + 1] - lst_ptr[b_] + 15) >> 4;
-                for (int gq = 0; gq < (ntl + 1) / 2; ++gq) items.push_back(b_ | (gq << 24));
-            }
-            RET(to_dev(ctx, ctx->win_items, items.data(), items.size()));
-            if (!items.empty())
-                if (win_planes3(ctx, T16)) { LAUNCH(ctx, "bg_win_proj", k_win_proj_i8<1>, dim3((unsigned)(items.size() * nsg)), dim3(512), 0, P->dig.as<uint4>(), T16, P->dig_sc.as<double>(), ctx->tdig.as<uint4>(),
-                       ctx->tscale.as<double>(), dLp.as<int>(), dLk.as<int>(), ctx->win_items.as<int>(), nsg, dUt.as<double>(), ut_stride); } else { LAUNCH(ctx, "bg_win_proj", k_win_proj_i8<0>, dim3((unsigned)(items.size() * nsg)), dim3(512), 0, P->dig.as<uint4>(), T16, P->dig_sc.as<double>(), ctx->tdig.as<uint4>(),
-                       ctx->tscale.as<double>(), dLp.as<int>(), dLk.as<int>(), ctx->win_items.as<int>(), nsg, dUt.as<double>(), ut_stride); }
-            win_i8 = true;
-        } else if (g.kstride == 1 || g.kstride == 2 || g.kstride == 4) {
-            const int nbig = (int)blk_nt[3].size();              // blall starts with the longest lists
-            if (nbig)
-                LAUNCH(ctx, "bg_win_proj", k_win_proj4<true>, dim3((unsigned)(nbig * nsg)), dim3(256), 0, P->Yc4.as<float4>(), g, dCc.as<float>(), ldc, dLp.as<int>(), dLk.as<int>(),
-                       dBl.as<int>(), nsg, dUt.as<double>(), ut_stride, dGb.as<double>(), gb_stride);
-            if (nb_ > nbig)
-                LAUNCH(ctx, "bg_win_proj", k_win_proj4<false>, dim3((unsigned)((nb_ - nbig) * nsg)), dim3(256), 0, P->Yc4.as<float4>(), g, dCc.as<float>(), ldc, dLp.as<int>(),
-                       dLk.as<int>(), dBl.as<int>() + nbig, nsg, dUt.as<double>(), ut_stride, dGb.as<double>(), gb_stride);
-        } else
-        LAUNCH(ctx, "bg_win_proj", k_win_proj, dim3((unsigned)(nb_ * nsg)), dim3(256), 0, P->Yc4.as<float4>(), g, dCc.as<float>(), ldc, dLp.as<int>(), dLk.as<int>(),
-               dBl.as<int>(), nsg, dUt.as<double>(), ut_stride, dGb.as<double>(), gb_stride);
-        proj_queued = true;
-        return 0;
-    };
-    if (incr && has_a && !build_base) RET(queue_projection());
-    ht.mark("projection queued");
-    RET(upload_csr());
-    ht.mark("A csr");
-
-    // ---- ind_active (:25-29) ----
-    RET(dActive.ensure(P->d));
-    int64_t nactive = P->d;
-    if (first_run) {
-        CK(hipMemsetAsync(dActive.p, 1, P->d, ctx->st()));
-    } else {
+    f.build_base = f.incr && !(P->base_valid && P->base_kstride == f.kstride);
+    if (f.build_base) P->drop_systems();
+    f.ht.mark("footprint block lists");
+    // the outlier branch (a clipped, frame-selected Bf) keeps the fp64 Gram kernel
+    f.use_i8 = (f.build_base || !f.incr) && !f.outl && gram_i8_ok(ctx, f.g.Tp);
+    geom_frames(f.g, f.g.Tp, f.use_i8);
+    // keep_pt: all frames, the block's neurons, the same centred traces -- the raw sums are kept with the patch, and so are the lists that index them (then the fit
+    // works out of the patch's copies)
+    f.keep_pt = f.incr && f.has_a && f.kstride == 1 && !P->derived && !(f.b0_only & 2) && ctx->opt("r1_virtual", 1) != 0;
+    if (f.keep_pt) { f.dLp = &P->pt_lp; f.dSlot = &P->pt_slot; P->pt_valid = false; }      // (until the new table is queued)
+}
+// ---- the window projection: it needs the footprint lists and the traces, nothing else, and takes 5 ms at the headline size ----
+static int fit_queue_projection(RingFit &f) {
+    cnmfe_ctx *ctx = f.ctx; Patch *P = f.P; const BgGeom &g = f.g;
+    RET(to_dev(ctx, *f.dLp, f.L.lst_ptr)); RET(to_dev(ctx, f.dLk, f.L.lst_k)); RET(to_dev(ctx, f.dBl, f.L.blall)); RET(f.dCsum.ensure((size_t)f.K * sizeof(double)));
+    LAUNCH(ctx, "bg_trace_subsum", k_trace_subsum, dim3(f.K), dim3(256), 0, f.dCc.as<float>(), f.ldc, g.Tp, g.kstride, f.dCsum.as<double>());
+    const int nb_ = (int)f.L.blall.size(), nbig = (int)f.L.blk_nt[3].size();                    // blall starts with the longest lists
+    f.nsg = plan::win_segments(nb_);
+    f.ut_stride = (int64_t)std::max<size_t>(1, f.L.lst_k.size()) * BLKPX; f.gb_stride = (int64_t)f.nblk * WIN_NLB * WIN_NLB;
+    RET(f.dUt.ensure((size_t)f.nsg * f.ut_stride * sizeof(double))); RET(f.dGb.ensure((size_t)f.nsg * f.gb_stride * sizeof(double)));
+    const int *dLp = f.dLp->as<int>(), *dLk = f.dLk.as<int>(), *dBl = f.dBl.as<int>();
+    if (win_i8_applies(ctx, P, g.kstride)) {
+        // the same sums out of the resident digit planes; G = Cc Cc' once, K x K
+        // (round 6 ran a strided fit here too -- planes of every frame, trace digits zeroed on the skipped frames: correct, and no faster than the fp64 kernel on
+        //  patches of 128 x 128, which reads its 2 GB at 5.5 TB/s already, while the K x K trace Gram became a kernel of its own: profiles/r06/c5shard_i8.txt)
+        // (the first fit of a patch: the digit planes did not exist when the traces went up)
+        if (!f.trace_i8_done) RET(trace_digits(ctx, "bg_trace_dig", f.dCc.as<float>(), f.ldc, f.K, f.T, P->dig_T16, true));
+        RET(win_proj_i8_launch(ctx, P, "bg_win_proj", f.L.lst_ptr, f.L.blall, dLp, dLk, f.nsg, f.dUt.as<double>(), f.ut_stride));
+        f.win_i8 = true;
+    } else if (g.kstride == 1 || g.kstride == 2 || g.kstride == 4)
+        RET(win_proj4_launch(ctx, "bg_win_proj", P, g, f.dCc.as<float>(), f.ldc, dLp, dLk, dBl, nbig, nb_, f.nsg, f.dUt.as<double>(), f.ut_stride, f.dGb.as<double>(), f.gb_stride));
+    else
+        LAUNCH(ctx, "bg_win_proj", k_win_proj, dim3((unsigned)(nb_ * f.nsg)), dim3(256), 0, P->Yc4.as<float4>(), g, f.dCc.as<float>(), f.ldc, dLp, dLk, dBl, f.nsg, f.dUt.as<double>(), f.ut_stride,
+               f.dGb.as<double>(), f.gb_stride);
+    f.proj_queued = true;
+    return 0;
+}
+// ---- ind_active (:25-29), b0 (:44) ----
+static int fit_active_b0(RingFit &f) {
+    cnmfe_ctx *ctx = f.ctx; Patch *P = f.P;
+    RET(f.dActive.ensure(P->d));
+    f.nactive = P->d;
+    if (f.first_run) { CK(hipMemsetAsync(f.dActive.p, 1, P->d, ctx->st())); } else {
         std::vector<float> asum(P->d_b, 0.f);
         // isempty(A) -> A = ones(d,1) (:14-16).  Bit 1 of b0_only: the reference passes A = [] because it subtracted A*C itself (bg_ssub > 1)
-        if (a_empty || (b0_only & 2)) std::fill(asum.begin(), asum.end(), 1.0f);
-        else if (has_a) for (int64_t q = 0; q < P->d_b; ++q) { double s = 0; for (int64_t e = csr.rowptr[q]; e < csr.rowptr[q + 1]; ++e) s += csr.val[e]; asum[q] = (float)s; }
-        RET(to_dev(ctx, dAsum, asum.data(), asum.size()));
-        CK(hipMemsetAsync(dMisc.p, 0, 64, ctx->st()));
-        LAUNCH(ctx, "bg_active", k_active, dim3((unsigned)((P->d + 255) / 256)), dim3(256), 0, P->W.as<float>(), g,
-               P->ring_dr.as<int>(), P->ring_dc.as<int>(), dAsum.as<float>(), dActive.as<unsigned char>(), dMisc.as<int>());
+        if (f.a_empty || (f.b0_only & 2)) std::fill(asum.begin(), asum.end(), 1.0f);
+        else if (f.has_a) for (int64_t q = 0; q < P->d_b; ++q) { double s = 0; for (int64_t e = f.csr.rowptr[q]; e < f.csr.rowptr[q + 1]; ++e) s += f.csr.val[e]; asum[q] = (float)s; }
+        RET(to_dev(ctx, f.dAsum, asum));
+        CK(hipMemsetAsync(f.dMisc.p, 0, 64, ctx->st()));
+        LAUNCH(ctx, "bg_active", k_active, dim3((unsigned)((P->d + 255) / 256)), dim3(256), 0, P->W.as<float>(), f.g,
+               P->ring_dr.as<int>(), P->ring_dc.as<int>(), f.dAsum.as<float>(), f.dActive.as<unsigned char>(), f.dMisc.as<int>());
         // the count is only reported (info[2]): it lands in pinned memory and is read if the call ends with a drain anyway (b0_out)
-        CK(hipMemcpyAsync((char *)P->stat_host + 8, dMisc.p, sizeof(int), hipMemcpyDeviceToHost, ctx->st()));
-        nactive = -1;
+        CK(hipMemcpyAsync((char *)P->stat_host + 8, f.dMisc.p, sizeof(int), hipMemcpyDeviceToHost, ctx->st()));
+        f.nactive = -1;
     }
-    // ---- b0 (:44) ----
-    LAUNCH(ctx, "bg_b0", k_b0, dim3((unsigned)((P->d + 255) / 256)), dim3(256), 0, P->ymean_d.as<double>(), g,
-           has_a ? dArow.as<int>() : nullptr, dAcol.as<int>(), dAval.as<float>(), dCm.as<double>(), P->b0.as<double>());
-
-    ht.mark("ind_active + b0");
-    {   // (pixels that are not active keep their weights: the solve kernel skips them; a patch without any costs the sweep of its tables)
-        // ---- pair list: blocks that hold ring pixels of some patch pixel (or patch pixels), displacement within +-maxd ----
-        std::vector<char> touched(nblk, 0);
-        {
-            const int pi0 = std::max(0, P->roff - g.p_radius) / BLK, pi1 = std::min(P->nr_b - 1, P->roff + P->nr - 1 + g.p_radius) / BLK;
-            const int pj0 = std::max(0, P->coff - g.p_radius) / BLK, pj1 = std::min(P->nc_b - 1, P->coff + P->nc - 1 + g.p_radius) / BLK;
-            for (int j = pj0; j <= pj1; ++j)
-                for (int i = pi0; i <= pi1; ++i) touched[j * g.nbr + i] = 1;
-        }
-        std::vector<int4> pairs; std::vector<int> pair_of((size_t)nblk * nrel, -1);
-        for (int j = 0; j < g.nbc; ++j)
-            for (int i = 0; i < g.nbr; ++i) {
-                if (!touched[j * g.nbr + i]) continue;
-                for (int dC = 0; dC <= maxd; ++dC)
-                    for (int dR = (dC == 0 ? 0 : -maxd); dR <= maxd; ++dR) {
-                        int i2 = i + dR, j2 = j + dC;
-                        if (i2 < 0 || i2 >= g.nbr || j2 >= g.nbc || !touched[j2 * g.nbr + i2]) continue;
-                        const int rel = rel_index(dR, dC, maxd);
-                        pair_of[(size_t)(j * g.nbr + i) * nrel + rel] = (int)pairs.size();
-                        pairs.push_back(make_int4(j * g.nbr + i, j2 * g.nbr + i2, rel, 0));
-                    }
-            }
-        const int npairs = (int)pairs.size();
-        // needed 16x16 sub-tiles: displacement set D = (O - O) u O u -O of the ring offsets O
-        const int DB = 2 * g.p_radius, DM = 2 * DB + 1;
-        std::vector<char> Dm((size_t)DM * DM, 0);
-        auto dset = [&](int dr, int dc) { if (dr >= -DB && dr <= DB && dc >= -DB && dc <= DB) Dm[(size_t)(dr + DB) * DM + dc + DB] = 1; };
-        for (int a = 0; a < p; ++a) {
-            dset(P->dr[a], P->dc[a]); dset(-P->dr[a], -P->dc[a]);
-            for (int b = 0; b < p; ++b) dset(P->dr[b] - P->dr[a], P->dc[b] - P->dc[a]);
-        }
-        std::vector<int> rel_dR(nrel), rel_dC(nrel);
-        for (int dC = 0; dC <= maxd; ++dC)
-            for (int dR = (dC == 0 ? 0 : -maxd); dR <= maxd; ++dR) { rel_dR[rel_index(dR, dC, maxd)] = dR; rel_dC[rel_index(dR, dC, maxd)] = dC; }
-        std::vector<unsigned short> needmask((size_t)nrel * 16, 0);
-        for (int rel = 0; rel < nrel; ++rel) {
-            const int dC = rel_dC[rel], dR = rel_dR[rel];
-            for (int pi = 0; pi < 16; ++pi)
-                for (int pj = 0; pj < 16; ++pj) {
-                    if (rel == 0 && pi > pj) continue;       // self pair: upper patch triangle (cov_lookup swaps)
-                    const int ri = (pi & 3) * 4, ci = (pi >> 2) * 4, rj = (pj & 3) * 4 + dR * 16, cj = (pj >> 2) * 4 + dC * 16;
-                    bool nd = false;
-                    for (int x = -3; x <= 3 && !nd; ++x)
-                        for (int y = -3; y <= 3; ++y) {
-                            const int ddr = rj - ri + x, ddc = cj - ci + y;
-                            if (ddr >= -DB && ddr <= DB && ddc >= -DB && ddc <= DB && Dm[(size_t)(ddr + DB) * DM + ddc + DB]) { nd = true; break; }
-                        }
-                    if (nd) needmask[rel * 16 + pi] |= (unsigned short)(1u << pj);
-                }
-        }
-        // work order: pair-major (the 13 displacement classes of one I block are consecutive), so heavy and light
-        // quadrants are mixed in time.  (Measured: class-major order, which makes concurrent workgroups equal-cost,
-        // was slower -- 150 vs 131 ms at 512x512x10000 -- and did not raise the L2 hit rate.)
-        std::vector<int> work;
-        for (int pp = 0; pp < npairs; ++pp)
-            for (int q = 0; q < 4; ++q) {
-                const int ih = q & 1, jh = q >> 1;
-                bool any = false;
-                for (int pi = ih * 8; pi < ih * 8 + 8; ++pi) if ((needmask[pairs[pp].z * 16 + pi] >> (jh * 8)) & 0xff) any = true;
-                if (any) work.push_back(pp * 4 + q);
-            }
-        const int nwork = (int)work.size();
-    ht.mark("pair / need / work tables");
-        DevBuf &dWork = ctx->tmp[11], &dNeed = ctx->tmp[7];
-        RET(to_dev(ctx, dPairs, pairs.data(), pairs.size()));
-        RET(to_dev(ctx, dPairOf, pair_of.data(), pair_of.size()));
-        RET(to_dev(ctx, dWork, work.data(), work.size()));
-        RET(to_dev(ctx, dNeed, needmask.data(), needmask.size()));
-        RET(ctx->cov.ensure((size_t)npairs * BLKPX * BLKPX * sizeof(double)));
-        if (ctx->opt("debug", 0)) CK(hipMemsetAsync(ctx->cov.p, 0xff, (size_t)npairs * BLKPX * BLKPX * sizeof(double), ctx->st()));   // NaN-poison skipped sub-tiles
-        int nwg = (nwork + 7) / 8 * 8;                      // multiple of 8 for the XCD remap (extra workgroups exit)
-        DevBuf &dTcnt = ctx->tmp[12], &dTl = ctx->tmp[13];
-        {
-            // tile lists per (displacement class, quadrant): needed 16x16 sub-tiles as i | j << 4 (quadrant coordinates)
-            std::vector<int> tcnt((size_t)nrel * 4, 0);
-            std::vector<int> tlist((size_t)nrel * 4 * 64, 0);
-            for (int rel = 0; rel < nrel; ++rel)
-                for (int q = 0; q < 4; ++q) {
-                    const int ih = q & 1, jh = q >> 1;
-                    int n = 0;
-                    for (int i = 0; i < 8; ++i) for (int j = 0; j < 8; ++j)
-                        if ((needmask[rel * 16 + ih * 8 + i] >> (jh * 8 + j)) & 1) tlist[(size_t)(rel * 4 + q) * 64 + n++] = i | (j << 4);
-                    tcnt[rel * 4 + q] = n;
-                }
-            RET(to_dev(ctx, dTcnt, tcnt.data(), tcnt.size()));
-            RET(to_dev(ctx, dTl, tlist.data(), tlist.size()));
-        }
-        // (every table above went through the pinned arena: no drain here, the big launches below queue behind whatever the stream still holds)
-        ht.mark("tile lists + uploads (sync)");
-        // incremental: the table of the video alone is built once (fp64 pipe) and kept with the patch; later fits skip B1 / B2a entirely
-        DevBuf &covT = incr ? P->cov_base : ctx->cov, &rsT = incr ? P->rowsum_base : ctx->rowsum;
-        const bool has_a_bf = has_a && !incr;
-        if (incr) {
-            RET(P->cov_base.ensure((size_t)npairs * BLKPX * BLKPX * sizeof(double)));
-            if (build_base && ctx->opt("debug", 0)) CK(hipMemsetAsync(P->cov_base.p, 0xff, (size_t)npairs * BLKPX * BLKPX * sizeof(double), ctx->st()));
-        }
-        if (!incr || build_base) {
-        // ---- B1: Bf tiled ----
-        RET(ctx->bf.ensure((size_t)nblk * g.Tpad * BLKPX * sizeof(float)));
+    return fit_b0(f, f.g);
+}
+// ---- pair list, needed sub-tiles, work and tile lists (ring_plan.hpp) and their uploads; the working table ----
+// (pixels that are not active keep their weights: the solve kernel skips them; a patch without any costs the sweep of its tables)
+static int fit_pair_tables(RingFit &f) {
+    cnmfe_ctx *ctx = f.ctx; Patch *P = f.P;
+    f.npairs = plan::ring_pairs(P->nr_b, P->nc_b, P->roff, P->coff, P->nr, P->nc, f.reach.p_radius, f.reach.maxd, &f.pairs, &f.pair_of);
+    plan::ring_tables(f.pairs, f.reach.maxd, f.reach.p_radius, P->dr.data(), P->dc.data(), P->p, f.tabs);
+    f.nwork = (int)f.tabs.work.size();
+    f.ht.mark("pair / need / work tables");
+    RET(to_dev(ctx, f.dPairs, f.pairs)); RET(to_dev(ctx, f.dPairOf, f.pair_of)); RET(to_dev(ctx, f.dWork, f.tabs.work)); RET(to_dev(ctx, f.dNeed, f.tabs.needmask));
+    const size_t cov_bytes = (size_t)f.npairs * BLKPX * BLKPX * sizeof(double);
+    RET(ctx->cov.ensure(cov_bytes));
+    if (ctx->opt("debug", 0)) CK(hipMemsetAsync(ctx->cov.p, 0xff, cov_bytes, ctx->st()));   // NaN-poison skipped sub-tiles
+    RET(to_dev(ctx, f.dTcnt, f.tabs.tcnt)); RET(to_dev(ctx, f.dTl, f.tabs.tlist));
+    // (every table above went through the pinned arena: no drain here, the big launches below queue behind whatever the stream still holds)
+    f.ht.mark("tile lists + uploads (sync)");
+    // incremental: the table of the video alone is built once and kept with the patch; later fits skip B1 / B2a entirely
+    if (f.incr) {
+        RET(P->cov_base.ensure(cov_bytes));
+        if (f.build_base && ctx->opt("debug", 0)) CK(hipMemsetAsync(P->cov_base.p, 0xff, cov_bytes, ctx->st()));
+    }
+    return 0;
+}
+// ---- B1: Bf tiled (fp32, or digit planes for the int8 Gram) and its row sums rsT ----
+static int fit_build_bf(RingFit &f, DevBuf &rsT) {
+    cnmfe_ctx *ctx = f.ctx; Patch *P = f.P; const BgGeom &g = f.g; const int nblk = f.nblk;
+    const bool has_a_bf = f.has_a && !f.incr;
+    RET(ctx->bf.ensure((size_t)nblk * g.Tpad * BLKPX * sizeof(float))); RET(rsT.ensure((size_t)nblk * BLKPX * sizeof(double)));
+    if (!f.use_i8) {
         const int tchunk = (int)((std::max<int64_t>(64, (g.Tpad + 15) / 16) + 7) & ~int64_t(7));
-        dim3 gb(nblk, (unsigned)((g.Tpad + tchunk - 1) / tchunk));
-        RET(rsT.ensure((size_t)nblk * BLKPX * sizeof(double)));
-        uint4 *digp = nullptr; double *digs = nullptr;          // where the digit planes of this build live
-        if (use_i8) {
-            // the VIDEO's planes stay resident with the patch (the fits' window projection reads them, win_proj_i8.hpp) when one more video's worth of memory
-            // leaves 8 GB free and the stride is 1; otherwise, and for the direct Gram of Bf, in the context's scratch
-            const size_t dbytes = (size_t)nblk * g.Tpad * BLKPX * sizeof(float);
-            bool resident = incr && kstride == 1 && !P->derived && ctx->opt("win_i8", 1) != 0;
-            if (resident && P->dig.cap < dbytes) {
-                size_t fr = 0, tot = 0;
-                CK(hipMemGetInfo(&fr, &tot));
-                if (fr < dbytes + ((size_t)8 << 30)) resident = false;
-            }
-            if (resident) {
-                RET(P->dig.ensure(dbytes)); RET(P->dig_sc.ensure((size_t)nblk * BLKPX * sizeof(double)));
-                digp = P->dig.as<uint4>(); digs = P->dig_sc.as<double>();
-                P->dig_T16 = g.Tpad >> 4; P->dig_valid = true; P->digp_valid = false;
-            } else {
-                RET(ctx->dig_scale.ensure((size_t)nblk * BLKPX * sizeof(double)));
-                digp = ctx->bf.as<uint4>(); digs = ctx->dig_scale.as<double>();
-            }
-            RET(ctx->dig_smax.ensure((size_t)nblk * BLKPX * sizeof(unsigned)));
-            CK(hipMemsetAsync(ctx->dig_smax.p, 0, (size_t)nblk * BLKPX * sizeof(unsigned), ctx->st()));
-            DigA da{has_a_bf ? dArow.as<int>() : nullptr, dAcol.as<int>(), dAval.as<float>(), dCc.as<float>(), ldc};
-            const int tchunk16 = (int)((std::max<int64_t>(64, (g.Tpad + 15) / 16) + 15) & ~int64_t(15));
-            const dim3 gd(nblk, (unsigned)((g.Tpad + tchunk16 - 1) / tchunk16));
-            LAUNCH(ctx, "bg_dig_scale", k_dig_scale, gd, dim3(256), 0, P->Yc4.as<float4>(), P->Tc, g, da, tchunk16, ctx->dig_smax.as<unsigned>());
-            RET(ctx->dig_rspart.ensure((size_t)gd.y * nblk * BLKPX * sizeof(double)));
-            LAUNCH(ctx, "bg_build_dig", k_build_dig, gd, dim3(256), 0, P->Yc4.as<float4>(), P->Tc, g, da, ctx->dig_smax.as<unsigned>(), digs, digp, tchunk16, ctx->dig_rspart.as<double>());
-            LAUNCH(ctx, "bg_rs_reduce", k_rs_reduce, dim3((unsigned)nblk), dim3(256), 0, ctx->dig_rspart.as<double>(), (int)gd.y, (int64_t)nblk * BLKPX, rsT.as<double>());
-            // round 6: a fit on every kstride-th frame (T > 100 pmax: BASELINE configs[4], T = 20000) built the planes of ITS frames above, in the scratch, for the table.
-            // The planes the spatial update's table and the temporal projection read hold EVERY frame and are built here, once per recording, under the same memory
-            // rule (until round 5 a strided recording ran both on the fp64 pipe: 2.9-3.0 ms each for a rank's share of configs[4], profiles/r05/bench_c5shard_v3.json;
-            // 2.5-2.6 ms now -- at that patch size all three video passes move their bytes at 5.5 TB/s whatever the pipe)
-            // (round 6, late: up to I8_SEG_FRAMES * 16 frames -- the projections that contract over FRAMES keep every int32 sum inside one frame segment of at most
-            //  I8_SEG_FRAMES frames, vproj.hip; the temporal projection contracts over pixels and has no such limit)
-            if (incr && kstride > 1 && !resident && !P->derived && !has_a_bf && T <= (int64_t)I8_SEG_FRAMES * 16 && ctx->opt("win_i8", 1) != 0) {
-                BgGeom g1 = g; g1.kstride = 1; g1.Tp = T; g1.Tpad = (T + 4 * GK - 1) / (4 * GK) * (4 * GK);
-                const size_t d1bytes = (size_t)nblk * g1.Tpad * BLKPX * sizeof(float);
-                bool ok = true;
-                if (P->dig.cap < d1bytes) { size_t fr = 0, tot = 0; CK(hipMemGetInfo(&fr, &tot)); if (fr < d1bytes + ((size_t)8 << 30)) ok = false; }
-                if (ok) {
-                    RET(P->dig.ensure(d1bytes)); RET(P->dig_sc.ensure((size_t)nblk * BLKPX * sizeof(double)));
-                    CK(hipMemsetAsync(ctx->dig_smax.p, 0, (size_t)nblk * BLKPX * sizeof(unsigned), ctx->st()));
-                    const int tch1 = (int)((std::max<int64_t>(64, (g1.Tpad + 15) / 16) + 15) & ~int64_t(15));
-                    const dim3 gd1(nblk, (unsigned)((g1.Tpad + tch1 - 1) / tch1));
-                    DigA dv{nullptr, nullptr, nullptr, nullptr, 0};
-                    LAUNCH(ctx, "bg_dig_scale", k_dig_scale, gd1, dim3(256), 0, P->Yc4.as<float4>(), P->Tc, g1, dv, tch1, ctx->dig_smax.as<unsigned>());
-                    LAUNCH(ctx, "bg_build_dig", k_build_dig, gd1, dim3(256), 0, P->Yc4.as<float4>(), P->Tc, g1, dv, ctx->dig_smax.as<unsigned>(), P->dig_sc.as<double>(), P->dig.as<uint4>(), tch1,
-                           (double *)nullptr);
-                    P->dig_T16 = g1.Tpad >> 4; P->dig_valid = true; P->digp_valid = false;
-                }
-            }
-        } else
-        LAUNCH(ctx, "bg_build_bf", k_build_bf, gb, dim3(256), 0, P->Yc4.as<float4>(), P->Tc, g,
-               has_a_bf ? dArow.as<int>() : nullptr, dAcol.as<int>(), dAval.as<float>(), dCc.as<float>(), ldc, ctx->bf.as<float>(), tchunk, rsT.as<double>());
-        if (outl) {
-            // ---- :50-56 clip, :60-67 frame selection ----
-            const size_t bfbytes = (size_t)nblk * g.Tpad * BLKPX * sizeof(float);
-            RET(ctx->bf2.ensure(bfbytes));
-            RET(ctx->outl_cnt.ensure((size_t)T * sizeof(int)));
-            CK(hipMemcpyAsync(ctx->bf2.p, ctx->bf.p, bfbytes, hipMemcpyDeviceToDevice, ctx->st()));
-            CK(hipMemsetAsync(ctx->outl_cnt.p, 0, (size_t)T * sizeof(int), ctx->st()));
-            LAUNCH(ctx, "bg_outlier_clip", k_outlier_clip, dim3((unsigned)((P->d + 255) / 256), (unsigned)(g.Tpad >> 2)), dim3(256), 0, ctx->bf.as<float4>(),
-                   ctx->bf2.as<float4>(), g, P->ring_dr.as<int>(), P->ring_dc.as<int>(), P->W.as<float>(), P->sn_b.as<float>(), thresh_outlier,
-                   ctx->outl_cnt.as<int>());
-            std::vector<int> sel;
-            const int64_t nmax = (int64_t)pmax * 100;                       // :61
-            if (nmax < T) {                                                 // :62
-                std::vector<int> cnt((size_t)T);
-                CK(hipMemcpyAsync(cnt.data(), ctx->outl_cnt.p, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, ctx->st()));
-                CK(hipStreamSynchronize(ctx->st()));
-                const double qv = matlab_quantile(cnt, (double)nmax / (double)T);   // :64
-                for (int64_t t = 0; t < T; ++t) if ((double)cnt[t] <= qv) sel.push_back((int)t);
-            } else for (int64_t t = 0; t < T; ++t) sel.push_back((int)t);
-            const int64_t Tpad_src = g.Tpad;
-            g.Tp = (int64_t)sel.size();
-            g.Tpad = (g.Tp + GK - 1) / GK * GK;
-            RET(to_dev(ctx, ctx->outl_sel, sel.data(), sel.size()));
-            LAUNCH(ctx, "bg_select_frames", k_select_frames, dim3(nblk, (unsigned)std::min<int64_t>(64, std::max<int64_t>(1, g.Tpad >> 2))), dim3(256), 0,
-                   ctx->bf2.as<float>(), Tpad_src, ctx->bf.as<float>(), g.Tpad, ctx->outl_sel.as<int>(), g.Tp);
-            CK(hipStreamSynchronize(ctx->st()));                           // `sel` is staged from this scope
-        }
-        if (g.bf4 < 2)
-            LAUNCH(ctx, "bg_rowsum", k_rowsum, dim3(nblk), dim3(256), 0, ctx->bf.as<float>(), g.Tpad, rsT.as<double>(), g.bf4);
-
-        {
-            const size_t shmem = (size_t)G4_NBUF * G4_STAGE_F * sizeof(float);
-            static bool attr4 = false;
-            if (!attr4) {
-                CK(hipFuncSetAttribute((const void *)k_gram4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-                attr4 = true;
-            }
-            if (use_i8) {
-                static bool attr8 = false;
-                if (!attr8) { CK(hipFuncSetAttribute((const void *)k_gram_i8, hipFuncAttributeMaxDynamicSharedMemorySize, GI_NBUF * GI_STAGE_B)); attr8 = true; }
-                LAUNCH(ctx, "bg_gram_i8", k_gram_i8, dim3(nwg), dim3(512), (size_t)GI_NBUF * GI_STAGE_B, digp, g.Tpad >> 4, dPairs.as<int4>(), dWork.as<int>(), nwork,
-                       dTcnt.as<int>(), dTl.as<int>(), digs, covT.as<double>());
-            } else
-                LAUNCH(ctx, "bg_gram_f64", k_gram4, dim3(nwg), dim3(256), shmem, ctx->bf.as<float>(), g.Tpad, dPairs.as<int4>(), dWork.as<int>(), nwork,
-                       dTcnt.as<int>(), dTl.as<int>(), 0, covT.as<double>());
-        }
-        if (incr) { P->base_valid = true; P->base_kstride = kstride; }
-        }
-        const int nt = (p + 15) / 16;
-        if (nt < 1 || nt > 8) return fail(CNMFE_EUNSUPPORTED, "fit_ring_model: %d ring neighbours (<= %d supported)", p, PMAX_RING);
-        DevBuf &dFill = ctx->solve_fill;                     // the fill values {0, 1} of missing neighbours, in global memory (ring_solve.hpp)
-        const double fillv[2] = {0.0, 1.0};
-        RET(to_dev(ctx, dFill, fillv, 2));
-        CovTab tab; tab.cov = ctx->cov.as<double>(); tab.pair_of = dPairOf.as<int>(); tab.nbr = g.nbr; tab.nbc = g.nbc; tab.maxd = maxd; tab.nrel = nrel;
-        DevBuf &dWcodes = ctx->wcodes;
-        const int woff = (g.p_radius + 15) >> 4;            // window origins reach -ceil(p_radius / 16) blocks (1 for rings up to 16 pixels, 2 up to 32)
-        const int nwin = (g.nbr + 2 * woff) * (g.nbc + 2 * woff);
-        // ---- packed systems (ring_solve_packed.hpp): the video's table re-laid once per pixel in the solve's register-tile order; the fits then apply the
-        // footprints' corrections in registers and neither sweep the table (k_cov_correct) nor gather from it.  Conditions: the incremental table,
-        // the memory (43 KB per pixel at p = 96), one launch (no split solve)
-        bool packed = incr && ctx->opt("solve_packed", 1) != 0 && (int64_t)nblk * std::max(1, K) < (int64_t)1 << 31 &&
-                      (int64_t)lst_k.size() * BLKPX < (int64_t)1 << 31;
-        const size_t sys_bytes = (size_t)P->d * ((size_t)(nt * (nt + 1) / 2) * 256 + 16 * nt) * sizeof(double);
-        if (packed && !(P->sys_valid && P->sys.cap >= sys_bytes)) {
-            if (P->sys.cap < sys_bytes) {
-                size_t fr = 0, tot = 0;
-                CK(hipMemGetInfo(&fr, &tot));
-                if (fr < sys_bytes + ((size_t)8 << 30)) packed = false;          // (not worth the last gigabytes: the table path needs none of this)
-            }
-            if (packed) {
-                RET(P->sys.ensure(sys_bytes));
-                RET(dWcodes.ensure((size_t)nwin * 256 * sizeof(int)));
-                LAUNCH(ctx, "bg_win_codes", k_win_codes, dim3((unsigned)nwin), dim3(256), 0, dPairOf.as<int>(), g.nbr, g.nbc, woff, maxd, nrel, dWcodes.as<int>());
-                CovTab tb = tab; tb.cov = P->cov_base.as<double>(); tb.wcodes = dWcodes.as<int>(); tb.woff = woff;
-                int *dErrP = nullptr;
-                RET(ctx_errflag(ctx, &dErrP));
-#define RSP_CASE(NT_) case NT_: LAUNCH(ctx, "bg_sys_pack", (k_sys_pack<NT_>), dim3((unsigned)P->d), dim3(64), 0, tb, g, P->ring_dr.as<int>(), P->ring_dc.as<int>(), \
-                                        P->rowsum_base.as<double>(), (const unsigned char *)nullptr, (float *)nullptr, dErrP, 0, (const int *)nullptr, dFill.as<double>(), P->sys.as<double>()); break;
-                switch (nt) { RSP_CASE(1) RSP_CASE(2) RSP_CASE(3) RSP_CASE(4) RSP_CASE(5) RSP_CASE(6) RSP_CASE(7) RSP_CASE(8) default: break; }
-#undef RSP_CASE
-                P->sys_valid = true; P->kinv_valid = false; P->kinv_lam_valid = false; P->kinv_fits = 0;
-            }
-        }
-        if (incr) {
-            // ---- B2a': U~ on the blocks near footprints, then one sweep base -> cov (table path) or nothing (packed path: the solve corrects in registers) ----
-            RET(ctx->rowsum.ensure((size_t)nblk * BLKPX * sizeof(double)));
-            if (has_a) {
-                if (!proj_queued) RET(queue_projection());             // (first fit of the patch: behind the video's table)
-                RET(to_dev(ctx, dSlot, slot_of.data(), slot_of.size()));
-                if (keep_pt) RET(P->pt_tab.ensure(std::max<size_t>(1, lst_k.size()) * BLKPX * sizeof(double)));
-                LAUNCH(ctx, "bg_win_fix", k_win_fix, dim3((unsigned)blall.size(), WIN_NLB / WF_S), dim3(256), 0, g, (int)K, dArow.as<int>(), dAcol.as<int>(), dAval.as<float>(), dLp.as<int>(),
-                       dSlot.as<short>(), dBl.as<int>(), nsg, dUt.as<double>(), ut_stride, dGb.as<double>(), gb_stride, keep_pt ? P->pt_tab.as<double>() : nullptr,
-                       win_i8 ? ctx->gk.as<double>() : (const double *)nullptr, dLk.as<int>());
-                if (keep_pt) {
-                    P->pt_K = K; P->pt_lp_h = lst_ptr; P->pt_slot_h = slot_of;
-                    P->pt_gen = bound_rows_of(ctx, C, c_order, K, P->pt_rows) ? ctx->bound_gen : -1;
-                    P->pt_valid = true;
-                }
-                const int csplit = npairs >= 8192 ? 1 : npairs >= 4096 ? 2 : 4;      // (small patches: a pair's sweep is a long serial loop, one workgroup per pair leaves the chip idle)
-                if (!packed)
-                LAUNCH(ctx, "bg_cov_correct", k_cov_correct, dim3((unsigned)npairs, (unsigned)csplit), dim3(256), 0, P->cov_base.as<double>(), ctx->cov.as<double>(), dPairs.as<int4>(),
-                       dNeed.as<unsigned short>(), g, (int)K, dArow.as<int>(), dAcol.as<int>(), dAval.as<float>(), dLp.as<int>(), dSlot.as<short>(), dUt.as<double>());
-                LAUNCH(ctx, "bg_rowsum_correct", k_rowsum_correct, dim3(nblk), dim3(256), 0, P->rowsum_base.as<double>(), ctx->rowsum.as<double>(), g,
-                       dArow.as<int>(), dAcol.as<int>(), dAval.as<float>(), dCsum.as<double>());
-                // ---- round 6 (ring_solve_staged.hpp): U~ and A of every neuron as dense images over its footprint's bounding box dilated by the ring radius,
-                // and per list position the neuron's window: the solve samples them with index arithmetic instead of walking CSR rows and slot tables ----
-                if (packed && ctx->opt("solve_staged", 1) != 0 && P->nr_b < 32768 && P->nc_b < 32768) {
-                    std::vector<int> nmeta((size_t)8 * K, 0), lmeta((size_t)8 * std::max<size_t>(1, lst_k.size()), 0);
-                    int64_t tot = 0;
-                    stage_ok = true;
-                    for (int k = 0; k < K; ++k) {
-                        int *mk = &nmeta[(size_t)8 * k];
-                        if (nbox[(size_t)4 * k + 1] < 0) continue;                   // (an empty footprint: on no list)
-                        // a centre whose ring reaches the footprint lies within one radius of its bounding box (the candidate test), and that ring's pixels within
-                        // two: U~ = Yc Cc' - ... is non-zero wherever the video is, and the correction pairs it with A on ANOTHER ring pixel
-                        const int R2 = 2 * g.p_radius;
-                        const int r0 = std::max(0, nbox[(size_t)4 * k] - R2), r1 = std::min(P->nr_b - 1, nbox[(size_t)4 * k + 1] + R2);
-                        const int c0 = std::max(0, nbox[(size_t)4 * k + 2] - R2), c1 = std::min(P->nc_b - 1, nbox[(size_t)4 * k + 3] + R2);
-                        mk[5] = std::max(0, nbox[(size_t)4 * k] - g.p_radius) | (std::min(P->nr_b - 1, nbox[(size_t)4 * k + 1] + g.p_radius) << 16);
-                        mk[6] = std::max(0, nbox[(size_t)4 * k + 2] - g.p_radius) | (std::min(P->nc_b - 1, nbox[(size_t)4 * k + 3] + g.p_radius) << 16);
-                        const int64_t n = (int64_t)(r1 - r0 + 1) * (c1 - c0 + 1);
-                        if (n > NWIN_MAX || tot + n > ((int64_t)1 << 30)) { stage_ok = false; break; }
-                        mk[0] = r0; mk[1] = c0; mk[2] = r1 - r0 + 1; mk[3] = c1 - c0 + 1; mk[4] = (int)tot;
-                        tot += n;
-                    }
-                    if (stage_ok) {
-                        for (size_t i = 0; i < lst_k.size(); ++i) {
-                            const int *mk = &nmeta[(size_t)8 * lst_k[i]];
-                            int *ml = &lmeta[8 * i];
-                            ml[0] = lst_k[i]; ml[1] = mk[0]; ml[2] = mk[1]; ml[3] = mk[2]; ml[4] = mk[3]; ml[5] = mk[4]; ml[6] = mk[5]; ml[7] = mk[6];
-                        }
-                        RET(to_dev(ctx, ctx->stg[0], nmeta.data(), nmeta.size()));
-                        RET(to_dev(ctx, ctx->stg[1], lmeta.data(), lmeta.size()));
-                        RET(ctx->stg[2].ensure((size_t)std::max<int64_t>(1, tot) * sizeof(double)));
-                        RET(ctx->stg[3].ensure((size_t)std::max<int64_t>(1, tot) * sizeof(float)));
-                        int *dErrW = nullptr;
-                        RET(ctx_errflag(ctx, &dErrW));
-                        LAUNCH(ctx, "bg_neuron_windows", k_nwin_build, dim3((unsigned)K), dim3(256), 0, ctx->stg[0].as<int>(), g, (int)K, dArow.as<int>(), dAcol.as<int>(), dAval.as<float>(),
-                               dLp.as<int>(), dSlot.as<short>(), dUt.as<double>(), ctx->stg[2].as<double>(), ctx->stg[3].as<float>(), dErrW);
-                    }
-                }
-            } else {                                                   // no footprints: Bf is the centred video itself
-                if (!packed)
-                CK(hipMemcpyAsync(ctx->cov.p, P->cov_base.p, (size_t)npairs * BLKPX * BLKPX * sizeof(double), hipMemcpyDeviceToDevice, ctx->st()));
-                CK(hipMemcpyAsync(ctx->rowsum.p, P->rowsum_base.p, (size_t)nblk * BLKPX * sizeof(double), hipMemcpyDeviceToDevice, ctx->st()));
-            }
-        }
-        ht.mark("base / correction launches");
-        // ---- B2b ----
-        const unsigned char *act = first_run ? nullptr : dActive.as<unsigned char>();
-        const int probe = (int)ctx->opt("solve_probe", 0);
-        if (packed) {
-            PackArgs pa{};
-            if (has_a) {
-                pa.arow = dArow.as<int>(); pa.acol = dAcol.as<int>(); pa.aval = dAval.as<float>(); pa.lst_ptr = dLp.as<int>(); pa.lst_k = dLk.as<int>();
-                pa.slot_of = dSlot.as<short>(); pa.K = (int)K; pa.Ut = dUt.as<double>();
-            }
-            int *dErrS = nullptr;
-            RET(ctx_errflag(ctx, &dErrS));
-            // ---- round 6 (ring_solve_inv.hpp): the fit out of the cached explicit inverses.  solve_inv: 0 off; 1 (default) the inverses are built in front of a
-            // patch's SECOND fit with footprints (a recording fitted once never pays the build) at the ridge its first fit left; 2 in front of the first ----
-            const int inv_mode = (int)ctx->opt("solve_inv", 0);             // (off by default: in the steady-state iteration the ridge drifts every fit, the series takes 1-2 terms per pixel and the fit is no faster than the factorising kernel -- DESIGN.md)
-            const size_t kinv_bytes = (size_t)P->d * (size_t)ri_stride(nt) * sizeof(double);
-            bool inv_ok = inv_mode != 0 && has_a && nt <= 6 && !(probe & 7);
-            if (inv_ok && P->kinv.cap < kinv_bytes) {
-                size_t fr = 0, tot = 0;
-                CK(hipMemGetInfo(&fr, &tot));
-                if (fr < kinv_bytes + ((size_t)8 << 30)) inv_ok = false;
-            }
-            double *lam_arr = nullptr;
-            if (inv_ok) {
-                if (P->kinv_lam.cap < (size_t)P->d * sizeof(double)) { RET(P->kinv_lam.ensure((size_t)P->d * sizeof(double))); P->kinv_lam_valid = false; }
-                RET(P->kinv_list.ensure(((size_t)2 * P->d + 4) * sizeof(int)));
-                if (!P->kinv_lam_valid) { CK(hipMemsetAsync(P->kinv_lam.p, 0, (size_t)P->d * sizeof(double), ctx->st())); P->kinv_lam_valid = true; }
-                lam_arr = P->kinv_lam.as<double>();
-                if (!P->kinv_valid && (P->kinv_fits >= 1 || inv_mode >= 2)) {
-                    RET(P->kinv.ensure(kinv_bytes));
-#define RI_CASE(NT_) case NT_: LAUNCH(ctx, "bg_ring_inverse", (k_ring_inverse<NT_>), dim3((unsigned)P->d), dim3(64), 0, P->sys.as<double>(), g, P->ring_dr.as<int>(), \
-                                        P->ring_dc.as<int>(), P->rowsum_base.as<double>(), (const double *)lam_arr, P->kinv.as<double>()); break;
-                    switch (nt) { RI_CASE(1) RI_CASE(2) RI_CASE(3) RI_CASE(4) RI_CASE(5) RI_CASE(6) default: break; }
-#undef RI_CASE
-                    P->kinv_valid = true;
-                }
-                ++P->kinv_fits;
-            }
-            if (inv_ok && P->kinv_valid) {
-                int *flist = P->kinv_list.as<int>(), *rlist = flist + P->d, *fcnt = flist + 2 * P->d;
-                CK(hipMemsetAsync(fcnt, 0, 4 * sizeof(int), ctx->st()));
-                InvArgs ia{};
-                ia.kp = P->kinv.as<double>(); ia.sys = P->sys.as<double>(); ia.csum = dCsum.as<double>(); ia.lam_out = lam_arr;
-                ia.flist = flist; ia.rlist = rlist; ia.fcnt = fcnt; ia.maxit = (int)ctx->opt("solve_inv_terms", 5);
-                const unsigned nlist = (unsigned)std::min<int64_t>(P->d, 2048);
-#define RA_CASE(NT_) case NT_: \
-                LAUNCH(ctx, "bg_ring_solve", (k_ring_apply<NT_>), dim3((unsigned)P->d), dim3(64), 0, ia, pa, g, P->ring_dr.as<int>(), P->ring_dc.as<int>(), ctx->rowsum.as<double>(), \
-                       act, P->W.as<float>(), dErrS, probe, (const int *)nullptr); \
-                LAUNCH(ctx, "bg_ring_solve_rest", (k_ring_solve6<NT_>), dim3((unsigned)P->d), dim3(64), 0, P->sys.as<double>(), pa, g, P->ring_dr.as<int>(), P->ring_dc.as<int>(), \
-                       ctx->rowsum.as<double>(), (const unsigned char *)nullptr, P->W.as<float>(), dErrS, probe, (const int *)flist, (const int *)fcnt, lam_arr); \
-                LAUNCH(ctx, "bg_ring_inverse_rest", (k_ring_inverse_list<NT_>), dim3(nlist), dim3(64), 0, P->sys.as<double>(), g, P->ring_dr.as<int>(), P->ring_dc.as<int>(), \
-                       P->rowsum_base.as<double>(), (const double *)lam_arr, P->kinv.as<double>(), (const int *)rlist, (const int *)(fcnt + 3)); break;
-                switch (nt) { RA_CASE(1) RA_CASE(2) RA_CASE(3) RA_CASE(4) RA_CASE(5) RA_CASE(6) default: break; }
-#undef RA_CASE
-            } else if (has_a && stage_ok && nt <= 6) {
-                StageArgs sg{dLp.as<int>(), ctx->stg[1].as<int>(), ctx->stg[2].as<double>(), ctx->stg[3].as<float>()};
-#define RS8_CASE(NT_) case NT_: LAUNCH(ctx, "bg_ring_solve", (k_ring_solve8<NT_>), dim3((unsigned)P->d), dim3(64), 0, P->sys.as<double>(), sg, g, P->ring_dr.as<int>(), \
-                                        P->ring_dc.as<int>(), ctx->rowsum.as<double>(), act, P->W.as<float>(), dErrS, probe, (const int *)nullptr, lam_arr); break;
-                switch (nt) { RS8_CASE(1) RS8_CASE(2) RS8_CASE(3) RS8_CASE(4) RS8_CASE(5) RS8_CASE(6) default: break; }
-#undef RS8_CASE
-            } else {
-#define RS6_CASE(NT_) case NT_: LAUNCH(ctx, "bg_ring_solve", (k_ring_solve6<NT_>), dim3((unsigned)P->d), dim3(64), 0, P->sys.as<double>(), pa, g, P->ring_dr.as<int>(), \
-                                        P->ring_dc.as<int>(), ctx->rowsum.as<double>(), act, P->W.as<float>(), dErrS, probe, (const int *)nullptr, (const int *)nullptr, lam_arr); break;
-            switch (nt) { RS6_CASE(1) RS6_CASE(2) RS6_CASE(3) RS6_CASE(4) RS6_CASE(5) RS6_CASE(6) RS6_CASE(7) RS6_CASE(8) default: break; }
-#undef RS6_CASE
-            }
-        } else {
-        RET(dWcodes.ensure((size_t)nwin * 256 * sizeof(int)));
-        LAUNCH(ctx, "bg_win_codes", k_win_codes, dim3((unsigned)nwin), dim3(256), 0, dPairOf.as<int>(), g.nbr, g.nbc, woff, maxd, nrel, dWcodes.as<int>());
-        tab.wcodes = dWcodes.as<int>(); tab.woff = woff;
-        RET(solve_launch(ctx, P, tab, g, ctx->rowsum.as<double>(), act, nt, probe, dFill.as<double>()));
+        LAUNCH(ctx, "bg_build_bf", k_build_bf, dim3(nblk, (unsigned)((g.Tpad + tchunk - 1) / tchunk)), dim3(256), 0, P->Yc4.as<float4>(), P->Tc, g,
+               has_a_bf ? f.dArow.as<int>() : nullptr, f.dAcol.as<int>(), f.dAval.as<float>(), f.dCc.as<float>(), f.ldc, ctx->bf.as<float>(), tchunk, rsT.as<double>());
+        return 0;
+    }
+    // the VIDEO's planes stay resident with the patch (the fits' window projection reads them, win_proj_i8.hpp) when one more video's worth of memory
+    // leaves 8 GB free and the stride is 1; otherwise, and for the direct Gram of Bf, in the context's scratch
+    const size_t dbytes = (size_t)nblk * g.Tpad * BLKPX * sizeof(float), sbytes = (size_t)nblk * BLKPX * sizeof(double);
+    bool resident = f.incr && planes_wanted(ctx, P, f.kstride);
+    if (resident) RET(fits_leaving(P->dig, dbytes, &resident));
+    if (resident) {
+        RET(P->dig.ensure(dbytes)); RET(P->dig_sc.ensure(sbytes));
+        f.digp = P->dig.as<uint4>(); f.digs = P->dig_sc.as<double>();
+        P->dig_T16 = g.Tpad >> 4; P->dig_valid = true; P->digp_valid = false;
+    } else {
+        RET(ctx->dig_scale.ensure(sbytes));
+        f.digp = ctx->bf.as<uint4>(); f.digs = ctx->dig_scale.as<double>();
+    }
+    int nchunk = 0;
+    RET(build_digits(ctx, P, g, DigA{has_a_bf ? f.dArow.as<int>() : nullptr, f.dAcol.as<int>(), f.dAval.as<float>(), f.dCc.as<float>(), f.ldc}, f.digs, f.digp, &nchunk));
+    LAUNCH(ctx, "bg_rs_reduce", k_rs_reduce, dim3((unsigned)nblk), dim3(256), 0, ctx->dig_rspart.as<double>(), nchunk, (int64_t)nblk * BLKPX, rsT.as<double>());
+    // round 6: a fit on every kstride-th frame (T > 100 pmax: BASELINE configs[4], T = 20000) built the planes of ITS frames above, in the scratch, for the table.
+    // The planes the spatial update's table and the temporal projection read hold EVERY frame and are built here, once per recording, under the same memory
+    // rule (until round 5 a strided recording ran both on the fp64 pipe: 2.9-3.0 ms each for a rank's share of configs[4], profiles/r05/bench_c5shard_v3.json;
+    // 2.5-2.6 ms now -- at that patch size all three video passes move their bytes at 5.5 TB/s whatever the pipe)
+    // (round 6, late: up to I8_SEG_FRAMES * 16 frames -- the projections that contract over FRAMES keep every int32 sum inside one frame segment of at most
+    //  I8_SEG_FRAMES frames, vproj.hip; the temporal projection contracts over pixels and has no such limit)
+    if (f.incr && f.kstride > 1 && !has_a_bf && f.T <= (int64_t)I8_SEG_FRAMES * 16 && planes_wanted(ctx, P, 1)) {
+        BgGeom g1 = g; g1.kstride = 1; geom_frames(g1, f.T, true);
+        bool ok = false;
+        RET(fits_leaving(P->dig, (size_t)nblk * g1.Tpad * BLKPX * sizeof(float), &ok));
+        if (ok) {
+            RET(P->dig.ensure((size_t)nblk * g1.Tpad * BLKPX * sizeof(float))); RET(P->dig_sc.ensure(sbytes));
+            RET(build_digits(ctx, P, g1, DigA{nullptr, nullptr, nullptr, nullptr, 0}, P->dig_sc.as<double>(), P->dig.as<uint4>(), nullptr));
+            P->dig_T16 = g1.Tpad >> 4; P->dig_valid = true; P->digp_valid = false;
         }
     }
+    return 0;
+}
+// ---- :50-56 clip, :60-67 frame selection (the outlier branch: Bf is rewritten in place, g's frames become the kept ones) ----
+static int fit_outlier_frames(RingFit &f) {
+    cnmfe_ctx *ctx = f.ctx; Patch *P = f.P; BgGeom &g = f.g; const int64_t T = f.T;
+    const size_t bfbytes = (size_t)f.nblk * g.Tpad * BLKPX * sizeof(float);
+    RET(ctx->bf2.ensure(bfbytes)); RET(ctx->outl_cnt.ensure((size_t)T * sizeof(int)));
+    CK(hipMemcpyAsync(ctx->bf2.p, ctx->bf.p, bfbytes, hipMemcpyDeviceToDevice, ctx->st()));
+    CK(hipMemsetAsync(ctx->outl_cnt.p, 0, (size_t)T * sizeof(int), ctx->st()));
+    LAUNCH(ctx, "bg_outlier_clip", k_outlier_clip, dim3((unsigned)((P->d + 255) / 256), (unsigned)(g.Tpad >> 2)), dim3(256), 0, ctx->bf.as<float4>(),
+           ctx->bf2.as<float4>(), g, P->ring_dr.as<int>(), P->ring_dc.as<int>(), P->W.as<float>(), P->sn_b.as<float>(), f.thresh_outlier,
+           ctx->outl_cnt.as<int>());
+    std::vector<int> sel;
+    const int64_t nmax = (int64_t)f.pmax * 100;                     // :61
+    if (nmax < T) {                                                 // :62
+        std::vector<int> cnt((size_t)T);
+        CK(hipMemcpyAsync(cnt.data(), ctx->outl_cnt.p, (size_t)T * sizeof(int), hipMemcpyDeviceToHost, ctx->st()));
+        CK(hipStreamSynchronize(ctx->st()));
+        const double qv = matlab_quantile(cnt, (double)nmax / (double)T);   // :64
+        for (int64_t t = 0; t < T; ++t) if ((double)cnt[t] <= qv) sel.push_back((int)t);
+    } else for (int64_t t = 0; t < T; ++t) sel.push_back((int)t);
+    const int64_t Tpad_src = g.Tpad;
+    geom_frames(g, (int64_t)sel.size(), false);
+    RET(to_dev(ctx, ctx->outl_sel, sel));
+    LAUNCH(ctx, "bg_select_frames", k_select_frames, dim3(f.nblk, (unsigned)std::min<int64_t>(64, std::max<int64_t>(1, g.Tpad >> 2))), dim3(256), 0,
+           ctx->bf2.as<float>(), Tpad_src, ctx->bf.as<float>(), g.Tpad, ctx->outl_sel.as<int>(), g.Tp);
+    CK(hipStreamSynchronize(ctx->st()));                           // `sel` is staged from this scope
+    return 0;
+}
+// ---- B1 + B2a: the table this fit has to build -- the video's (kept with the patch) or the direct Gram of Bf (the context's working table) ----
+static int fit_base_table(RingFit &f) {
+    cnmfe_ctx *ctx = f.ctx; Patch *P = f.P; const BgGeom &g = f.g;
+    DevBuf &covT = f.incr ? P->cov_base : ctx->cov, &rsT = f.incr ? P->rowsum_base : ctx->rowsum;
+    RET(fit_build_bf(f, rsT));
+    if (f.outl) RET(fit_outlier_frames(f));
+    if (g.bf4 < 2) LAUNCH(ctx, "bg_rowsum", k_rowsum, dim3(f.nblk), dim3(256), 0, ctx->bf.as<float>(), g.Tpad, rsT.as<double>(), g.bf4);
+    const int nwg = (f.nwork + 7) / 8 * 8;                    // multiple of 8 for the XCD remap (extra workgroups exit)
+    const size_t shmem = (size_t)G4_NBUF * G4_STAGE_F * sizeof(float);
+    static bool attr4 = false, attr8 = false;
+    if (!attr4) { CK(hipFuncSetAttribute((const void *)k_gram4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); attr4 = true; }
+    if (f.use_i8) {
+        if (!attr8) { CK(hipFuncSetAttribute((const void *)k_gram_i8, hipFuncAttributeMaxDynamicSharedMemorySize, GI_NBUF * GI_STAGE_B)); attr8 = true; }
+        LAUNCH(ctx, "bg_gram_i8", k_gram_i8, dim3(nwg), dim3(512), (size_t)GI_NBUF * GI_STAGE_B, f.digp, g.Tpad >> 4, f.dPairs.as<int4>(), f.dWork.as<int>(), f.nwork,
+               f.dTcnt.as<int>(), f.dTl.as<int>(), f.digs, covT.as<double>());
+    } else
+        LAUNCH(ctx, "bg_gram_f64", k_gram4, dim3(nwg), dim3(256), shmem, ctx->bf.as<float>(), g.Tpad, f.dPairs.as<int4>(), f.dWork.as<int>(), f.nwork,
+               f.dTcnt.as<int>(), f.dTl.as<int>(), 0, covT.as<double>());
+    if (f.incr) { P->base_valid = true; P->base_kstride = f.kstride; }
+    return 0;
+}
+// the block-pair codes per window origin (k_win_codes): for the pack and for the table solve
+static int fit_win_codes(RingFit &f) {
+    const int woff = f.reach.woff, nwin = (f.g.nbr + 2 * woff) * (f.g.nbc + 2 * woff);
+    RET(f.ctx->wcodes.ensure((size_t)nwin * 256 * sizeof(int)));
+    LAUNCH(f.ctx, "bg_win_codes", k_win_codes, dim3((unsigned)nwin), dim3(256), 0, f.dPairOf.as<int>(), f.g.nbr, f.g.nbc, woff, f.reach.maxd, f.reach.nrel, f.ctx->wcodes.as<int>());
+    return 0;
+}
+// ---- packed systems (ring_solve_packed.hpp): the video's table re-laid once per pixel in the solve's register-tile order; the fits then apply the
+// footprints' corrections in registers and neither sweep the table (k_cov_correct) nor gather from it.  Conditions: the incremental table,
+// the memory, one launch (no split solve) ----
+static int fit_pack(RingFit &f) {
+    cnmfe_ctx *ctx = f.ctx; Patch *P = f.P; const int nt = f.nt;
+    const double fillv[2] = {0.0, 1.0};                      // the fill values {0, 1} of missing neighbours, in global memory (ring_solve.hpp)
+    RET(to_dev(ctx, ctx->solve_fill, fillv, 2));
+    f.packed = f.incr && pack_wanted(ctx, nt) && (int64_t)f.nblk * std::max(1, f.K) < (int64_t)1 << 31 && (int64_t)f.L.lst_k.size() * BLKPX < (int64_t)1 << 31;
+    const size_t sys_bytes = sys_bytes_of(P->d, nt);
+    if (!f.packed || (P->sys_valid && P->sys.cap >= sys_bytes)) return 0;
+    RET(fits_leaving(P->sys, sys_bytes, &f.packed));         // (not worth the last gigabytes: the table path needs none of this)
+    if (!f.packed) return 0;
+    RET(P->sys.ensure(sys_bytes));
+    RET(fit_win_codes(f));
+    CovTab tb = f.covtab(); tb.cov = P->cov_base.as<double>(); tb.wcodes = ctx->wcodes.as<int>(); tb.woff = f.reach.woff;
+    int *dErrP = nullptr;
+    RET(ctx_errflag(ctx, &dErrP));
+    RET(nt_dispatch<8>(nt, [&](auto c) -> int {
+        LAUNCH(ctx, "bg_sys_pack", (k_sys_pack<NT_OF(c)>), dim3((unsigned)P->d), dim3(64), 0, tb, f.g, P->ring_dr.as<int>(), P->ring_dc.as<int>(), P->rowsum_base.as<double>(),
+               (const unsigned char *)nullptr, (float *)nullptr, dErrP, 0, (const int *)nullptr, ctx->solve_fill.as<double>(), P->sys.as<double>());
+        return 0; }));
+    P->drop_inverses(); P->sys_valid = true;
+    return 0;
+}
+// ---- round 6 (ring_solve_staged.hpp): U~ and A of every neuron as dense images over its footprint's bounding box dilated by the ring radius, and per list
+// position the neuron's window: the solve samples them with index arithmetic instead of walking CSR rows and slot tables ----
+static int fit_stage_windows(RingFit &f) {
+    cnmfe_ctx *ctx = f.ctx; Patch *P = f.P;
+    if (!(f.packed && ctx->opt("solve_staged", 1) != 0 && P->nr_b < 32768 && P->nc_b < 32768)) return 0;
+    static thread_local std::vector<int> nmeta, lmeta;
+    const int64_t tot = plan::stage_windows(f.K, fit_nbox, f.L.lst_k, P->nr_b, P->nc_b, f.reach.p_radius, nmeta, lmeta);
+    if (tot < 0) return 0;                                     // (a window too large: k_ring_solve6 serves this fit)
+    f.stage_ok = true;
+    RET(to_dev(ctx, ctx->stg[0], nmeta)); RET(to_dev(ctx, ctx->stg[1], lmeta));
+    RET(ctx->stg[2].ensure((size_t)std::max<int64_t>(1, tot) * sizeof(double)));
+    RET(ctx->stg[3].ensure((size_t)std::max<int64_t>(1, tot) * sizeof(float)));
+    int *dErrW = nullptr;
+    RET(ctx_errflag(ctx, &dErrW));
+    LAUNCH(ctx, "bg_neuron_windows", k_nwin_build, dim3((unsigned)f.K), dim3(256), 0, ctx->stg[0].as<int>(), f.g, (int)f.K, f.dArow.as<int>(), f.dAcol.as<int>(), f.dAval.as<float>(),
+           f.dLp->as<int>(), f.dSlot->as<short>(), f.dUt.as<double>(), ctx->stg[2].as<double>(), ctx->stg[3].as<float>(), dErrW);
+    return 0;
+}
+// ---- B2a': U~ on the blocks near footprints, then one sweep base -> cov (table path) or nothing (packed path: the solve corrects in registers) ----
+static int fit_corrections(RingFit &f, const float *C, int c_order) {
+    cnmfe_ctx *ctx = f.ctx; Patch *P = f.P; const BgGeom &g = f.g; const int K = (int)f.K;
+    RET(ctx->rowsum.ensure((size_t)f.nblk * BLKPX * sizeof(double)));
+    if (!f.has_a) {                                            // no footprints: Bf is the centred video itself
+        if (!f.packed) CK(hipMemcpyAsync(ctx->cov.p, P->cov_base.p, (size_t)f.npairs * BLKPX * BLKPX * sizeof(double), hipMemcpyDeviceToDevice, ctx->st()));
+        CK(hipMemcpyAsync(ctx->rowsum.p, P->rowsum_base.p, (size_t)f.nblk * BLKPX * sizeof(double), hipMemcpyDeviceToDevice, ctx->st()));
+        return 0;
+    }
+    if (!f.proj_queued) RET(fit_queue_projection(f));          // (first fit of the patch: behind the video's table)
+    RET(to_dev(ctx, *f.dSlot, f.L.slot_of));
+    if (f.keep_pt) RET(P->pt_tab.ensure(std::max<size_t>(1, f.L.lst_k.size()) * BLKPX * sizeof(double)));
+    LAUNCH(ctx, "bg_win_fix", k_win_fix, dim3((unsigned)f.L.blall.size(), WIN_NLB / WF_S), dim3(256), 0, g, K, f.dArow.as<int>(), f.dAcol.as<int>(), f.dAval.as<float>(), f.dLp->as<int>(),
+           f.dSlot->as<short>(), f.dBl.as<int>(), f.nsg, f.dUt.as<double>(), f.ut_stride, f.dGb.as<double>(), f.gb_stride, f.keep_pt ? P->pt_tab.as<double>() : nullptr,
+           f.win_i8 ? ctx->gk.as<double>() : (const double *)nullptr, f.dLk.as<int>());
+    if (f.keep_pt) {
+        P->pt_K = K; P->pt_lp_h = f.L.lst_ptr; P->pt_slot_h = f.L.slot_of;
+        P->pt_gen = bound_rows_of(ctx, C, c_order, K, P->pt_rows) ? ctx->bound_gen : -1;
+        P->pt_valid = true;
+    }
+    const int csplit = f.npairs >= 8192 ? 1 : f.npairs >= 4096 ? 2 : 4;      // (small patches: a pair's sweep is a long serial loop, one workgroup per pair leaves the chip idle)
+    if (!f.packed)
+        LAUNCH(ctx, "bg_cov_correct", k_cov_correct, dim3((unsigned)f.npairs, (unsigned)csplit), dim3(256), 0, P->cov_base.as<double>(), ctx->cov.as<double>(), f.dPairs.as<int4>(),
+               f.dNeed.as<unsigned short>(), g, K, f.dArow.as<int>(), f.dAcol.as<int>(), f.dAval.as<float>(), f.dLp->as<int>(), f.dSlot->as<short>(), f.dUt.as<double>());
+    LAUNCH(ctx, "bg_rowsum_correct", k_rowsum_correct, dim3(f.nblk), dim3(256), 0, P->rowsum_base.as<double>(), ctx->rowsum.as<double>(), g,
+           f.dArow.as<int>(), f.dAcol.as<int>(), f.dAval.as<float>(), f.dCsum.as<double>());
+    return fit_stage_windows(f);
+}
+// ---- B2b on the packed systems: out of the cached inverses (ring_solve_inv.hpp), the staged windows (k_ring_solve8) or the CSR rows (k_ring_solve6) ----
+static int fit_solve_packed(RingFit &f, const unsigned char *act, int probe) {
+    cnmfe_ctx *ctx = f.ctx; Patch *P = f.P; const BgGeom &g = f.g; const int nt = f.nt;
+    const int *dr = P->ring_dr.as<int>(), *dc = P->ring_dc.as<int>(); const double *sys = P->sys.as<double>(), *rowsum = ctx->rowsum.as<double>(); float *W = P->W.as<float>();
+    const unsigned d = (unsigned)P->d;
+    PackArgs pa{};
+    if (f.has_a) {
+        pa.arow = f.dArow.as<int>(); pa.acol = f.dAcol.as<int>(); pa.aval = f.dAval.as<float>(); pa.lst_ptr = f.dLp->as<int>(); pa.lst_k = f.dLk.as<int>();
+        pa.slot_of = f.dSlot->as<short>(); pa.K = (int)f.K; pa.Ut = f.dUt.as<double>();
+    }
+    int *dErrS = nullptr;
+    RET(ctx_errflag(ctx, &dErrS));
+    // solve_inv: 0 off; 1 the inverses are built in front of a patch's SECOND fit with footprints (a recording fitted once never pays the build) at the ridge its
+    // first fit left; 2 in front of the first  (off by default: in the steady-state iteration the ridge drifts every fit, the series takes 1-2 terms per pixel and
+    // the fit is no faster than the factorising kernel -- DESIGN.md)
+    const int inv_mode = (int)ctx->opt("solve_inv", 0);
+    const size_t kinv_bytes = (size_t)P->d * (size_t)ri_stride(nt) * sizeof(double);
+    bool inv_ok = inv_mode != 0 && f.has_a && nt <= 6 && !(probe & 7);
+    if (inv_ok) RET(fits_leaving(P->kinv, kinv_bytes, &inv_ok));
+    double *lam_arr = nullptr;
+    if (inv_ok) {
+        if (P->kinv_lam.cap < (size_t)P->d * sizeof(double)) { RET(P->kinv_lam.ensure((size_t)P->d * sizeof(double))); P->kinv_lam_valid = false; }
+        RET(P->kinv_list.ensure(((size_t)2 * P->d + 4) * sizeof(int)));
+        if (!P->kinv_lam_valid) { CK(hipMemsetAsync(P->kinv_lam.p, 0, (size_t)P->d * sizeof(double), ctx->st())); P->kinv_lam_valid = true; }
+        lam_arr = P->kinv_lam.as<double>();
+        if (!P->kinv_valid && (P->kinv_fits >= 1 || inv_mode >= 2)) {
+            RET(P->kinv.ensure(kinv_bytes));
+            RET(nt_dispatch<6>(nt, [&](auto c) -> int {
+                LAUNCH(ctx, "bg_ring_inverse", (k_ring_inverse<NT_OF(c)>), dim3(d), dim3(64), 0, sys, g, dr, dc, P->rowsum_base.as<double>(), (const double *)lam_arr, P->kinv.as<double>());
+                return 0; }));
+            P->kinv_valid = true;
+        }
+        ++P->kinv_fits;
+    }
+    if (inv_ok && P->kinv_valid) {
+        int *flist = P->kinv_list.as<int>(), *rlist = flist + P->d, *fcnt = flist + 2 * P->d;
+        CK(hipMemsetAsync(fcnt, 0, 4 * sizeof(int), ctx->st()));
+        InvArgs ia{};
+        ia.kp = P->kinv.as<double>(); ia.sys = P->sys.as<double>(); ia.csum = f.dCsum.as<double>(); ia.lam_out = lam_arr;
+        ia.flist = flist; ia.rlist = rlist; ia.fcnt = fcnt; ia.maxit = (int)ctx->opt("solve_inv_terms", 5);
+        const unsigned nlist = (unsigned)std::min<int64_t>(P->d, 2048);
+        return nt_dispatch<6>(nt, [&](auto c) -> int {
+            LAUNCH(ctx, "bg_ring_solve", (k_ring_apply<NT_OF(c)>), dim3(d), dim3(64), 0, ia, pa, g, dr, dc, rowsum, act, W, dErrS, probe, (const int *)nullptr);
+            LAUNCH(ctx, "bg_ring_solve_rest", (k_ring_solve6<NT_OF(c)>), dim3(d), dim3(64), 0, sys, pa, g, dr, dc, rowsum, (const unsigned char *)nullptr, W, dErrS, probe, (const int *)flist,
+                   (const int *)fcnt, lam_arr);
+            LAUNCH(ctx, "bg_ring_inverse_rest", (k_ring_inverse_list<NT_OF(c)>), dim3(nlist), dim3(64), 0, sys, g, dr, dc, P->rowsum_base.as<double>(), (const double *)lam_arr,
+                   P->kinv.as<double>(), (const int *)rlist, (const int *)(fcnt + 3));
+            return 0; });
+    }
+    if (f.has_a && f.stage_ok && nt <= 6) {
+        StageArgs sg{f.dLp->as<int>(), ctx->stg[1].as<int>(), ctx->stg[2].as<double>(), ctx->stg[3].as<float>()};
+        return nt_dispatch<6>(nt, [&](auto c) -> int {
+            LAUNCH(ctx, "bg_ring_solve", (k_ring_solve8<NT_OF(c)>), dim3(d), dim3(64), 0, sys, sg, g, dr, dc, rowsum, act, W, dErrS, probe, (const int *)nullptr, lam_arr);
+            return 0; });
+    }
+    return nt_dispatch<8>(nt, [&](auto c) -> int {
+        LAUNCH(ctx, "bg_ring_solve", (k_ring_solve6<NT_OF(c)>), dim3(d), dim3(64), 0, sys, pa, g, dr, dc, rowsum, act, W, dErrS, probe, (const int *)nullptr, (const int *)nullptr, lam_arr);
+        return 0; });
+}
+// ---- B2b ----
+static int fit_solve(RingFit &f) {
+    cnmfe_ctx *ctx = f.ctx;
+    const unsigned char *act = f.first_run ? nullptr : f.dActive.as<unsigned char>();
+    const int probe = (int)ctx->opt("solve_probe", 0);
+    if (f.packed) return fit_solve_packed(f, act, probe);
+    RET(fit_win_codes(f));
+    CovTab tab = f.covtab(); tab.wcodes = ctx->wcodes.as<int>(); tab.woff = f.reach.woff;
+    return solve_launch(ctx, f.P, tab, f.g, ctx->rowsum.as<double>(), act, f.nt, probe, ctx->solve_fill.as<double>());
+}
+
+int bg_fit_ring(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
+                const float *C, int c_order, int with_projection, float *b0_out, int64_t info[4], int b0_only, double thresh_outlier) {
+    RingFit f(ctx, P);
+    f.K = K; f.A_colptr = A_colptr; f.A_rowidx = A_rowidx; f.A_val = A_val; f.C = C; f.c_order = c_order; f.b0_only = b0_only; f.thresh_outlier = thresh_outlier; f.T = P->T;
+    f.outl = thresh_outlier == thresh_outlier; f.has_a = K > 0 && A_colptr[K] > 0; f.a_empty = K == 0;
+    if (f.outl && !P->sn_ready && !(b0_only & 1)) return fail(CNMFE_ESTATE, "fit_ring_model with thresh_outlier needs the noise levels of the block (cnmfe_set_noise)");
+    RET(fit_traces_up(f));
+    f.ht.mark("traces");
+    if (b0_only & 1) {
+        RET(fit_upload_csr(f));                               // bg_ssub > 1: b0 = mean(Y - A*C, 2) on the patch (update_background_parallel.m:222-223)
+        // (no drain: every upload above went through the pinned arena -- or, too large for it, waited itself -- and what reads b0 is stream-ordered behind this)
+        RET(fit_b0(f, bg_geom(P)));
+        P->ysig_valid = false;
+        return 0;
+    }
+    RET(fit_geometry(f, with_projection));
+    fit_lists(f);
+    // the window projection first when the video's table exists (a later fit of a patch): the host builds the CSR rows of A, ind_active and the pair tables underneath it
+    if (f.incr && f.has_a && !f.build_base) RET(fit_queue_projection(f));
+    f.ht.mark("projection queued");
+    RET(fit_upload_csr(f));
+    f.ht.mark("A csr");
+    RET(fit_active_b0(f));
+    f.ht.mark("ind_active + b0");
+    RET(fit_pair_tables(f));
+    if (!f.incr || f.build_base) RET(fit_base_table(f));
+    if (f.nt < 1 || f.nt > 8) return fail(CNMFE_EUNSUPPORTED, "fit_ring_model: %d ring neighbours (<= %d supported)", P->p, PMAX_RING);
+    RET(fit_pack(f));
+    if (f.incr) RET(fit_corrections(f, C, c_order));
+    f.ht.mark("base / correction launches");
+    RET(fit_solve(f));
     RET(ring_stats_enqueue(ctx, P));                         // what the NEXT fit of this patch asks of the W being written now
-    ht.mark("solve launch");
+    f.ht.mark("solve launch");
     if (b0_out) {
         std::vector<double> tmp(P->d);
         CK(hipMemcpyAsync(tmp.data(), P->b0.p, P->d * sizeof(double), hipMemcpyDeviceToHost, ctx->st()));
         CK(hipStreamSynchronize(ctx->st()));
         for (int64_t i = 0; i < P->d; ++i) b0_out[i] = (float)tmp[i];
-        if (nactive < 0) nactive = *reinterpret_cast<const int *>((const char *)P->stat_host + 8);
+        if (f.nactive < 0) f.nactive = *reinterpret_cast<const int *>((const char *)P->stat_host + 8);
     }
     // without b0_out the call returns with the fit in flight (every later engine call is stream-ordered behind it)
-    if (info) { info[0] = first_run ? 1 : 0; info[1] = kstride; info[2] = nactive; info[3] = pmax; }
+    if (info) { info[0] = f.first_run ? 1 : 0; info[1] = f.kstride; info[2] = f.nactive; info[3] = f.pmax; }
     P->ysig_valid = false;
     return 0;
 }
@@ -1330,21 +1172,8 @@ int bg_fit_ring(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, co
 // k_win_proj_i8 leaves it (per-segment partial sums in real units)
 int win_i8_table(cnmfe_ctx *ctx, Patch *P, const char *name_dig, const char *name_proj, int K, const float *dCc, int64_t ldc, const std::vector<int> &lst_ptr, const std::vector<int> &blall,
                  const int *dLp, const int *dLk, int nsg, double *dUt, int64_t ut_stride) {
-    const int64_t T16 = P->dig_T16;
-    RET(ctx->tdig.ensure((size_t)K * T16 * 4 * sizeof(uint4)));
-    RET(ctx->tscale.ensure((size_t)K * sizeof(double)));
-    LAUNCH(ctx, name_dig, k_trace_dig, dim3(K), dim3(256), 0, dCc, ldc, (int64_t)P->T, T16, ctx->tdig.as<uint4>(), ctx->tscale.as<double>());
-    std::vector<int> items;
-    for (int b_ : blall) {
-        const int ntl = (lst_ptr[b_ + 1] - lst_ptr[b_] + 15) >> 4;
-        for (int gq = 0; gq < (ntl + 1) / 2; ++gq) items.push_back(b_ | (gq << 24));
-    }
-    RET(to_dev(ctx, ctx->win_items, items.data(), items.size()));
-    if (!items.empty())
-        if (win_planes3(ctx, T16)) { LAUNCH(ctx, name_proj, k_win_proj_i8<1>, dim3((unsigned)(items.size() * nsg)), dim3(512), 0, P->dig.as<uint4>(), T16, P->dig_sc.as<double>(), ctx->tdig.as<uint4>(),
-               ctx->tscale.as<double>(), dLp, dLk, ctx->win_items.as<int>(), nsg, dUt, ut_stride); } else { LAUNCH(ctx, name_proj, k_win_proj_i8<0>, dim3((unsigned)(items.size() * nsg)), dim3(512), 0, P->dig.as<uint4>(), T16, P->dig_sc.as<double>(), ctx->tdig.as<uint4>(),
-               ctx->tscale.as<double>(), dLp, dLk, ctx->win_items.as<int>(), nsg, dUt, ut_stride); }
-    return 0;
+    RET(trace_digits(ctx, name_dig, dCc, ldc, K, P->T, P->dig_T16, false));
+    return win_proj_i8_launch(ctx, P, name_proj, lst_ptr, blall, dLp, dLk, nsg, dUt, ut_stride);
 }
 
 // loads this translation unit's code object now (HIP loads it at the first launch of one of its kernels -- milliseconds each that would otherwise fall into the first iteration): cnmfe_create

@@ -204,6 +204,8 @@ struct Patch {
     // the bytes of `sys` once more), the ridge every fit leaves per pixel, and the list of pixels a fit's fast path (k_ring_apply) left to k_ring_solve6
     // (kinv_list: [d] pixels, then 4 counters).  They belong to `sys`: invalid whenever it is
     DevBuf kinv, kinv_lam, kinv_list; bool kinv_valid = false, kinv_lam_valid = false; int kinv_fits = 0;
+    void drop_inverses() { kinv_valid = false; kinv_lam_valid = false; kinv_fits = 0; }
+    void drop_systems() { sys_valid = false; drop_inverses(); }
     // the centred video as 32-bit fixed-point digit planes [blk][frame/16][plane][256 px] x 16 B + per-pixel scales (gram_i8.hpp), kept for the fits' window projection
     // (win_proj_i8.hpp) when the memory allows: frame stride 1 only
     DevBuf dig, dig_sc; int64_t dig_T16 = 0; bool dig_valid = false;
@@ -441,6 +443,7 @@ template <class T> inline int to_dev(cnmfe_ctx *ctx, DevBuf &b, const T *h, size
     CK(hipStreamSynchronize(ctx->st()));                                   // too large for the arena: straight from the caller's buffer
     return 0;
 }
+template <class T> inline int to_dev(cnmfe_ctx *ctx, DevBuf &b, const std::vector<T> &h) { return to_dev(ctx, b, h.data(), h.size()); }
 // [k][t] row-major fp32 copy of a K x T matrix given in `order`; device result has row stride ldc (multiple of 4)
 int upload_traces(cnmfe_ctx *ctx, DevBuf &dst, const float *C, int32_t K, int64_t T, int order, int64_t *ldc);
 int download_traces(cnmfe_ctx *ctx, const float *dC, int64_t ldc, float *C, int32_t K, int64_t T, int order);
@@ -452,6 +455,8 @@ int tu_warm_resid(); int tu_warm_bg();
 int win_i8_table(cnmfe_ctx *ctx, Patch *P, const char *name_dig, const char *name_proj, int K, const float *dCc, int64_t ldc, const std::vector<int> &lst_ptr, const std::vector<int> &blall,
                  const int *dLp, const int *dLk, int nsg, double *dUt, int64_t ut_stride);   // bg.hip: the int8 window projection of all frames (the spatial update's table, vproj.hip)
 int tu_warm_factor(); int tu_warm_deconv(); int tu_warm_ssub(); int tu_warm_vproj();   // one per translation unit: load its code object (cnmfe_create)
+// bg.hip, THE memory rule: a buffer that has to grow to `bytes` may do so only if that leaves 8 GB of the device free (quarter: or a quarter of the device, if that is more)
+int fits_leaving(const DevBuf &b, size_t bytes, bool *fits, bool quarter = false);
 int bg_reserve(cnmfe_ctx *ctx, Patch *P);                 // bg.hip: the ring fit's large buffers, sized by the geometry, allocated ahead of the first fit
 int residual_run(cnmfe_ctx *ctx, Patch *P, int pid, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx,
                  const float *A_val, const float *C, int c_order, float *Ysig_out, int out_memspace, DevBuf *outbuf = nullptr, int tables_only = 0);

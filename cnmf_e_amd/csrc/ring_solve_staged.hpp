@@ -15,7 +15,6 @@
 
 namespace cnmfe {
 
-constexpr int NWIN_MAX = 32768;                      // entries of one neuron's window; a larger footprint sends the fit to k_ring_solve6
 
 struct StageArgs {
     const int *lst_ptr;                              // per 16x16 block: its list of traces

@@ -22,18 +22,6 @@
 
 namespace cnmfe {
 
-static BgGeom vp_geom(const Patch *P) {
-    BgGeom g{};
-    g.nr = P->nr; g.nc = P->nc; g.nr_b = P->nr_b; g.nc_b = P->nc_b; g.roff = P->roff; g.coff = P->coff;
-    g.r0_abs = P->brect[0]; g.c0_abs = P->brect[2]; g.d1 = P->d1; g.d2 = P->d2;
-    g.nbr = (P->nr_b + BLK - 1) / BLK; g.nbc = (P->nc_b + BLK - 1) / BLK;
-    g.d = P->d; g.d_b = P->d_b; g.T = P->T; g.kstride = 1; g.Tp = P->T; g.Tpad = (P->T + 15) / 16 * 16;
-    g.p = P->p; g.p_radius = 0;
-    for (int i = 0; i < P->p; ++i) g.p_radius = std::max(g.p_radius, std::max(std::abs(P->dr[i]), std::abs(P->dc[i])));
-    g.nbw = ((2 * g.p_radius) >> 4) + 2; g.bf4 = 1;
-    return g;
-}
-
 // ------------------------------------------------------------------------------------------------------------------------------------------
 // spatial:  U(e) = P(m_e, k_e) - sum_i W(m_e, i) P(m_e + o_i, k_e)
 // ------------------------------------------------------------------------------------------------------------------------------------------
@@ -123,7 +111,7 @@ static void reach_blocks(const Patch *P, const BgGeom &g, int R, const int32_t *
 int vproj_spatial(cnmfe_ctx *ctx, Patch *P, int32_t K, const float *C, int c_order, const int64_t *IND_colptr, const int32_t *IND_rowidx,
                   const int *dErow, const int *dEcol, const float *dCc, int64_t ldc, float *dU, double *dQ) {
     HostTrace ht(ctx, "vproj_spatial");
-    const BgGeom g = vp_geom(P);
+    const BgGeom g = bg_geom(P);
     const int nblk = g.nbr * g.nbc, R = g.p_radius;
     const int64_t nnz = IND_colptr[K];
     if ((int64_t)nblk * K >= (int64_t(1) << 31)) return 1;
@@ -153,54 +141,31 @@ int vproj_spatial(cnmfe_ctx *ctx, Patch *P, int32_t K, const float *C, int c_ord
     }
     ht.mark(reuse ? "need lists (table of the fit)" : "need lists (table to build)");
     if (!reuse) {
-        // the table of exactly these pairs, by the fit's own kernel: lists per block, longest first
-        std::vector<int> cnt((size_t)nblk + 1, 0);
-        for (int b : need) ++cnt[b + 1];
-        std::vector<int> lst_ptr((size_t)nblk + 1, 0);
-        for (int b = 0; b < nblk; ++b) {
-            if (cnt[b + 1] > WIN_NLB) return 1;            // denser than the window kernel is built for: the sweep serves this update
-            lst_ptr[b + 1] = lst_ptr[b] + cnt[b + 1];
-        }
-        std::vector<int> lst_k(need.size()), fill((size_t)nblk, 0), blk_nt[4], blall;
-        std::vector<short> slot_of((size_t)nblk * K, (short)-1);
-        for (int32_t k = 0; k < K; ++k)
-            for (int i = need_ptr[k]; i < need_ptr[k + 1]; ++i) {
-                const int b = need[i], s_ = fill[b]++;
-                lst_k[lst_ptr[b] + s_] = k; slot_of[(size_t)b * K + k] = (short)s_;
-            }
-        for (int b = 0; b < nblk; ++b) { const int n = lst_ptr[b + 1] - lst_ptr[b]; if (n) blk_nt[(n - 1) >> 4].push_back(b); }
-        for (int t = 3; t >= 0; --t) blall.insert(blall.end(), blk_nt[t].begin(), blk_nt[t].end());
+        // the table of exactly these pairs, by the fit's own kernel and list format (ring_plan.hpp); a block denser than the window kernel is built for: the sweep serves this update
+        plan::BlockLists L;
+        if (!plan::block_lists(nblk, K, need.data(), need_ptr.data(), L)) return 1;
         DevBuf &dLk = ctx->inc[1], &dBl = ctx->inc[3], &dUt = ctx->inc[4];
         P->pt_valid = false;
-        RET(to_dev(ctx, P->pt_lp, lst_ptr.data(), lst_ptr.size()));
-        RET(to_dev(ctx, P->pt_slot, slot_of.data(), slot_of.size()));
-        RET(to_dev(ctx, dLk, lst_k.data(), lst_k.size()));
-        RET(to_dev(ctx, dBl, blall.data(), blall.size()));
-        const int nb_ = (int)blall.size();
-        const int64_t nent = (int64_t)std::max<size_t>(1, lst_k.size()) * BLKPX;
+        RET(to_dev(ctx, P->pt_lp, L.lst_ptr)); RET(to_dev(ctx, P->pt_slot, L.slot_of));
+        RET(to_dev(ctx, dLk, L.lst_k)); RET(to_dev(ctx, dBl, L.blall));
+        const int nb_ = (int)L.blall.size();
+        const int64_t nent = (int64_t)std::max<size_t>(1, L.lst_k.size()) * BLKPX;
         RET(P->pt_tab.ensure((size_t)nent * sizeof(double)));
         if (nb_ > 0) {
-            int nsg = nb_ >= 512 ? std::max(1, std::min(8, (2048 + nb_ - 1) / nb_)) : std::max(1, std::min(16, (4096 + nb_ - 1) / std::max(1, nb_)));
+            int nsg = plan::win_segments(nb_);
             // the int8 kernel sums a frame segment in int32 (4 digit pairs x 2^14 per frame): at most I8_SEG_FRAMES frames per segment -- a longer recording gets more segments
             const bool i8_tab = !P->derived && P->dig_valid && P->T <= (int64_t)I8_SEG_FRAMES * 16 && ctx->opt("win_i8", 1) != 0;
             if (i8_tab) nsg = std::max(nsg, (int)((P->T + I8_SEG_FRAMES - 1) / I8_SEG_FRAMES));
             RET(dUt.ensure((size_t)nsg * nent * sizeof(double)));
-            const int nbig = (int)blk_nt[3].size();
             if (i8_tab) {
                 // round 6: the table on the int8 pipe out of the resident digit planes, by the fit's own kernel (win_proj_i8.hpp) -- what a recording whose fit runs on
                 // every other frame needs every iteration (the fit's table covers ITS frames only: BASELINE configs[4]), and any patch whose fit left no table
-                RET(win_i8_table(ctx, P, "spatial_trace_dig", "spatial_ptab_proj", K, dCc, ldc, lst_ptr, blall, P->pt_lp.as<int>(), dLk.as<int>(), nsg, dUt.as<double>(), nent));
-            } else {
-            if (nbig)
-                LAUNCH(ctx, "spatial_ptab_proj", k_win_proj4<true>, dim3((unsigned)(nbig * nsg)), dim3(256), 0, P->Yc4.as<float4>(), g, dCc, ldc, P->pt_lp.as<int>(), dLk.as<int>(),
-                       dBl.as<int>(), nsg, dUt.as<double>(), nent, (double *)nullptr, (int64_t)0);
-            if (nb_ > nbig)
-                LAUNCH(ctx, "spatial_ptab_proj", k_win_proj4<false>, dim3((unsigned)((nb_ - nbig) * nsg)), dim3(256), 0, P->Yc4.as<float4>(), g, dCc, ldc, P->pt_lp.as<int>(),
-                       dLk.as<int>(), dBl.as<int>() + nbig, nsg, dUt.as<double>(), nent, (double *)nullptr, (int64_t)0);
-            }
+                RET(win_i8_table(ctx, P, "spatial_trace_dig", "spatial_ptab_proj", K, dCc, ldc, L.lst_ptr, L.blall, P->pt_lp.as<int>(), dLk.as<int>(), nsg, dUt.as<double>(), nent));
+            } else
+                RET(win_proj4_launch(ctx, "spatial_ptab_proj", P, g, dCc, ldc, P->pt_lp.as<int>(), dLk.as<int>(), dBl.as<int>(), (int)L.blk_nt[3].size(), nb_, nsg, dUt.as<double>(), nent, nullptr, 0));
             LAUNCH(ctx, "spatial_ptab_sum", k_vp_segsum, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, dUt.as<double>(), nent, nsg, nent, P->pt_tab.as<double>());
         }
-        P->pt_K = K; P->pt_lp_h.swap(lst_ptr); P->pt_slot_h.swap(slot_of);
+        P->pt_K = K; P->pt_lp_h.swap(L.lst_ptr); P->pt_slot_h.swap(L.slot_of);
         P->pt_rows = rows; P->pt_gen = have_rows ? ctx->bound_gen : -1;
         P->pt_valid = true;
         for (int32_t k = 0; k < K; ++k) kmap[k] = k;
@@ -470,7 +435,7 @@ static int vp_launch_proj(cnmfe_ctx *ctx, Patch *V, const BgGeom &g, const VpLis
 int vproj_temporal(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
                    const int64_t *dColptr, const int *dErow, const float *dAval, float *dU, int64_t ldu) {
     HostTrace ht(ctx, "vproj_temporal");
-    const BgGeom g = vp_geom(P);
+    const BgGeom g = bg_geom(P);
     const int nblk = g.nbr * g.nbc, R = g.p_radius;
     if (16 + 2 * R > VP_WS) return 1;
     (void)A_val;
@@ -503,7 +468,7 @@ int vproj_temporal(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr,
     bool i8 = !P->derived && P->dig_valid && ctx->opt("proj_i8", 1) != 0 && nent > 0 && P->dig_T16 * 16 >= ldu;
     if (i8 && !P->digp_valid) {
         const size_t dbytes = (size_t)nblk * P->dig_T16 * 16 * 64 * sizeof(uint4);
-        if (P->digp.cap < dbytes) { size_t fr = 0, tot = 0; CK(hipMemGetInfo(&fr, &tot)); i8 = fr >= dbytes + ((size_t)8 << 30); }
+        RET(fits_leaving(P->digp, dbytes, &i8));
         if (i8) {
             RET(P->digp.ensure(dbytes));
             LAUNCH(ctx, "temporal_dig_pixmajor", k_dig_pixmajor, dim3((unsigned)nblk, (unsigned)P->dig_T16), dim3(256), 0, P->dig.as<uint4>(), P->dig_T16, P->digp.as<uint4>());
@@ -543,7 +508,7 @@ int vproj_temporal(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr,
         const size_t ybytes = (size_t)nblk * ncg_t * 64 * 64 * sizeof(float4);
         if (!P->yt4_valid) {
             bool ok = true;
-            if (P->yt4.cap < ybytes) { size_t fr = 0, tot = 0; CK(hipMemGetInfo(&fr, &tot)); ok = fr >= ybytes + ((size_t)8 << 30); }
+            RET(fits_leaving(P->yt4, ybytes, &ok));
             if (ok) {
                 RET(P->yt4.ensure(ybytes));
                 LAUNCH(ctx, "temporal_tile_video", k_tile_video, dim3((unsigned)nblk, (unsigned)ncg_t), dim3(256), 0, P->Yc4.as<float4>(), g, P->Tc, ncg_t, P->yt4.as<float4>());
@@ -804,8 +769,8 @@ int vproj_temporal_ssub(cnmfe_ctx *ctx, Patch *M, int32_t K, const int64_t *A_co
     Patch *R = get_patch(ctx, M->ss_res);
     if (!R || !R->ring_ready) return 1;
     RET(ssub_taps(ctx, M, R));
-    const BgGeom g = vp_geom(R);
-    const BgGeom gM = vp_geom(M);
+    const BgGeom g = bg_geom(R);
+    const BgGeom gM = bg_geom(M);
     const int nblk = g.nbr * g.nbc, RL = g.p_radius, ws = 16 + 2 * RL;
     if (ws > VP_WS) return 1;
     const int d1s = M->ss_d1s, d2s = M->ss_d2s;

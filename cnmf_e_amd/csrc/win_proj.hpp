@@ -3,6 +3,7 @@
 #pragma once
 #include "common.hpp"
 #include "ring_solve_core.hpp"
+#include "ring_plan.hpp"
 
 namespace cnmfe {
 
@@ -23,7 +24,19 @@ struct BgGeom {
     int bf4;                               // Bf layout: 0 = [blk][frame][256], 1 = [blk][frame/4][256][4] (k_gram4)
 };
 
-constexpr int WIN_NLB = 64;
+// frames of a fit: Tp used frames, padded for the Bf layout (i8: digit planes, steps of four 16-frame stages; otherwise float4 chunks, steps of 16)
+inline void geom_frames(BgGeom &g, int64_t Tp, bool i8) { const int64_t q = i8 ? 64 : 16; g.Tp = Tp; g.bf4 = i8 ? 3 : 1; g.Tpad = (Tp + q - 1) / q * q; }
+// THE geometry of a patch: a fit (or a projection) on every kstride-th frame
+inline BgGeom bg_geom(const Patch *P, int kstride = 1, bool i8 = false) {
+    BgGeom g{};
+    const plan::Reach r = plan::ring_reach(P->dr.data(), P->dc.data(), P->p);
+    g.nr = P->nr; g.nc = P->nc; g.nr_b = P->nr_b; g.nc_b = P->nc_b; g.roff = P->roff; g.coff = P->coff;
+    g.r0_abs = P->brect[0]; g.c0_abs = P->brect[2]; g.d1 = P->d1; g.d2 = P->d2;
+    g.nbr = (P->nr_b + BLK - 1) / BLK; g.nbc = (P->nc_b + BLK - 1) / BLK;
+    g.d = P->d; g.d_b = P->d_b; g.T = P->T; g.kstride = kstride; g.p = P->p; g.p_radius = r.p_radius; g.nbw = r.nbw;
+    geom_frames(g, (P->T + kstride - 1) / kstride, i8);   // numel(1:k:T)
+    return g;
+}
 #ifndef WIN_AHEAD_N
 #define WIN_AHEAD_N 2
 #endif
@@ -153,5 +166,11 @@ __global__ void __launch_bounds__(256, (BIG ? 1 : 2)) k_win_proj4(const float4 *
     }
 }
 
-
+// the blocks of `blall` (device copy dBl: the nbig blocks of the longest class first, nb in all), nsg frame segments each
+inline int win_proj4_launch(cnmfe_ctx *ctx, const char *name, const Patch *P, const BgGeom &g, const float *dCc, int64_t ldc, const int *dLp, const int *dLk, const int *dBl, int nbig, int nb,
+                            int nsg, double *dUt, int64_t ut_stride, double *dGb, int64_t gb_stride) {
+    if (nbig) LAUNCH(ctx, name, k_win_proj4<true>, dim3((unsigned)(nbig * nsg)), dim3(256), 0, P->Yc4.as<float4>(), g, dCc, ldc, dLp, dLk, dBl, nsg, dUt, ut_stride, dGb, gb_stride);
+    if (nb > nbig) LAUNCH(ctx, name, k_win_proj4<false>, dim3((unsigned)((nb - nbig) * nsg)), dim3(256), 0, P->Yc4.as<float4>(), g, dCc, ldc, dLp, dLk, dBl + nbig, nsg, dUt, ut_stride, dGb, gb_stride);
+    return 0;
+}
 }  // namespace cnmfe

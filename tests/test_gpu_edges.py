@@ -948,3 +948,37 @@ def test_temporal_jobs_across_patches_equal_the_per_patch_updates(deconv):
     assert np.array_equal(r0, r1) and np.array_equal(c0, c1) and (a0 != a1).nnz == 0
     assert np.isfinite(c1).all() and np.abs(c1).max() > 0
     assert lv <= 2 * 3 * 8, lv                                 # levels x maxIter launches per update for ALL four patches together, not per patch
+
+
+def test_denser_than_the_window_kernel_falls_back_to_the_direct_gram(eng):
+    """More than 64 footprints within reach of one 16 x 16 block (70 here, all inside one block): the window kernels' lists overflow and the fit leaves the
+    incremental path for the direct Gram of Bf -- the kernels gram_incremental = 0 runs, on the same inputs (the int8 Gram of Bf, the table solve), so two
+    consecutive fits under the default options and under gram_incremental = 0 agree bit for bit in W, b0 and info."""
+    d1, d2, T, r, K = 40, 36, 300, 5, 70
+    f, Y, video = _video(eng, d1, d2, T, 3, r, 13)
+    rng = np.random.default_rng(17)
+    rows, cols, vals = [], [], []
+    for k in range(K):                                           # one to three pixels each, in rows 16..31 x columns 16..31: block (1, 1) of the field
+        n = int(rng.integers(1, 4))
+        q = rng.choice(256, n, replace=False)
+        rows += [(16 + int(x) // 16) * d1 + 16 + int(x) % 16 for x in q]; cols += [k] * n; vals += list(0.5 + rng.random(n))
+    A = sp.csc_matrix((np.array(vals, np.float32), (rows, cols)), shape=(d1 * d2, K))
+    Cm = (0.1 + rng.random((K, T))).astype(np.float32)
+    seq = [(A, Cm), (A * 0.9, Cm * 1.1)]
+    def run(incr):
+        eng.set_option("gram_incremental", incr)
+        eng.ring_init(0, r)
+        out = []
+        for Ai, Ci in seq:
+            b0, info = eng.fit_ring_model(0, Ai.tocsc(), Ci)
+            out.append((eng.ring_csr(0).data, b0, info))
+        return out
+    try:
+        eng.set_option("gram_i8", 1)
+        default, direct = run(1), run(0)
+        for (wa, ba, ia), (wb, bb, ib) in zip(default, direct):
+            assert np.all(np.isfinite(wa)) and np.abs(wa).max() > 0
+            assert np.array_equal(wa, wb) and np.array_equal(ba, bb)
+            assert ia == ib
+    finally:
+        eng.set_option("gram_incremental", 1); eng.set_option("gram_i8", 1)
