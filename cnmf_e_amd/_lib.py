@@ -143,6 +143,11 @@ PROTOTYPES = {
     "cnmfe_get_option": (C.c_int, [c_ctx, C.c_char_p, C.POINTER(C.c_int64)]),
     "cnmfe_temporal_early_project": (C.c_int, [c_ctx, C.c_int32, i64p, i32p, C.POINTER(C.c_int64)]),
     "cnmfe_temporal_early_claim": (C.c_int, [c_ctx, C.c_int64]),
+    "cnmfe_traces_load": (C.c_int, [c_ctx, C.c_int32, C.c_int64, f32p, f32p, f32p, f32p, C.c_int]),
+    "cnmfe_trace_corr": (C.c_int, [c_ctx, C.c_int32, C.c_int64, f32p, C.c_int, C.c_int, f64p]),
+    "cnmfe_trace_diff_spikes": (C.c_int, [c_ctx, C.c_int32, C.c_int64, f32p, C.c_int, f32p, f32p]),
+    "cnmfe_trace_tags": (C.c_int, [c_ctx, C.c_int32, f64p]),
+    "cnmfe_merge_apply": (C.c_int, [c_ctx, C.c_int32, i32p, i32p, f64p, C.c_int32, i32p, C.POINTER(DeconvOpts), f32p, f32p, f32p, f32p, f32p]),
 }
 # exports younger than the oldest build CNMFE_LIB is used with (A/B runs against the parent commit's library)
 OPTIONAL = {"cnmfe_get_option", "cnmfe_temporal_early_project", "cnmfe_temporal_early_claim"}
@@ -151,6 +156,7 @@ OPTIONAL = {"cnmfe_get_option", "cnmfe_temporal_early_project", "cnmfe_temporal_
 F32, F64, U16, U8, F16 = 0, 1, 2, 3, 4
 HOST, DEVICE = 0, 1
 COLMAJOR, ROWMAJOR, BOUND, BOUND_ROWS = 0, 1, 2, 3
+RES_CRAW, RES_S, RES_DIFF = 4, 5, 6         # trace sources of the merge entry points: the context's resident C_raw / S, the last cnmfe_trace_diff_spikes
 SPATIAL_HALS, SPATIAL_HALS_THRESH, SPATIAL_NNLS = 0, 1, 2
 
 

@@ -646,7 +646,9 @@ int cnmfe_set_option(cnmfe_ctx *ctx, const char *name, int64_t value) {
 int cnmfe_get_option(cnmfe_ctx *ctx, const char *name, int64_t *value) {
     if (!ctx || !name || !value) return fail(CNMFE_EINVAL, "null argument");
     const struct { const char *n; int64_t v; } counters[] = {{"temporal_early_hits", ctx->early_hits}, {"temporal_early_drops", ctx->early_drops}, {"temporal_early_declined", ctx->early_declined},
-                                                              {"temporal_early_entries", ctx->early_nent}, {"temporal_proj_entries", ctx->last_nent}, {"temporal_nowait", ctx->sweep_nowait}};
+                                                              {"temporal_early_entries", ctx->early_nent}, {"temporal_proj_entries", ctx->last_nent}, {"temporal_nowait", ctx->sweep_nowait},
+                                                              {"merge_trace_uploads", ctx->merge_uploads},
+                                                              {"bound_K", ctx->bound_valid ? (int64_t)ctx->bound_K : 0}, {"bound_T", ctx->bound_valid ? ctx->bound_T : 0}};
     for (const auto &c : counters) if (!strcmp(c.n, name)) { *value = c.v; return 0; }
     auto it = ctx->opts.find(name);
     if (it == ctx->opts.end()) return fail(CNMFE_EINVAL, "option '%s' is unknown or was never set (its default holds)", name);
@@ -1744,6 +1746,58 @@ int cnmfe_deconv_temporal_bound(cnmfe_ctx *ctx, const cnmfe_deconv_opts *opts, f
     CK(hipSetDevice(ctx->device));
     GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;          // (lanes: lane 0, behind the other lanes; they wait for what this queues)
     return deconv_bound_run(ctx, opts, C_out, C_raw_out, S_out, kernel_pars_out, sn_out);
+}
+
+// ---- merging (merge.hpp) ----
+static int merge_src_check(int32_t K, int64_t T, const float *X, int src) {
+    if (K < 0 || T <= 0) return fail(CNMFE_EINVAL, "bad K / T");
+    if (src < CNMFE_COLMAJOR || src > CNMFE_RES_DIFF || src == CNMFE_BOUND_ROWS) return fail(CNMFE_EINVAL, "bad trace source %d", src);
+    if (K > 0 && (src == CNMFE_COLMAJOR || src == CNMFE_ROWMAJOR) && !X) return fail(CNMFE_EINVAL, "null trace matrix");
+    return 0;
+}
+int cnmfe_traces_load(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *C, const float *C_raw, const float *S, const float *kernel_pars, int c_order) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    if (K <= 0 || T <= 0 || !C) return fail(CNMFE_EINVAL, "bad K / T / null C");
+    if (c_order != CNMFE_ROWMAJOR && c_order != CNMFE_COLMAJOR) return fail(CNMFE_EINVAL, "bad c_order");
+    CK(hipSetDevice(ctx->device));
+    GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
+    return traces_load_run(ctx, K, T, C, C_raw, S, kernel_pars, c_order);
+}
+int cnmfe_trace_corr(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, int raw, double *out) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    RET(merge_src_check(K, T, X, src));
+    if (K == 0) return 0;
+    if (!out) return fail(CNMFE_EINVAL, "null output");
+    CK(hipSetDevice(ctx->device));
+    GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
+    return trace_corr_run(ctx, K, T, X, src, raw, out);
+}
+int cnmfe_trace_diff_spikes(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, float *sn_out, float *S_out) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    RET(merge_src_check(K, T, X, src));
+    if (K == 0) { ctx->diff_K = 0; return 0; }
+    CK(hipSetDevice(ctx->device));
+    GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
+    return trace_diff_spikes_run(ctx, K, T, X, src, sn_out, S_out);
+}
+int cnmfe_trace_tags(cnmfe_ctx *ctx, int32_t K, double *out) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    if (K < 0) return fail(CNMFE_EINVAL, "bad K");
+    if (K == 0) return 0;
+    if (!out) return fail(CNMFE_EINVAL, "null output");
+    CK(hipSetDevice(ctx->device));
+    GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
+    return trace_tags_run(ctx, K, out);
+}
+int cnmfe_merge_apply(cnmfe_ctx *ctx, int32_t ngroups, const int32_t *grp_ptr, const int32_t *grp_idx, const double *w, int32_t nkeep, const int32_t *keep,
+                      const cnmfe_deconv_opts *opts, float *C_out, float *C_raw_out, float *S_out, float *kernel_pars_out, float *sn_out) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    if (ngroups < 0 || nkeep < 0) return fail(CNMFE_EINVAL, "bad group / keep count");
+    if (ngroups > 0 && (!grp_ptr || !grp_idx || !w || !opts)) return fail(CNMFE_EINVAL, "null group arrays / deconvolution options");
+    if (nkeep > 0 && !keep) return fail(CNMFE_EINVAL, "null keep list");
+    CK(hipSetDevice(ctx->device));
+    GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
+    return merge_apply_run(ctx, ngroups, grp_ptr, grp_idx, w, nkeep, keep, opts, C_out, C_raw_out, S_out, kernel_pars_out, sn_out);
 }
 
 int cnmfe_post_process_spatial(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr,

@@ -380,6 +380,12 @@ struct cnmfe_ctx {
     int64_t early_seq = 0, early_hits = 0, early_drops = 0, early_declined = 0, early_nent = 0, sweep_nowait = 0;   // counters (cnmfe_get_option)
     std::vector<cnmfe::TemporalJob *> tjobs; int tjobs_used = 0;          // cnmfe_hals_temporal_job: kept (with their buffers) from update to update, counted from cnmfe_stitch_begin
     cnmfe::DevBuf dcv_c, dcv_s, dcv_pars, dcv_sn;          // cnmfe_deconv_temporal_bound: C_raw - b (after the swap with `bound`), S, kernel_pars, sn -- read by the copy stream, so not shared scratch
+    // merging (merge.hpp): dcv_c / dcv_s / dcv_pars / dcv_sn are the C_raw, S, kernel_pars, sn that belong to the bound matrix C while res_gen == bound_gen
+    // (cnmfe_deconv_temporal_bound, cnmfe_traces_load, cnmfe_merge_apply set it; every other change of the bound matrix' content leaves it behind)
+    int64_t res_gen = -1; bool res_has_s = false;
+    cnmfe::DevBuf mrg[23];                                 // [0] an uploaded source, [1] the result of cnmfe_trace_diff_spikes (diff_K x diff_T), [2..5] moments / K x K / sn, [6..22] cnmfe_merge_apply
+    int32_t diff_K = 0; int64_t diff_T = 0;
+    int64_t merge_uploads = 0;                             // counter merge_trace_uploads: K x T matrices the merge / tag entry points took from the host
     int32_t last_t_K = 0; int64_t last_t_ldc = 0, last_t_T = 0; bool last_t_valid = false;
     // overlap-region stitch of update_temporal_parallel.m:264-280: acc[k][0..T) = sum_m aa_m(k) C_raw_m(k,:), acc[k][ld-1..] ... see cnmfe_stitch_begin
     cnmfe::DevBuf stitch;     // K rows of stitch_ld floats: [0, T) the weighted sum, column stitch_ld - 4 the sum of the weights
@@ -508,6 +514,13 @@ int fast_temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colp
 int deconv_bound_run(cnmfe_ctx *ctx, const cnmfe_deconv_opts *opts, float *C_out, float *C_raw_out, float *S_out, float *pars_out, float *sn_out);
 int deconv_all_run(cnmfe_ctx *ctx, int32_t K, int64_t T, float *C_raw, int c_order, const cnmfe_deconv_opts *opts,
                    float *C_out, float *S_out, float *pars_out, float *sn_out);
+// merge.hpp (deconv.hip)
+int trace_corr_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, int raw, double *out);
+int trace_diff_spikes_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, float *sn_out, float *S_out);
+int trace_tags_run(cnmfe_ctx *ctx, int32_t K, double *out);
+int traces_load_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *C, const float *C_raw, const float *S, const float *pars, int c_order);
+int merge_apply_run(cnmfe_ctx *ctx, int32_t ng, const int32_t *gptr, const int32_t *gidx, const double *w, int32_t nkeep, const int32_t *keep,
+                    const cnmfe_deconv_opts *opts, float *C_out, float *C_raw_out, float *S_out, float *pars_out, float *sn_out);
 int postproc_run(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx,
                  const float *A_val, uint8_t *keep);
 int ensure_ymean(cnmfe_ctx *ctx, Patch *P);

@@ -1205,6 +1205,7 @@ int deconv_bound_run(cnmfe_ctx *ctx, const cnmfe_deconv_opts *opts, float *C_out
         RET(deconv_launch(ctx, c, shmem, io, dList.as<int>() + k0, std::min(batch, K - k0), ctx->dscr));
     ctx->bound.swap(dC); ++ctx->bound_gen;                  // bound = C (row-major), dcv_c = C_raw - b
     ctx->bound_order = CNMFE_ROWMAJOR;
+    ctx->res_gen = ctx->bound_gen; ctx->res_has_s = true;   // (merge.hpp: dcv_* belong to this bound matrix)
     if (C_out || C_raw_out || S_out || pars_out || sn_out) {
         if (!ctx->copy_stream) {
             CK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
@@ -1225,6 +1226,10 @@ int deconv_bound_run(cnmfe_ctx *ctx, const cnmfe_deconv_opts *opts, float *C_out
     }
     return 0;
 }
+
+}  // namespace cnmfe
+#include "merge.hpp"      // (h) merging: trace correlations, tags and the merged rows (its kernels need get_sn and block_sum, its merged row the launcher above)
+namespace cnmfe {
 
 // loads this translation unit's code object now (HIP loads it at the first launch of one of its kernels -- milliseconds each that would otherwise fall into the first iteration): cnmfe_create
 int tu_warm_deconv() { hipFuncAttributes at; return hipFuncGetAttributes(&at, (const void *)k_sn_pixels) == hipSuccess ? 0 : -1; }

@@ -55,6 +55,13 @@
 //   [Cn_patch, PNR_patch, Sn_patch, Yres] = cnmfe_mex('peel_open_residual', h, pid, A_patch, C_or_rows, psf)   the second pass (initComponents_residual_parallel.m:186-220):
 //                                                                          the session on the PATCH and on Ysig - A_patch C, after 'residual' / 'residual_ssub'; the images are
 //                                                                          nr x nc of the patch, Yres (asked for as 4th output) d x T single; extract / apply then take the seed in the patch
+// Merging (merge_high_corr.m:50-85,172-196,236 and its two siblings, Sources2D.m:1683-1715; the K x K criteria and the groups are the caller's).  A trace SOURCE is the
+// last argument: a K x T matrix (uploaded), or 'bound' | 'craw' | 's' | 'diff' followed by K, T -- the context's own C, C_raw, S, the last 'trace_diff_spikes':
+//   cnmfe_mex('traces_load', h, C, C_raw, S, kernel_pars)                  the object's matrices become the context's ([] for what it lacks); not needed after 'deconv' on the bound matrix
+//   R = cnmfe_mex('trace_corr', h, raw, source...)                         corr(X') (raw = 1: X * X') as K x K double
+//   [sn, S_] = cnmfe_mex('trace_diff_spikes', h, source...)                the S-less branch (:57-66); the result stays on the device as the source 'diff'
+//   q = cnmfe_mex('trace_tags', h, K)                                      K x 4: max(C), std(C_raw - C), GetSn(C_raw), spikes after frame 1
+//   [C, C_raw, S, pars, sn] = cnmfe_mex('merge_apply', h, grp_ptr, grp_idx, w, keep, T, smin, max_tau)   merged traces, their deconvolution, obj.delete: on the device
 #include "mex.h"
 #include "matrix.h"
 #include <string.h>
@@ -228,6 +235,81 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
         if (nout > 2) pout[2] = to_double(S, K, T);
         if (nout > 3) pout[3] = to_double(kp, K, 1);
         if (nout > 4) pout[4] = to_double(sn, K, 1);
+        return;
+    }
+    // ---- merging (cnmfe.h section (h)).  A trace SOURCE is the last argument: a K x T single / double matrix (uploaded), or one of the names 'bound', 'craw', 's',
+    // 'diff' followed by K, T (the context's own matrices: nothing is uploaded)
+    if (!strcmp(cmd, "trace_corr") || !strcmp(cmd, "trace_diff_spikes")) {
+        // R = cnmfe_mex('trace_corr', h, raw, X)  |  cnmfe_mex('trace_corr', h, raw, name, K, T)                       (K x K double)
+        // [sn, S_] = cnmfe_mex('trace_diff_spikes', h, X)  |  cnmfe_mex('trace_diff_spikes', h, name, K, T)           (K x 1, K x T double)
+        const int corr = !strcmp(cmd, "trace_corr"), a0 = corr ? 3 : 2;
+        if (nin != a0 + 1 && nin != a0 + 3) FAIL("%s: the source is a matrix, or a name followed by K, T", cmd);
+        size_t K, T; const float *X = NULL; int src = CNMFE_COLMAJOR;
+        if (mxIsChar(pin[a0])) {
+            char nm[16];
+            if (nin != a0 + 3 || mxGetString(pin[a0], nm, sizeof(nm))) FAIL("%s: a named source needs K, T", cmd);
+            src = !strcmp(nm, "bound") ? CNMFE_BOUND : !strcmp(nm, "craw") ? CNMFE_RES_CRAW : !strcmp(nm, "s") ? CNMFE_RES_S : !strcmp(nm, "diff") ? CNMFE_RES_DIFF : -1;
+            if (src < 0) FAIL("%s: unknown source '%s' (bound, craw, s, diff)", cmd, nm);
+            K = (size_t)mxGetScalar(pin[a0 + 1]); T = (size_t)mxGetScalar(pin[a0 + 2]);
+        } else {
+            if (nin != a0 + 1) FAIL("%s: too many inputs behind a matrix source", cmd);
+            K = mxGetM(pin[a0]); T = mxGetN(pin[a0]); X = f32_of(pin[a0], NULL);
+        }
+        if (corr) {
+            pout[0] = mxCreateDoubleMatrix(K, K, mxREAL);
+            CHECK(cnmfe_trace_corr(c, (int32_t)K, (int64_t)T, X, src, mxGetScalar(pin[2]) != 0, mxGetPr(pout[0])));      // (symmetric: row-major is column-major)
+            return;
+        }
+        float *sn = (float *)mxCalloc(K + 1, sizeof(float)), *S_ = (float *)mxCalloc(K * T + 1, sizeof(float));
+        CHECK(cnmfe_trace_diff_spikes(c, (int32_t)K, (int64_t)T, X, src, sn, nout > 1 ? S_ : NULL));
+        pout[0] = to_double(sn, K, 1);
+        if (nout > 1) { pout[1] = mxCreateDoubleMatrix(K, T, mxREAL); double *p = mxGetPr(pout[1]); for (size_t k = 0; k < K; ++k) for (size_t t = 0; t < T; ++t) p[k + t * K] = S_[k * T + t]; }
+        return;
+    }
+    if (!strcmp(cmd, "traces_load")) {                          // cnmfe_mex('traces_load', h, C, C_raw, S, kernel_pars): [] for a matrix the object does not have
+        if (nin != 6) FAIL("traces_load: 6 inputs required (h, C, C_raw, S, kernel_pars)");
+        const size_t K = mxGetM(pin[2]), T = mxGetN(pin[2]);
+        for (int a = 3; a <= 4; ++a) if (!mxIsEmpty(pin[a]) && (mxGetM(pin[a]) != K || mxGetN(pin[a]) != T)) FAIL("traces_load: C_raw and S must have the shape of C");
+        if (!mxIsEmpty(pin[5]) && mxGetNumberOfElements(pin[5]) != K) FAIL("traces_load: kernel_pars must have one entry per trace");
+        CHECK(cnmfe_traces_load(c, (int32_t)K, (int64_t)T, f32_of(pin[2], NULL), mxIsEmpty(pin[3]) ? NULL : f32_of(pin[3], NULL), mxIsEmpty(pin[4]) ? NULL : f32_of(pin[4], NULL),
+                                mxIsEmpty(pin[5]) ? NULL : f32_of(pin[5], NULL), CNMFE_COLMAJOR));
+        return;
+    }
+    if (!strcmp(cmd, "trace_tags")) {                           // q = cnmfe_mex('trace_tags', h, K): K x 4 double = [max(C), std(C_raw - C), GetSn(C_raw), #spikes after frame 1]
+        if (nin != 3) FAIL("trace_tags: 3 inputs required (h, K)");
+        const size_t K = (size_t)mxGetScalar(pin[2]);
+        double *q = (double *)mxCalloc(4 * K + 1, sizeof(double));
+        CHECK(cnmfe_trace_tags(c, (int32_t)K, q));
+        pout[0] = mxCreateDoubleMatrix(K, 4, mxREAL);
+        for (size_t k = 0; k < K; ++k) for (int j = 0; j < 4; ++j) mxGetPr(pout[0])[k + j * K] = q[4 * k + j];
+        return;
+    }
+    if (!strcmp(cmd, "merge_apply")) {
+        // [C, C_raw, S, kernel_pars, sn] = cnmfe_mex('merge_apply', h, grp_ptr, grp_idx, w, keep, T, smin, max_tau): grp_ptr = offsets 0 .. n of the groups in grp_idx / w
+        // (numel = groups + 1, or [] for a plain delete), grp_idx and keep 1-based rows, T = frames of the context's matrices
+        if (nin != 9) FAIL("merge_apply: 9 inputs required (h, grp_ptr, grp_idx, w, keep, T, smin, max_tau)");
+        for (int a = 2; a <= 5; ++a) if (!mxIsEmpty(pin[a]) && !mxIsDouble(pin[a])) FAIL("merge_apply: index and weight vectors must be double");
+        int64_t Tb = 0;
+        if (cnmfe_get_option(c, "bound_T", &Tb) != 0 || (double)Tb != mxGetScalar(pin[6])) FAIL("merge_apply: T = %d, but the context's matrices have %d frames", (int)mxGetScalar(pin[6]), (int)Tb);   // (the outputs are sized with it)
+        const size_t np_ = mxGetNumberOfElements(pin[2]), ng = np_ ? np_ - 1 : 0, n = mxGetNumberOfElements(pin[3]), nk = mxGetNumberOfElements(pin[5]), T = (size_t)mxGetScalar(pin[6]);
+        if (mxGetNumberOfElements(pin[4]) != n) FAIL("merge_apply: one weight per group member");
+        int32_t *gp = (int32_t *)mxCalloc(ng + 2, sizeof(int32_t)), *gi = (int32_t *)mxCalloc(n + 1, sizeof(int32_t)), *kp_ = (int32_t *)mxCalloc(nk + 1, sizeof(int32_t));
+        for (size_t i = 0; i < np_; ++i) gp[i] = (int32_t)mxGetPr(pin[2])[i];
+        if (ng && (size_t)gp[ng] != n) FAIL("merge_apply: grp_ptr must end at numel(grp_idx)");
+        for (size_t i = 0; i < n; ++i) gi[i] = (int32_t)mxGetPr(pin[3])[i] - 1;
+        for (size_t i = 0; i < nk; ++i) kp_[i] = (int32_t)mxGetPr(pin[5])[i] - 1;
+        cnmfe_deconv_opts o; deconv_opts_of(&o, mxGetScalar(pin[7]), mxGetScalar(pin[8]));
+        float *M[3];
+        for (int j = 0; j < 3; ++j) M[j] = (float *)mxCalloc(nk * T + 1, sizeof(float));
+        float *kp = (float *)mxCalloc(nk + 1, sizeof(float)), *sn = (float *)mxCalloc(nk + 1, sizeof(float));
+        CHECK(cnmfe_merge_apply(c, (int32_t)ng, gp, gi, n ? mxGetPr(pin[4]) : NULL, (int32_t)nk, kp_, &o, M[0], M[1], M[2], kp, sn));
+        for (int j = 0; j < 3 && j < (nout > 0 ? nout : 1); ++j) {
+            pout[j] = mxCreateDoubleMatrix(nk, T, mxREAL);
+            double *p = mxGetPr(pout[j]);
+            for (size_t k = 0; k < nk; ++k) for (size_t t = 0; t < T; ++t) p[k + t * nk] = M[j][k * T + t];
+        }
+        if (nout > 3) pout[3] = to_double(kp, nk, 1);
+        if (nout > 4) pout[4] = to_double(sn, nk, 1);
         return;
     }
     if (!strcmp(cmd, "postprocess")) {

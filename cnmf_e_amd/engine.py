@@ -216,6 +216,7 @@ class Engine:
         """device_ptr: address of a row-major fp32 DEVICE copy of Cm (e.g. the tensor an all-reduce just produced): the engine then binds
         with a device-to-device copy; Cm stays the host-side identity of the bound matrix"""
         Cm = None if Cm is None or Cm.shape[0] == 0 else Cm
+        self._res = None                                  # (a new binding: the context's C_raw / S no longer belong to the bound matrix)
         if isinstance(Cm, DeviceTraces):
             device_ptr = Cm.data_ptr()
         if Cm is None or Cm.dtype != np.float32 or not Cm.flags["C_CONTIGUOUS"]:
@@ -845,7 +846,93 @@ class Engine:
                                                   C.cast(pars._ptr, L.f32p), C.cast(sn._ptr, L.f32p)))
         self._mark_batch(Cout, Craw, S, pars, sn)
         self._bound = Cout
+        self._res = (Cout, Craw, S)                       # C_raw - b and S stay in the context beside the bound C: what the merge entry points read
         return Cout, Craw, S, pars, sn
+
+    # ---- merging (cnmfe.h section (h)): the K x T side of merge_high_corr / merge_neurons_dist_corr / merge_close_neighbors / tag_neurons_parallel ----
+    # The context's RESIDENT matrices (C bound, C_raw and S beside it) are known to this wrapper by the identity of the host objects that stand for them, like the
+    # bound matrix: _res = (C, C_raw, S or None), valid while C is still the bound one.
+    def residents_are(self, Cm, C_raw, S):
+        r = getattr(self, "_res", None)
+        return (r is not None and Cm is not None and r[0] is getattr(self, "_bound", None) and Cm is r[0] and C_raw is r[1] and S is r[2])
+
+    def traces_load(self, Cm, C_raw=None, S=None, kernel_pars=None):
+        """the caller's C, C_raw (None: C), S (None: none) and kernel_pars become the context's matrices (cnmfe_traces_load): two or three K x T uploads"""
+        K, T = Cm.shape
+        if K == 0:
+            self._res = None
+            return
+        c = _traces(Cm, K, T)
+        r = c if (C_raw is None or C_raw is Cm) else _traces(C_raw, K, T)
+        s_ = None if S is None else _traces(S, K, T)
+        kp = None if kernel_pars is None else np.ascontiguousarray(np.asarray(kernel_pars, dtype=np.float32).ravel())
+        if kp is not None and kp.size != K:
+            kp = None
+        L.check(L.lib.cnmfe_traces_load(self._ctx, K, T, _p(c, L.f32p), _p(r, L.f32p), _p(s_, L.f32p), _p(kp, L.f32p), L.ROWMAJOR))
+        self._bound = Cm
+        self._res = (Cm, Cm if C_raw is None else C_raw, S)
+
+    def _tsrc(self, X):
+        """(pointer, source, K, T, keep-alive) of a trace source: the bound matrix, a resident, the last trace_diff_spikes ("diff"), or a host matrix"""
+        r = getattr(self, "_res", None)
+        live = r is not None and r[0] is getattr(self, "_bound", None)
+        if isinstance(X, str) and X == "diff":
+            K, T = self._diff_shape
+            return None, L.RES_DIFF, K, T, None
+        K, T = X.shape
+        if K and X is getattr(self, "_bound", None):
+            return None, L.BOUND, K, T, None
+        if K and live and X is r[1]:
+            return None, L.RES_CRAW, K, T, None
+        if K and live and r[2] is not None and X is r[2]:
+            return None, L.RES_S, K, T, None
+        a = _traces(X, K, T)
+        return _p(a, L.f32p), L.ROWMAJOR, K, T, a
+
+    def trace_corr(self, X, raw=False):
+        """corr(X') (raw: X X') of a K x T trace matrix as K x K float64 -- no upload when X is the bound matrix, a resident, or "diff" """
+        ptr, src, K, T, _keep = self._tsrc(X)
+        out = np.empty((K, K), dtype=np.float64)
+        L.check(L.lib.cnmfe_trace_corr(self._ctx, K, T, ptr, src, int(bool(raw)), _p(out, L.f64p)))
+        return out
+
+    def trace_diff_spikes(self, X, want=False):
+        """merge_high_corr.m:57-66 without S: the thresholded difference traces stay on the device as the source "diff"; want=True also returns (sn, S_)"""
+        ptr, src, K, T, _keep = self._tsrc(X)
+        sn = np.zeros(K, dtype=np.float32) if want else None
+        S_ = np.zeros((K, T), dtype=np.float32) if want else None
+        L.check(L.lib.cnmfe_trace_diff_spikes(self._ctx, K, T, ptr, src, _p(sn, L.f32p), _p(S_, L.f32p)))
+        self._diff_shape = (K, T)
+        return (sn, S_) if want else "diff"
+
+    def trace_tags(self):
+        """per trace of the context's C, C_raw, S: [max(C), std(C_raw - C), GetSn(C_raw), |{S(2:end) > 0}|] as K x 4 float64 (cnmfe_trace_tags)"""
+        K = self._res[0].shape[0]
+        out = np.empty((K, 4), dtype=np.float64)
+        L.check(L.lib.cnmfe_trace_tags(self._ctx, K, _p(out, L.f64p)))
+        return out
+
+    def merge_apply(self, groups, weights, keep, deconv_options=None):
+        """cnmfe_merge_apply on the context's matrices: groups / weights = lists of row-index / float64 arrays (a group's first row receives the merged trace),
+        keep = the rows that stay.  Returns the new (C, C_raw, S or None, kernel_pars, sn) as host arrays; C is the bound matrix, the others the residents."""
+        had_s = self._res[2] is not None
+        T = self._res[0].shape[1]
+        keep = np.ascontiguousarray(keep, dtype=np.int32)
+        gptr = np.zeros(len(groups) + 1, dtype=np.int32)
+        for i, g in enumerate(groups):
+            gptr[i + 1] = gptr[i] + len(g)
+        gidx = np.ascontiguousarray(np.concatenate([np.asarray(g) for g in groups]) if groups else np.zeros(0), dtype=np.int32)
+        w = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.float64) for x in weights]) if groups else np.zeros(0), dtype=np.float64)
+        opts = self._dopts(deconv_options) if groups else None
+        n = keep.size
+        Cn, Rn = np.empty((n, T), dtype=np.float32), np.empty((n, T), dtype=np.float32)
+        Sn = np.empty((n, T), dtype=np.float32) if had_s else None
+        kp, sn = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
+        L.check(L.lib.cnmfe_merge_apply(self._ctx, len(groups), _p(gptr, L.i32p), _p(gidx, L.i32p), _p(w, L.f64p), n, _p(keep, L.i32p),
+                                        None if opts is None else C.byref(opts), _p(Cn, L.f32p), _p(Rn, L.f32p), _p(Sn, L.f32p), _p(kp, L.f32p), _p(sn, L.f32p)))
+        self._bound = Cn if n else None
+        self._res = (Cn, Rn, Sn) if n else None
+        return Cn, Rn, Sn, kp, sn
 
     def _mark_batch(self, *lazies):
         """the asynchronous call just made queued one batch of downloads: its generation number goes to the buffers it fills"""

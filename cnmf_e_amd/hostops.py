@@ -368,3 +368,89 @@ def greedy_roi_block(sess, Cn, PNR, gSiz, psf, min_corr, min_pnr, min_pixel, bd,
                 searching = False
                 break
     return dict(A=out_A, C=out_C, C_raw=out_Craw, S=out_S, kernel_pars=out_kp, center=np.asarray(center, dtype=np.int64).reshape(-1, 2))
+
+
+# --------------------------------------------------------------------------------------
+# merging: the K x K side of merge_high_corr / merge_neurons_dist_corr / merge_close_neighbors (float64; the K x T side is the engine's)
+# --------------------------------------------------------------------------------------
+def footprint_overlap(A):
+    """temp = A ./ sqrt(sum(A.^2, 1));  A_overlap = temp' * temp  (merge_high_corr.m:52-54) as a dense K x K float64 matrix; an empty footprint gives
+    NaN in its row and column (0 * Inf), which fails every >= like the reference's"""
+    A = sp.csc_matrix(A).astype(np.float64)
+    ss = np.asarray(A.multiply(A).sum(axis=0)).ravel()
+    with np.errstate(divide="ignore"):
+        inv = 1.0 / np.sqrt(ss)
+    ok = ss > 0
+    temp = A @ sp.diags(np.where(ok, inv, 0.0))
+    out = np.asarray((temp.T @ temp).todense())
+    out[~ok, :] = np.nan; out[:, ~ok] = np.nan
+    return out
+
+
+def neuron_centers(A, d1, d2, method="max"):
+    """(yy, xx), 1-based like the reference: [~, temp] = max(A, [], 1); [yy, xx] = ind2sub([d1 d2], temp)  (merge_neurons_dist_corr.m:64-65), or with
+    method 'mean' / 'center' the centre of mass com(A, d1, d2) (utilities/com.m:20-28, clamped as :26-28).  Footprints are non-negative: a column without a positive
+    entry reports pixel 1 as MATLAB's max of an all-zero column does."""
+    A = sp.csc_matrix(A)
+    K = A.shape[1]
+    if str(method).lower() in ("mean", "center"):
+        Af = A.astype(np.float64)
+        pix = np.arange(d1 * d2)
+        xy = np.vstack([pix % d1 + 1.0, pix // d1 + 1.0])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cm = (Af.T @ xy.T) / np.asarray(Af.sum(axis=0)).ravel()[:, None]
+        cm = np.asarray(cm)
+        cm[cm < 0] = 0
+        cm[cm[:, 0] > d1, 0] = d1; cm[cm[:, 1] > d2, 1] = d2
+        return cm[:, 0], cm[:, 1]
+    ind = np.zeros(K, dtype=np.int64)
+    for k in range(K):
+        lo, hi = A.indptr[k], A.indptr[k + 1]
+        if hi > lo:
+            j = int(np.argmax(A.data[lo:hi]))             # (first maximum, rows ascending: MATLAB's tie rule)
+            if A.data[lo + j] > 0:
+                ind[k] = A.indices[lo + j]
+    return (ind % d1 + 1).astype(np.float64), (ind // d1 + 1).astype(np.float64)
+
+
+def center_distances(yy, xx):
+    """dist_v = sqrt((xx - xx').^2 + (yy - yy').^2)  (merge_neurons_dist_corr.m:67)"""
+    yy = np.asarray(yy, dtype=np.float64); xx = np.asarray(xx, dtype=np.float64)
+    return np.sqrt((xx[:, None] - xx[None, :]) ** 2 + (yy[:, None] - yy[None, :]) ** 2)
+
+
+def decay_times(kernel_pars):
+    """taud(m) = ar2exp(kernel_pars(m))(1) for AR(1) (OASIS_matlab/functions/ar2exp.m:3-10): the roots of x^2 - g x are {g, 0}, d = max, tau_d = -1 / log(d)"""
+    g = np.asarray(kernel_pars, dtype=np.float64).ravel()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return -1.0 / np.log(np.maximum(g, 0.0))
+
+
+def merge_groups(flag):
+    """graph_connected_comp(sparse(flag_merge)) with the singletons dropped (merge_high_corr.m:82-85): a list of ascending index arrays, ordered by their
+    lowest member (the component labels of the reference follow the first node of each component)"""
+    from scipy.sparse.csgraph import connected_components
+    flag = np.asarray(flag, dtype=bool)
+    K = flag.shape[0]
+    if K == 0:
+        return []
+    n, lab = connected_components(sp.csr_matrix(flag | flag.T), directed=False)
+    groups = [np.flatnonzero(lab == c) for c in range(n)]
+    groups = [g for g in groups if g.size > 1]
+    return sorted(groups, key=lambda g: int(g[0]))
+
+
+def merge_iterate(G, M, niter=10):
+    """The ten alternations ai = data ci' / (ci ci'), ci = ai' data / (ai' ai) of merge_high_corr.m:176-181 with data = A(:, IDs) C_raw(IDs, :) never formed:
+    every ci lies in the row span of C_raw(IDs, :), ci = w' C_raw(IDs, :), and every ai in the column span of A(:, IDs), ai = A(:, IDs) g.  With
+    G = C_raw(IDs, :) C_raw(IDs, :)' and M = A(:, IDs)' A(:, IDs) (n x n) the steps are g = G w / (w' G w), w = M g / (g' M g), starting from w = e1
+    (ci = C_raw(IDs(1), :)).  Returns (g, w) after `niter` rounds."""
+    G = np.asarray(G, dtype=np.float64); M = np.asarray(M, dtype=np.float64)
+    w = np.zeros(G.shape[0]); w[0] = 1.0
+    g = w
+    for _ in range(niter):
+        Gw = G @ w
+        g = Gw / (w @ Gw)
+        Mg = M @ g
+        w = Mg / (g @ Mg)
+    return g, w

@@ -26,6 +26,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from . import _lib as L
+from . import hostops
 from .engine import BoundRows, DeviceTraces, Engine
 
 __all__ = ["Options", "PatchedVideo", "Sources2D", "distribute_geometry", "determine_search_location", "seed_psf", "bspline_basis"]
@@ -73,6 +74,10 @@ class Options:
     min_pixel: float = 5.0           # :99 / :288   minimum number of non-zero pixels of a neuron
     bd: int | None = 3               # :100 / :289  margin of the FOV without seed pixels; None = [] -> gSiz (initComponents_parallel.m:200-203)
     K: int | None = None             # maximum number of neurons per patch (initComponents_parallel's argument; None = [] -> as many as are found)
+    # merging (merge_high_corr, merge_neurons_dist_corr, merge_close_neighbors): CNMFSetParms.m names at :70,110-111, their defaults at :260,299-300
+    merge_thr: object = 0.85         # :70 / :260   scalar, or [A overlap, corr(C), corr(S)] (+ a fourth entry: the largest difference of the decay times)
+    dmin: object = 1.0               # :110 / :299  largest distance of two neuron centres that may merge (merge_close_neighbors: + a second entry, decay times)
+    method_dist: str = "max"         # :111 / :300  'max' (the footprint's brightest pixel) | 'mean' / 'center' (its centre of mass)
 
 
 def _mround(x):
@@ -1245,6 +1250,209 @@ class Sources2D:
         if self.P.get("kernel_pars") is not None and len(self.P["kernel_pars"]) == self.A.shape[1]:
             self.P["kernel_pars"] = np.asarray(self.P["kernel_pars"])[keep]       # :807-809
         self.set_components(sp.csc_matrix(self.A)[:, keep], np.asarray(self.C)[keep], C_raw)   # :799-806
+
+    # -- merging and tagging: the calls of demo_large_data_1p.m between the updates ------------------------------------
+    # Shared by the three merges: the K x K criteria, graph_connected_comp and the n x n form of a group's alternation run here in float64 (hostops.py); whatever
+    # is K x T -- corr(C'), corr(S'), the Gram of C_raw, the merged trace, its deconvolution, the compaction -- runs on the engine, on the matrices it holds.
+    # On a sharded run every rank holds the same A, C, C_raw, S after the stitch and performs the same merge on its own engine: there is no collective, and the
+    # device reductions run in a fixed order, so equal inputs give equal bits on every rank.
+    def _merge_check(self, show_merge):
+        if show_merge:
+            raise NotImplementedError("show_merge = true (manual verification of every merge) is not built")
+        self.engine._dopts(self.options.deconv_options)                         # (anything but AR(1) FOOPSI: NotImplementedError, like the other unbuilt options)
+
+    def _trace_objs(self):
+        """(C, C_raw, S or None) as the reference reads them: C_raw = C when there is none (merge_high_corr.m:24-26), S only with the right height (:57)"""
+        K = self.A.shape[1]
+        C_raw = self.C_raw if (self.C_raw is not None and self.C_raw.shape[0] == K) else self.C
+        S = getattr(self, "S", None)
+        if S is not None and (S.shape[0] != K or K == 0):
+            S = None
+        return self.C, C_raw, S
+
+    def _traces_SRC(self):
+        """_trace_objs() as the engine's resident matrices: nothing moves when they already are (after update_temporal_parallel with deconv_flag), else one
+        cnmfe_traces_load"""
+        Cm, C_raw, S = self._trace_objs()
+        if Cm.shape[0] and not self.engine.residents_are(Cm, C_raw, S):
+            self.engine.traces_load(Cm, C_raw, S, self.P.get("kernel_pars"))
+        return Cm, C_raw, S
+
+    def _corr_minus_eye(self, X):
+        Cc = self.engine.trace_corr(X)
+        return Cc - np.eye(Cc.shape[0])                                                                 # corr(C_') - eye(K)
+
+    def _decay_ok(self, max_decay_diff):
+        taud = hostops.decay_times(self.P["kernel_pars"])                                               # :74-79
+        with np.errstate(invalid="ignore"):
+            return np.abs(taud[:, None] - taud[None, :]) < float(max_decay_diff)
+
+    def _centers_close(self, dmin, method_dist):
+        yy, xx = hostops.neuron_centers(self.A, self.video.d1, self.video.d2, method_dist)
+        return hostops.center_distances(yy, xx) <= float(np.atleast_1d(dmin)[0])
+
+    def _merge_apply(self, groups):
+        """merge_high_corr.m:116-236 without the figure: per group the alternation (hostops.merge_iterate on the Gram sub-blocks), the merged footprint, and ONE
+        cnmfe_merge_apply for all merged traces, their deconvolution and obj.delete(ind_del).  Returns (merged_ROIs, newIDs), 0-based."""
+        K = self.A.shape[1]
+        if not groups:
+            return [], np.zeros(0, dtype=np.int64)
+        _, C_raw, _ = self._traces_SRC()
+        Graw = self.engine.trace_corr(C_raw, raw=True)                              # C_raw C_raw': every group's G is a sub-block
+        A = sp.csc_matrix(self.A).astype(np.float64)
+        weights, cols = [], {}
+        for IDs in groups:
+            As = A[:, IDs]
+            M = np.asarray((As.T @ As).todense())
+            g, w = hostops.merge_iterate(Graw[np.ix_(IDs, IDs)], M)
+            active = np.flatnonzero(np.asarray(As.sum(axis=1)).ravel() > 0)         # :173
+            ai = np.asarray(As[active] @ g).ravel()                                 # :179 of the last round
+            cols[int(IDs[0])] = (active, ai)
+            weights.append(w)
+        ind_del = np.zeros(K, dtype=bool)
+        for IDs in groups:
+            ind_del[IDs[1:]] = True                                                 # :191
+        keep = np.flatnonzero(~ind_del)
+        newIDs = np.flatnonzero(np.isin(keep, [int(g[0]) for g in groups]))         # :189,197-198
+        Cn, Rn, Sn, kp, sn = self.engine.merge_apply(groups, weights, keep, self.options.deconv_options)
+        # obj.A(active_pixel, IDs(1)) = ai (:183), then the deleted columns go (:236)
+        A32 = sp.csc_matrix(self.A, dtype=np.float32)
+        parts = []
+        for k in keep:
+            if int(k) in cols:
+                active, ai = cols[int(k)]
+                nz = ai != 0
+                parts.append(sp.csc_matrix((ai[nz].astype(np.float32), (active[nz], np.zeros(int(nz.sum()), dtype=np.int64))), shape=(A32.shape[0], 1)))
+            else:
+                parts.append(A32[:, [int(k)]])
+        A_new = sp.hstack(parts, format="csc").astype(np.float32)
+        A_new.sort_indices()
+        self._set_after_merge(A_new, keep, Cn, Rn, Sn, kp, sn, merged=newIDs)
+        return [np.asarray(g) for g in groups], newIDs
+
+    def _set_after_merge(self, A_new, keep, Cn, Rn, Sn, kp, sn, merged=None):
+        """what obj.delete does to the handle's other fields (Sources2D.m:791-809), around the matrices the engine just compacted"""
+        K = self.A.shape[1]
+        for name in ("ids", "tags"):
+            val = getattr(self, name, None)
+            if val is not None and len(val) == K:
+                setattr(self, name, np.asarray(val)[keep])
+        had_S = getattr(self, "S", None) is not None and np.asarray(self.S).shape[0] == K
+        self.A, self.C, self.C_raw = A_new, Cn, Rn
+        if had_S:
+            self.S = Sn
+        old_kp = self.P.get("kernel_pars")
+        if (old_kp is not None and len(old_kp) == K) or (merged is not None and len(merged)):
+            self.P["kernel_pars"] = kp                                              # :188 (rows never deconvolved keep 0: "not yet estimated")
+        if self.P.get("neuron_sn") is not None and len(self.P["neuron_sn"]) == K:
+            self.P["neuron_sn"] = sn
+        self._update_b0_new()
+
+    def merge_high_corr(self, show_merge=False, merge_thr=None):
+        """[merged_ROIs, newIDs] = merge_high_corr(obj, show_merge, merge_thr)  (@Sources2D/merge_high_corr.m): neurons whose footprints overlap, whose traces C
+        and whose spike trains S correlate at least merge_thr = [A, C, S] are merged, component by component of that relation; a scalar is the threshold on
+        corr(C') alone (:41-43), a fourth entry the largest admitted difference of the decay times (:72-81).  Without an S of the right height the spike trains
+        are the thresholded differences of C_raw (:57-66), taken on the device.  Indices are 0-based; a group keeps its lowest member.
+        Departures from the reference: a scalar or 4-vector argument is honoured (the reference's `numel(merge_thr) ~= 3` test at :38-40 replaces it by
+        options.merge_thr); the `catch` branch that deletes a group whose deconvolution threw (:192-194) cannot occur -- the kernel raises nothing per trace; when S is
+        absent it stays absent (the reference's obj.S(IDs(1), :) = ... would create one).  A merged trace without spikes gets C = C_raw - b (cnmfe.h).
+        When nothing qualifies the method returns ([], []) with nothing touched and nothing rebound.
+        Sharded runs: every rank holds the same A, C, C_raw, S after the stitch and performs the same merge on its own engine; there is no collective, and the
+        device reductions run in a fixed order, so equal inputs give equal bits on every rank.
+        Traffic: when C, C_raw and S are the engine's own (after update_temporal_parallel with deconv_flag) no K x T matrix is uploaded (counter
+        merge_trace_uploads); A_prev, C_prev, W and b0 are left alone, as in the reference."""
+        self._merge_check(show_merge)
+        thr = np.atleast_1d(np.asarray(self.options.merge_thr if merge_thr is None else merge_thr, dtype=np.float64))
+        if thr.size == 1:
+            thr = np.array([0.0, thr[0], 0.0])                                      # :41-43
+        if thr.size not in (3, 4):
+            raise ValueError("merge_thr must be a scalar, [A, C, S] or [A, C, S, max_decay_diff]")
+        K = self.A.shape[1]
+        if K < 2:
+            return [], np.zeros(0, dtype=np.int64)
+        Cm, C_raw, S = self._trace_objs()                                           # (read where they are: the engine's own cost nothing, others one scratch upload each)
+        A_overlap = hostops.footprint_overlap(self.A)                               # :52-54
+        S_src = S if S is not None else self.engine.trace_diff_spikes(C_raw)        # :56-66
+        S_corr = self._corr_minus_eye(S_src)                                        # :67
+        C_corr = self._corr_minus_eye(Cm)                                           # :68
+        with np.errstate(invalid="ignore"):
+            flag = (A_overlap >= thr[0]) & (C_corr >= thr[1]) & (S_corr >= thr[2])  # :71
+        if thr.size > 3:
+            flag &= self._decay_ok(thr[3])                                          # :72-81
+        return self._merge_apply(hostops.merge_groups(flag))
+
+    def merge_neurons_dist_corr(self, show_merge=False, merge_thr=None, dmin=None, method_dist=None, max_decay_diff=None):
+        """[merged_ROIs, newIDs] = merge_neurons_dist_corr(obj, show_merge, merge_thr, dmin, method_dist, max_decay_diff)  (@Sources2D/merge_neurons_dist_corr.m):
+        neurons whose centres lie within dmin pixels (method_dist 'max': the brightest pixel, 'mean' / 'center': the centre of mass) and whose traces correlate
+        at least merge_thr (a scalar; of a vector the entry for C) are merged.  Everything else as merge_high_corr, its departures included."""
+        self._merge_check(show_merge)
+        o = self.options
+        thr = np.atleast_1d(np.asarray(o.merge_thr if merge_thr is None else merge_thr, dtype=np.float64))
+        thr = float(thr[0] if thr.size == 1 else thr[1])
+        K = self.A.shape[1]
+        if K < 2:
+            return [], np.zeros(0, dtype=np.int64)
+        Cm, _, _ = self._trace_objs()
+        close = self._centers_close(o.dmin if dmin is None else dmin, o.method_dist if method_dist is None else method_dist)   # :58-67
+        with np.errstate(invalid="ignore"):
+            flag = close & (self._corr_minus_eye(Cm) >= thr)                        # :70-73
+        if max_decay_diff is not None:
+            flag &= self._decay_ok(max_decay_diff)                                  # :74-82
+        return self._merge_apply(hostops.merge_groups(flag))
+
+    def merge_close_neighbors(self, show_merge=False, dmin=None, method_dist=None):
+        """[merged_ROIs, newIDs] = merge_close_neighbors(obj, show_merge, dmin, method_dist)  (@Sources2D/merge_close_neighbors.m): neurons whose centres lie
+        within dmin(1) pixels are merged whatever their traces do; a second entry of dmin bounds the difference of their decay times (:66-79).  Everything else
+        as merge_high_corr, its departures included."""
+        self._merge_check(show_merge)
+        o = self.options
+        dmin = np.atleast_1d(np.asarray(o.dmin if dmin is None else dmin, dtype=np.float64))
+        if self.A.shape[1] < 2:
+            return [], np.zeros(0, dtype=np.int64)
+        flag = self._centers_close(dmin, o.method_dist if method_dist is None else method_dist)     # :49-62
+        if dmin.size > 1:
+            flag &= self._decay_ok(dmin[1])
+        return self._merge_apply(hostops.merge_groups(flag))
+
+    def tag_neurons_parallel(self, min_pnr=3):
+        """tags_ = tag_neurons_parallel(obj, min_pnr)  (Sources2D.m:1683-1715): per neuron the sum of 1 (fewer than options.min_pixel positive pixels) and, with
+        deconv_flag, 2 (no spike after the first frame), 4 (std(C_raw - C) / GetSn(C_raw) < 0.1) and 8 (max(C) / std(C_raw - C) < min_pnr).  The four per-trace
+        quantities come from one kernel over the engine's C, C_raw and S (cnmfe_trace_tags); sets and returns obj.tags (uint16)."""
+        A = sp.csc_matrix(self.A)
+        K = A.shape[1]
+        nz_pixels = np.asarray((A > 0).sum(axis=0)).ravel()                         # :1695
+        tags = (nz_pixels < self.options.min_pixel).astype(np.uint16)               # :1696
+        if self.options.deconv_flag and K:
+            _, _, S = self._traces_SRC()
+            if S is None:
+                raise ValueError("tag_neurons_parallel with deconv_flag needs obj.S (run update_temporal_parallel or deconvTemporal first)")
+            q = self.engine.trace_tags()
+            with np.errstate(divide="ignore", invalid="ignore"):
+                tags += (q[:, 3] < 1).astype(np.uint16) * 2                          # :1700-1701
+                tags += (q[:, 1] / q[:, 2] < 0.1).astype(np.uint16) * 4              # :1703-1706
+                tags += (q[:, 0] / q[:, 1] < min_pnr).astype(np.uint16) * 8          # :1709-1710
+        self.tags = tags
+        return tags
+
+    def remove_false_positives(self, show_delete=False):
+        """ids = remove_false_positives(obj)  (Sources2D.m:744-759): delete every neuron tag_neurons_parallel tagged; returns their (0-based) indices.  The rows go
+        on the device (cnmfe_merge_apply without groups) when the engine holds the matrices, which it does after tag_neurons_parallel with deconv_flag."""
+        if show_delete:
+            raise NotImplementedError("show_delete = true (viewNeurons) is not built")
+        tags = self.tag_neurons_parallel()
+        ids = np.flatnonzero(tags)
+        if ids.size == 0:
+            return ids
+        K = self.A.shape[1]
+        C_raw = self.C_raw if (self.C_raw is not None and self.C_raw.shape[0] == K) else self.C
+        S = getattr(self, "S", None)
+        if not self.engine.residents_are(self.C, C_raw, S if (S is not None and S.shape[0] == K) else None):
+            self.delete(ids)
+            return ids
+        keep = np.setdiff1d(np.arange(K), ids)
+        Cn, Rn, Sn, kp, sn = self.engine.merge_apply([], [], keep)
+        self._set_after_merge(sp.csc_matrix(self.A, dtype=np.float32)[:, keep], keep, Cn, Rn, Sn, kp, sn)
+        return ids
 
     def deconvTemporal(self):
         """@Sources2D/deconvTemporal.m:29-105: deconvolve every row of C_raw again (fresh time constants); sets

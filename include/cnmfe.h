@@ -341,6 +341,42 @@ int cnmfe_deconv_temporal(cnmfe_ctx *ctx, int32_t K, int64_t T, float *C_raw, in
 int cnmfe_deconv_temporal_bound(cnmfe_ctx *ctx, const cnmfe_deconv_opts *opts, float *C_out, float *C_raw_out, float *S_out,
                                 float *kernel_pars_out, float *sn_out);
 
+/* ---- (h) merging: the calls of demos/demo_large_data_1p.m:146-147,168,175-178,189,205-207,212 between the updates
+ * @Sources2D/merge_high_corr.m:50-85,172-196,236   merge_neurons_dist_corr.m:58-86,180-201,243   merge_close_neighbors.m:49-83,174-195,237
+ * @Sources2D/Sources2D.m:744-759 (remove_false_positives -> tag_neurons_parallel :1683-1715)
+ * The K x K criteria, graph_connected_comp and the n x n form of a group's alternation are the host's (float64: sources2d.Sources2D.merge_*, hostops.py); everything that
+ * is K x T runs here, on the matrices the context already holds: the bound matrix C and, beside it, the RESIDENT C_raw, S, kernel_pars and sn that
+ * cnmfe_deconv_temporal_bound leaves (C_raw - b and S "stay in the context").  They belong together until the bound matrix' content changes by any other call.
+ * A trace SOURCE (X, src) is: a host pointer with src = CNMFE_COLMAJOR / CNMFE_ROWMAJOR (one upload: counted by the read-only counter merge_trace_uploads of
+ * cnmfe_get_option), or X ignored and src = CNMFE_BOUND (C), CNMFE_RES_CRAW, CNMFE_RES_S (the residents), CNMFE_RES_DIFF (the last result of
+ * cnmfe_trace_diff_spikes).  K and T must be the source's.  Every reduction runs in a fixed order: two calls on equal inputs are bit-identical, on any GPU. */
+enum { CNMFE_RES_CRAW = 4, CNMFE_RES_S = 5, CNMFE_RES_DIFF = 6 };
+/* the residents from the host (a caller whose matrices are NOT the context's: deconv_flag = false, a sharded run): C is bound as by cnmfe_traces_bind, C_raw (NULL: C),
+ * S (NULL: none -- the context then has no S, cnmfe_trace_tags reports -1 spikes) and kernel_pars (K floats or NULL = 0) become the residents.  Two or three uploads. */
+int cnmfe_traces_load(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *C, const float *C_raw, const float *S, const float *kernel_pars, int c_order);
+/* out (K x K doubles, symmetric) = corr(X') -- Pearson's r of the rows, merge_high_corr.m:67-68, merge_neurons_dist_corr.m:70 (the caller subtracts eye(K)) -- or, raw != 0,
+ * the uncentred Gram X X' (its sub-blocks are the G of a group's alternation :176-181).  Mean and centred sum of squares per row in fp64, the products on the fp64 matrix
+ * pipe with the fp64 mean subtracted from every operand.  A row without variance gives NaN in its row and column (MATLAB's 0 / 0).  K = 0 is legal. */
+int cnmfe_trace_corr(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, int raw, double *out);
+/* merge_high_corr.m:57-66, the branch without S:  S_ = diff(X, 1, 2);  S_(:, end + 1) = 0;  S_(S_ < 2 * GetSn(S_)) = 0  with GetSn per row (fp32 differences, the Welch
+ * estimator of the traces).  The result stays in the context as the source CNMFE_RES_DIFF; sn_out (K floats) and S_out (K x T ROW-MAJOR) may be NULL.  64 <= T <= 20400. */
+int cnmfe_trace_diff_spikes(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, float *sn_out, float *S_out);
+/* tag_neurons_parallel's per-trace quantities (Sources2D.m:1700-1709) of the context's C, C_raw, S, one workgroup per trace, one pass:
+ * out[4 k + 0] = max(C(k, :)), [1] = std(C_raw(k, :) - C(k, :), 0) in fp64, [2] = GetSn(C_raw(k, :)), [3] = |{t >= 2 : S(k, t) > 0}| (-1 without an S).
+ * K must be the bound matrix'; the bit arithmetic (and nnz(A(:, k)) < min_pixel) is the host's.  64 <= T <= 20400. */
+int cnmfe_trace_tags(cnmfe_ctx *ctx, int32_t K, double *out /* 4 K */);
+/* The K-changing step of the three merges and of obj.delete, in place on the context's matrices (K rows before, nkeep after):
+ *   group g = rows grp_idx[grp_ptr[g] .. grp_ptr[g + 1]) with weights w[...] (same positions): ci = w' C_raw(IDs, :) summed in fp64 in that order and rounded to fp32
+ *   once is the new C_raw row of IDs(1) = its first member (:184); deconvolveCa(ci, deconv_options_0) by the AR(1) FOOPSI kernel of cnmfe_deconv_temporal with a fresh
+ *   time constant gives the row's C, S, kernel_pars and sn (:187-188; C_raw keeps ci itself -- the reference subtracts no baseline here);
+ *   then rows keep[0 .. nkeep) (distinct, any order; every group's first member among them, its other members normally not) are gathered into new matrices:
+ *   obj.delete(ind_del) (:236).  The compacted C becomes the bound matrix (row-major, as cnmfe_traces_bind would make it), C_raw / S / kernel_pars / sn the residents.
+ * ngroups = 0 (opts may be NULL) is the device-side delete.  Host outputs (nkeep x T row-major, nkeep floats) may each be NULL; the call returns when they are written.
+ * A merged trace without a stable AR(1) model or without any spike gets C = C_raw - b as in deconvTemporal.m:53-55 (the reference's deconvolveCa returns zeros).
+ * CNMFE_ESTATE without residents, CNMFE_EINVAL on an index out of range, a repeated kept row, an empty group or a group whose first member is not kept. */
+int cnmfe_merge_apply(cnmfe_ctx *ctx, int32_t ngroups, const int32_t *grp_ptr, const int32_t *grp_idx, const double *w, int32_t nkeep, const int32_t *keep,
+                      const cnmfe_deconv_opts *opts, float *C_out, float *C_raw_out, float *S_out, float *kernel_pars_out, float *sn_out);
+
 /* ---- T5: the overlap-region stitch of the temporal update, on the device
  * @Sources2D/update_temporal_parallel.m:264-280:
  *     C_new(ind_m, :) += aa_m .* C_raw_m;  aa(ind_m) += aa_m   over the patches m;   C_raw = C_new ./ aa  (aa == 0 -> 1);
@@ -524,7 +560,9 @@ int cnmfe_set_option(cnmfe_ctx *ctx, const char *name, int64_t value);
 /* The value cnmfe_set_option (or CNMFE_OPTS) gave an option last; an option that was never set reports CNMFE_EINVAL (its default, above, holds).  Also the
  * read-only counters of the hand-over: temporal_early_hits / _drops (early projections a temporal update took / found but could not take), temporal_early_declined
  * (requests the projection could not serve), temporal_early_entries / temporal_proj_entries ((block, neuron) entries of the last early / of the last projection),
- * temporal_nowait (temporal updates whose levels were queued without the host wait). */
+ * temporal_nowait (temporal updates whose levels were queued without the host wait), and merge_trace_uploads (K x T matrices the merge / tag entry points and
+ * cnmfe_traces_load took from the host: 0 while they work on the context's own matrices), and bound_K / bound_T (the shape of the bound trace matrix, 0 without
+ * one: what a gateway sizes the outputs of cnmfe_merge_apply with). */
 int cnmfe_get_option(cnmfe_ctx *ctx, const char *name, int64_t *value);
 
 /* The hand-over between the spatial and the temporal update (option temporal_early).  After cnmfe_update_spatial_fetch_connected[_async] of a patch that is the
