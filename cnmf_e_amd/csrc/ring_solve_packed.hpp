@@ -41,28 +41,68 @@ constexpr int RSP_NS = 8;                           // neurons staged before the
 
 // T(a, b) -= u(a) alpha(b) + alpha(a) u(b) on every tile.  A tile (four registers = one vector value) is updated as a whole: element-wise updates interleaved
 // across tiles made the compiler copy half-updated vectors around and spill a third of them.
+//
+// alpha is the footprint sampled on the ring: a thin curve that meets two or three of the NT blocks of 16 ring pixels.  `bm` (wave-uniform; rsp_blocks) has bit B
+// set when any alpha(16 B .. 16 B + 15) is non-zero.  A term whose alpha block is all zeros is fma(x, +-0, t) = t for every finite x: it is not computed, and neither
+// are the LDS reads and conversions only such terms would use.  The terms are therefore grouped by the alpha block they read, one scalar branch per block:
+// block B owns u(I) alpha(B) on the tiles (I, B), I >= B (its column), and alpha(B) u(J) on the tiles (B, J), J <= B (its row).  With B ascending a tile (I, J)
+// still takes its alpha(J) term before its alpha(I) term, as fma(aa, ub, fma(ua, ab, t)) did: the same operations on the same values.
+// (A branch per tile and term -- 42 of them per neuron -- gave most of the instructions saved back: 5242 -> 4853 vector instructions per wave for 1.7 % of the time.)
+constexpr int RSP_MB = 8;                           // bits per staged slot in the packed block masks (NT <= 8)
+// a wave-uniform value the compiler may not share between its uses: a condition on it is a scalar compare and branch where it stands, not a 64-bit lane mask
+// hoisted to the top and kept in two scalar registers (the NT = 6 kernels have none to spare: what does not fit moves through a reserved vector register)
+__device__ __forceinline__ int rsp_opaque(int v) { asm volatile("" : "+s"(v)); return v; }
+__device__ __forceinline__ unsigned rsp_blocks(unsigned long long b) {      // a ballot over 64 consecutive ring pixels -> one bit per 16 of them
+    return ((b & 0xffffull) ? 1u : 0u) | ((b & 0xffff0000ull) ? 2u : 0u) | ((b & 0xffff00000000ull) ? 4u : 0u) | ((b >> 48) ? 8u : 0u);
+}
+
 template <int NT>
-__device__ __forceinline__ void rsp_rank2(double4_t (&T)[(NT * (NT + 1)) / 2], const double *su, const float *sa, int c, int rq) {
-    double ua[NT], aa[NT];
+__device__ __forceinline__ void rsp_rank2(double4_t (&T)[(NT * (NT + 1)) / 2], const double *su, const float *sa, unsigned bm, int c, int rq) {
+    static_assert(NT <= RSP_MB, "one mask bit per tile row");
 #pragma unroll
-    for (int I = 0; I < NT; ++I) { ua[I] = -su[16 * I + c]; aa[I] = -(double)sa[16 * I + c]; }
+    for (int B = 0; B < NT; ++B) {
+        if (!(((unsigned)rsp_opaque((int)bm) >> B) & 1u)) continue;
+        double4_t ab;
 #pragma unroll
-    for (int J = 0; J < NT; ++J) {
-        double4_t ub, ab;
+        for (int r = 0; r < 4; ++r) ab[r] = (double)sa[16 * B + rq + 4 * r];
+        double ua[NT];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { ub[r] = su[16 * J + rq + 4 * r]; ab[r] = (double)sa[16 * J + rq + 4 * r]; }
+        for (int I = B; I < NT; ++I) ua[I] = -su[16 * I + c];
+        const double aa = -(double)sa[16 * B + c];
+        // the row two tiles at a time, the column with the first two: the LDS reads of a whole row and column hoisted to the top keep 70 registers alive that
+        // the tiles need (the clobber pins the loads at IR level, the scheduling barrier the FMAs in the machine scheduler; the pin behind a tile keeps its FMAs
+        // from sinking below the loop)
 #pragma unroll
-        for (int I = J; I < NT; ++I) {
-            double4_t t = T[rs_tix(I, J)];
+        for (int J0 = 0; J0 <= B; J0 += 2) {
+            double4_t ub[2];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) t[r] = fma(aa[I], ub[r], fma(ua[I], ab[r], t[r]));
-            asm volatile("" : "+v"(t));                     // the FMAs stay HERE: sunk below the loop behind them (with every column's LDS reads hoisted above it) they cost 70 registers
-            T[rs_tix(I, J)] = t;
+            for (int j = 0; j < 2; ++j)
+                if (J0 + j <= B) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) ub[j][r] = su[16 * (J0 + j) + rq + 4 * r];
+                }
+            if (J0 == 0) {
+#pragma unroll
+                for (int I = B; I < NT; ++I) {
+                    double4_t t = T[rs_tix(I, B)];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) t[r] = fma(ua[I], ab[r], t[r]);
+                    asm volatile("" : "+v"(t));
+                    T[rs_tix(I, B)] = t;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                if (J0 + j <= B) {
+                    double4_t t = T[rs_tix(B, J0 + j)];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) t[r] = fma(aa, ub[j][r], t[r]);
+                    asm volatile("" : "+v"(t));
+                    T[rs_tix(B, J0 + j)] = t;
+                }
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
         }
-        // (the LDS reads of all NT columns hoisted to the top keep 70 registers alive that the tiles need: the clobber pins the loads at IR level,
-        //  the scheduling barrier the FMAs in the machine scheduler)
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
     }
 }
 
@@ -145,7 +185,7 @@ k_ring_solve6(const double *__restrict__ sys, PackArgs pa, BgGeom g, const int *
     // ---- the footprints' corrections: one symmetric rank-2 update per neuron with a pixel on the ring or under the centre.  A round stages U~ and A of up to
     // RSP_CH neurons for every ring pixel in LDS (two dependent gathers: slot, value); the FIRST round runs before the system is loaded -- with the 168 tile
     // registers live the compiler spilled a third of them around this phase --, later rounds (more than RSP_CH neurons on one ring: rare) run under them
-    unsigned long long mask = 0;
+    unsigned long long mask = 0, bmk = 0;                  // bmk: per staged slot RSP_MB bits, the blocks of 16 ring pixels its A meets (rsp_rank2)
     int lbm = 0, nst = 0;
     if (corr) {
         mask = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)s_mask[0]) |
@@ -159,36 +199,56 @@ k_ring_solve6(const double *__restrict__ sys, PackArgs pa, BgGeom g, const int *
             ks[i] = -1;
             if (mask) { const int s = __builtin_ctzll(mask); mask &= mask - 1; ks[i] = pa.lst_k[lbm + s]; ++nst; }
         }
+        const int nhere = nst - slot0;                      // slots of this round that hold a neuron: the others are neither computed nor stored (nothing reads them)
+        bmk &= ~(((1ull << (RSP_MB * RSP_CH)) - 1ull) << (RSP_MB * slot0));
+        int sh = 0;
 #pragma unroll 1
-        for (int a = lane; a <= N; a += 64) {
+        for (int a = lane; a <= N; a += 64, sh += 4) {
             const int q = s_q[a];
             int sl[RSP_CH];
 #pragma unroll
-            for (int i = 0; i < RSP_CH; ++i) sl[i] = (q >= 0 && ks[i] >= 0) ? (int)pa.slot_of[(int64_t)s_bk[a] + ks[i]] : -2;
+            for (int h = 0; h < RSP_CH; h += 2)
+                if (h == 0 || h < rsp_opaque(nhere)) {
+#pragma unroll
+                    for (int i = h; i < h + 2; ++i) sl[i] = (q >= 0 && ks[i] >= 0) ? (int)pa.slot_of[(int64_t)s_bk[a] + ks[i]] : -2;
+                }
             double uu[RSP_CH];
 #pragma unroll
-            for (int i = 0; i < RSP_CH; ++i) {
-                bad |= sl[i] == -1;
-                uu[i] = sl[i] >= 0 ? pa.Ut[(int64_t)s_ulp[a] + (int64_t)sl[i] * 256] : 0.0;
-            }
+            for (int h = 0; h < RSP_CH; h += 2)
+                if (h == 0 || h < rsp_opaque(nhere)) {
+#pragma unroll
+                    for (int i = h; i < h + 2; ++i) {
+                        bad |= sl[i] == -1;
+                        uu[i] = sl[i] >= 0 ? pa.Ut[(int64_t)s_ulp[a] + (int64_t)sl[i] * 256] : 0.0;
+                    }
+                }
             const int en = s_en[a];
 #pragma unroll
-            for (int i = 0; i < RSP_CH; ++i) {
-                float av = 0.f;
+            for (int h = 0; h < RSP_CH; h += 2)
+                if (h == 0 || h < rsp_opaque(nhere)) {
 #pragma unroll
-                for (int j = 0; j < RSP_CAP; ++j) if (j < en && s_ec[a][j] == ks[i]) av = s_ev[a][j];
-                if (en > RSP_CAP && ks[i] >= 0) {
-                    const int e0 = s_e0[a];
-                    for (int j = RSP_CAP; j < en; ++j) if (pa.acol[e0 + j] == ks[i]) av = pa.aval[e0 + j];
+                    for (int i = h; i < h + 2; ++i) {
+                        float av = 0.f;
+#pragma unroll
+                        for (int j = 0; j < RSP_CAP; ++j) if (j < en && s_ec[a][j] == ks[i]) av = s_ev[a][j];
+                        if (en > RSP_CAP && ks[i] >= 0) {
+                            const int e0 = s_e0[a];
+                            for (int j = RSP_CAP; j < en; ++j) if (pa.acol[e0 + j] == ks[i]) av = pa.aval[e0 + j];
+                        }
+                        s_u[slot0 + i][a] = uu[i]; s_a[slot0 + i][a] = av;
+                        // (this pass holds the ring pixels 16 sh .. 16 sh + 63; the centre, a = N, falls on bit NT and is masked off)
+                        const unsigned blocks = (rsp_blocks(__ballot(av != 0.f)) << sh) & ((1u << NT) - 1u);
+                        bmk |= (unsigned long long)blocks << (RSP_MB * (slot0 + i));
+                    }
                 }
-                s_u[slot0 + i][a] = uu[i]; s_a[slot0 + i][a] = av;
-            }
         }
+        bmk = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)bmk) |
+              ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bmk >> 32)) << 32);
     };
     auto apply = [&](double4_t (&T)[NTILE]) {
         __syncthreads();
         for (int i = 0; i < nst; ++i) {
-            rsp_rank2<NT>(T, s_u[i], s_a[i], c, rq);
+            rsp_rank2<NT>(T, s_u[i], s_a[i], (unsigned)(bmk >> (RSP_MB * i)) & ((1u << RSP_MB) - 1u), c, rq);
             const double uN = s_u[i][N], aN = (double)s_a[i][N];
             for (int a = lane; a < N; a += 64) s_vec[1][a] -= fma(s_u[i][a], aN, (double)s_a[i][a] * uN);
         }

@@ -118,9 +118,10 @@ k_ring_solve8(const double *__restrict__ sys, StageArgs sa_, BgGeom g, const int
     RSP_LAP();                                              // 1: list, geometry, border vectors issued
     // ---- staging: up to RSP_NS candidates per round, every sample of the round in flight at once; `live`: the slots with a non-zero A on ring or centre ----
     unsigned live = 0;
+    unsigned long long bmk = 0;                             // per slot RSP_MB bits: the blocks of 16 ring pixels its A meets (rsp_rank2)
     int nst = 0;
     auto stage = [&]() {
-        nst = 0; live = 0;
+        nst = 0; live = 0; bmk = 0;
         int r0[RSP_NS], c0[RSP_NS], hh[RSP_NS], ww[RSP_NS], of[RSP_NS];
 #pragma unroll
         for (int i = 0; i < RSP_NS; ++i) {
@@ -133,31 +134,49 @@ k_ring_solve8(const double *__restrict__ sys, StageArgs sa_, BgGeom g, const int
                 nst = i + 1;
             }
         }
+        // slots are filled in order, so a pair of slots from nst on holds nothing: it is neither sampled nor stored (nothing reads it; the first pair
+        // holds at least one neuron).  All loads of the round still precede its first store.
+        int sh = 0;
 #pragma unroll 1
-        for (int a = lane; a <= N; a += 64) {
+        for (int a = lane; a <= N; a += 64, sh += 4) {
             const int q = s_q[a], rc = s_rc[a];
             const int rb = rc & 0xffff, cb = rc >> 16;
             double uu[RSP_NS]; float av[RSP_NS];
 #pragma unroll
-            for (int i = 0; i < RSP_NS; ++i) {
-                const int rr = rb - r0[i], cc = cb - c0[i];
-                const bool in = q >= 0 && i < nst && rr >= 0 && rr < hh[i] && cc >= 0 && cc < ww[i];
-                const int idx = of[i] + cc * hh[i] + rr;
-                uu[i] = in ? sa_.nwu[idx] : 0.0; av[i] = in ? sa_.nwa[idx] : 0.f;
-            }
+            for (int h = 0; h < RSP_NS; h += 2)
+                if (h == 0 || h < rsp_opaque(nst)) {
 #pragma unroll
-            for (int i = 0; i < RSP_NS; ++i) {
-                s_u[i][a] = uu[i]; s_a[i][a] = av[i];
-                if (__ballot(av[i] != 0.f) != 0ull) live |= 1u << i;
-            }
+                    for (int i = h; i < h + 2; ++i) {
+                        const int rr = rb - r0[i], cc = cb - c0[i];
+                        const bool in = q >= 0 && i < nst && rr >= 0 && rr < hh[i] && cc >= 0 && cc < ww[i];
+                        const int idx = of[i] + cc * hh[i] + rr;
+                        uu[i] = in ? sa_.nwu[idx] : 0.0; av[i] = in ? sa_.nwa[idx] : 0.f;
+                    }
+                }
+#pragma unroll
+            for (int h = 0; h < RSP_NS; h += 2)
+                if (h == 0 || h < rsp_opaque(nst)) {
+#pragma unroll
+                    for (int i = h; i < h + 2; ++i) {
+                        s_u[i][a] = uu[i]; s_a[i][a] = av[i];
+                        const unsigned long long nz = __ballot(av[i] != 0.f);
+                        if (nz != 0ull) {
+                            live |= 1u << i;
+                            // (this pass holds the ring pixels 16 sh .. 16 sh + 63; the centre, a = N, falls on bit NT and is masked off)
+                            bmk |= (unsigned long long)((rsp_blocks(nz) << sh) & ((1u << NT) - 1u)) << (RSP_MB * i);
+                        }
+                    }
+                }
         }
         live = (unsigned)__builtin_amdgcn_readfirstlane((int)live);
+        bmk = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)bmk) |
+              ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bmk >> 32)) << 32);
     };
     auto apply = [&](double4_t (&T)[NTILE]) {
         __syncthreads();
         for (int i = 0; i < nst; ++i) {
             if (!((live >> i) & 1u)) continue;
-            rsp_rank2<NT>(T, s_u[i], s_a[i], c, rq);
+            rsp_rank2<NT>(T, s_u[i], s_a[i], (unsigned)(bmk >> (RSP_MB * i)) & ((1u << RSP_MB) - 1u), c, rq);
             const double uN = s_u[i][N], aN = (double)s_a[i][N];
             for (int a = lane; a < N; a += 64) s_vec[1][a] -= fma(s_u[i][a], aN, (double)s_a[i][a] * uN);
         }
