@@ -330,6 +330,26 @@ int ring_stats_get(cnmfe_ctx *ctx, Patch *P, int *pmax, bool *first) {
 
 // length(unique(W_old(1,:)))==2 on row 1 of the resident W, implicit zeros of the sparse row included
 int ring_first_run(cnmfe_ctx *ctx, Patch *P, bool *first) { return ring_stats_get(ctx, P, nullptr, first); }
+// the side stream of option fit_side: a second hardware queue of this context, at the compute stream's priority (a lower one would leave the fit's set-up waiting
+// behind the projection it is meant to run beside, a higher one would hold the projection back)
+int ctx_side_stream(cnmfe_ctx *ctx) {
+    if (ctx->side_stream) return 0;
+    int prio = 0;
+    CK(hipStreamGetPriority(ctx->stream_, &prio));
+    hipStream_t s = nullptr;
+    CK(hipStreamCreateWithPriority(&s, hipStreamDefault, prio));
+    hipLaunchKernelGGL(k_scratch_warm, dim3(1), dim3(64), 0, s, (int *)nullptr, 3);       // (its hardware queue now, not inside the fit that forks first)
+    hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_side_fork, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_side_join, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        (void)hipStreamDestroy(s);
+        if (ctx->ev_side_fork) { (void)hipEventDestroy(ctx->ev_side_fork); ctx->ev_side_fork = nullptr; }
+        return fail(CNMFE_EHIP, "side stream of option fit_side: %s", hipGetErrorString(e));
+    }
+    ctx->side_stream = s;
+    return 0;
+}
 int ctx_errflag(cnmfe_ctx *ctx, int **dflag) {
     if (!ctx->errflag.p) {
         RET(ctx->errflag.ensure(sizeof(int)));
@@ -621,6 +641,10 @@ void cnmfe_destroy(cnmfe_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     (void)ctx->join_lanes();
     (void)hipStreamSynchronize(ctx->st());
+    // (every fit joins its side scope into the compute stream before it returns: nothing is in flight there)
+    if (ctx->side_stream) { (void)hipStreamSynchronize(ctx->side_stream); (void)hipStreamDestroy(ctx->side_stream); ctx->side_stream = nullptr; }
+    if (ctx->ev_side_fork) { (void)hipEventDestroy(ctx->ev_side_fork); ctx->ev_side_fork = nullptr; }
+    if (ctx->ev_side_join) { (void)hipEventDestroy(ctx->ev_side_join); ctx->ev_side_join = nullptr; }
     delete ctx;
 }
 
@@ -635,7 +659,7 @@ int cnmfe_synchronize(cnmfe_ctx *ctx) {
 int cnmfe_set_option(cnmfe_ctx *ctx, const char *name, int64_t value) {
     if (!ctx || !name) return fail(CNMFE_EINVAL, "null argument");
     // behaviour switches (include/cnmfe.h) and, behind them, the probes of scripts/ (diagnostics: solve_probe, r1_probe, deconv_trace, host_trace, debug)
-    static const char *known[] = {"r1_variant", "r1_delta", "r1_lazy", "r1_defer", "r1_virtual", "gram_incremental", "prealloc", "solve_packed", "sweep_dag", "win_i8_planes", "solve_staged", "solve_inv", "solve_inv_terms", "gram_i8", "win_i8", "proj_tiled", "proj_i8", "proj_i8_planes", "ssub_virtual", "temporal_early",
+    static const char *known[] = {"r1_variant", "r1_delta", "r1_lazy", "r1_defer", "r1_virtual", "gram_incremental", "prealloc", "solve_packed", "sweep_dag", "win_i8_planes", "solve_staged", "solve_inv", "solve_inv_terms", "gram_i8", "win_i8", "proj_tiled", "proj_i8", "proj_i8_planes", "ssub_virtual", "temporal_early", "fit_side",
                                   "solve_probe", "r1_probe", "deconv_trace", "host_trace", "debug", nullptr};
     if (!strcmp(name, "lanes")) { RET(lanes_set(ctx, value)); ctx->opts[name] = value; return 0; }
     for (int i = 0; known[i]; ++i) if (!strcmp(known[i], name)) { ctx->opts[name] = value; if (!strcmp(name, "host_trace")) ctx->trace_level = (int)value; return 0; }

@@ -504,6 +504,23 @@ __global__ void __launch_bounds__(256) k_win_codes(const int *__restrict__ pair_
 #include "win_proj_i8.hpp"
 namespace cnmfe {
 
+// sum(A, 2) of the block region out of the CSR rows the fit uploads anyway: per row the fp64 sum of its entries in the order they are stored, rounded to fp32 once
+// (what the host loop did before its result went over the bus); arow == nullptr: the constant `fillv` (A = ones(d, 1), or no entries at all)
+__global__ void __launch_bounds__(256) k_asum(const int *__restrict__ arow, const float *__restrict__ aval, float fillv, int64_t n, float *__restrict__ asum) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    if (!arow) { asum[q] = fillv; return; }
+    double s = 0;
+    for (int e = arow[q]; e < arow[q + 1]; ++e) s += aval[e];
+    asum[q] = (float)s;
+}
+// slot_of[b * K + k] = position of neuron k in block b's list lst_k[lst_ptr[b] ..) -- the inverse of the lists that are on the device already; the caller has
+// filled the table with -1.  One workgroup per block.
+__global__ void __launch_bounds__(64) k_slot_build(const int *__restrict__ lst_ptr, const int *__restrict__ lst_k, int K, short *__restrict__ slot_of) {
+    const int b = blockIdx.x, p0 = lst_ptr[b], n = lst_ptr[b + 1] - p0;
+    for (int s = threadIdx.x; s < n; s += blockDim.x) slot_of[(int64_t)b * K + lst_k[p0 + s]] = (short)s;
+}
+
 // ind_active = abs(W_old)*sum(A,2) > 0  (fit_ring_model.m:28)
 __global__ void k_active(const float *__restrict__ W, BgGeom g, const int *__restrict__ dr, const int *__restrict__ dc,
                          const float *__restrict__ asum, unsigned char *__restrict__ active, int *__restrict__ nactive) {
@@ -642,26 +659,39 @@ static size_t sys_bytes_of(int64_t d, int nt) { return (size_t)d * ((size_t)(nt 
 
 // ---- launch helpers: the fit and win_i8_table go through them ----
 // digits of the centred traces for the int8 window projection (gram: and their K x K Gram matrix, which k_win_fix then takes G from)
+static int trace_gram(cnmfe_ctx *ctx, const float *dCc, int64_t ldc, int K, int64_t T) {
+    RET(ctx->gk.ensure((size_t)K * K * sizeof(double)));
+    LAUNCH(ctx, "bg_trace_gram", k_trace_gram, dim3((unsigned)(((K + 15) >> 4) * (((K + 15) >> 4) + 1) / 2)), dim3(64 * TG_W), 0, dCc, ldc, T, K, ctx->gk.as<double>());
+    return 0;
+}
 static int trace_digits(cnmfe_ctx *ctx, const char *name, const float *dCc, int64_t ldc, int K, int64_t T, int64_t T16, bool gram) {
     RET(ctx->tdig.ensure((size_t)K * T16 * 4 * sizeof(uint4))); RET(ctx->tscale.ensure((size_t)K * sizeof(double)));
     if (gram) RET(ctx->gk.ensure((size_t)K * K * sizeof(double)));
     LAUNCH(ctx, name, k_trace_dig, dim3(K), dim3(256), 0, dCc, ldc, T, T16, ctx->tdig.as<uint4>(), ctx->tscale.as<double>());
-    if (gram) LAUNCH(ctx, "bg_trace_gram", k_trace_gram, dim3((unsigned)(((K + 15) >> 4) * (((K + 15) >> 4) + 1) / 2)), dim3(64 * TG_W), 0, dCc, ldc, T, K, ctx->gk.as<double>());
-    return 0;
+    return gram ? trace_gram(ctx, dCc, ldc, K, T) : 0;
 }
 // round 5 (win_proj_i8.hpp): the window projection on the int8 matrix pipe out of the resident digit planes, one work item per (block, pair of trace groups)
-static int win_proj_i8_launch(cnmfe_ctx *ctx, Patch *P, const char *name, const std::vector<int> &lst_ptr, const std::vector<int> &blall, const int *dLp, const int *dLk, int nsg,
-                              double *dUt, int64_t ut_stride) {
+// (in two steps: the upload of the work items, then the launch -- a fit that forks its side stream does so between them, with every upload of the compute stream sent)
+static int win_proj_i8_items(cnmfe_ctx *ctx, const std::vector<int> &lst_ptr, const std::vector<int> &blall, size_t *nitems) {
     static thread_local std::vector<int> items;
     plan::win_i8_items(blall, lst_ptr, items);
-    RET(to_dev(ctx, ctx->win_items, items));
-    if (items.empty()) return 0;
+    *nitems = items.size();
+    return to_dev(ctx, ctx->win_items, items);
+}
+static int win_proj_i8_go(cnmfe_ctx *ctx, Patch *P, const char *name, size_t nitems, const int *dLp, const int *dLk, int nsg, double *dUt, int64_t ut_stride) {
+    if (!nitems) return 0;
     const int64_t T16 = P->dig_T16;
-#define WPI8_GO(V0_) LAUNCH(ctx, name, k_win_proj_i8<V0_>, dim3((unsigned)(items.size() * nsg)), dim3(512), 0, P->dig.as<uint4>(), T16, P->dig_sc.as<double>(), ctx->tdig.as<uint4>(), \
+#define WPI8_GO(V0_) LAUNCH(ctx, name, k_win_proj_i8<V0_>, dim3((unsigned)(nitems * nsg)), dim3(512), 0, P->dig.as<uint4>(), T16, P->dig_sc.as<double>(), ctx->tdig.as<uint4>(), \
                             ctx->tscale.as<double>(), dLp, dLk, ctx->win_items.as<int>(), nsg, dUt, ut_stride)
     if (win_planes3(ctx, T16)) WPI8_GO(1); else WPI8_GO(0);
 #undef WPI8_GO
     return 0;
+}
+static int win_proj_i8_launch(cnmfe_ctx *ctx, Patch *P, const char *name, const std::vector<int> &lst_ptr, const std::vector<int> &blall, const int *dLp, const int *dLk, int nsg,
+                              double *dUt, int64_t ut_stride) {
+    size_t nitems = 0;
+    RET(win_proj_i8_items(ctx, lst_ptr, blall, &nitems));
+    return win_proj_i8_go(ctx, P, name, nitems, dLp, dLk, nsg, dUt, ut_stride);
 }
 // the digit planes of g's frames (gram_i8.hpp): the resident video minus da's footprints -> scales digs, planes digp; nchunk != nullptr: and the row sums per frame
 // chunk in dig_rspart (*nchunk of them, reduced by k_rs_reduce)
@@ -727,18 +757,21 @@ struct RingFit {
     bool first_run = false; int pmax = 0, kstride = 1;
     BgGeom g; plan::Reach reach; int nblk = 0, nt = 0;
     // the plan (ring_plan.hpp)
-    plan::BlockLists L; std::vector<plan::Pair> pairs; std::vector<int> pair_of; plan::Tables tabs; int npairs = 0, nwork = 0;
+    plan::BlockLists L; int npairs = 0, nwork = 0;            // (the pair / need / work / tile tables stay with the patch: Patch::RingTabs, fit_need_tables)
     // the path verdicts, each decided in one place.  fit_lists: incr = the incremental Gram (the video's table kept with the patch + this fit's corrections), build_base = this
     // fit builds that table, use_i8 = this fit's Gram (that table, or the direct Gram of Bf) runs on the int8 pipe, keep_pt = the window projection is the P = Yc Cc' table
     // the next spatial update wants.  fit_traces_up: trace_i8_done = the int8 window projection's trace digits and K x K Gram are queued.  fit_queue_projection: proj_queued;
     // win_i8 = it ran on the int8 pipe (k_win_fix takes G from the K x K matrix).  fit_pack: packed = the solve reads the packed systems.  fit_stage_windows: stage_ok
     bool incr = false, build_base = false, use_i8 = false, keep_pt = false, trace_i8_done = false, proj_queued = false, win_i8 = false, packed = false, stage_ok = false;
+    // option fit_side (SideScope below).  fit_traces_up: gram_pending = the K x K trace Gram is still to be queued (the side scope takes it, or fit_queue_projection).
+    // fit_side_setup: setup_done = the CSR rows, ind_active, b0 and slot_of are queued; stage_planned = so are the staged windows' metadata (stage_tot their length)
+    bool gram_pending = false, setup_done = false, stage_planned = false; int64_t stage_tot = -1;
     int nsg = 1; int64_t ut_stride = 0, gb_stride = 0;
     uint4 *digp = nullptr; double *digs = nullptr;             // where the digit planes of this build live
     // device views
     DevBuf &dC, &dCc, &dCm, &dArow, &dAcol, &dAval, &dMisc, &dAsum, &dActive, &dPairs, &dPairOf, &dWork, &dNeed, &dTcnt, &dTl, &dLk, &dBl, &dUt, &dCsum, &dGb, *dLp, *dSlot;
     RingFit(cnmfe_ctx *c, Patch *p_) : ctx(c), P(p_), ht(c, "fit_ring"), dC(c->tmp[0]), dCc(c->tmp[1]), dCm(c->tmp[2]), dArow(c->tmp[3]), dAcol(c->tmp[4]), dAval(c->tmp[5]), dMisc(c->tmp[6]),
-        dAsum(c->tmp[7]), dActive(c->tmp[8]), dPairs(c->tmp[9]), dPairOf(c->tmp[10]), dWork(c->tmp[11]), dNeed(c->tmp[7]), dTcnt(c->tmp[12]), dTl(c->tmp[13]), dLk(c->inc[1]),
+        dAsum(c->tmp[7]), dActive(c->tmp[8]), dPairs(p_->rt.dPairs), dPairOf(p_->rt.dPairOf), dWork(p_->rt.dWork), dNeed(p_->rt.dNeed), dTcnt(p_->rt.dTcnt), dTl(p_->rt.dTl), dLk(c->inc[1]),
         dBl(c->inc[3]), dUt(c->inc[4]), dCsum(c->inc[5]), dGb(c->inc[6]), dLp(&c->inc[0]), dSlot(&c->inc[2]) {}
     const int *arow() const { return has_a ? dArow.as<int>() : nullptr; }
     CovTab covtab() const { CovTab t{}; t.cov = ctx->cov.as<double>(); t.pair_of = dPairOf.as<int>(); t.nbr = g.nbr; t.nbc = g.nbc; t.maxd = reach.maxd; t.nrel = reach.nrel; return t; }
@@ -752,10 +785,17 @@ static int fit_traces_up(RingFit &f) {
     // win_proj_i8.hpp: what depends on the traces alone goes out NOW -- the host's footprint block lists (0.2 ms at the headline size) are built underneath it
     // instead of in front of an idle GPU (the stride is not known yet: a fit that turns out to use another than the table in place has queued 0.1 ms for nothing)
     if (!f.outl && ctx->opt("gram_incremental", 1) != 0 && win_i8_applies(ctx, P, P->base_valid ? P->base_kstride : 1)) {
-        RET(trace_digits(ctx, "bg_trace_dig", f.dCc.as<float>(), f.ldc, f.K, f.T, P->dig_T16, true));
+        // (fit_side: the K x K Gram waits until the fit knows whether its side scope runs -- the projection reads the digits only)
+        f.gram_pending = ctx->opt("fit_side", 1) != 0 && ctx->lanes.empty();
+        RET(trace_digits(ctx, "bg_trace_dig", f.dCc.as<float>(), f.ldc, f.K, f.T, P->dig_T16, !f.gram_pending));
         f.trace_i8_done = true;
     }
     return 0;
+}
+static int fit_trace_gram(RingFit &f) {
+    if (!f.gram_pending) return 0;
+    f.gram_pending = false;
+    return trace_gram(f.ctx, f.dCc.as<float>(), f.ldc, f.K, f.T);
 }
 // the CSR rows of A (b0, ind_active, the table corrections): built AFTER the window projection is queued when that can go first
 static int fit_upload_csr(RingFit &f) {
@@ -813,30 +853,81 @@ static void fit_lists(RingFit &f) {
     f.keep_pt = f.incr && f.has_a && f.kstride == 1 && !P->derived && !(f.b0_only & 2) && ctx->opt("r1_virtual", 1) != 0;
     if (f.keep_pt) { f.dLp = &P->pt_lp; f.dSlot = &P->pt_slot; P->pt_valid = false; }      // (until the new table is queued)
 }
+// ---- option fit_side: the fit's set-up on a second stream, beside the window projection ----
+// A steady-state fit (the video's table exists: incr && has_a && !build_base) queues its 1.5 ms window projection first.  What follows up to k_win_fix -- the trace
+// sums and the K x K trace Gram, the CSR rows of A, sum(A, 2), ind_active and its count, b0, slot_of, the staged windows' metadata -- reads nothing the projection
+// writes and writes nothing it reads (the buffer table: DESIGN.md section 3, B1 / B2), and is a dozen latency-bound dispatches the compute stream would run one after
+// the other behind it.  The scope puts them on the context's side stream:
+//   fork()   every held-back upload of the compute stream sent, the error word in place, an event recorded on the compute stream; the side stream waits for it
+//            -- and with it for everything queued earlier (the updates that used the same scratch)
+//   enter()  the side stream takes the compute stream's place in the context: launches, held-back uploads (k_pin_copy) and the pinned arena's half-switch events
+//            all go through cnmfe_ctx::st(), so they follow without knowing (what the lanes do with a whole scratch set)
+//   leave()  the side stream's held-back uploads sent, an event recorded on it, the streams swapped back, the compute stream waits for the event
+// fit_side = 1: fork, projection on the compute stream, enter .. leave -- the set-up runs under the projection.  2: fork, enter .. leave, THEN the projection: the same
+// streams and code with nothing concurrent (tests; a wrong stream shows in both, a hazard of the overlap in 1 only).  0: one stream, the order of before.
+// Between fork and leave the compute stream is given the projection's launches and nothing else: no upload, no event of the arena.
+struct SideScope {
+    cnmfe_ctx *ctx; bool inside = false;
+    explicit SideScope(cnmfe_ctx *c) : ctx(c) {}
+    int fork() {
+        int *dErr = nullptr;
+        RET(ctx_errflag(ctx, &dErr));                            // (allocated and cleared on the compute stream, before anything can raise it from the other one)
+        RET(ctx_side_stream(ctx));
+        CK(hipEventRecord(ctx->ev_side_fork, ctx->st()));
+        CK(hipStreamWaitEvent(ctx->side_stream, ctx->ev_side_fork, 0));
+        return 0;
+    }
+    int enter() { (void)ctx->st(); std::swap(ctx->stream_, ctx->side_stream); inside = true; return 0; }
+    int leave() {
+        if (!inside) return 0;
+        const hipError_t e = hipEventRecord(ctx->ev_side_join, ctx->st());
+        std::swap(ctx->stream_, ctx->side_stream); inside = false;
+        CK(e);
+        CK(hipStreamWaitEvent(ctx->stream_, ctx->ev_side_join, 0));
+        return 0;
+    }
+    ~SideScope() { if (inside) (void)leave(); }                  // (an error inside the scope: the streams go back, and the compute stream still waits for what was queued)
+};
+// which way this fit goes (0: no side scope).  lanes > 1: every lane is a stream of its own already, and the patches' fits overlap each other
+static int fit_side_mode(const RingFit &f) {
+    const int64_t m = f.ctx->opt("fit_side", 1);
+    return (m == 1 || m == 2) && f.ctx->lanes.empty() && f.incr && f.has_a && !f.build_base ? (int)m : 0;
+}
+static int fit_side_setup(RingFit &f);
+
 // ---- the window projection: it needs the footprint lists and the traces, nothing else, and takes 5 ms at the headline size ----
-static int fit_queue_projection(RingFit &f) {
+static int fit_queue_projection(RingFit &f, int side = 0) {
     cnmfe_ctx *ctx = f.ctx; Patch *P = f.P; const BgGeom &g = f.g;
+    SideScope sc(ctx);
     RET(to_dev(ctx, *f.dLp, f.L.lst_ptr)); RET(to_dev(ctx, f.dLk, f.L.lst_k)); RET(to_dev(ctx, f.dBl, f.L.blall)); RET(f.dCsum.ensure((size_t)f.K * sizeof(double)));
-    LAUNCH(ctx, "bg_trace_subsum", k_trace_subsum, dim3(f.K), dim3(256), 0, f.dCc.as<float>(), f.ldc, g.Tp, g.kstride, f.dCsum.as<double>());
+    if (!side) LAUNCH(ctx, "bg_trace_subsum", k_trace_subsum, dim3(f.K), dim3(256), 0, f.dCc.as<float>(), f.ldc, g.Tp, g.kstride, f.dCsum.as<double>());
     const int nb_ = (int)f.L.blall.size(), nbig = (int)f.L.blk_nt[3].size();                    // blall starts with the longest lists
     f.nsg = plan::win_segments(nb_);
     f.ut_stride = (int64_t)std::max<size_t>(1, f.L.lst_k.size()) * BLKPX; f.gb_stride = (int64_t)f.nblk * WIN_NLB * WIN_NLB;
     RET(f.dUt.ensure((size_t)f.nsg * f.ut_stride * sizeof(double))); RET(f.dGb.ensure((size_t)f.nsg * f.gb_stride * sizeof(double)));
     const int *dLp = f.dLp->as<int>(), *dLk = f.dLk.as<int>(), *dBl = f.dBl.as<int>();
-    if (win_i8_applies(ctx, P, g.kstride)) {
+    f.win_i8 = win_i8_applies(ctx, P, g.kstride);
+    size_t nitems = 0;
+    if (f.win_i8) {
+        // (the first fit of a patch, or a fit back at stride 1: the digit planes did not exist, or were not this stride's, when the traces went up)
+        if (!f.trace_i8_done) { f.gram_pending = side != 0; RET(trace_digits(ctx, "bg_trace_dig", f.dCc.as<float>(), f.ldc, f.K, f.T, P->dig_T16, !f.gram_pending)); f.trace_i8_done = true; }
+        if (!side) RET(fit_trace_gram(f));
+        RET(win_proj_i8_items(ctx, f.L.lst_ptr, f.L.blall, &nitems));
+    }
+    if (side) RET(sc.fork());
+    if (side == 2) { RET(sc.enter()); RET(fit_side_setup(f)); RET(sc.leave()); }
+    if (f.win_i8) {
         // the same sums out of the resident digit planes; G = Cc Cc' once, K x K
         // (round 6 ran a strided fit here too -- planes of every frame, trace digits zeroed on the skipped frames: correct, and no faster than the fp64 kernel on
         //  patches of 128 x 128, which reads its 2 GB at 5.5 TB/s already, while the K x K trace Gram became a kernel of its own: profiles/r06/c5shard_i8.txt)
-        // (the first fit of a patch: the digit planes did not exist when the traces went up)
-        if (!f.trace_i8_done) RET(trace_digits(ctx, "bg_trace_dig", f.dCc.as<float>(), f.ldc, f.K, f.T, P->dig_T16, true));
-        RET(win_proj_i8_launch(ctx, P, "bg_win_proj", f.L.lst_ptr, f.L.blall, dLp, dLk, f.nsg, f.dUt.as<double>(), f.ut_stride));
-        f.win_i8 = true;
+        RET(win_proj_i8_go(ctx, P, "bg_win_proj", nitems, dLp, dLk, f.nsg, f.dUt.as<double>(), f.ut_stride));
     } else if (g.kstride == 1 || g.kstride == 2 || g.kstride == 4)
         RET(win_proj4_launch(ctx, "bg_win_proj", P, g, f.dCc.as<float>(), f.ldc, dLp, dLk, dBl, nbig, nb_, f.nsg, f.dUt.as<double>(), f.ut_stride, f.dGb.as<double>(), f.gb_stride));
     else
         LAUNCH(ctx, "bg_win_proj", k_win_proj, dim3((unsigned)(nb_ * f.nsg)), dim3(256), 0, P->Yc4.as<float4>(), g, f.dCc.as<float>(), f.ldc, dLp, dLk, dBl, f.nsg, f.dUt.as<double>(), f.ut_stride,
                f.dGb.as<double>(), f.gb_stride);
     f.proj_queued = true;
+    if (side == 1) { RET(sc.enter()); RET(fit_side_setup(f)); RET(sc.leave()); }
     return 0;
 }
 // ---- ind_active (:25-29), b0 (:44) ----
@@ -845,11 +936,12 @@ static int fit_active_b0(RingFit &f) {
     RET(f.dActive.ensure(P->d));
     f.nactive = P->d;
     if (f.first_run) { CK(hipMemsetAsync(f.dActive.p, 1, P->d, ctx->st())); } else {
-        std::vector<float> asum(P->d_b, 0.f);
         // isempty(A) -> A = ones(d,1) (:14-16).  Bit 1 of b0_only: the reference passes A = [] because it subtracted A*C itself (bg_ssub > 1)
-        if (f.a_empty || (f.b0_only & 2)) std::fill(asum.begin(), asum.end(), 1.0f);
-        else if (f.has_a) for (int64_t q = 0; q < P->d_b; ++q) { double s = 0; for (int64_t e = f.csr.rowptr[q]; e < f.csr.rowptr[q + 1]; ++e) s += f.csr.val[e]; asum[q] = (float)s; }
-        RET(to_dev(ctx, f.dAsum, asum));
+        // (sum(A, 2) out of the CSR rows that are on the device by now: k_asum)
+        const bool ones = f.a_empty || (f.b0_only & 2);
+        RET(f.dAsum.ensure((size_t)P->d_b * sizeof(float)));
+        LAUNCH(ctx, "bg_asum", k_asum, dim3((unsigned)((P->d_b + 255) / 256)), dim3(256), 0, !ones && f.has_a ? f.dArow.as<int>() : (const int *)nullptr, f.dAval.as<float>(), ones ? 1.0f : 0.0f,
+               (int64_t)P->d_b, f.dAsum.as<float>());
         CK(hipMemsetAsync(f.dMisc.p, 0, 64, ctx->st()));
         LAUNCH(ctx, "bg_active", k_active, dim3((unsigned)((P->d + 255) / 256)), dim3(256), 0, P->W.as<float>(), f.g,
                P->ring_dr.as<int>(), P->ring_dc.as<int>(), f.dAsum.as<float>(), f.dActive.as<unsigned char>(), f.dMisc.as<int>());
@@ -863,22 +955,41 @@ static int fit_active_b0(RingFit &f) {
 // (pixels that are not active keep their weights: the solve kernel skips them; a patch without any costs the sweep of its tables)
 static int fit_pair_tables(RingFit &f) {
     cnmfe_ctx *ctx = f.ctx; Patch *P = f.P;
-    f.npairs = plan::ring_pairs(P->nr_b, P->nc_b, P->roff, P->coff, P->nr, P->nc, f.reach.p_radius, f.reach.maxd, &f.pairs, &f.pair_of);
-    plan::ring_tables(f.pairs, f.reach.maxd, f.reach.p_radius, P->dr.data(), P->dc.data(), P->p, f.tabs);
-    f.nwork = (int)f.tabs.work.size();
+    // the tables follow the block geometry and the ring offsets alone: under an unchanged key the fit takes the pair count from the patch and leaves the tables to
+    // whichever of its kernels reads them (fit_need_tables) -- in a steady-state packed fit none does
+    Patch::RingTabs &rt = P->rt;
+    const int geo[8] = {(int)P->nr_b, (int)P->nc_b, (int)P->roff, (int)P->coff, (int)P->nr, (int)P->nc, f.reach.p_radius, f.reach.maxd};
+    if (!(rt.keyed && std::equal(geo, geo + 8, rt.geo) && rt.dr == P->dr && rt.dc == P->dc)) {
+        rt.keyed = rt.built = false;
+        rt.npairs = plan::ring_pairs(geo[0], geo[1], geo[2], geo[3], geo[4], geo[5], geo[6], geo[7], nullptr, nullptr);
+        std::copy(geo, geo + 8, rt.geo); rt.dr = P->dr; rt.dc = P->dc; rt.keyed = true;
+    }
+    f.npairs = rt.npairs;
     f.ht.mark("pair / need / work tables");
-    RET(to_dev(ctx, f.dPairs, f.pairs)); RET(to_dev(ctx, f.dPairOf, f.pair_of)); RET(to_dev(ctx, f.dWork, f.tabs.work)); RET(to_dev(ctx, f.dNeed, f.tabs.needmask));
     const size_t cov_bytes = (size_t)f.npairs * BLKPX * BLKPX * sizeof(double);
     RET(ctx->cov.ensure(cov_bytes));
     if (ctx->opt("debug", 0)) CK(hipMemsetAsync(ctx->cov.p, 0xff, cov_bytes, ctx->st()));   // NaN-poison skipped sub-tiles
-    RET(to_dev(ctx, f.dTcnt, f.tabs.tcnt)); RET(to_dev(ctx, f.dTl, f.tabs.tlist));
-    // (every table above went through the pinned arena: no drain here, the big launches below queue behind whatever the stream still holds)
     f.ht.mark("tile lists + uploads (sync)");
     // incremental: the table of the video alone is built once and kept with the patch; later fits skip B1 / B2a entirely
     if (f.incr) {
         RET(P->cov_base.ensure(cov_bytes));
         if (f.build_base && ctx->opt("debug", 0)) CK(hipMemsetAsync(P->cov_base.p, 0xff, cov_bytes, ctx->st()));
     }
+    return 0;
+}
+// the tables themselves, for a fit one of whose kernels reads them (the table builds: pairs, work, tile lists; k_win_codes: pair_of; k_cov_correct: pairs, needmask):
+// computed and uploaded when the key changed since they last were, into buffers of the patch's own -- the context's scratch is anybody's between two fits
+static int fit_need_tables(RingFit &f) {
+    cnmfe_ctx *ctx = f.ctx; Patch *P = f.P; Patch::RingTabs &rt = P->rt;
+    if (!rt.built) {
+        plan::ring_pairs(rt.geo[0], rt.geo[1], rt.geo[2], rt.geo[3], rt.geo[4], rt.geo[5], rt.geo[6], rt.geo[7], &rt.pairs, &rt.pair_of);
+        plan::ring_tables(rt.pairs, f.reach.maxd, f.reach.p_radius, P->dr.data(), P->dc.data(), P->p, rt.tabs);
+        rt.nwork = (int)rt.tabs.work.size();
+        RET(to_dev(ctx, rt.dPairs, rt.pairs)); RET(to_dev(ctx, rt.dPairOf, rt.pair_of)); RET(to_dev(ctx, rt.dWork, rt.tabs.work)); RET(to_dev(ctx, rt.dNeed, rt.tabs.needmask));
+        RET(to_dev(ctx, rt.dTcnt, rt.tabs.tcnt)); RET(to_dev(ctx, rt.dTl, rt.tabs.tlist));
+        rt.built = true;
+    }
+    f.nwork = rt.nwork;
     return 0;
 }
 // ---- B1: Bf tiled (fp32, or digit planes for the int8 Gram) and its row sums rsT ----
@@ -957,6 +1068,7 @@ static int fit_outlier_frames(RingFit &f) {
 static int fit_base_table(RingFit &f) {
     cnmfe_ctx *ctx = f.ctx; Patch *P = f.P; const BgGeom &g = f.g;
     DevBuf &covT = f.incr ? P->cov_base : ctx->cov, &rsT = f.incr ? P->rowsum_base : ctx->rowsum;
+    RET(fit_need_tables(f));
     RET(fit_build_bf(f, rsT));
     if (f.outl) RET(fit_outlier_frames(f));
     if (g.bf4 < 2) LAUNCH(ctx, "bg_rowsum", k_rowsum, dim3(f.nblk), dim3(256), 0, ctx->bf.as<float>(), g.Tpad, rsT.as<double>(), g.bf4);
@@ -977,6 +1089,7 @@ static int fit_base_table(RingFit &f) {
 // the block-pair codes per window origin (k_win_codes): for the pack and for the table solve
 static int fit_win_codes(RingFit &f) {
     const int woff = f.reach.woff, nwin = (f.g.nbr + 2 * woff) * (f.g.nbc + 2 * woff);
+    RET(fit_need_tables(f));
     RET(f.ctx->wcodes.ensure((size_t)nwin * 256 * sizeof(int)));
     LAUNCH(f.ctx, "bg_win_codes", k_win_codes, dim3((unsigned)nwin), dim3(256), 0, f.dPairOf.as<int>(), f.g.nbr, f.g.nbc, woff, f.reach.maxd, f.reach.nrel, f.ctx->wcodes.as<int>());
     return 0;
@@ -986,8 +1099,8 @@ static int fit_win_codes(RingFit &f) {
 // the memory, one launch (no split solve) ----
 static int fit_pack(RingFit &f) {
     cnmfe_ctx *ctx = f.ctx; Patch *P = f.P; const int nt = f.nt;
-    const double fillv[2] = {0.0, 1.0};                      // the fill values {0, 1} of missing neighbours, in global memory (ring_solve.hpp)
-    RET(to_dev(ctx, ctx->solve_fill, fillv, 2));
+    const double fillv[2] = {0.0, 1.0};                      // the fill values {0, 1} of missing neighbours, in global memory (ring_solve.hpp): constants, uploaded once
+    if (!ctx->solve_fill.p) RET(to_dev(ctx, ctx->solve_fill, fillv, 2));
     f.packed = f.incr && pack_wanted(ctx, nt) && (int64_t)f.nblk * std::max(1, f.K) < (int64_t)1 << 31 && (int64_t)f.L.lst_k.size() * BLKPX < (int64_t)1 << 31;
     const size_t sys_bytes = sys_bytes_of(P->d, nt);
     if (!f.packed || (P->sys_valid && P->sys.cap >= sys_bytes)) return 0;
@@ -1007,20 +1120,53 @@ static int fit_pack(RingFit &f) {
 }
 // ---- round 6 (ring_solve_staged.hpp): U~ and A of every neuron as dense images over its footprint's bounding box dilated by the ring radius, and per list
 // position the neuron's window: the solve samples them with index arithmetic instead of walking CSR rows and slot tables ----
-static int fit_stage_windows(RingFit &f) {
+static bool fit_stage_wanted(const RingFit &f) { return f.ctx->opt("solve_staged", 1) != 0 && f.P->nr_b < 32768 && f.P->nc_b < 32768; }
+// (the host's part and the uploads: they depend on the footprints' boxes and the lists alone, so a fit that is sure of its packed systems plans in its side scope)
+static int fit_stage_plan(RingFit &f) {
     cnmfe_ctx *ctx = f.ctx; Patch *P = f.P;
-    if (!(f.packed && ctx->opt("solve_staged", 1) != 0 && P->nr_b < 32768 && P->nc_b < 32768)) return 0;
     static thread_local std::vector<int> nmeta, lmeta;
-    const int64_t tot = plan::stage_windows(f.K, fit_nbox, f.L.lst_k, P->nr_b, P->nc_b, f.reach.p_radius, nmeta, lmeta);
+    const int64_t tot = f.stage_tot = plan::stage_windows(f.K, fit_nbox, f.L.lst_k, P->nr_b, P->nc_b, f.reach.p_radius, nmeta, lmeta);
+    f.stage_planned = true;
     if (tot < 0) return 0;                                     // (a window too large: k_ring_solve6 serves this fit)
-    f.stage_ok = true;
     RET(to_dev(ctx, ctx->stg[0], nmeta)); RET(to_dev(ctx, ctx->stg[1], lmeta));
     RET(ctx->stg[2].ensure((size_t)std::max<int64_t>(1, tot) * sizeof(double)));
     RET(ctx->stg[3].ensure((size_t)std::max<int64_t>(1, tot) * sizeof(float)));
+    return 0;
+}
+static int fit_stage_windows(RingFit &f) {
+    cnmfe_ctx *ctx = f.ctx;
+    if (!(f.packed && fit_stage_wanted(f))) return 0;
+    if (!f.stage_planned) RET(fit_stage_plan(f));
+    if (f.stage_tot < 0) return 0;
+    f.stage_ok = true;
     int *dErrW = nullptr;
     RET(ctx_errflag(ctx, &dErrW));
     LAUNCH(ctx, "bg_neuron_windows", k_nwin_build, dim3((unsigned)f.K), dim3(256), 0, ctx->stg[0].as<int>(), f.g, (int)f.K, f.dArow.as<int>(), f.dAcol.as<int>(), f.dAval.as<float>(),
            f.dLp->as<int>(), f.dSlot->as<short>(), f.dUt.as<double>(), ctx->stg[2].as<double>(), ctx->stg[3].as<float>(), dErrW);
+    return 0;
+}
+// slot_of on the device: the inverse of the lists lst_ptr / lst_k that went up for the projection (the host's copy stays with the patch for the spatial update's reuse test)
+static int fit_slot_table(RingFit &f) {
+    const size_t bytes = (size_t)f.nblk * std::max(1, (int)f.K) * sizeof(short);
+    RET(f.dSlot->ensure(bytes));
+    CK(hipMemsetAsync(f.dSlot->p, 0xff, bytes, f.ctx->st()));
+    LAUNCH(f.ctx, "bg_slot_table", k_slot_build, dim3((unsigned)f.nblk), dim3(64), 0, f.dLp->as<int>(), f.dLk.as<int>(), (int)f.K, f.dSlot->as<short>());
+    return 0;
+}
+// what a steady-state fit queues between its window projection and k_win_fix without reading anything the projection writes (SideScope: on the side stream)
+static int fit_side_setup(RingFit &f) {
+    cnmfe_ctx *ctx = f.ctx; Patch *P = f.P;
+    LAUNCH(ctx, "bg_trace_subsum", k_trace_subsum, dim3(f.K), dim3(256), 0, f.dCc.as<float>(), f.ldc, f.g.Tp, f.g.kstride, f.dCsum.as<double>());
+    if (f.win_i8) RET(fit_trace_gram(f));
+    RET(fit_upload_csr(f));
+    f.ht.mark("A csr");
+    RET(fit_active_b0(f));
+    f.ht.mark("ind_active + b0");
+    RET(fit_slot_table(f));
+    // the staged windows' metadata, when the packed systems are in place already (then fit_pack has nothing to decide)
+    if (f.incr && pack_wanted(ctx, f.nt) && P->sys_valid && P->sys.cap >= sys_bytes_of(P->d, f.nt) && (int64_t)f.nblk * std::max(1, f.K) < (int64_t)1 << 31 &&
+        (int64_t)f.L.lst_k.size() * BLKPX < (int64_t)1 << 31 && fit_stage_wanted(f)) RET(fit_stage_plan(f));
+    f.setup_done = true;
     return 0;
 }
 // ---- B2a': U~ on the blocks near footprints, then one sweep base -> cov (table path) or nothing (packed path: the solve corrects in registers) ----
@@ -1033,7 +1179,7 @@ static int fit_corrections(RingFit &f, const float *C, int c_order) {
         return 0;
     }
     if (!f.proj_queued) RET(fit_queue_projection(f));          // (first fit of the patch: behind the video's table)
-    RET(to_dev(ctx, *f.dSlot, f.L.slot_of));
+    if (!f.setup_done) RET(fit_slot_table(f));
     if (f.keep_pt) RET(P->pt_tab.ensure(std::max<size_t>(1, f.L.lst_k.size()) * BLKPX * sizeof(double)));
     LAUNCH(ctx, "bg_win_fix", k_win_fix, dim3((unsigned)f.L.blall.size(), WIN_NLB / WF_S), dim3(256), 0, g, K, f.dArow.as<int>(), f.dAcol.as<int>(), f.dAval.as<float>(), f.dLp->as<int>(),
            f.dSlot->as<short>(), f.dBl.as<int>(), f.nsg, f.dUt.as<double>(), f.ut_stride, f.dGb.as<double>(), f.gb_stride, f.keep_pt ? P->pt_tab.as<double>() : nullptr,
@@ -1044,6 +1190,7 @@ static int fit_corrections(RingFit &f, const float *C, int c_order) {
         P->pt_valid = true;
     }
     const int csplit = f.npairs >= 8192 ? 1 : f.npairs >= 4096 ? 2 : 4;      // (small patches: a pair's sweep is a long serial loop, one workgroup per pair leaves the chip idle)
+    if (!f.packed) RET(fit_need_tables(f));
     if (!f.packed)
         LAUNCH(ctx, "bg_cov_correct", k_cov_correct, dim3((unsigned)f.npairs, (unsigned)csplit), dim3(256), 0, P->cov_base.as<double>(), ctx->cov.as<double>(), f.dPairs.as<int4>(),
                f.dNeed.as<unsigned short>(), g, K, f.dArow.as<int>(), f.dAcol.as<int>(), f.dAval.as<float>(), f.dLp->as<int>(), f.dSlot->as<short>(), f.dUt.as<double>());
@@ -1139,12 +1286,15 @@ int bg_fit_ring(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, co
     RET(fit_geometry(f, with_projection));
     fit_lists(f);
     // the window projection first when the video's table exists (a later fit of a patch): the host builds the CSR rows of A, ind_active and the pair tables underneath it
-    if (f.incr && f.has_a && !f.build_base) RET(fit_queue_projection(f));
+    // (option fit_side: and that set-up is queued on the side stream, so the GPU runs it underneath the projection as well)
+    if (f.incr && f.has_a && !f.build_base) RET(fit_queue_projection(f, fit_side_mode(f)));
     f.ht.mark("projection queued");
-    RET(fit_upload_csr(f));
-    f.ht.mark("A csr");
-    RET(fit_active_b0(f));
-    f.ht.mark("ind_active + b0");
+    if (!f.setup_done) {
+        RET(fit_upload_csr(f));
+        f.ht.mark("A csr");
+        RET(fit_active_b0(f));
+        f.ht.mark("ind_active + b0");
+    }
     RET(fit_pair_tables(f));
     if (!f.incr || f.build_base) RET(fit_base_table(f));
     if (f.nt < 1 || f.nt > 8) return fail(CNMFE_EUNSUPPORTED, "fit_ring_model: %d ring neighbours (<= %d supported)", P->p, PMAX_RING);

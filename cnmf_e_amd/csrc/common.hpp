@@ -13,6 +13,7 @@
 #include <map>
 #include <algorithm>
 #include "../../include/cnmfe.h"
+#include "ring_plan.hpp"
 
 namespace cnmfe {
 
@@ -197,6 +198,16 @@ struct Patch {
     // recording whose T / (100 pmax) sits at an integer -- T = 20000 with pmax around 66 -- alternates between two strides from fit to fit; one kept table
     // meant a full fp64 rebuild (10-15 ms per patch) on every flip.  Allocated only when a second stride turns up.
     DevBuf cov_base_alt, rowsum_base_alt; bool base_alt_valid = false; int base_alt_kstride = 0;
+    // The block-pair tables of the ring fit (ring_plan.hpp: ring_pairs, ring_tables) on the host and the device.  They follow the block geometry and the ring offsets
+    // only -- not A, C or the frame stride -- so they stay with the patch under the key they were computed from (bg.hip, fit_pair_tables / fit_need_tables): a fit
+    // whose kernels read none of them (the steady-state packed fit) neither computes nor uploads them, and a table swap between two frame strides leaves them alone.
+    struct RingTabs {
+        bool keyed = false, built = false;                 // key / npairs hold; the host vectors and the device copies hold
+        int geo[8] = {0, 0, 0, 0, 0, 0, 0, 0}; std::vector<int32_t> dr, dc;      // the key: nr_b, nc_b, roff, coff, nr, nc, p_radius, maxd + the ring offsets
+        int npairs = 0, nwork = 0;
+        std::vector<plan::Pair> pairs; std::vector<int> pair_of; plan::Tables tabs;
+        DevBuf dPairs, dPairOf, dWork, dNeed, dTcnt, dTl;
+    } rt;
     // the video's normal equations per patch pixel, packed in the ring solve's register-tile order (ring_solve_packed.hpp): gathered once from cov_base
     // (and once more for a second frame stride), 43 KB per pixel at p = 96
     DevBuf sys, sys_alt; bool sys_valid = false, sys_alt_valid = false;
@@ -322,6 +333,9 @@ struct cnmfe_ctx {
     cnmfe::PinArena pin;
     int64_t spatial_nnz = -1;                              // values of the last cnmfe_update_spatial still in scr[6] (deferred fetch)
     hipStream_t copy_stream = nullptr;                     // device -> pinned host downloads that should not hold up the compute stream
+    // option fit_side (bg.hip, SideScope): the second stream a steady-state ring fit queues its set-up on, beside the window projection; created at its first use at
+    // the compute stream's priority, with the event the side stream waits for (fork) and the one the compute stream waits for (join)
+    hipStream_t side_stream = nullptr; hipEvent_t ev_side_fork = nullptr, ev_side_join = nullptr;
     hipEvent_t ev_bound_ready = nullptr, ev_copy_done = nullptr; bool copy_pending = false;
     // every batch of downloads on the copy stream gets a generation number and an event of its own: a host buffer waits for ITS batch (cnmfe_copy_wait),
     // not for whatever was queued on the copy stream since (cnmfe_stitch_wait) -- releasing last iteration's traces must not wait for this iteration's
@@ -542,6 +556,7 @@ int ring_stats_enqueue(cnmfe_ctx *ctx, Patch *P);                    // after W 
 int ring_stats_get(cnmfe_ctx *ctx, Patch *P, int *pmax, bool *first); // waits for that event only (falls back to a fresh evaluation)
 int center_traces(cnmfe_ctx *ctx, const float *C, int64_t ldc, int32_t K, int64_t T, DevBuf &Cc, DevBuf &Cmean);
 int upload_centered(cnmfe_ctx *ctx, DevBuf &stage, const float *C, int32_t K, int64_t T, int order, DevBuf &Cc, DevBuf &Cmean, int64_t *ldc_out);
+int ctx_side_stream(cnmfe_ctx *ctx);                    // api.hip: the side stream of option fit_side and its two events (created on first use)
 int ctx_errflag(cnmfe_ctx *ctx, int **dflag);            // the device error word (allocated and cleared on first use)
 int ctx_check_errflag(cnmfe_ctx *ctx);                   // after a stream sync: CNMFE_ESTATE if a kernel raised it (and clears it)
 }  // namespace cnmfe

@@ -549,6 +549,11 @@ int cnmfe_synchronize(cnmfe_ctx *ctx);
  *                     spatial update's connectivity kernel (cnmfe_temporal_early_project, below) and the Gauss-Seidel levels are queued without the host wait for
  *                     A'A (aa and its check are taken on the device; the wait stays when a footprint term over more than 512 traces was applied, whose list kernel
  *                     may overflow).  2: the projection only, 3: the levels only, 0: neither.  Results are bit-equal (tests/test_gpu_handover.py)
+ *   fit_side          default 1: a ring fit that queues its window projection first (the video's table exists and A has entries: every fit of a patch but its first)
+ *                     queues what follows up to k_win_fix and reads nothing the projection writes -- the trace sums and the K x K trace Gram, the CSR rows of A,
+ *                     sum(A, 2), ind_active, b0, slot_of, the staged windows' metadata -- on a second stream of the context, forked in front of the projection and joined
+ *                     in front of k_win_fix, so the GPU runs it underneath the projection.  2: the same streams, joined in front of the projection (nothing overlaps:
+ *                     tests).  0: one stream.  Inert with lanes > 1.  Results are bit-equal (tests/test_gpu_fit_side.py)
  *   prealloc          default 1: cnmfe_fit_reserve may allocate the fit's large buffers ahead of the first fit
  * A deployment short of HBM sets win_i8 = proj_tiled = 0 (and solve_packed = 0) or leaves it to the engine, which falls back by itself.
  * Diagnostics (scripts/): solve_probe, r1_probe (phase probes: results are NOT the product's), deconv_trace, host_trace (1: host-side phase times of every call on
