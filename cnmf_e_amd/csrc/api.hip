@@ -365,7 +365,7 @@ static int errflag_raise(cnmfe_ctx *ctx, int h, bool taken = false) {
     if (!taken) CK(hipMemsetAsync(ctx->errflag.p, 0, sizeof(int), ctx->st()));
     // whatever raised the flag left truncated or inconsistent tables behind (the footprint terms beside a residual, a P table): nothing kept with the patches may
     // be trusted by a later call -- the next residual sweeps again, the next spatial update builds its own table
-    for (auto &kv : ctx->patches) { Patch *q = kv.second; q->ysig_valid = false; q->ysig_virtual = false; q->pend = false; q->res_ac = false; q->res_kind = 0; q->pt_valid = false; }
+    for (auto &kv : ctx->patches) { Patch *q = kv.second; q->residual.invalidate(); q->pt_valid = false; }
     ctx->bgs_patch = -1;
     if (h & 8) return fail(CNMFE_EHIP, "temporal update: the device's aa = diag(A'A) disagrees with the host-side test of a column (flag %d)", h);
     if (h & 2) return fail(CNMFE_EUNSUPPORTED, "a pixel's ring touches more than 256 footprints of A_prev (flag %d)", h);
@@ -592,6 +592,17 @@ static int lanes_set(cnmfe_ctx *ctx, int64_t n) {
     return 0;
 }
 
+// the guards of every call that reads the residual of a patch; `_full`: calls that serve the residual of cnmfe_residual only
+static int require_residual(const Patch *P, int patch_id) {
+    if (!P->residual.valid()) return fail(CNMFE_ESTATE, "cnmfe_residual has not been run for patch %d", patch_id);
+    return 0;
+}
+static int require_residual_full(const Patch *P, int patch_id, const char *what) {
+    RET(require_residual(P, patch_id));
+    if (P->residual.source != rplan::SRC_FULL) return fail(CNMFE_EUNSUPPORTED, "%s needs the residual of cnmfe_residual (bg_ssub = 1)", what);
+    return 0;
+}
+
 extern "C" {
 
 const char *cnmfe_last_error(void) { return g_err; }
@@ -752,7 +763,7 @@ int cnmfe_upload_block(cnmfe_ctx *ctx, int patch_id, const void *Y, int dtype, i
     CK(hipStreamSynchronize(ctx->st()));
     std::fill(P->frame_seen.begin() + t0, P->frame_seen.begin() + t0 + nt, (uint8_t)1);
     P->frames_uploaded += nt;
-    P->ymean_valid = false; P->ysig_valid = false; P->base_valid = false; P->base_alt_valid = false; P->drop_systems(); P->sys_alt_valid = false; P->pt_valid = false; P->dig_valid = false; P->digp_valid = false; P->yt4_valid = false;
+    P->ymean_valid = false; P->residual.invalidate(); P->base_valid = false; P->base_alt_valid = false; P->drop_systems(); P->sys_alt_valid = false; P->pt_valid = false; P->dig_valid = false; P->digp_valid = false; P->yt4_valid = false;
     return 0;
 }
 
@@ -797,7 +808,7 @@ int cnmfe_ring_init(cnmfe_ctx *ctx, int patch_id, int32_t radius, int32_t num_ne
     CK(hipStreamSynchronize(ctx->st()));
     P->stat_valid = false;
     if (P->stat_host) { (void)hipHostFree(P->stat_host); P->stat_host = nullptr; }      // sized by the number of ring offsets
-    P->ring_ready = true; P->ysig_valid = false; P->base_valid = false; P->base_alt_valid = false; P->drop_systems(); P->sys_alt_valid = false; P->pt_valid = false;   // (the kept covariance tables cover the sub-tiles THIS ring needs)
+    P->ring_ready = true; P->residual.invalidate(); P->base_valid = false; P->base_alt_valid = false; P->drop_systems(); P->sys_alt_valid = false; P->pt_valid = false;   // (the kept covariance tables cover the sub-tiles THIS ring needs)
     return 0;
 }
 
@@ -863,7 +874,7 @@ int cnmfe_ring_set_values(cnmfe_ctx *ctx, int patch_id, const float *val) {
     CK(hipMemcpyAsync(P->W.p, W.data(), W.size() * sizeof(float), hipMemcpyHostToDevice, ctx->st()));
     CK(hipStreamSynchronize(ctx->st()));
     P->stat_valid = false;
-    P->ysig_valid = false;
+    P->residual.invalidate();
     return 0;
 }
 
@@ -899,7 +910,7 @@ int cnmfe_b0_set(cnmfe_ctx *ctx, int patch_id, const float *b0) {
     for (int64_t i = 0; i < P->d; ++i) tmp[i] = (double)b0[i];
     CK(hipMemcpyAsync(P->b0.p, tmp.data(), P->d * sizeof(double), hipMemcpyHostToDevice, ctx->st()));
     CK(hipStreamSynchronize(ctx->st()));
-    P->ysig_valid = false;
+    P->residual.invalidate();
     return 0;
 }
 
@@ -946,7 +957,7 @@ int cnmfe_fit_ring_model(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64_t 
     RET(ensure_ymean(ctx, P));
     int64_t dummy[4];
     int rc = bg_fit_ring(ctx, P, K, A_colptr, A_rowidx, A_val, C, c_order, with_projection, b0_out, info ? info : dummy, 0, thresh_outlier);
-    P->ysig_valid = false;
+    P->residual.invalidate();
     return rc;
 }
 
@@ -987,7 +998,7 @@ int cnmfe_get_sn(cnmfe_ctx *ctx, int patch_id, float *sn_out) {
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
     Patch *P = get_patch(ctx, patch_id);
     if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
-    if (!P->ysig_valid) return fail(CNMFE_ESTATE, "cnmfe_residual has not been run for patch %d", patch_id);
+    RET(require_residual(P, patch_id));
     RET(residual_materialize(ctx, P));                       // a pending footprint term must be in Ysig for this consumer
     if (!sn_out) return fail(CNMFE_EINVAL, "null sn_out");
     CK(hipSetDevice(ctx->device));
@@ -1061,7 +1072,7 @@ int cnmfe_peel_open_residual(cnmfe_ctx *ctx, int patch_id, int32_t Ksel, const i
     if (P->derived) return fail(CNMFE_EUNSUPPORTED, "a peel session of a derived (bg_ssub) patch is not built: patch %d", patch_id);
     if (psf_n > 0 && (psf_n % 2 == 0 || psf_n > 25)) return fail(CNMFE_EUNSUPPORTED, "seed images: the filter must be odd-sized and at most 25 x 25 (got %d; pad an even kernel)", psf_n);
     if (P->T < 64 || P->T > 20400) return fail(CNMFE_EUNSUPPORTED, "seed images support 64 <= nframes <= 20400 (the residual session reads all %lld frames)", (long long)P->T);
-    if (!P->ysig_valid) return fail(CNMFE_ESTATE, "cnmfe_residual has not been run for patch %d", patch_id);
+    RET(require_residual(P, patch_id));
     if (P->peel) return fail(CNMFE_ESTATE, "patch %d already has an open peel session", patch_id);
     RET(check_csc("A", Ksel, P->d, A_colptr, A_rowidx));
     if (Ksel > 0 && ((!A_val && A_colptr[Ksel] > 0) || (!C && c_order != CNMFE_BOUND))) return fail(CNMFE_EINVAL, "null A_val / C");
@@ -1070,7 +1081,7 @@ int cnmfe_peel_open_residual(cnmfe_ctx *ctx, int patch_id, int32_t Ksel, const i
     P->peel = new PeelSession();
     const int rc = peel_open_residual_run(ctx, P, Ksel, A_colptr, A_rowidx, A_val, C, c_order, psf, psf_n, sig, Cn_patch, PNR_patch, Sn_patch, Yres_out, out_memspace);
     // a failed open (CNMFE_ENOMEM ...) has realised the residual all the same: it is dropped as a close would drop it, so that the next update requests its own
-    if (rc != 0) { (void)hipStreamSynchronize(ctx->st()); delete P->peel; P->peel = nullptr; P->ysig_valid = false; }
+    if (rc != 0) { (void)hipStreamSynchronize(ctx->st()); delete P->peel; P->peel = nullptr; P->residual.invalidate(); }
     return rc;
 }
 
@@ -1111,7 +1122,7 @@ int cnmfe_peel_close(cnmfe_ctx *ctx, int patch_id) {
     if (!P->peel) return fail(CNMFE_ESTATE, "patch %d has no open peel session", patch_id);
     CK(hipSetDevice(ctx->device));
     CK(hipStreamSynchronize(ctx->st()));
-    if (P->peel->residual) P->ysig_valid = false;            // the residual was requested for the session and goes with it
+    if (P->peel->residual) P->residual.invalidate();            // the residual was requested for the session and goes with it
     delete P->peel; P->peel = nullptr;
     return 0;
 }
@@ -1122,7 +1133,7 @@ int cnmfe_update_spatial(cnmfe_ctx *ctx, int patch_id, int algorithm, int32_t K,
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
     Patch *P = get_patch(ctx, patch_id);
     if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
-    if (!P->ysig_valid) return fail(CNMFE_ESTATE, "cnmfe_residual has not been run for patch %d", patch_id);
+    RET(require_residual(P, patch_id));
     // (a pending footprint term enters through the projection, spatial_run; only a term that cannot is folded into Ysig first)
     if (algorithm < CNMFE_SPATIAL_HALS || algorithm > CNMFE_SPATIAL_NNLS) return fail(CNMFE_EINVAL, "unknown spatial algorithm %d", algorithm);
     if (K <= 0) return fail(CNMFE_EINVAL, "K=%d", K);
@@ -1243,7 +1254,7 @@ int cnmfe_hals_temporal(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64_t *
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
     Patch *P = get_patch(ctx, patch_id);
     if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
-    if (!P->ysig_valid) return fail(CNMFE_ESTATE, "cnmfe_residual has not been run for patch %d", patch_id);
+    RET(require_residual(P, patch_id));
     if (K <= 0) return fail(CNMFE_EINVAL, "K=%d", K);
     RET(check_csc("A", K, P->d, A_colptr, A_rowidx));
     if ((!A_val && A_colptr[K] > 0) || (!C_in && c_order != CNMFE_BOUND)) return fail(CNMFE_EINVAL, "null A_val / C_in");   // all-zero columns are legal: aa = 0, row left alone (HALS_temporal.m:51)
@@ -1258,7 +1269,7 @@ int cnmfe_hals_temporal_deconv(cnmfe_ctx *ctx, int patch_id, int32_t K, const in
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
     Patch *P = get_patch(ctx, patch_id);
     if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
-    if (!P->ysig_valid) return fail(CNMFE_ESTATE, "cnmfe_residual has not been run for patch %d", patch_id);
+    RET(require_residual(P, patch_id));
     if (K <= 0) return fail(CNMFE_EINVAL, "K=%d", K);
     RET(check_csc("A", K, P->d, A_colptr, A_rowidx));
     if ((!A_val && A_colptr[K] > 0) || (!C_in && c_order != CNMFE_BOUND) || !opts || !kernel_pars) return fail(CNMFE_EINVAL, "null A_val / C_in / opts / kernel_pars");
@@ -1272,7 +1283,7 @@ int cnmfe_fast_temporal(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64_t *
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
     Patch *P = get_patch(ctx, patch_id);
     if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
-    if (!P->ysig_valid) return fail(CNMFE_ESTATE, "cnmfe_residual has not been run for patch %d", patch_id);
+    RET(require_residual(P, patch_id));
     RET(residual_materialize(ctx, P));                       // a pending footprint term must be in Ysig for this consumer
     if (K <= 0) return fail(CNMFE_EINVAL, "K=%d", K);
     RET(check_csc("A", K, P->d, A_colptr, A_rowidx));
@@ -1286,8 +1297,7 @@ int cnmfe_compute_rss(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64_t *A_
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
     Patch *P = get_patch(ctx, patch_id);
     if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
-    if (!P->ysig_valid) return fail(CNMFE_ESTATE, "cnmfe_residual has not been run for patch %d", patch_id);
-    if (P->res_kind != 1) return fail(CNMFE_EUNSUPPORTED, "compute_RSS needs the residual of cnmfe_residual (bg_ssub = 1)");
+    RET(require_residual_full(P, patch_id, "compute_RSS"));
     if (K < 0 || !b0_block || !b0_new || !rss_out) return fail(CNMFE_EINVAL, "bad K / null b0_block / b0_new / rss_out");
     if (K > 0) {
         RET(check_csc("A", K, P->d, A_colptr, A_rowidx));
@@ -1302,8 +1312,7 @@ int cnmfe_reconstruct_background(cnmfe_ctx *ctx, int patch_id, const float *b0_b
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
     Patch *P = get_patch(ctx, patch_id);
     if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
-    if (!P->ysig_valid) return fail(CNMFE_ESTATE, "cnmfe_residual has not been run for patch %d", patch_id);
-    if (P->res_kind != 1) return fail(CNMFE_EUNSUPPORTED, "reconstruct_background needs the residual of cnmfe_residual (bg_ssub = 1)");
+    RET(require_residual_full(P, patch_id, "reconstruct_background"));
     if (!b0_block || !b0_new || !Ybg_out) return fail(CNMFE_EINVAL, "null b0_block / b0_new / Ybg_out");
     if (frame0 < 0 || nframes <= 0 || frame0 + nframes > P->T || nframes > 65535) return fail(CNMFE_EINVAL, "frames [%lld, %lld) outside [0, %lld) or more than 65535 at once", (long long)frame0, (long long)(frame0 + nframes), (long long)P->T);
     CK(hipSetDevice(ctx->device));
@@ -1329,7 +1338,7 @@ int cnmfe_hals_temporal_job(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64
     if (!ctx || !job_out) return fail(CNMFE_EINVAL, "null context / job_out");
     Patch *P = get_patch(ctx, patch_id);
     if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
-    if (!P->ysig_valid) return fail(CNMFE_ESTATE, "cnmfe_residual has not been run for patch %d", patch_id);
+    RET(require_residual(P, patch_id));
     if (!ctx->stitch_open) return fail(CNMFE_ESTATE, "cnmfe_stitch_begin has not been called (it opens a round of temporal jobs)");
     if (K <= 0) return fail(CNMFE_EINVAL, "K=%d", K);
     RET(check_csc("A", K, P->d, A_colptr, A_rowidx));

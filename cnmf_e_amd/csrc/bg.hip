@@ -1280,7 +1280,7 @@ int bg_fit_ring(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, co
         RET(fit_upload_csr(f));                               // bg_ssub > 1: b0 = mean(Y - A*C, 2) on the patch (update_background_parallel.m:222-223)
         // (no drain: every upload above went through the pinned arena -- or, too large for it, waited itself -- and what reads b0 is stream-ordered behind this)
         RET(fit_b0(f, bg_geom(P)));
-        P->ysig_valid = false;
+        P->residual.invalidate();
         return 0;
     }
     RET(fit_geometry(f, with_projection));
@@ -1313,7 +1313,7 @@ int bg_fit_ring(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, co
     }
     // without b0_out the call returns with the fit in flight (every later engine call is stream-ordered behind it)
     if (info) { info[0] = f.first_run ? 1 : 0; info[1] = f.kstride; info[2] = f.nactive; info[3] = f.pmax; }
-    P->ysig_valid = false;
+    P->residual.invalidate();
     return 0;
 }
 

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include "../../include/cnmfe.h"
 #include "ring_plan.hpp"
+#include "residual_plan.hpp"
 
 namespace cnmfe {
 
@@ -142,6 +143,38 @@ struct PeelSession { DevBuf hy, yw, sn, q, ci, scr; int64_t n = 0, nq = 0; int M
 // the video a seed / peel pass reads: [ceil(n / 4)][d] float4, nr x nc pixels column-major
 struct SeedSrc { const float4 *y4; int64_t d; int nr, nc; };
 
+// ---- the residual of a patch: what lies beside Ysig (the rules that move it: residual_plan.hpp; DESIGN.md, "Residual state") ------
+// The footprint term (W A)(C - mean C) as kept beside Ysig: ELL rows of W A per patch pixel (cnt | k | v), the centred traces (cc, K rows of stride ldc) and the
+// means they were centred about (cm, fp64).  ac: the term has footprints at all (else the buffers are not read).
+struct FootTerm {
+    bool ac = false; int64_t ldc = 0; int32_t K = 0;
+    DevBuf cnt, k, v, cc, cm;
+    void set(bool ac_, int64_t ldc_, int32_t K_) { ac = ac_; ldc = ldc_; K = K_; }
+    // the term a call has just built in the context's scratch moves here, what lay here goes back as scratch: buffers change hands, none is allocated or freed
+    void take(bool ac_, int64_t ldc_, int32_t K_, DevBuf &cnt_, DevBuf &k_, DevBuf &v_, DevBuf &cc_, DevBuf &cm_) {
+        set(ac_, ldc_, K_);
+        if (ac_) { cnt.swap(cnt_); k.swap(k_); v.swap(v_); cc.swap(cc_); cm.swap(cm_); }
+    }
+    void swap(FootTerm &o) { std::swap(ac, o.ac); std::swap(ldc, o.ldc); std::swap(K, o.K); cnt.swap(o.cnt); k.swap(o.k); v.swap(o.v); cc.swap(o.cc); cm.swap(o.cm); }
+    rplan::TermView view() const { return {ac, ldc, K}; }
+};
+// Ysig of a patch is in one of three forms.  NONE: nothing valid (the video, W or b0 changed: invalidate()).  VIRTUAL: a request is recorded and no sweep has run --
+// the two updates take Ysig C' and A' Ysig from the centred video (vproj.hip), whoever reads Ysig itself calls residual_realize first.  RESIDENT: Patch::ysig holds
+// Ysig with the `applied` term in it.  In both valid forms a further term may be `pending`: the residual the caller asked for is Ysig - applied + pending; the updates
+// add that difference through their projections (residual_term_project / residual_term_fold_spatial), every other reader folds it in (residual_materialize).
+// residual_run / ssub_residual move NONE -> VIRTUAL | RESIDENT, residual_realize VIRTUAL -> RESIDENT, residual_materialize pending -> applied.
+struct ResidualState {
+    rplan::Form form = rplan::NONE;
+    int source = rplan::SRC_NONE;      // who wrote it: 1 = cnmfe_residual, 2 = cnmfe_residual_ssub (compute_RSS / reconstruct_background serve 1 only)
+    int64_t gen = 0;                   // counts the requests of this patch: what a projection queued ahead of its consumer is valid for
+    bool has_pending = false;
+    FootTerm applied, pending;
+    bool valid() const { return form != rplan::NONE; }
+    bool is_virtual() const { return form == rplan::VIRTUAL; }
+    void invalidate() { form = rplan::NONE; source = rplan::SRC_NONE; has_pending = false; applied.ac = false; }      // frees nothing; gen keeps counting
+    rplan::TermsView terms() const { return {has_pending, applied.view(), pending.view()}; }
+};
+
 // ---- per-patch resident state ----------------------------------------------------
 struct Patch {
     int32_t prect[4], brect[4];        // 1-based inclusive [r0 r1 c0 c1]
@@ -166,29 +199,14 @@ struct Patch {
     bool ring_ready = false;
     DevBuf sn_b;                       // d_b fp32 noise levels of the block pixels (cnmfe_set_noise): only the outlier branch of the ring fit reads them
     bool sn_ready = false;
-    // the background-subtracted video of this patch, Ysig4[ceil(T/4)][d] float4, as left by the last cnmfe_residual; valid until the
-    // video, W or b0 change.  It stays resident per patch: a further cnmfe_residual under the same W, b0 differs from it only by the
-    // footprint term (W*A)(C - mean C), whose applied instance is kept beside it (ELL rows + centred traces) -- see residual_run
-    DevBuf ysig;
-    bool ysig_valid = false;
-    // sweep-free ("virtual") residual, round 4: nothing between two background fits needs Ysig itself, only its projections.  After a fit cnmfe_residual only
-    // RECORDS the request (ysig_valid and ysig_virtual set, the footprint term pending as before): the spatial update takes Ysig C' out of the table
-    // P = Yc Cc' below (U = P - W P, vproj.hip), the temporal update projects the centred video through B = A - W'A.  Whoever needs Ysig itself (GetSn,
-    // compute_RSS, an export, fast_temporal ...) calls residual_realize first, which runs the sweep.
-    bool ysig_virtual = false;
+    DevBuf ysig;                       // Ysig4[ceil(T/4)][d] float4, the background-subtracted video of this patch where it is resident; `residual` says what it holds
+    ResidualState residual;
     // P(j,k) = sum_t Yc_j(t) Cc_k(t) in fp64 per 16x16 block of the block region and list slot: pt_tab[(pt_lp[b] + slot) * 256 + lp_of(pixel)], pt_slot[b * pt_K + k]
     // = slot or -1.  The ring fit's window projection computes exactly this (all frames, the same centred traces) and leaves it here; otherwise the
     // spatial update builds it.  Columns are rows pt_rows[] of the bound trace matrix of generation pt_gen (-1: some other matrix -- not reusable).
     DevBuf pt_tab, pt_lp, pt_slot;
     bool pt_valid = false; int32_t pt_K = 0; int64_t pt_gen = -1;
     std::vector<int32_t> pt_rows; std::vector<int> pt_lp_h; std::vector<short> pt_slot_h;
-    int64_t res_gen = 0;               // counts the residual requests of this patch (residual_run, ssub_residual): what a projection queued ahead of its consumer is valid for
-    bool res_ac = false; int res_kind = 0; int64_t res_ldc = 0;    // res_kind: who wrote Ysig and the term beside it: 1 = cnmfe_residual, 2 = cnmfe_residual_ssub (0: no term kept)
-    DevBuf resCnt, resK, resV, resCc, resCm;              // resCm: the means the centred traces were taken about (fp64, per trace)
-    // a footprint term asked for by the last cnmfe_residual but not yet folded into Ysig: cnmfe_hals_temporal only needs A' Ysig and adds
-    // A' (W A)(C - mean C) algebraically (factor.hip), every other consumer calls residual_materialize first
-    bool pend = false, pend_ac = false; int64_t pend_ldc = 0; int32_t pend_K = 0, res_K = 0;
-    DevBuf pendCnt, pendK, pendV, pendCc, pendCm;
     // incremental ring regression (bg.hip): the block-pair covariance table and row sums of the centred VIDEO (no footprints subtracted),
     // valid for one frame stride until the video changes
     DevBuf cov_base, rowsum_base;
@@ -222,7 +240,7 @@ struct Patch {
     DevBuf dig, dig_sc; int64_t dig_T16 = 0; bool dig_valid = false;
     DevBuf yt4; bool yt4_valid = false;                   // vproj.hip: the centred video tiled by 16 x 16 block (k_tile_video), for the temporal projection
     DevBuf digp; bool digp_valid = false;                 // vproj_i8.hpp: the digit planes once more, pixel-major (k_dig_pixmajor), for the temporal projection on the int8 pipe
-    // bg_ssub > 1 (ssub.hip, round 5: the sweep-free residual of res_kind 2): the low-resolution residual patch and the factor of the last cnmfe_residual_ssub, and
+    // bg_ssub > 1 (ssub.hip, round 5: the sweep-free residual of source 2): the low-resolution residual patch and the factor of the last cnmfe_residual_ssub, and
     // imresize's bicubic UPSAMPLING taps of the block region's rows / columns (low-resolution index + weight, ss_Pr / ss_Pc per row / column) on the host and the
     // device, their ranges per row / column (made monotone: ss_rlo[r] <= every tap index of the rows >= r, ss_rhi[r] >= those of the rows <= r), and the
     // TRANSPOSED taps (per low-resolution row / column the block-region rows / columns it feeds, CSR) for up' A of the temporal projection
@@ -384,7 +402,7 @@ struct cnmfe_ctx {
     // for; temporal_run takes it only when the caller claimed the token (its A IS that spatial result) and every field still holds, and drops it otherwise.
     struct EarlyU {
         bool valid = false; int64_t token = 0, claimed = 0;
-        cnmfe::Patch *P = nullptr; int32_t K = 0; int64_t ldc = 0, T = 0, spatial_gen = 0, res_gen = 0;      // res_gen: W, b0 and the video only change in front of a new residual request
+        cnmfe::Patch *P = nullptr; int32_t K = 0; int64_t ldc = 0, T = 0, spatial_gen = 0, request_gen = 0;      // request_gen (ResidualState::gen): W, b0 and the video only change in front of a new residual request
         int64_t proj_i8 = 0, proj_i8_planes = 0, proj_tiled = 0;                                             // the options that select the projection kernel
     } early;
     cnmfe::DevBuf early_a, early_u;
@@ -394,9 +412,9 @@ struct cnmfe_ctx {
     int64_t early_seq = 0, early_hits = 0, early_drops = 0, early_declined = 0, early_nent = 0, sweep_nowait = 0;   // counters (cnmfe_get_option)
     std::vector<cnmfe::TemporalJob *> tjobs; int tjobs_used = 0;          // cnmfe_hals_temporal_job: kept (with their buffers) from update to update, counted from cnmfe_stitch_begin
     cnmfe::DevBuf dcv_c, dcv_s, dcv_pars, dcv_sn;          // cnmfe_deconv_temporal_bound: C_raw - b (after the swap with `bound`), S, kernel_pars, sn -- read by the copy stream, so not shared scratch
-    // merging (merge.hpp): dcv_c / dcv_s / dcv_pars / dcv_sn are the C_raw, S, kernel_pars, sn that belong to the bound matrix C while res_gen == bound_gen
+    // merging (merge.hpp): dcv_c / dcv_s / dcv_pars / dcv_sn are the C_raw, S, kernel_pars, sn that belong to the bound matrix C while residents_gen == bound_gen
     // (cnmfe_deconv_temporal_bound, cnmfe_traces_load, cnmfe_merge_apply set it; every other change of the bound matrix' content leaves it behind)
-    int64_t res_gen = -1; bool res_has_s = false;
+    int64_t residents_gen = -1; bool res_has_s = false;
     cnmfe::DevBuf mrg[23];                                 // [0] an uploaded source, [1] the result of cnmfe_trace_diff_spikes (diff_K x diff_T), [2..5] moments / K x K / sn, [6..22] cnmfe_merge_apply
     int32_t diff_K = 0; int64_t diff_T = 0;
     int64_t merge_uploads = 0;                             // counter merge_trace_uploads: K x T matrices the merge / tag entry points took from the host
@@ -485,7 +503,8 @@ int rss_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, const 
             const float *b0_block, const float *b0_new, double *rss_out);
 int bg_reconstruct_run(cnmfe_ctx *ctx, Patch *P, const float *b0_block, const float *b0_new, int64_t frame0, int64_t nframes, float *out, int out_memspace);
 int residual_materialize(cnmfe_ctx *ctx, Patch *P);       // fold a pending footprint term into the resident Ysig (no-op without one); realizes a virtual residual first
-int residual_realize(cnmfe_ctx *ctx, Patch *P);           // a virtual residual (Patch::ysig_virtual) becomes a resident one: the ring sweep runs now (no-op otherwise)
+rplan::ResidualOpts residual_opts(cnmfe_ctx *ctx);        // resid.hip: the residual's options with their defaults -- the one place that names them
+int residual_realize(cnmfe_ctx *ctx, Patch *P);           // a VIRTUAL residual (ResidualState) becomes a resident one: the ring sweep runs now (no-op otherwise)
 // rows of the bound trace matrix a (C, c_order) argument names: false when it is some other matrix
 bool bound_rows_of(const cnmfe_ctx *ctx, const float *C, int c_order, int32_t K, std::vector<int32_t> &rows);
 // vproj.hip -- the projections of a virtual residual.  Return 1 when they cannot serve the request (the caller realizes the residual and projects Ysig).
@@ -494,15 +513,14 @@ int vproj_spatial(cnmfe_ctx *ctx, Patch *P, int32_t K, const float *C, int c_ord
                   const int *dErow, const int *dEcol, const float *dCc, int64_t ldc, float *dU, double *dQ = nullptr);
 int vproj_temporal(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
                    const int64_t *dColptr, const int *dErow, const float *dAval, float *dU, int64_t ldu);
-// the same for a residual of cnmfe_residual_ssub (res_kind 2): through the resampling maps, DESIGN.md section 3 bg_ssub
+// the same for a residual of cnmfe_residual_ssub (source 2): through the resampling maps, DESIGN.md section 3 bg_ssub
 int vproj_spatial_ssub(cnmfe_ctx *ctx, Patch *M, int32_t K, const float *C, int c_order, const int64_t *IND_colptr, const int32_t *IND_rowidx,
                        const int *dErow, const int *dEcol, const float *dCc, int64_t ldc, float *dU);
 int vproj_temporal_ssub(cnmfe_ctx *ctx, Patch *M, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
                         const int64_t *dColptr, const int *dErow, const float *dAval, float *dU, int64_t ldu);
 int ssub_taps(cnmfe_ctx *ctx, Patch *M, const Patch *R);  // ssub.hip: the upsampling taps of M's block region from R's grid, host + device (once per patch)
-int ssub_realize(cnmfe_ctx *ctx, Patch *M);               // ssub.hip: the low-resolution sweep + upsample behind a virtual residual of res_kind 2
+int ssub_realize(cnmfe_ctx *ctx, Patch *M);               // ssub.hip: the low-resolution sweep + upsample behind a virtual residual of source 2
 int residual_term_project(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *dColptr, const int *dErow, const float *dAval, float *dU, int64_t ldu, int *dOverflow);   // 1: cannot be applied, materialise instead; *dOverflow set on the device if a footprint meets > 512 traces
-bool residual_term_foldable_spatial(const Patch *P, int32_t K, int64_t ldc);   // the pending term can enter the spatial update through its projection (no pass over Ysig)
 int residual_term_fold_spatial(cnmfe_ctx *ctx, Patch *P, int32_t K, int64_t nnz, const int *dErow, const int *dEcol, const float *dCc, int64_t ldc, float *dU, DevBuf &dG);
 int check_csc_pub(const char *what, int32_t ncol, int64_t nrow, const int64_t *colptr, const int32_t *rowidx);
 int spatial_run(cnmfe_ctx *ctx, Patch *P, int algorithm, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx,

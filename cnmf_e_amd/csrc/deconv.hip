@@ -1205,7 +1205,7 @@ int deconv_bound_run(cnmfe_ctx *ctx, const cnmfe_deconv_opts *opts, float *C_out
         RET(deconv_launch(ctx, c, shmem, io, dList.as<int>() + k0, std::min(batch, K - k0), ctx->dscr));
     ctx->bound.swap(dC); ++ctx->bound_gen;                  // bound = C (row-major), dcv_c = C_raw - b
     ctx->bound_order = CNMFE_ROWMAJOR;
-    ctx->res_gen = ctx->bound_gen; ctx->res_has_s = true;   // (merge.hpp: dcv_* belong to this bound matrix)
+    ctx->residents_gen = ctx->bound_gen; ctx->res_has_s = true;   // (merge.hpp: dcv_* belong to this bound matrix)
     if (C_out || C_raw_out || S_out || pars_out || sn_out) {
         if (!ctx->copy_stream) {
             CK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));

@@ -535,7 +535,7 @@ int spatial_run(cnmfe_ctx *ctx, Patch *P, int algorithm, int32_t K, const int64_
     HostTrace ht(ctx, "spatial");
     int64_t ldc;
     RET(upload_centered(ctx, dC, C, K, T, c_order, dCc, dCm, &ldc));
-    if (P->pend && !residual_term_foldable_spatial(P, K, ldc)) RET(residual_materialize(ctx, P));    // (a term that cannot enter through the projection below)
+    if (!rplan::term_foldable_spatial(P->residual.terms(), K, ldc)) RET(residual_materialize(ctx, P));    // (a term that cannot enter through the projection below)
     // A restricted to the IND pattern (A(~active_pixel) = 0, HALS_spatial.m:26); NNLS starts from 0 (:32)
     std::vector<float> aval(nnz, 0.f);
     std::vector<int32_t> ecol(nnz);
@@ -576,9 +576,9 @@ int spatial_run(cnmfe_ctx *ctx, Patch *P, int algorithm, int32_t K, const int64_
     ht.mark("buffers");
     // a virtual residual (no sweep has run, resid.hip): U = P - W P out of the table P = Yc Cc' (vproj.hip); if that path cannot serve this update the sweep
     // runs now and Ysig is projected as before
-    bool virt = P->ysig_virtual;
+    bool virt = P->residual.is_virtual();
     if (virt) {
-        const int rcv = P->res_kind == 2 ? vproj_spatial_ssub(ctx, P, K, C, c_order, IND_colptr, IND_rowidx, dErow.as<int>(), dEcol.as<int>(), dCc.as<float>(), ldc, dU.as<float>())
+        const int rcv = P->residual.source == rplan::SRC_SSUB ? vproj_spatial_ssub(ctx, P, K, C, c_order, IND_colptr, IND_rowidx, dErow.as<int>(), dEcol.as<int>(), dCc.as<float>(), ldc, dU.as<float>())
                                          : vproj_spatial(ctx, P, K, C, c_order, IND_colptr, IND_rowidx, dErow.as<int>(), dEcol.as<int>(), dCc.as<float>(), ldc, dU.as<float>());
         if (rcv < 0) return rcv;
         if (rcv > 0) { RET(residual_realize(ctx, P)); virt = false; }
@@ -722,8 +722,8 @@ int temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, c
         cnmfe_ctx::EarlyU &E = ctx->early;
         if (E.valid) {
             early_hit = (te_mode == 1 || te_mode == 2) && E.claimed == E.token && E.P == P && E.K == K && E.ldc == ldc && E.T == T && E.spatial_gen == ctx->spatial_gen
-                        && E.res_gen == P->res_gen && nnz > 0 && P->ysig_virtual && P->res_kind == 1 && ctx->lanes.empty()
-                        && !(P->pend && (P->pend_ldc != ldc || (P->res_ac && P->res_ldc != ldc)))                       // (the term would be folded into Ysig below: no virtual residual then)
+                        && E.request_gen == P->residual.gen && nnz > 0 && P->residual.is_virtual() && P->residual.source == rplan::SRC_FULL && ctx->lanes.empty()
+                        && rplan::terms_match_stride(P->residual.terms(), ldc)                                          // (the term would be folded into Ysig below: no virtual residual then)
                         && E.proj_i8 == ctx->opt("proj_i8", 1) && E.proj_i8_planes == ctx->opt("proj_i8_planes", 3) && E.proj_tiled == ctx->opt("proj_tiled", 1);
             E.valid = false;                                 // consumed either way
             ++(early_hit ? ctx->early_hits : ctx->early_drops);
@@ -752,11 +752,11 @@ int temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, c
     };
     if (nnz > 0) {
         // a footprint term still pending on the residual enters through A' (W A)(C - mean C); if it cannot, it is folded into Ysig first
-        if (P->pend && (P->pend_ldc != ldc || (P->res_ac && P->res_ldc != ldc))) RET(residual_materialize(ctx, P));
+        if (!rplan::terms_match_stride(P->residual.terms(), ldc)) RET(residual_materialize(ctx, P));
         // a virtual residual: A' Ysig = B' Yc + A' (Ymean - b0), B = A - W'A, one block-tiled pass over the centred video (vproj.hip)
-        bool virt = P->ysig_virtual;
+        bool virt = P->residual.is_virtual();
         if (virt && !early_hit) {
-            const int rcv = P->res_kind == 2 ? vproj_temporal_ssub(ctx, P, K, A_colptr, A_rowidx, A_val, dColptr.as<int64_t>(), dErow.as<int>(), dAval.as<float>(), dU.as<float>(), ldc)
+            const int rcv = P->residual.source == rplan::SRC_SSUB ? vproj_temporal_ssub(ctx, P, K, A_colptr, A_rowidx, A_val, dColptr.as<int64_t>(), dErow.as<int>(), dAval.as<float>(), dU.as<float>(), ldc)
                                              : vproj_temporal(ctx, P, K, A_colptr, A_rowidx, A_val, dColptr.as<int64_t>(), dErow.as<int>(), dAval.as<float>(), dU.as<float>(), ldc);
             if (rcv < 0) return rcv;
             if (rcv > 0) { RET(residual_realize(ctx, P)); virt = false; }
@@ -769,7 +769,7 @@ int temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, c
         const int rc_ = residual_term_project(ctx, P, K, dColptr.as<int64_t>(), dErow.as<int>(), dAval.as<float>(), dU.as<float>(), ldc, dOvf.as<int>());
         if (rc_ < 0) return rc_;
         if (rc_ > 0) RET(reproject());
-        else term_applied = P->pend;
+        else term_applied = P->residual.has_pending;
     }
     ht.mark(early_hit ? "uploads (projection queued ahead)" : "uploads + projection launch");
     // T2: overlap graph + V values (neighbour lists include k itself: V(k,k) = aa(k))
@@ -833,9 +833,9 @@ int temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, c
     }
     // No host wait in front of the levels (temporal_early 1 or 3, no deconvolution): aa and its test against `upd` are taken on the device (k_aa_gather).  The one
     // thing left that needs a host decision is the overflow word of the term projection: k_term_project lists the traces near a footprint in lst[512] and
-    // raises it when a 513th turns up -- impossible when the term has at most 512 traces (pend_K / res_K), so the wait is kept exactly when a term was
+    // raises it when a 513th turns up -- impossible when the term has at most 512 traces (rplan::TERM_LIST), so the wait is kept exactly when a term was
     // applied that has more
-    const bool ovf_possible = term_applied && ((P->pend_ac && P->pend_K > 512) || (P->res_ac && P->res_K > 512));
+    const bool ovf_possible = term_applied && rplan::term_overflow_possible(P->residual.terms());
     const bool nowait = (te_mode == 1 || te_mode == 3) && !dopts && !ovf_possible;
     std::vector<float> aa(K);
     if (nowait) {
@@ -1014,7 +1014,7 @@ int temporal_early_project(cnmfe_ctx *ctx, int32_t K, const int64_t *IND_colptr,
     // (no virtual residual: also what a spatial update leaves whose own table lists were too long -- they are the lists of the masks grown by the ring, the
     //  very lists built below, so vproj_temporal's own limit of 64 masks over a block is met there first and the residual realised)
     if (!P || ctx->spatial_K != K || nnz == 0 || ctx->spatial_nnz != nnz || ctx->conn_gen != ctx->spatial_gen
-        || P->d != (int64_t)P->d1 * P->d2 || !P->ysig_valid || !P->ysig_virtual || P->res_kind != 1) { ++ctx->early_declined; return 0; }
+        || P->d != (int64_t)P->d1 * P->d2 || !P->residual.is_virtual() || P->residual.source != rplan::SRC_FULL) { ++ctx->early_declined; return 0; }
     HostTrace ht(ctx, "temporal_early");
     const int64_t T = P->T, ldc = (T + 3) & ~int64_t(3);    // (the row stride upload_traces gives the traces of this T)
     DevBuf *S_ = ctx->scr;
@@ -1026,7 +1026,7 @@ int temporal_early_project(cnmfe_ctx *ctx, int32_t K, const int64_t *IND_colptr,
     if (rcv < 0) return rcv;
     if (rcv > 0) { ++ctx->early_declined; return 0; }        // more than 64 masks over one block, too large a partial buffer: the temporal update projects as before
     cnmfe_ctx::EarlyU &E = ctx->early;
-    E.P = P; E.K = K; E.ldc = ldc; E.T = T; E.spatial_gen = ctx->spatial_gen; E.res_gen = P->res_gen;
+    E.P = P; E.K = K; E.ldc = ldc; E.T = T; E.spatial_gen = ctx->spatial_gen; E.request_gen = P->residual.gen;
     E.proj_i8 = ctx->opt("proj_i8", 1); E.proj_i8_planes = ctx->opt("proj_i8_planes", 3); E.proj_tiled = ctx->opt("proj_tiled", 1);
     E.token = ++ctx->early_seq; E.claimed = 0; E.valid = true;
     ctx->early_nent = ctx->last_nent;

@@ -168,7 +168,7 @@ static int welch_cfg(int64_t T, DeconvCfg &c, size_t &shmem) {
     return 0;
 }
 
-static bool residents_valid(const cnmfe_ctx *ctx) { return ctx->bound_valid && ctx->res_gen == ctx->bound_gen; }
+static bool residents_valid(const cnmfe_ctx *ctx) { return ctx->bound_valid && ctx->residents_gen == ctx->bound_gen; }
 
 // the K x ldc device matrix a (X, src) argument names; host matrices go through mrg[0] and count as an upload
 static int merge_source(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, const float **dX) {
@@ -261,7 +261,7 @@ int traces_load_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *C, const 
     if (pars) CK(hipMemcpyAsync(ctx->dcv_pars.p, pars, (size_t)K * 4, hipMemcpyHostToDevice, ctx->st()));
     CK(hipStreamSynchronize(ctx->st()));
     ctx->bound_K = K; ctx->bound_T = T; ctx->bound_order = c_order; ctx->bound_valid = true;
-    ctx->res_gen = ctx->bound_gen; ctx->res_has_s = S != nullptr;
+    ctx->residents_gen = ctx->bound_gen; ctx->res_has_s = S != nullptr;
     return 0;
 }
 
@@ -322,7 +322,7 @@ int merge_apply_run(cnmfe_ctx *ctx, int32_t ng, const int32_t *gptr, const int32
     ctx->bound.swap(nC); ctx->dcv_c.swap(nR); ctx->dcv_s.swap(nS); ctx->dcv_pars.swap(nPars); ctx->dcv_sn.swap(nSn);
     ++ctx->bound_gen;
     ctx->bound_K = nkeep; ctx->bound_order = CNMFE_ROWMAJOR; ctx->bound_valid = nkeep > 0;
-    ctx->res_gen = ctx->bound_gen; ctx->diff_K = 0;
+    ctx->residents_gen = ctx->bound_gen; ctx->diff_K = 0;
     if (nkeep > 0) {
         const size_t rb = (size_t)T * 4, pb = (size_t)ldc * 4;
         if (C_out) CK(hipMemcpy2DAsync(C_out, rb, ctx->bound.p, pb, rb, nkeep, hipMemcpyDeviceToHost, ctx->st()));

@@ -689,10 +689,14 @@ static int launch_r1_v(cnmfe_ctx *ctx, int variant, const R1Args &a, bool has_ac
     return launch_r1_dma<R, 32, 16>(ctx, a, has_ac, grid);
 }
 
-static void tile_shape(int variant, int &TR, int &TC) {
-    TR = 32; TC = 16;                                     // variant 10
-    if (variant == 11) { TR = ARC_TR; TC = ARC_TC; }
-    else if (variant == 14) { TR = DUO_T; TC = DUO_T; }
+static_assert(rplan::R1_ARC_TR == ARC_TR && rplan::R1_ARC_TC == ARC_TC && rplan::R1_DUO_T == DUO_T, "residual_plan.hpp: tile shapes of the sweep's kernels");
+
+// the residual's options with their defaults (include/cnmfe.h, cnmfe_set_option): read here and nowhere else
+rplan::ResidualOpts residual_opts(cnmfe_ctx *ctx) {
+    rplan::ResidualOpts o;
+    o.delta = ctx->opt("r1_delta", 1); o.lazy = ctx->opt("r1_lazy", 1); o.defer = ctx->opt("r1_defer", 1); o.virt = ctx->opt("r1_virtual", 1);
+    o.ssub_virtual = ctx->opt("ssub_virtual", 1); o.variant = ctx->opt("r1_variant", 14); o.probe = ctx->opt("r1_probe", 0);
+    return o;
 }
 
 // the ABI hands Ysig out frame-major (d x T column-major); resident it is 4-frame interleaved
@@ -711,31 +715,33 @@ int ysig_export(cnmfe_ctx *ctx, Patch *P, DevBuf &ysig, float *Ysig_out, int out
 // Ysig += (pending term) - (applied term); the pending term becomes the applied one
 int residual_materialize(cnmfe_ctx *ctx, Patch *P) {
     RET(residual_realize(ctx, P));                           // a virtual residual: the sweep runs now (every caller is about to read Ysig itself)
-    if (!P->pend) return 0;
-    if (!P->ysig_valid || !P->ysig.p) return fail(CNMFE_ESTATE, "pending footprint term without a resident residual");
-    if (P->pend_ac || P->res_ac) {
+    ResidualState &rs = P->residual;
+    // (a caller without a validity test of its own -- temporal_sweep_jobs, behind an invalidation between the job and its sweep -- must not go on to read Ysig)
+    if (!rs.valid() || (rs.has_pending && !P->ysig.p)) return fail(CNMFE_ESTATE, "pending footprint term without a resident residual");
+    if (!rs.has_pending) return 0;
+    const FootTerm &pe = rs.pending, &ap = rs.applied;
+    if (pe.ac || ap.ac) {
         const int64_t nblk = (P->d + 255) / 256;
         int64_t nseg = std::max<int64_t>(1, std::min<int64_t>(P->Tc, (8192 + nblk - 1) / nblk));
         const int64_t cseg = (P->Tc + nseg - 1) / nseg;
         nseg = (P->Tc + cseg - 1) / cseg;
         const dim3 grid((unsigned)nblk, (unsigned)nseg);
-#define DELTA_ARGS P->ysig.as<float4>(), P->d, P->Tc, cseg, P->pendCnt.as<int>(), P->pendK.as<int>(), P->pendV.as<float>(), P->pendCc.as<float>(), P->pend_ldc, \
-                   P->resCnt.as<int>(), P->resK.as<int>(), P->resV.as<float>(), P->resCc.as<float>(), P->res_ldc, (int)ctx->opt("r1_probe", 0)
-        if (P->pend_ac && P->res_ac) LAUNCH(ctx, "residual_delta", (k_residual_delta<true, true>), grid, dim3(256), 0, DELTA_ARGS);
-        else if (P->pend_ac)         LAUNCH(ctx, "residual_delta", (k_residual_delta<true, false>), grid, dim3(256), 0, DELTA_ARGS);
-        else                         LAUNCH(ctx, "residual_delta", (k_residual_delta<false, true>), grid, dim3(256), 0, DELTA_ARGS);
+#define DELTA_ARGS P->ysig.as<float4>(), P->d, P->Tc, cseg, pe.cnt.as<int>(), pe.k.as<int>(), pe.v.as<float>(), pe.cc.as<float>(), pe.ldc, \
+                   ap.cnt.as<int>(), ap.k.as<int>(), ap.v.as<float>(), ap.cc.as<float>(), ap.ldc, (int)residual_opts(ctx).probe
+        if (pe.ac && ap.ac) LAUNCH(ctx, "residual_delta", (k_residual_delta<true, true>), grid, dim3(256), 0, DELTA_ARGS);
+        else if (pe.ac)       LAUNCH(ctx, "residual_delta", (k_residual_delta<true, false>), grid, dim3(256), 0, DELTA_ARGS);
+        else                  LAUNCH(ctx, "residual_delta", (k_residual_delta<false, true>), grid, dim3(256), 0, DELTA_ARGS);
 #undef DELTA_ARGS
     }
-    P->res_ac = P->pend_ac; P->res_ldc = P->pend_ldc; P->res_K = P->pend_K;
-    if (P->pend_ac) { P->resCnt.swap(P->pendCnt); P->resK.swap(P->pendK); P->resV.swap(P->pendV); P->resCc.swap(P->pendCc); P->resCm.swap(P->pendCm); }
-    P->pend = false;
+    rs.applied.take(pe.ac, pe.ldc, pe.K, rs.pending.cnt, rs.pending.k, rs.pending.v, rs.pending.cc, rs.pending.cm);
+    rs.has_pending = false;
     return 0;
 }
 
 // U(k,:) += sign * sum_l M(k,l) Cc_l,  M(k,l) = sum_m A(m,k) (W A_term)(m,l): the footprint term of the residual seen through A'.
 // One workgroup per neuron k; deterministic (no floating-point atomics): the traces l that the rings of k's pixels touch are found with a
 // bitmap, listed in ascending order, and each M(k,l) is summed over k's pixels in storage order by one thread.
-constexpr int TERM_KMAX = 8192;
+using rplan::TERM_KMAX;
 __global__ void __launch_bounds__(256) k_term_project(const int64_t *__restrict__ colptr, const int *__restrict__ erow, const float *__restrict__ aval, int64_t d,
                                                       const int *__restrict__ cnt, const int *__restrict__ wk, const float *__restrict__ wv,
                                                       const float *__restrict__ Cc, int64_t ldcc, int Kterm, float sign, float *__restrict__ U, int64_t ldu, int *__restrict__ overflow) {
@@ -803,15 +809,14 @@ __global__ void __launch_bounds__(256) k_term_project(const int64_t *__restrict_
 
 // A' Ysig for the residual the caller asked for: dU holds A' (resident Ysig); add the pending footprint term and take the applied one out
 int residual_term_project(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *dColptr, const int *dErow, const float *dAval, float *dU, int64_t ldu, int *dOverflow) {
-    if (!P->pend) return 0;
-    // more than 512 traces near one footprint, or trace ids beyond the bitmap: fold the term into Ysig instead (the caller re-projects)
-    if ((P->pend_ac && (P->pend_K > TERM_KMAX || P->pend_ldc != ldu)) || (P->res_ac && (P->res_K > TERM_KMAX || P->res_ldc != ldu))) return 1;
-    if (P->pend_ac)
-        LAUNCH(ctx, "temporal_term_project", k_term_project, dim3(K), dim3(256), 0, dColptr, dErow, dAval, P->d, P->pendCnt.as<int>(), P->pendK.as<int>(),
-               P->pendV.as<float>(), P->pendCc.as<float>(), P->pend_ldc, (int)P->pend_K, 1.f, dU, ldu, dOverflow);
-    if (P->res_ac)
-        LAUNCH(ctx, "temporal_term_project", k_term_project, dim3(K), dim3(256), 0, dColptr, dErow, dAval, P->d, P->resCnt.as<int>(), P->resK.as<int>(),
-               P->resV.as<float>(), P->resCc.as<float>(), P->res_ldc, (int)P->res_K, -1.f, dU, ldu, dOverflow);
+    const ResidualState &rs = P->residual;
+    if (!rs.has_pending) return 0;
+    // trace ids beyond the bitmap, or another row stride: fold the term into Ysig instead (the caller re-projects)
+    if (!rplan::term_projectable(rs.terms(), ldu)) return 1;
+    for (const FootTerm *t : {&rs.pending, &rs.applied})
+        if (t->ac)
+            LAUNCH(ctx, "temporal_term_project", k_term_project, dim3(K), dim3(256), 0, dColptr, dErow, dAval, P->d, t->cnt.as<int>(), t->k.as<int>(),
+                   t->v.as<float>(), t->cc.as<float>(), t->ldc, (int)t->K, t == &rs.pending ? 1.f : -1.f, dU, ldu, dOverflow);
     return 0;
 }
 
@@ -844,27 +849,20 @@ __global__ void __launch_bounds__(256) k_term_fold_spatial(const int *__restrict
     for (int j = 0; j < n; ++j) s = fmaf(wv[(int64_t)j * d + m], G[(int64_t)wk[(int64_t)j * d + m] * KB + k], s);
     U[e] += sign * s;
 }
-constexpr int64_t FOLD_MAX_PAIRS = int64_t(1) << 16;
-// can the pending / applied terms of P be taken in through a spatial projection onto K traces with row stride ldc?
-bool residual_term_foldable_spatial(const Patch *P, int32_t K, int64_t ldc) {
-    if (!P->pend) return true;
-    if (P->pend_ac && (P->pend_ldc != ldc || (int64_t)P->pend_K * K > FOLD_MAX_PAIRS)) return false;
-    if (P->res_ac && (P->res_ldc != ldc || (int64_t)P->res_K * K > FOLD_MAX_PAIRS)) return false;
-    return true;
-}
 int residual_term_fold_spatial(cnmfe_ctx *ctx, Patch *P, int32_t K, int64_t nnz, const int *dErow, const int *dEcol, const float *dCc, int64_t ldc, float *dU, DevBuf &dG) {
-    if (!P->pend || nnz == 0) return 0;
+    const ResidualState &rs = P->residual;
+    if (!rs.has_pending || nnz == 0) return 0;
     const int64_t T = P->T;
-    auto one = [&](int Kt, const DevBuf &cnt, const DevBuf &wk, const DevBuf &wv, const DevBuf &cc, float sign) -> int {
-        if (Kt <= 0) return 0;
-        RET(dG.ensure((size_t)Kt * K * sizeof(float)));
-        LAUNCH(ctx, "spatial_term_gram", k_cross_gram, dim3((unsigned)K, (unsigned)Kt), dim3(256), 0, cc.as<float>(), ldc, dCc, ldc, T, (int)K, dG.as<float>());
-        LAUNCH(ctx, "spatial_term_fold", k_term_fold_spatial, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, dErow, dEcol, nnz, P->d, cnt.as<int>(), wk.as<int>(),
-               wv.as<float>(), dG.as<float>(), (int)K, sign, dU);
+    auto one = [&](const FootTerm &t, float sign) -> int {
+        if (!t.ac || t.K <= 0) return 0;
+        RET(dG.ensure((size_t)t.K * K * sizeof(float)));
+        LAUNCH(ctx, "spatial_term_gram", k_cross_gram, dim3((unsigned)K, (unsigned)t.K), dim3(256), 0, t.cc.as<float>(), ldc, dCc, ldc, T, (int)K, dG.as<float>());
+        LAUNCH(ctx, "spatial_term_fold", k_term_fold_spatial, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, dErow, dEcol, nnz, P->d, t.cnt.as<int>(), t.k.as<int>(),
+               t.v.as<float>(), dG.as<float>(), (int)K, sign, dU);
         return 0;
     };
-    if (P->pend_ac) RET(one(P->pend_K, P->pendCnt, P->pendK, P->pendV, P->pendCc, 1.f));
-    if (P->res_ac)  RET(one(P->res_K, P->resCnt, P->resK, P->resV, P->resCc, -1.f));
+    RET(one(rs.pending, 1.f));
+    RET(one(rs.applied, -1.f));
     return 0;
 }
 
@@ -946,6 +944,7 @@ int rss_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, const 
             const float *b0_block, const float *b0_new, double *rss_out) {
     RET(residual_materialize(ctx, P));
     const int64_t T = P->T, d = P->d;
+    const FootTerm &ap = P->residual.applied;
     DevBuf &dC = ctx->tmp[0], &dCnt = ctx->tmp[3], &dK = ctx->tmp[4], &dV = ctx->tmp[5], &dB0b = ctx->tmp[6], &dB0n = ctx->tmp[7], &dKap = ctx->tmp[12], &dPart = ctx->tmp[13];
     const bool has_a = K > 0 && A_colptr[K] > 0;
     int64_t ldc = 4;
@@ -965,7 +964,7 @@ int rss_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, const 
     RET(dKap.ensure((size_t)d * sizeof(float)));
     LAUNCH(ctx, "rss_const", k_rss_const, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, d, P->nr, P->nr_b, P->nc_b, P->roff, P->coff, P->p, P->ring_dr.as<int>(),
            P->ring_dc.as<int>(), P->W.as<float>(), P->ymean_f.as<float>(), P->b0.as<double>(), dB0b.as<float>(), dB0n.as<float>(),
-           P->res_ac ? P->resCnt.as<int>() : nullptr, P->resK.as<int>(), P->resV.as<float>(), P->resCm.as<double>(), dKap.as<float>());
+           ap.ac ? ap.cnt.as<int>() : nullptr, ap.k.as<int>(), ap.v.as<float>(), ap.cm.as<double>(), dKap.as<float>());
     const int64_t nblk = (d + 255) / 256;
     int64_t nseg = std::max<int64_t>(1, std::min<int64_t>(P->Tc, (8192 + nblk - 1) / nblk));
     const int64_t cseg = (P->Tc + nseg - 1) / nseg;
@@ -1000,12 +999,13 @@ __global__ void __launch_bounds__(256) k_bg_out(const float4 *__restrict__ yc4, 
 int bg_reconstruct_run(cnmfe_ctx *ctx, Patch *P, const float *b0_block, const float *b0_new, int64_t frame0, int64_t nframes, float *out, int out_memspace) {
     RET(residual_materialize(ctx, P));
     const int64_t d = P->d;
+    const FootTerm &ap = P->residual.applied;
     DevBuf &dB0b = ctx->tmp[6], &dB0n = ctx->tmp[7], &dKap = ctx->tmp[12];
     RET(to_dev(ctx, dB0b, b0_block, (size_t)P->d_b)); RET(to_dev(ctx, dB0n, b0_new, (size_t)d));
     RET(dKap.ensure((size_t)d * sizeof(float)));
     LAUNCH(ctx, "rss_const", k_rss_const, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, d, P->nr, P->nr_b, P->nc_b, P->roff, P->coff, P->p, P->ring_dr.as<int>(),
            P->ring_dc.as<int>(), P->W.as<float>(), P->ymean_f.as<float>(), P->b0.as<double>(), dB0b.as<float>(), dB0n.as<float>(),
-           P->res_ac ? P->resCnt.as<int>() : nullptr, P->resK.as<int>(), P->resV.as<float>(), P->resCm.as<double>(), dKap.as<float>());
+           ap.ac ? ap.cnt.as<int>() : nullptr, ap.k.as<int>(), ap.v.as<float>(), ap.cm.as<double>(), dKap.as<float>());
     float *dst = out;
     if (out_memspace != CNMFE_DEVICE) { RET(ctx->stage.ensure((size_t)d * nframes * sizeof(float))); dst = ctx->stage.as<float>(); }
     LAUNCH(ctx, "bg_reconstruct", k_bg_out, dim3((unsigned)((d + 255) / 256), (unsigned)nframes), dim3(256), 0, P->Yc4.as<float4>(), P->d_b, P->nr, P->nr_b, P->roff, P->coff,
@@ -1025,9 +1025,8 @@ static int r1_sweep(cnmfe_ctx *ctx, Patch *P, DevBuf &ysig, bool has_ac, int64_t
            P->ymean_f.as<float>(), P->b0.as<double>(), dDlt.as<float>(), P->d, P->nr, P->nr_b, P->roff, P->coff);
 
     // is the resident ring the full get_nhood(radius) ring?  (then a compile-time kernel exists for 15 / 18)
-    int variant = (int)ctx->opt("r1_variant", 14);
+    const rplan::ResidualOpts opts = residual_opts(ctx);
     const int h = P->radius;
-    if (variant >= 0 && variant != 10 && variant != 11 && variant != 14) variant = 14;
     bool full_ring = true;
     { int n = 0;
       for (int c = -h; c <= h && full_ring; ++c) for (int r = -h; r <= h; ++r) { int d2 = c * c + r * r;
@@ -1036,16 +1035,9 @@ static int r1_sweep(cnmfe_ctx *ctx, Patch *P, DevBuf &ysig, bool has_ac, int64_t
     // The footprint term (W A_prev)(C_prev - mean) of a patch with halo neurons need not go through the sweep at all: the sweep runs without it (so the
     // faster duo-role kernel serves patched runs too) and the term stays PENDING beside Ysig -- the spatial and the temporal update both take it in
     // algebraically, through their projections (residual_term_fold_spatial, residual_term_project); any other consumer materialises it first.
-    const bool defer_term = has_ac && variant == 14 && h == 15 && full_ring && can_defer && ctx->opt("r1_lazy", 1) != 0 && ctx->opt("r1_defer", 1) != 0;
-    const bool sweep_ac = has_ac && !defer_term;
-    if (variant == 14 && (sweep_ac || h != 15)) variant = 11;   // duo roles (resid_duo.hpp): radius 15, no footprint term inside the sweep
-    if (h == 18 && variant >= 11) variant = 10;               // arc kernels: radius 15 only (ds_read immediates)
-    // the low-resolution rings of bg_ssub = 2, 3 (ceil(15/2) = 8, ceil(18/2) = 9, ceil(15/3) = 5, ceil(18/3) = 6): LDS-DMA kernel only
-    const bool small_special = full_ring && (h == 5 || h == 6 || h == 8 || h == 9) && variant >= 0;
-    if (small_special) variant = 10;
-    const bool special = (full_ring && (h == 15 || h == 18) && variant >= 0) || small_special;
-    int TR = 16, TC = 16;
-    if (special) tile_shape(variant, TR, TC);
+    const rplan::R1Kernel kp = rplan::r1_kernel_plan(opts, h, full_ring, has_ac, can_defer);
+    const int variant = kp.variant, TR = kp.TR, TC = kp.TC;
+    const bool defer_term = kp.defer_term, sweep_ac = kp.sweep_ac, special = kp.special;
     const int HR = TR + 2 * h, HC = TC + 2 * h;
 
     R1Args a;
@@ -1058,7 +1050,7 @@ static int r1_sweep(cnmfe_ctx *ctx, Patch *P, DevBuf &ysig, bool has_ac, int64_t
     a.wa_v = sweep_ac ? dWaV.as<float>() : nullptr; a.Cc = sweep_ac ? dCc.as<float>() : nullptr; a.ldc = ldc;
     a.Ysig4 = ysig.as<float4>();
     a.ntile_r = (P->nr + TR - 1) / TR;
-    a.probe = (int)ctx->opt("r1_probe", 0);
+    a.probe = (int)opts.probe;
     const int ntile_c = (P->nc + TC - 1) / TC;
     const int64_t ntiles = (int64_t)a.ntile_r * ntile_c;
     // enough workgroups to fill 256 CUs several times over; segments are a multiple of 4 frames
@@ -1102,22 +1094,20 @@ static int r1_sweep(cnmfe_ctx *ctx, Patch *P, DevBuf &ysig, bool has_ac, int64_t
 
 // a virtual residual becomes a resident one: the sweep without any footprint term (the term, if any, is pending beside it either way)
 int residual_realize(cnmfe_ctx *ctx, Patch *P) {
-    if (!P->ysig_virtual) return 0;
-    if (!P->ysig_valid) { P->ysig_virtual = false; return 0; }
-    if (P->res_kind == 2) return ssub_realize(ctx, P);      // bg_ssub > 1: the low-resolution sweep and its upsample (ssub.hip)
+    if (!P->residual.is_virtual()) return 0;
+    if (P->residual.source == rplan::SRC_SSUB) return ssub_realize(ctx, P);      // bg_ssub > 1: the low-resolution sweep and its upsample (ssub.hip)
     RET(P->ysig.ensure((size_t)P->d * P->Tc * sizeof(float4)));
     RET(r1_sweep(ctx, P, P->ysig, false, 4, false, nullptr));
-    P->ysig_virtual = false;
+    P->residual.form = rplan::RESIDENT;
     return 0;
 }
 
 int residual_run(cnmfe_ctx *ctx, Patch *P, int pid, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx,
                  const float *A_val, const float *C, int c_order, float *Ysig_out, int out_memspace, DevBuf *outbuf, int tables_only) {
     const int64_t T = P->T;
-    ++P->res_gen;
-    DevBuf &ysig = outbuf ? *outbuf : P->ysig;               // bg_ssub > 1 sweeps the low-resolution patch into its own buffer
-    // the resident Ysig of this patch is still the residual under the current video, W and b0: only the footprint term changes
-    const bool delta = !outbuf && P->ysig_valid && P->res_kind == 1 && (P->ysig.p || P->ysig_virtual) && ctx->opt("r1_delta", 1) != 0;
+    ResidualState &rs = P->residual;
+    ++rs.gen;
+    DevBuf &ysig = outbuf ? *outbuf : P->ysig;               // bg_ssub > 1 sweeps the low-resolution patch into its own buffer: the patch's own state stays as it is
     DevBuf &dC = ctx->tmp[0], &dCc = ctx->tmp[1], &dCm = ctx->tmp[2], &dArow = ctx->tmp[3], &dAcol = ctx->tmp[4], &dAval = ctx->tmp[5],
            &dWaCnt = ctx->tmp[8], &dWaK = ctx->tmp[9], &dWaV = ctx->tmp[10];
     int64_t ldc = 4;
@@ -1150,49 +1140,41 @@ int residual_run(cnmfe_ctx *ctx, Patch *P, int pid, int32_t Ksel, const int64_t 
                    P->roff, P->coff, P->p, P->ring_dr.as<int>(), P->ring_dc.as<int>(), dArow.as<int>(), dAcol.as<int>(), dAval.as<float>(), nnzA,
                    dWaCnt.as<int>(), dWaK.as<int>(), dWaV.as<float>(), dErrWa, wa_cap);
     }
-    if (tables_only) { ctx->last_ldc = ldc; return 0; }       // bg_ssub: the caller only wants (W*A) and the centred traces (tmp[8..10], tmp[1])
-    // the footprint term this call leaves applied is kept beside Ysig (the scratch buffers above change hands with the patch's)
-    auto keep = [&]() {
-        if (outbuf) return;
-        P->res_ac = has_ac; P->res_ldc = ldc; P->res_kind = 1; P->res_K = Ksel; P->pend = false;
-        if (has_ac) { P->resCnt.swap(dWaCnt); P->resK.swap(dWaK); P->resV.swap(dWaV); P->resCc.swap(dCc); P->resCm.swap(dCm); }
-    };
-    if (delta) {
-        // lazy: keep the term pending; cnmfe_hals_temporal folds it in algebraically, anybody else materialises it
-        if (ctx->opt("r1_lazy", 1) != 0 && !Ysig_out) {
-            P->pend = true; P->pend_ac = has_ac; P->pend_ldc = ldc; P->pend_K = Ksel;
-            if (has_ac) { P->pendCnt.swap(dWaCnt); P->pendK.swap(dWaK); P->pendV.swap(dWaV); P->pendCc.swap(dCc); P->pendCm.swap(dCm); }
-            return 0;
-        }
-        P->pend = true; P->pend_ac = has_ac; P->pend_ldc = ldc; P->pend_K = Ksel;
-        if (has_ac) { P->pendCnt.swap(dWaCnt); P->pendK.swap(dWaK); P->pendV.swap(dWaV); P->pendCc.swap(dCc); P->pendCm.swap(dCm); }
+    const rplan::Plan plan = rplan::residual_plan({rs.form, rs.source, P->ysig.p != nullptr},
+                                                  {rplan::SRC_FULL, has_ac, Ysig_out != nullptr, outbuf != nullptr, tables_only != 0, (double)P->d_b * (double)T}, residual_opts(ctx));
+    if (plan.tables) { ctx->last_ldc = ldc; return 0; }      // bg_ssub: the caller only wants (W*A) and the centred traces (tmp[8..10], tmp[1])
+    // the term of this call moves beside Ysig (the scratch buffers above change hands with the patch's)
+    auto pend = [&](int32_t Kt) { rs.has_pending = true; rs.pending.take(has_ac, ldc, Kt, dWaCnt, dWaK, dWaV, dCc, dCm); };
+    switch (plan.action) {
+    case rplan::PendOnly:                                    // the kept Ysig is still the residual under the current video, W and b0: only the term changes, and
+        pend(Ksel);                                          // it stays pending; cnmfe_hals_temporal folds it in algebraically, anybody else materialises it
+        return 0;
+    case rplan::PendAndFold:
+        pend(Ksel);
         RET(residual_materialize(ctx, P));
         if (Ysig_out) RET(ysig_export(ctx, P, ysig, Ysig_out, out_memspace));
         return 0;
-    }
-    // Sweep-free residual (round 4, option "r1_virtual", default 1): nobody has asked for Ysig itself -- the request is only recorded.  The spatial update
-    // takes Ysig C' out of the table P = Yc Cc' (U = P - W P), the temporal update projects the centred video through B = A - W'A (vproj.hip), a footprint
-    // term pends beside the virtual Ysig exactly as beside a resident one; every other consumer goes through residual_realize, which runs the sweep then.
-    if (!outbuf && !Ysig_out && ctx->opt("r1_virtual", 1) != 0 && ctx->opt("r1_lazy", 1) != 0 && ctx->opt("r1_delta", 1) != 0) {
-        P->res_ac = false; P->res_ldc = ldc; P->res_kind = 1; P->res_K = 0;
-        P->pend = has_ac; P->pend_ac = has_ac; P->pend_ldc = ldc; P->pend_K = has_ac ? Ksel : 0;
-        if (has_ac) { P->pendCnt.swap(dWaCnt); P->pendK.swap(dWaK); P->pendV.swap(dWaV); P->pendCc.swap(dCc); P->pendCm.swap(dCm); }
+    case rplan::Record:
+        // Sweep-free residual (round 4, option "r1_virtual", default 1): nobody has asked for Ysig itself -- the request is only recorded.  The spatial update
+        // takes Ysig C' out of the table P = Yc Cc' (U = P - W P), the temporal update projects the centred video through B = A - W'A (vproj.hip), a footprint
+        // term pends beside the virtual Ysig exactly as beside a resident one; every other consumer goes through residual_realize, which runs the sweep then.
+        rs.applied.set(false, ldc, 0); rs.source = rplan::SRC_FULL;
+        pend(has_ac ? Ksel : 0); rs.has_pending = has_ac;
         ctx->last_ldc = ldc;
-        P->ysig_valid = true; P->ysig_virtual = true;
+        rs.form = rplan::VIRTUAL;
         return 0;
+    case rplan::Sweep:
+        break;
     }
     RET(ysig.ensure((size_t)P->d * P->Tc * sizeof(float4)));
     bool defer_term = false;
     RET(r1_sweep(ctx, P, ysig, has_ac, ldc, !outbuf && !Ysig_out, &defer_term));
-    if (!outbuf) P->ysig_virtual = false;
-    if (defer_term) {                                        // Ysig carries no term; the one asked for waits beside it
-        P->res_ac = false; P->res_ldc = ldc; P->res_kind = 1; P->res_K = 0;
-        P->pend = true; P->pend_ac = true; P->pend_ldc = ldc; P->pend_K = Ksel;
-        P->pendCnt.swap(dWaCnt); P->pendK.swap(dWaK); P->pendV.swap(dWaV); P->pendCc.swap(dCc); P->pendCm.swap(dCm);
-    } else
-        keep();
     ctx->last_ldc = ldc;
-    P->ysig_valid = true;
+    if (!outbuf) {
+        rs.source = rplan::SRC_FULL; rs.form = rplan::RESIDENT;
+        if (defer_term) { rs.applied.set(false, ldc, 0); pend(Ksel); }      // Ysig carries no term; the one asked for waits beside it
+        else { rs.has_pending = false; rs.applied.take(has_ac, ldc, Ksel, dWaCnt, dWaK, dWaV, dCc, dCm); }
+    }
     if (Ysig_out) RET(ysig_export(ctx, P, ysig, Ysig_out, out_memspace));
     // without an output buffer the call returns with the kernel in flight: every consumer of Ysig is an engine
     // call on the same stream, so the caller's host work overlaps the sweep (include/cnmfe.h, cnmfe_residual)

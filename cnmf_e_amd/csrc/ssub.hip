@@ -375,9 +375,9 @@ int ssub_fit(cnmfe_ctx *ctx, Patch *M, Patch *F, Patch *R, int ssub, int32_t K, 
         if (R->p != F->p || R->d != F->d) return fail(CNMFE_ESTATE, "fit / residual low-resolution patches have different rings");
         CK(hipMemcpyAsync(R->W.p, F->W.p, (size_t)F->p * F->d * sizeof(float), hipMemcpyDeviceToDevice, ctx->st()));
         R->stat_valid = false;
-        R->ysig_valid = false;
+        R->residual.invalidate();
     }
-    M->ysig_valid = false;
+    M->residual.invalidate();
     return 0;
 }
 
@@ -508,7 +508,7 @@ int ssub_realize(cnmfe_ctx *ctx, Patch *M) {
     RET(ssub_taps(ctx, M, R));
     RET(residual_run(ctx, R, M->ss_res, 0, nullptr, nullptr, nullptr, nullptr, CNMFE_BOUND, nullptr, CNMFE_HOST, &ctx->ysig_low, 0));
     RET(ssub_upsample(ctx, M, R));
-    M->ysig_virtual = false;
+    M->residual.form = rplan::RESIDENT;
     return 0;
 }
 
@@ -516,7 +516,8 @@ int ssub_residual(cnmfe_ctx *ctx, Patch *M, int pid, Patch *R, int res_id, int s
                   const float *va, const float *C, int c_order, float *Ysig_out, int out_memspace) {
     int d1s, d2s; low_dims(M, ssub, d1s, d2s);
     if (R->d1 != d1s || R->d2 != d2s || R->T != M->T) return fail(CNMFE_ESTATE, "patch %d is not the low-resolution residual patch of patch %d", res_id, pid);
-    ++M->res_gen;
+    ResidualState &rs = M->residual;
+    ++rs.gen;
     std::vector<int64_t> ocp; std::vector<int32_t> ori; std::vector<float> ova;
     const bool has_a = K > 0 && cp[K] > 0;
     HostTrace ht(ctx, "residual_ssub");
@@ -527,20 +528,18 @@ int ssub_residual(cnmfe_ctx *ctx, Patch *M, int pid, Patch *R, int res_id, int s
     // Ysig = [Y' + (Ymean - b0) - up(W down(Y'))] + up(W down(A_prev)) (C - mean C): while the video, W (of the residual patch) and b0 are
     // unchanged a further call only changes the second bracket, exactly as in cnmfe_residual -- its full-resolution ELL form (k_wa_upsample)
     // goes through the same pending-term / streaming-delta machinery (resid.hip), so the iteration does at most ONE low-resolution sweep + upsample.
-    // Round 5: and usually none -- a request nobody asks the output of is only RECORDED (ysig_virtual, as cnmfe_residual does since round 4): the spatial and
+    // Round 5: and usually none -- a request nobody asks the output of is only RECORDED (VIRTUAL, as cnmfe_residual does since round 4): the spatial and
     // the temporal update take their projections through the resampling maps (vproj.hip, vproj_*_ssub), every other consumer realises it (ssub_realize).
-    const bool lazy = ctx->opt("r1_delta", 1) != 0;
-    const bool reuse = M->ysig_valid && M->res_kind == 2 && (M->ysig.p || M->ysig_virtual) && lazy;
     // (ssub_virtual 1, the default: only where it pays -- profiles/r05/ssub_virtual_check.txt: the sweep-free form wins at 512 x 512 x 10000 (8.2 against 13.9 ms per
     //  iteration) and loses on patches of 256 x 256 x 3000 and below (5.8 against 4.6 ms: its list building, k_vp_build_b_ssub and two extra passes over the
     //  low-resolution video outweigh a sweep that small); 2: always)
-    const int64_t sv = ctx->opt("ssub_virtual", 1);
-    const bool virt_new = !reuse && !Ysig_out && lazy && (sv >= 2 || (sv == 1 && (double)M->d_b * (double)M->T >= 5e8)) && ctx->opt("r1_virtual", 1) != 0 && ctx->opt("r1_lazy", 1) != 0;
-    const bool tables = reuse || virt_new;
+    const rplan::Plan plan = rplan::residual_plan({rs.form, rs.source, M->ysig.p != nullptr},
+                                                  {rplan::SRC_SSUB, has_a, Ysig_out != nullptr, false, false, (double)M->d_b * (double)M->T}, residual_opts(ctx));
+    const bool tables = plan.tables;
     RET(residual_run(ctx, R, res_id, has_a ? K : 0, has_a ? ocp.data() : nullptr, ori.data(), ova.data(), C, c_order, nullptr, CNMFE_HOST, &ctx->ysig_low, tables ? 1 : 0));
     const int64_t ldc_t = ctx->last_ldc;
     ht.mark("low-resolution W*A tables");
-    // the centred traces of this call move to the patch (pendCc / resCc) and the buffer the patch held before comes back as tmp[1]: a swap
+    // the centred traces of this call move to the patch (the term's cc) and the buffer the patch held before comes back as tmp[1]: a swap
     // both ways, no hipMalloc / hipFree per call (the guard hands the leftover buffer back on every exit path)
     struct GiveBack { DevBuf b; DevBuf &home; ~GiveBack() { if (b.p && !home.p) b.swap(home); } } gb{DevBuf(), ctx->tmp[1]};
     DevBuf &tCc = gb.b;
@@ -549,31 +548,37 @@ int ssub_residual(cnmfe_ctx *ctx, Patch *M, int pid, Patch *R, int res_id, int s
     // interpolation window meets more than UP_CAP footprints raises the context's error flag (reported by the next call that waits, like the low-resolution ring's own
     // limit in k_ring_wa): reading a flag back here cost a drain of the stream in each of the iteration's two residual calls
     {
-        DevBuf &tCnt = tables ? M->pendCnt : M->resCnt, &tK = tables ? M->pendK : M->resK, &tV = tables ? M->pendV : M->resV;
+        FootTerm &t = tables ? rs.pending : rs.applied;
         if (has_a) {
             int *dErr = nullptr;
             RET(ctx_errflag(ctx, &dErr));
-            RET(tCnt.ensure((size_t)M->d * sizeof(int))); RET(tK.ensure((size_t)UP_CAP * M->d * sizeof(int))); RET(tV.ensure((size_t)UP_CAP * M->d * sizeof(float)));
+            RET(t.cnt.ensure((size_t)M->d * sizeof(int))); RET(t.k.ensure((size_t)UP_CAP * M->d * sizeof(int))); RET(t.v.ensure((size_t)UP_CAP * M->d * sizeof(float)));
             LAUNCH(ctx, "ssub_wa_upsample", k_wa_upsample, dim3((unsigned)((M->d + UP_NT - 1) / UP_NT)), dim3(UP_NT), 0, M->d, M->nr, M->nr_b, M->roff, M->coff, d1s, R->d,
                    M->ss_ir.as<int>(), M->ss_wr.as<float>(), M->ss_Pr, M->ss_ic.as<int>(), M->ss_wc.as<float>(), M->ss_Pc, ctx->tmp[8].as<int>(), ctx->tmp[9].as<int>(),
-                   ctx->tmp[10].as<float>(), tCnt.as<int>(), tK.as<int>(), tV.as<float>(), dErr);
-            (tables ? M->pendCc : M->resCc).swap(tCc);
+                   ctx->tmp[10].as<float>(), t.cnt.as<int>(), t.k.as<int>(), t.v.as<float>(), dErr);
+            t.cc.swap(tCc);
         }
-        if (tables) {
-            if (virt_new) {
-                M->res_ac = false; M->res_ldc = ldc_t; M->res_K = 0; M->res_kind = 2;
-                M->ysig_valid = true; M->ysig_virtual = true;
-            }
-            M->pend = reuse ? true : has_a; M->pend_ac = has_a; M->pend_ldc = ldc_t; M->pend_K = K;
-            if (ctx->opt("r1_lazy", 1) == 0 || Ysig_out) RET(residual_materialize(ctx, M));
+        t.set(has_a, ldc_t, K);
+        switch (plan.action) {
+        case rplan::Record:
+            rs.applied.set(false, ldc_t, 0); rs.source = rplan::SRC_SSUB; rs.form = rplan::VIRTUAL;
+            rs.has_pending = has_a;
+            return 0;
+        case rplan::PendOnly:
+            rs.has_pending = true;
+            return 0;
+        case rplan::PendAndFold:
+            rs.has_pending = true;
+            RET(residual_materialize(ctx, M));
             if (Ysig_out) RET(ysig_export(ctx, M, M->ysig, Ysig_out, out_memspace));
             return 0;
+        case rplan::Sweep:
+            rs.has_pending = false; rs.source = rplan::SRC_SSUB;
+            break;
         }
-        M->res_ac = has_a; M->res_ldc = ldc_t; M->res_K = K; M->pend = false;
-        M->res_kind = 2; M->ysig_virtual = false;
     }
     RET(ssub_upsample(ctx, M, R));
-    M->ysig_valid = true;
+    rs.form = rplan::RESIDENT;
     if (Ysig_out) RET(ysig_export(ctx, M, M->ysig, Ysig_out, out_memspace));
     return 0;
 }

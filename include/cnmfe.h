@@ -516,6 +516,13 @@ int cnmfe_synchronize(cnmfe_ctx *ctx);
  *                     reads / sweep without the term and keep it pending.  Default 1 each.
  *   r1_virtual        default 1: a cnmfe_residual without an output buffer records its request and the two updates project the centred video instead of a swept
  *                     Ysig; 0 restores the sweep
+ *                     How the four combine (one rule for cnmfe_residual and cnmfe_residual_ssub, cnmf_e_amd/csrc/residual_plan.hpp): while a residual of the same call
+ *                     is kept for the patch (swept or recorded) and r1_delta is on, a request only adds its footprint term -- pending with r1_lazy and no output
+ *                     buffer, folded in at once otherwise.  Else a request without an output buffer is recorded when r1_virtual, r1_lazy and r1_delta are all on
+ *                     (its term pends: recording needs the other two).  Else the sweep runs; r1_defer needs r1_lazy as well.  r1_delta = 0 therefore sweeps on
+ *                     every request.  r1_variant: any value other than -1, 10, 11, 14 means 14; 14 serves radius 15 without a footprint term inside the sweep (11
+ *                     takes over with one), 11 radius 15, 10 radius 15 / 18 and the low-resolution radii 5, 6, 8, 9 (where it is the only specialised kernel);
+ *                     a ring that is not the full ring of its radius, or any other radius, runs the generic kernel
  *   ssub_virtual      the same for cnmfe_residual_ssub (through the resampling maps): 2 always, 1 (default) on patches of at least 5e8 samples -- below that the
  *                     low-resolution sweep is the faster form, profiles/r05/ssub_virtual_check.txt --, 0: the low-resolution sweep + upsample
  *   gram_incremental  default 1: the covariance table of the VIDEO is kept and corrected per fit (see cnmfe_fit_ring_model); 0: the direct Gram of Bf every fit
