@@ -669,9 +669,9 @@ int cnmfe_synchronize(cnmfe_ctx *ctx) {
 
 int cnmfe_set_option(cnmfe_ctx *ctx, const char *name, int64_t value) {
     if (!ctx || !name) return fail(CNMFE_EINVAL, "null argument");
-    // behaviour switches (include/cnmfe.h) and, behind them, the probes of scripts/ (diagnostics: solve_probe, r1_probe, deconv_trace, host_trace, debug)
+    // behaviour switches (include/cnmfe.h) and, behind them, the probes of scripts/ (diagnostics: solve_probe, r1_probe, deconv_trace, trace_long, host_trace, debug)
     static const char *known[] = {"r1_variant", "r1_delta", "r1_lazy", "r1_defer", "r1_virtual", "gram_incremental", "prealloc", "solve_packed", "sweep_dag", "win_i8_planes", "solve_staged", "solve_inv", "solve_inv_terms", "gram_i8", "win_i8", "proj_tiled", "proj_i8", "proj_i8_planes", "ssub_virtual", "temporal_early", "fit_side",
-                                  "solve_probe", "r1_probe", "deconv_trace", "host_trace", "debug", nullptr};
+                                  "solve_probe", "r1_probe", "deconv_trace", "trace_long", "host_trace", "debug", nullptr};
     if (!strcmp(name, "lanes")) { RET(lanes_set(ctx, value)); ctx->opts[name] = value; return 0; }
     for (int i = 0; known[i]; ++i) if (!strcmp(known[i], name)) { ctx->opts[name] = value; if (!strcmp(name, "host_trace")) ctx->trace_level = (int)value; return 0; }
     return fail(CNMFE_EINVAL, "unknown option '%s'", name);
@@ -1029,8 +1029,8 @@ static int seed_args(cnmfe_ctx *ctx, int patch_id, const float *psf, int32_t &ps
     if (psf_n > 0 && (psf_n % 2 == 0 || psf_n > 25)) return fail(CNMFE_EUNSUPPORTED, "seed images: the filter must be odd-sized and at most 25 x 25 (got %d; pad an even kernel)", psf_n);
     if (M > 16) return fail(CNMFE_EUNSUPPORTED, "seed images: at most 16 detrend basis columns (got %d)", M);
     if (frame0 != 0) return fail(CNMFE_EUNSUPPORTED, "seed images read the frames from the first one on (frame0 = %lld)", (long long)frame0);
-    if (nframes < 64 || nframes > std::min<int64_t>(P->T, 20400))
-        return fail(CNMFE_EUNSUPPORTED, "seed images support 64 <= nframes <= min(T, 20400) (got %lld of %lld)", (long long)nframes, (long long)P->T);
+    if (nframes < 64 || nframes > std::min<int64_t>(P->T, WELCH_TMAX))
+        return fail(CNMFE_EUNSUPPORTED, "seed images support 64 <= nframes <= min(T, WELCH_TMAX = %d) (got %lld of %lld)", WELCH_TMAX, (long long)nframes, (long long)P->T);
     return 0;
 }
 
@@ -1071,7 +1071,7 @@ int cnmfe_peel_open_residual(cnmfe_ctx *ctx, int patch_id, int32_t Ksel, const i
     if (!psf) psf_n = 0;
     if (P->derived) return fail(CNMFE_EUNSUPPORTED, "a peel session of a derived (bg_ssub) patch is not built: patch %d", patch_id);
     if (psf_n > 0 && (psf_n % 2 == 0 || psf_n > 25)) return fail(CNMFE_EUNSUPPORTED, "seed images: the filter must be odd-sized and at most 25 x 25 (got %d; pad an even kernel)", psf_n);
-    if (P->T < 64 || P->T > 20400) return fail(CNMFE_EUNSUPPORTED, "seed images support 64 <= nframes <= 20400 (the residual session reads all %lld frames)", (long long)P->T);
+    if (P->T < 64 || P->T > WELCH_TMAX) return fail(CNMFE_EUNSUPPORTED, "seed images support 64 <= nframes <= WELCH_TMAX = %d (the residual session reads all %lld frames)", WELCH_TMAX, (long long)P->T);
     RET(require_residual(P, patch_id));
     if (P->peel) return fail(CNMFE_ESTATE, "patch %d already has an open peel session", patch_id);
     RET(check_csc("A", Ksel, P->d, A_colptr, A_rowidx));

@@ -135,6 +135,9 @@ inline void csc_to_csr(int64_t nrow, int32_t ncol, const int64_t *colptr, const 
         }
 }
 
+// the longest trace the Welch estimator takes: pwelch's segment length floor(T / 4.5) <= 32768 = the largest transform built (two 16384-point halves in LDS)
+constexpr int WELCH_TMAX = 147456;
+
 // a greedy-initialisation session of one patch (peel.hpp, cnmfe_peel_open .. cnmfe_peel_close): the filtered block HY, the working copy Yw of the video (both
 // [ceil(n / 4)][d_b] float4), GetSn of HY per block pixel (fp64), the detrend basis, ci | y_bg (fp64, n each) and the box kernels' scratch
 // The session runs on the geometry of its SOURCE video: the centred block (cnmfe_peel_open: d = d_b, nr_b x nc_b, y_bg adds the pixel mean back) or the

@@ -14,8 +14,7 @@
 
 namespace cnmfe {
 
-// the longest trace the Welch estimator takes: pwelch's segment length floor(T / 4.5) <= 32768 = the largest transform built (two 16384-point halves in LDS)
-constexpr int WELCH_TMAX = 147456;
+// (WELCH_TMAX, the longest trace the Welch estimator takes, lives in common.hpp: the entry points of api.hip refuse by it)
 struct DeconvCfg {
     int T, P2, nfft, L, nov, nseg;     // trace length, pow2 >= T, Welch geometry
     int split;                         // round 6: nfft = 32768 (73728 < T <= 147456) as two 16384-point transforms (even / odd samples) + one butterfly, LDS = re | im of one of them
@@ -1028,6 +1027,62 @@ int sn_video_run(cnmfe_ctx *ctx, Patch *P, int64_t nframes, float *sn_out) {
     CK(hipMemcpyAsync(sn_out, dSn.p, (size_t)P->d_b * sizeof(float), hipMemcpyDeviceToHost, ctx->st()));
     CK(hipStreamSynchronize(ctx->st()));
     return 0;
+}
+
+// ---- the Welch set-up of the session and trace kernels (seed.hpp, peel.hpp, merge.hpp): geometry, flavour and tier from T for all four of them --------
+// Every one of those kernels has an LDS flavour (the trace | the transform | its tables in one workgroup's LDS: 4 (ceil4(T) + 2.5 nfft) <= 160 KB - 256, T <= 20416)
+// and a LONG flavour whose trace lives in global memory (a scratch row, the output row, or the matrix itself) and whose LDS holds what get_sn needs for the tier,
+// by the rule of sn_pixels_launch above:
+//   nfft <= 8192  (T <= 36868)   re | im | twiddles in LDS, get_sn<., 17, false> -- the LDS flavour's instantiation: where both can run they agree bit for bit
+//   nfft = 16384  (T <= 73728)   re | im in LDS, the tables in a 3 nfft-float slot of global memory per workgroup
+//   nfft = 32768  (T <= 147456)  the split transform (kernels of their own, as k_deconv<true, true>): one 16384-point half in LDS, the other in the slot
+// Option trace_long = 1 (diagnostic) takes the long flavour at every T.
+struct WelchPlan {
+    DeconvCfg c; bool lng = false, tab_global = false; size_t shmem = 0;
+    // workgroups of a long launch over `count` items: a workgroup of the two upper tiers owns a CU's LDS, so more than one per CU only adds slots
+    unsigned nwg(int64_t count) const { return (unsigned)std::min<int64_t>(count, tab_global ? 256 : 1024); }
+};
+static int welch_cfg(cnmfe_ctx *ctx, int64_t T, WelchPlan &w) {
+    if (T < 64 || T > WELCH_TMAX) return fail(CNMFE_EUNSUPPORTED, "GetSn of a trace supports 64 <= T <= WELCH_TMAX = %d frames (got %lld)", WELCH_TMAX, (long long)T);
+    DeconvCfg &c = w.c;
+    c = DeconvCfg{};
+    c.T = (int)T; c.P2 = 1; while (c.P2 < T) c.P2 <<= 1;
+    c.L = (int)(T / 4.5); c.nov = c.L / 2;                                   // pwelch defaults, as sn_pixels_launch
+    c.nfft = 256; while (c.nfft < c.L) c.nfft <<= 1;
+    c.nseg = (int)((T - c.nov) / (c.L - c.nov));
+    c.split = c.nfft > 16384 ? 1 : 0;
+    const size_t lim = 160 * 1024 - 256, tfm = (2 * (size_t)c.nfft + (size_t)c.nfft / 2) * sizeof(float);
+    w.shmem = (((size_t)T + 3) & ~size_t(3)) * sizeof(float) + tfm;
+    w.lng = w.shmem > lim || ctx->opt("trace_long", 0) != 0;
+    w.tab_global = false;
+    if (w.lng) {
+        w.tab_global = tfm > lim;
+        w.shmem = w.tab_global ? (c.split ? 1 : 2) * (size_t)c.nfft * sizeof(float) : tfm;
+    }
+    return 0;
+}
+// the tables' slots of a long launch of `nwg` workgroups (nullptr: they live in LDS)
+static int welch_tabs(cnmfe_ctx *ctx, const WelchPlan &w, unsigned nwg, float **tabs) {
+    *tabs = nullptr;
+    if (!w.tab_global) return 0;
+    RET(ctx->dscr.tbuf.ensure((size_t)nwg * 3 * w.c.nfft * sizeof(float)));
+    *tabs = ctx->dscr.tbuf.as<float>();
+    return 0;
+}
+// launches the flavour a plan names: KL<false> / KL<true> are the long kernel without / with the split transform (their first arguments: cfg, tabs), KS the LDS one
+#define WELCH_LAUNCH_LONG(ctx, name, KL, w, grid, tabs, ...) do { \
+    if ((w).c.split) { \
+        if ((w).shmem > 64 * 1024) CK(hipFuncSetAttribute((const void *)KL<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(w).shmem)); \
+        LAUNCH(ctx, name, KL<true>, dim3(grid), dim3(256), (w).shmem, (w).c, tabs, __VA_ARGS__); \
+    } else { \
+        if ((w).shmem > 64 * 1024) CK(hipFuncSetAttribute((const void *)KL<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(w).shmem)); \
+        LAUNCH(ctx, name, KL<false>, dim3(grid), dim3(256), (w).shmem, (w).c, tabs, __VA_ARGS__); \
+    } } while (0)
+
+// get_sn of a long kernel: MAXB = 17 unless split (33: nfft / 4 + 1 bins over 256 threads), the tables in this workgroup's slot
+template <bool SPLIT, class YT>
+__device__ __forceinline__ double get_sn_long(const YT &y, const DeconvCfg &c, float *lds, double *red, float *tabs) {
+    return get_sn<YT, SPLIT ? 33 : 17, SPLIT>(y, c, lds, red, false, tabs ? tabs + (int64_t)blockIdx.x * 3 * c.nfft : nullptr);
 }
 
 }  // namespace cnmfe

@@ -8,6 +8,8 @@
 //                                    inside the kernel, per operand, so nothing of the fp32-centred copy's seven digits enters)
 //   k_trace_diff_spikes              S_ = diff(C_raw) with a zero last column, entries below 2 GetSn(S_) zeroed (merge_high_corr.m:57-66)
 //   k_trace_tags                     max(C), std(C_raw - C), GetSn(C_raw), |{S(2:end) > 0}| per trace in one pass (Sources2D.m:1700-1709)
+//                                    (both: the trace in LDS beside the Welch transform up to 20416 frames; k_trace_diff_spikes_long / k_trace_tags_long beyond, up
+//                                    to WELCH_TMAX = 147456 -- the difference trace in its output row, C_raw's row read in place, no scratch but the tables' slots)
 //   k_merge_rows + k_merge_compact   ci = w' C_raw(IDs, :) in fp64, rounded once; the rows that stay, gathered into new matrices that are swapped in
 // Every reduction runs in a fixed order: equal inputs give equal bits (on every rank of a sharded run).
 #pragma once
@@ -130,6 +132,60 @@ __global__ void __launch_bounds__(256) k_trace_tags(DeconvCfg c, const float *__
     }
 }
 
+// The long flavours (welch_cfg, deconv.hip): a workgroup walks the traces blockIdx.x, blockIdx.x + gridDim.x, ...; no trace lives in LDS, which holds the
+// transform alone.  The difference trace is written to its output row first, read from there by get_sn and thresholded in place; the tags read C_raw's row where
+// it lies.  Same threads, strides and sums as the LDS flavours: equal bits where both run.
+template <bool SPLIT>
+__global__ void __launch_bounds__(256) k_trace_diff_spikes_long(DeconvCfg c, float *__restrict__ tabs, const float *__restrict__ X, int64_t ldc, int K,
+                                                                float *__restrict__ out, float *__restrict__ sn_out) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ double red[4];
+    const int tid = threadIdx.x, T = c.T, Tal = (T + 3) & ~3;
+    for (int k = blockIdx.x; k < K; k += gridDim.x) {
+        const float *row = X + (int64_t)k * ldc;
+        float *y = out + (int64_t)k * ldc;                   // (ldc = ceil4(T): the row is the LDS flavour's copy, padding included)
+        for (int t = tid; t < Tal; t += 256) y[t] = t < T - 1 ? row[t + 1] - row[t] : 0.f;
+        __threadfence_block();
+        __syncthreads();
+        const double sn = get_sn_long<SPLIT>(y, c, lds, red, tabs);
+        for (int t = tid; t < (int)ldc; t += 256) { const float v = y[t]; y[t] = (t < T && !((double)v < 2.0 * sn)) ? v : 0.f; }
+        if (tid == 0 && sn_out) sn_out[k] = (float)sn;
+        __syncthreads();
+    }
+}
+
+template <bool SPLIT>
+__global__ void __launch_bounds__(256) k_trace_tags_long(DeconvCfg c, float *__restrict__ tabs, const float *__restrict__ Cm, const float *__restrict__ Craw,
+                                                         const float *__restrict__ S, int64_t ldc, int K, double *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ double red[4];
+    __shared__ float mred[4];
+    const int tid = threadIdx.x, T = c.T;
+    for (int k = blockIdx.x; k < K; k += gridDim.x) {
+        const int64_t off = (int64_t)k * ldc;
+        const float *y = Craw + off;
+        float mx = -INFINITY; double s = 0, cnt = 0;
+        for (int t = tid; t < T; t += 256) {
+            const float r = y[t], cv = Cm[off + t];
+            mx = fmaxf(mx, cv); s += (double)r - (double)cv; if (S && t >= 1 && S[off + t] > 0.f) cnt += 1;
+        }
+        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        if ((tid & 63) == 0) mred[tid >> 6] = mx;
+        const double m = block_sum(s, red) / (double)T;            // (its barriers publish mred)
+        cnt = block_sum(cnt, red);
+        double q = 0;
+        for (int t = tid; t < T; t += 256) { const double d = ((double)y[t] - (double)Cm[off + t]) - m; q += d * d; }
+        q = block_sum(q, red);
+        const double sn = get_sn_long<SPLIT>(y, c, lds, red, tabs);
+        if (tid == 0) {
+            double *o = out + 4 * (int64_t)k;
+            o[0] = (double)fmaxf(fmaxf(mred[0], mred[1]), fmaxf(mred[2], mred[3]));
+            o[1] = sqrt(q / (double)(T > 1 ? T - 1 : 1)); o[2] = sn; o[3] = S ? cnt : -1.0;
+        }
+        __syncthreads();                                     // (the next trace rewrites mred)
+    }
+}
+
 // ci = w' C_raw(IDs, :) of group g: fp64 sum in the group's order, rounded to fp32 once; written twice (mci stays, mraw is what k_deconv reads and rewrites)
 __global__ void __launch_bounds__(256) k_merge_rows(const float *__restrict__ Craw, int64_t ldc, int64_t T, const int *__restrict__ gptr, const int *__restrict__ gidx,
                                                     const double *__restrict__ w, float *__restrict__ mci, float *__restrict__ mraw) {
@@ -156,17 +212,7 @@ __global__ void __launch_bounds__(256) k_merge_compact(MergeMats mm, int64_t ldc
 
 // ---- host side ----------------------------------------------------------------------------------------------
 
-static int welch_cfg(int64_t T, DeconvCfg &c, size_t &shmem) {
-    if (T < 64) return fail(CNMFE_EUNSUPPORTED, "GetSn of a trace needs at least 64 frames (got %lld)", (long long)T);
-    c = DeconvCfg{};
-    c.T = (int)T; c.P2 = 1; while (c.P2 < T) c.P2 <<= 1;
-    c.L = (int)(T / 4.5); c.nov = c.L / 2;                                   // pwelch defaults, as sn_pixels_run
-    c.nfft = 256; while (c.nfft < c.L) c.nfft <<= 1;
-    c.nseg = (int)((T - c.nov) / (c.L - c.nov));
-    shmem = ((((size_t)T + 3) & ~size_t(3)) + 2 * (size_t)c.nfft + (size_t)c.nfft / 2) * sizeof(float);
-    if (shmem > 160 * 1024 - 256) return fail(CNMFE_EUNSUPPORTED, "trace of %lld frames does not fit the trace kernels' LDS (trace + Welch transform in 160 KB: T <= 20400)", (long long)T);
-    return 0;
-}
+// (welch_cfg / WelchPlan, the one Welch set-up of these kernels and of seed.hpp / peel.hpp, sits in deconv.hip beside sn_pixels_launch, whose tier rule it follows)
 
 static bool residents_valid(const cnmfe_ctx *ctx) { return ctx->bound_valid && ctx->residents_gen == ctx->bound_gen; }
 
@@ -215,15 +261,22 @@ int trace_corr_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src
 int trace_diff_spikes_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, float *sn_out, float *S_out) {
     const int64_t ldc = (T + 3) & ~int64_t(3);
     if (src == CNMFE_RES_DIFF) return fail(CNMFE_EINVAL, "cnmfe_trace_diff_spikes cannot read its own result");
-    DeconvCfg c; size_t shmem;
-    RET(welch_cfg(T, c, shmem));
+    WelchPlan w;
+    RET(welch_cfg(ctx, T, w));
     const float *dX;
     RET(merge_source(ctx, K, T, X, src, &dX));
     ctx->diff_K = 0;
     DevBuf &dOut = ctx->mrg[1], &dSn = ctx->mrg[5];
     RET(dOut.ensure((size_t)K * ldc * 4)); RET(dSn.ensure((size_t)K * 4));
-    if (shmem > 64 * 1024) CK(hipFuncSetAttribute((const void *)k_trace_diff_spikes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    LAUNCH(ctx, "trace_diff_spikes", k_trace_diff_spikes, dim3((unsigned)K), dim3(256), shmem, c, dX, ldc, dOut.as<float>(), dSn.as<float>());
+    if (w.lng) {
+        const unsigned nwg = w.nwg(K);
+        float *tabs;
+        RET(welch_tabs(ctx, w, nwg, &tabs));
+        WELCH_LAUNCH_LONG(ctx, "trace_diff_spikes", k_trace_diff_spikes_long, w, nwg, tabs, dX, ldc, (int)K, dOut.as<float>(), dSn.as<float>());
+    } else {
+        if (w.shmem > 64 * 1024) CK(hipFuncSetAttribute((const void *)k_trace_diff_spikes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.shmem));
+        LAUNCH(ctx, "trace_diff_spikes", k_trace_diff_spikes, dim3((unsigned)K), dim3(256), w.shmem, w.c, dX, ldc, dOut.as<float>(), dSn.as<float>());
+    }
     ctx->diff_K = K; ctx->diff_T = T;
     if (sn_out) CK(hipMemcpyAsync(sn_out, dSn.p, (size_t)K * 4, hipMemcpyDeviceToHost, ctx->st()));
     if (S_out) CK(hipMemcpy2DAsync(S_out, T * 4, dOut.p, ldc * 4, T * 4, K, hipMemcpyDeviceToHost, ctx->st()));
@@ -234,13 +287,20 @@ int trace_diff_spikes_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, 
 int trace_tags_run(cnmfe_ctx *ctx, int32_t K, double *out) {
     if (!residents_valid(ctx) || ctx->bound_K != K) return fail(CNMFE_ESTATE, "the context holds no C, C_raw of %d traces (cnmfe_deconv_temporal_bound, cnmfe_traces_load)", K);
     const int64_t T = ctx->bound_T, ldc = (T + 3) & ~int64_t(3);
-    DeconvCfg c; size_t shmem;
-    RET(welch_cfg(T, c, shmem));
+    WelchPlan w;
+    RET(welch_cfg(ctx, T, w));
     DevBuf &dOut = ctx->mrg[4];
     RET(dOut.ensure((size_t)K * 4 * 8));
-    if (shmem > 64 * 1024) CK(hipFuncSetAttribute((const void *)k_trace_tags, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    LAUNCH(ctx, "trace_tags", k_trace_tags, dim3((unsigned)K), dim3(256), shmem, c, ctx->bound.as<float>(), ctx->dcv_c.as<float>(),
-           ctx->res_has_s ? ctx->dcv_s.as<float>() : (const float *)nullptr, ldc, dOut.as<double>());
+    const float *dS = ctx->res_has_s ? ctx->dcv_s.as<float>() : (const float *)nullptr;
+    if (w.lng) {
+        const unsigned nwg = w.nwg(K);
+        float *tabs;
+        RET(welch_tabs(ctx, w, nwg, &tabs));
+        WELCH_LAUNCH_LONG(ctx, "trace_tags", k_trace_tags_long, w, nwg, tabs, (const float *)ctx->bound.as<float>(), (const float *)ctx->dcv_c.as<float>(), dS, ldc, (int)K, dOut.as<double>());
+    } else {
+        if (w.shmem > 64 * 1024) CK(hipFuncSetAttribute((const void *)k_trace_tags, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.shmem));
+        LAUNCH(ctx, "trace_tags", k_trace_tags, dim3((unsigned)K), dim3(256), w.shmem, w.c, ctx->bound.as<float>(), ctx->dcv_c.as<float>(), dS, ldc, dOut.as<double>());
+    }
     CK(hipMemcpyAsync(out, dOut.p, (size_t)K * 4 * 8, hipMemcpyDeviceToHost, ctx->st()));
     CK(hipStreamSynchronize(ctx->st()));
     return ctx_check_errflag(ctx);

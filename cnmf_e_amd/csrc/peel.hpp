@@ -8,6 +8,9 @@
 // by d_b float4s and a box column is the contiguous run, so the box kernels put 64 lanes on the box rows and one wave on each of 4 interleaved frame quads:
 // workgroup = (box column, frame chunk).  Every sum is a per-lane fp64 partial, and the partials are added in ascending (chunk, wave) order by a second small
 // kernel: two identical sessions are bit-identical.  Only frames t < n enter anything (the last quad's padding does not).
+// Frames: 64 <= n <= WELCH_TMAX = 147456.  Every kernel but two takes n as a loop bound (64-bit offsets q * d_b; grid.y = frame chunks <= 32, grid.x = ceil(n / 4)
+// <= 36864 for k_peel_traces).  The two that hold a whole trace -- k_seed_stats (seed.hpp) and k_peel_trace_stats -- have a long flavour beyond 20416 frames whose
+// trace stays in global memory (welch_cfg, deconv.hip); k_peel_trace_stats_long needs no scratch: ci already lies there as doubles.
 // A session runs on the geometry of its source video (PeelSession::d / nr / nc): the block for cnmfe_peel_open, the PATCH and its residual video
 // Yres = Ysig - A C (k_peel_yres) for cnmfe_peel_open_residual, the second pass of @Sources2D/initComponents_residual_parallel.m:186-220.
 #pragma once
@@ -231,6 +234,40 @@ __global__ void __launch_bounds__(256) k_peel_trace_stats(DeconvCfg c, const flo
     for (int t = tid; t < n - 1; t += 256) { const double dv = (y0(t + 1) - y0(t)) - dmean; dv2 = fma(dv, dv, dv2); }
     const double dstd = sqrt(block_sum(dv2, red) / (double)(n - 2));
     const double sn = get_sn(y, c, scr, red, false);         // (block_sum's barriers have published y)
+    if (tid == 0) {
+        mom[0] = mb; mom[1] = mc; mom[2] = sbb; mom[3] = sbc; mom[4] = scc;
+        st[0] = dmx; st[1] = dstd; st[2] = nrm; st[3] = sn; st[4] = (double)cnt[0]; st[5] = (double)cnt[1];
+    }
+}
+
+// The long flavour (welch_cfg, deconv.hip): ci stays where it is, in global memory as doubles, and get_sn reads it through an accessor that rounds each sample to
+// float on the fly -- the values the LDS copy holds; LDS is the transform alone.  Every sum as in k_peel_trace_stats: equal bits where both run.
+struct PeelCiAcc {
+    const double *ci;
+    __device__ __forceinline__ float operator[](int t) const { return (float)ci[t]; }
+};
+template <bool SPLIT>
+__global__ void __launch_bounds__(256) k_peel_trace_stats_long(DeconvCfg c, float *__restrict__ tabs, const float4 *__restrict__ hy4, int64_t d_b, int64_t pctr,
+                                                               const double *__restrict__ ci, const double *__restrict__ ybg, const int *__restrict__ cnt,
+                                                               double *__restrict__ mom, double *__restrict__ st) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ double red[4];
+    const int tid = threadIdx.x, n = c.T;
+    double sb = 0, sc = 0, s2 = 0;
+    for (int t = tid; t < n; t += 256) { const double cv = ci[t]; sb += ybg[t]; sc += cv; s2 = fma(cv, cv, s2); }
+    const double mb = block_sum(sb, red) / (double)n, mc = block_sum(sc, red) / (double)n, nrm = sqrt(block_sum(s2, red));
+    double sbb = 0, sbc = 0, scc = 0;
+    for (int t = tid; t < n; t += 256) { const double bv = ybg[t] - mb, cv = ci[t] - mc; sbb = fma(bv, bv, sbb); sbc = fma(bv, cv, sbc); scc = fma(cv, cv, scc); }
+    sbb = block_sum(sbb, red); sbc = block_sum(sbc, red); scc = block_sum(scc, red);
+    auto y0 = [&](int t) { return (double)reinterpret_cast<const float *>(hy4 + (int64_t)(t >> 2) * d_b + pctr)[t & 3]; };
+    double dmx = -INFINITY, ds = 0;
+    for (int t = tid; t < n - 1; t += 256) { const double dv = y0(t + 1) - y0(t); dmx = fmax(dmx, dv); ds += dv; }
+    dmx = peel_block_max(dmx, red);
+    const double dmean = block_sum(ds, red) / (double)(n - 1);
+    double dv2 = 0;
+    for (int t = tid; t < n - 1; t += 256) { const double dv = (y0(t + 1) - y0(t)) - dmean; dv2 = fma(dv, dv, dv2); }
+    const double dstd = sqrt(block_sum(dv2, red) / (double)(n - 2));
+    const double sn = get_sn_long<SPLIT>(PeelCiAcc{ci}, c, lds, red, tabs);
     if (tid == 0) {
         mom[0] = mb; mom[1] = mc; mom[2] = sbb; mom[3] = sbc; mom[4] = scc;
         st[0] = dmx; st[1] = dstd; st[2] = nrm; st[3] = sn; st[4] = (double)cnt[0]; st[5] = (double)cnt[1];
@@ -487,12 +524,10 @@ int peel_extract_run(cnmfe_ctx *ctx, Patch *P, int r, int c, int gSiz, double *c
     int nch, qchunk;
     peel_chunks(nq, nch, qchunk);
     const int npart = nch * PEEL_QL;
-    DeconvCfg cfg{};
-    cfg.T = (int)n; cfg.P2 = 1; while (cfg.P2 < n) cfg.P2 <<= 1;
-    cfg.L = (int)(n / 4.5); cfg.nov = cfg.L / 2;
-    cfg.nfft = 256; while (cfg.nfft < cfg.L) cfg.nfft <<= 1;
-    cfg.nseg = (int)((n - cfg.nov) / (cfg.L - cfg.nov));
-    const size_t sh_stats = ((((size_t)n + 3) & ~size_t(3)) + 2 * (size_t)cfg.nfft + (size_t)cfg.nfft / 2) * sizeof(float);
+    WelchPlan w;
+    RET(welch_cfg(ctx, n, w));
+    float *tabs;
+    RET(welch_tabs(ctx, w, 1, &tabs));
     const size_t o_part = 0, o_corr = o_part + peel_al((size_t)npart * npix * 3 * sizeof(double)), o_ai = o_corr + peel_al((size_t)npix * sizeof(double)),
                  o_hi = o_ai + peel_al((size_t)npix * sizeof(double)), o_lo = o_hi + peel_al((size_t)npix * sizeof(int)), o_cnt = o_lo + peel_al((size_t)npix * sizeof(int)),
                  o_mom = o_cnt + 256, o_st = o_mom + 256, total = o_st + 256;
@@ -508,8 +543,12 @@ int peel_extract_run(cnmfe_ctx *ctx, Patch *P, int r, int c, int gSiz, double *c
     const size_t sh_tr = (size_t)4 * npix * sizeof(double) + 264 * sizeof(int);
     LAUNCH(ctx, "peel_traces", k_peel_traces, dim3((unsigned)nq), dim3(256), sh_tr, hy4, yw4, (S->M > 0 || S->residual) ? (const double *)nullptr : P->ymean_d.as<double>(), d_b, nr_b, b,
            dHi, dLo, dCnt, (int)n, dCi, dBg);
-    if (sh_stats > 64 * 1024) CK(hipFuncSetAttribute((const void *)k_peel_trace_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_stats));
-    LAUNCH(ctx, "peel_trace_stats", k_peel_trace_stats, dim3(1), dim3(256), sh_stats, cfg, hy4, d_b, pctr, dCi, dBg, dCnt, dMom, dSt);
+    if (w.lng) {
+        WELCH_LAUNCH_LONG(ctx, "peel_trace_stats", k_peel_trace_stats_long, w, 1, tabs, hy4, d_b, pctr, (const double *)dCi, (const double *)dBg, (const int *)dCnt, dMom, dSt);
+    } else {
+        if (w.shmem > 64 * 1024) CK(hipFuncSetAttribute((const void *)k_peel_trace_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.shmem));
+        LAUNCH(ctx, "peel_trace_stats", k_peel_trace_stats, dim3(1), dim3(256), w.shmem, w.c, hy4, d_b, pctr, dCi, dBg, dCnt, dMom, dSt);
+    }
     LAUNCH(ctx, "peel_mom_part", k_peel_mom_part, dim3((unsigned)b.nc, (unsigned)nch), dim3(256), 0, yw4, d_b, nr_b, b, dCi, dBg, dMom, (int)n, qchunk, dPart);
     LAUNCH(ctx, "peel_ai_fin", k_peel_ai_fin, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, dPart, npart, npix, dMom, dAi);
     CK(hipMemcpyAsync(corr_box, dCorr, (size_t)npix * sizeof(double), hipMemcpyDeviceToHost, ctx->st()));

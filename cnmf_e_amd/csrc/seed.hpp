@@ -4,6 +4,8 @@
 // Included by deconv.hip below get_sn (the noise of the filtered trace is the same Welch estimator).  Three passes over the block:
 //   k_seed_filter   HY = imfilter(Y, psf, 'replicate') of the centred video, 4 frames at a time        reads Yc4 once (+ halo), writes HY4 once
 //   k_seed_stats    per pixel: detrend, median, max, GetSn, the 3 Sn threshold, mean and rms           reads HY4 once
+//                   (k_seed_stats: trace | Welch transform in one workgroup's LDS, up to 20416 frames; k_seed_stats_long beyond, up to WELCH_TMAX = 147456:
+//                   the trace in a scratch row of global memory -- at most 1024 rows of ceil4(n) floats, 256 from nfft = 16384 on -- and LDS the transform alone)
 //   k_seed_corr     Z = the thresholded, standardised traces rebuilt on the fly; sum_t Z_p sum_N8 Z_n   reads HY4 once (+ 1-pixel halo)
 //   k_seed_cn       the partial sums of the frame chunks in a fixed order, / nframes / |N8|
 // The pixel mean the resident video lacks is a constant per pixel after the filter: it leaves with the median (and lies in the span of the splines).
@@ -114,6 +116,64 @@ __global__ void __launch_bounds__(256) k_seed_stats(DeconvCfg c, const float4 *_
     }
 }
 
+// The long flavour (welch_cfg, deconv.hip: the trace and the transform do not share 160 KB of LDS, or option trace_long): a workgroup walks the pixels
+// blockIdx.x, blockIdx.x + gridDim.x, ... and keeps the trace of the one it is at in ITS row of `rows` (ceil4(n) floats of global memory, filled by one strided
+// pass over hy4; every later pass -- the detrend, the selection's histograms, the overlapped Welch segments, the statistics -- reads contiguous memory no other
+// workgroup touches).  LDS holds the transform alone, the coefficients and the histogram are static.  Same 256 threads, strides, fma order and (below the split
+// tier) get_sn instantiation as k_seed_stats: at a frame count both take, their outputs are equal bit for bit.
+template <bool SPLIT>
+__global__ void __launch_bounds__(256) k_seed_stats_long(DeconvCfg c, float *__restrict__ tabs, const float4 *__restrict__ hy4, int64_t d_b, const double *__restrict__ Q,
+                                                         int M, double sig, float *__restrict__ rows, double *__restrict__ rec, float *__restrict__ pnr,
+                                                         double *__restrict__ sn_keep) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ double red[4];
+    __shared__ double coef[SEED_MMAX];
+    __shared__ int hist[260];
+    const int tid = threadIdx.x, n = c.T;
+    const int Tal = (n + 3) & ~3;
+    float *y = rows + (int64_t)blockIdx.x * Tal;
+    for (int64_t p = blockIdx.x; p < d_b; p += gridDim.x) {
+        double *orec = rec + p * (int64_t)(SEED_REC + M);
+        for (int i = tid; i < Tal / 4; i += 256) *reinterpret_cast<float4 *>(y + 4 * i) = hy4[(int64_t)i * d_b + p];
+        __threadfence_block();                               // (the row is written and read by this workgroup alone; the barriers order it)
+        __syncthreads();
+        if (M > 0) {
+            for (int m = 0; m < M; ++m) {
+                double s = 0;
+                for (int t = tid; t < n; t += 256) s = fma(Q[(int64_t)m * n + t], (double)y[t], s);
+                s = block_sum(s, red);
+                if (tid == 0) { coef[m] = s; orec[SEED_REC + m] = s; }
+            }
+            __syncthreads();
+            for (int t = tid; t < n; t += 256) y[t] = seed_detrend(y[t], coef, Q + t, n, M);
+            __threadfence_block();
+            __syncthreads();
+        }
+        float vk, vk1;
+        select_pair(y, n, (n - 1) / 2, hist, vk, vk1);
+        const float med = (n & 1) ? vk : (float)(0.5 * ((double)vk + (double)vk1));
+        float mx = -INFINITY;
+        __syncthreads();
+        for (int t = tid; t < n; t += 256) { const float v = y[t] - med; y[t] = v; mx = fmaxf(mx, v); }
+        __threadfence_block();
+        mx = seed_block_max(mx, red);
+        const double sn = get_sn_long<SPLIT>(y, c, lds, red, tabs);
+        const double thr = sig * sn;
+        double s = 0;
+        for (int t = tid; t < n; t += 256) { const double v = (double)y[t]; s += v < thr ? 0.0 : v; }
+        const double mean = block_sum(s, red) / (double)n;
+        s = 0;
+        for (int t = tid; t < n; t += 256) { const double v = (double)y[t]; const double x = (v < thr ? 0.0 : v) - mean; s = fma(x, x, s); }
+        const double rms = sqrt(block_sum(s, red) / (double)n);
+        if (tid == 0) {
+            orec[0] = thr; orec[1] = mean; orec[2] = rms == 0.0 ? 1.0 : 1.0 / rms; orec[3] = (double)med;
+            pnr[p] = (float)((double)mx / sn);
+            if (sn_keep) sn_keep[p] = sn;
+        }
+        __syncthreads();                                     // (the next pixel overwrites the row and the coefficients)
+    }
+}
+
 // One workgroup per (pixel tile, frame chunk): the records of the tile and its 1-pixel halo in LDS, then per frame quad Z of those 18 x 18 pixels (0 outside the
 // block: imfilter's zero padding, correlation_image.m:75) and Z_p * (sum of the 8 neighbours) added in fp64.  part[chunk][pixel].
 __global__ void __launch_bounds__(256) k_seed_corr(const float4 *__restrict__ hy4, int64_t d_b, int nr_b, int nc_b, int ntr, int n, int qchunk,
@@ -205,16 +265,12 @@ int seed_images_run(cnmfe_ctx *ctx, const SeedSrc &src, const float *psf, int32_
     const int64_t n = nframes, d_b = src.d;
     const int nr_b = src.nr, nc_b = src.nc;
     const int64_t nq = (n + 3) / 4;
-    DeconvCfg c{};
-    c.T = (int)n; c.P2 = 1; while (c.P2 < n) c.P2 <<= 1;
-    c.L = (int)(n / 4.5); c.nov = c.L / 2;                                   // pwelch defaults, as sn_video_run
-    c.nfft = 256; while (c.nfft < c.L) c.nfft <<= 1;
-    c.nseg = (int)((n - c.nov) / (c.L - c.nov));
-    const size_t sh_stats = ((((size_t)n + 3) & ~size_t(3)) + 2 * (size_t)c.nfft + (size_t)c.nfft / 2) * sizeof(float);
-    if (sh_stats > 160 * 1024 - 256) return fail(CNMFE_EUNSUPPORTED, "%lld frames do not fit the seed statistics kernel's LDS (trace + Welch transform in 160 KB: <= 20400)", (long long)n);
+    WelchPlan w;
+    RET(welch_cfg(ctx, n, w));
     // everything the call allocates lives in these two and is released when it returns (seeding runs once per recording, the fits want the room): the filtered
     // block, and ONE allocation for all the small arrays -- every hipFree drains the device, and a patched run makes this call once per patch
-    // (a peel session -- peel.hpp -- keeps the filtered block and the noise levels: `keep`)
+    // (a peel session -- peel.hpp -- keeps the filtered block and the noise levels: `keep`; the long flavour's trace rows and table slots are the context's
+    // deconvolution scratch, which the long deconvolution of the same recording needs at that size anyway)
     DevBuf hy_call, small;
     DevBuf &hy = keep ? keep->hy : hy_call;
     const int ntr = (nr_b + SEED_TILE - 1) / SEED_TILE, ntc = (nc_b + SEED_TILE - 1) / SEED_TILE;
@@ -256,9 +312,17 @@ int seed_images_run(cnmfe_ctx *ctx, const SeedSrc &src, const float *psf, int32_
                src.y4, d_b, nr_b, nc_b, ntr, R, dTaps, (int)taps.size(), hy.as<float4>());
         hy4 = hy.as<float4>();
     }
-    if (sh_stats > 64 * 1024) CK(hipFuncSetAttribute((const void *)k_seed_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_stats));
-    LAUNCH(ctx, "seed_stats", k_seed_stats, dim3((unsigned)d_b), dim3(256), sh_stats, c, hy4, d_b, dQ, (int)M, (double)sig, dRec, dPnr,
-           keep ? keep->sn.as<double>() : (double *)nullptr);
+    double *dSnKeep = keep ? keep->sn.as<double>() : (double *)nullptr;
+    if (w.lng) {
+        const unsigned nwg = w.nwg(d_b);
+        float *tabs;
+        RET(welch_tabs(ctx, w, nwg, &tabs));
+        RET(ctx->dscr.ybuf.ensure((size_t)nwg * (size_t)(4 * nq) * sizeof(float)));
+        WELCH_LAUNCH_LONG(ctx, "seed_stats", k_seed_stats_long, w, nwg, tabs, hy4, d_b, (const double *)dQ, (int)M, (double)sig, ctx->dscr.ybuf.as<float>(), dRec, dPnr, dSnKeep);
+    } else {
+        if (w.shmem > 64 * 1024) CK(hipFuncSetAttribute((const void *)k_seed_stats, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w.shmem));
+        LAUNCH(ctx, "seed_stats", k_seed_stats, dim3((unsigned)d_b), dim3(256), w.shmem, w.c, hy4, d_b, dQ, (int)M, (double)sig, dRec, dPnr, dSnKeep);
+    }
     const size_t sh_corr = ((size_t)4 * SEED_HN + (size_t)SEED_HN * recw) * sizeof(double);
     LAUNCH(ctx, "seed_corr", k_seed_corr, dim3((unsigned)ntile, (unsigned)nsplit), dim3(256), sh_corr, hy4, d_b, nr_b, nc_b, ntr, (int)n, qchunk,
            dQ, (int)M, dRec, dPart);

@@ -146,8 +146,10 @@ int cnmfe_estimate_noise(cnmfe_ctx *ctx, int patch_id, int64_t nframes, float *s
  * psf: psf_n x psf_n, column-major, psf_n odd and <= 25 (an even kernel is zero-padded by the caller: sources2d.seed_psf); NULL / 0 = no filter (gSig <= 0).
  * Q: nframes x M orthonormal columns (column-major, M <= 16) spanning the detrend basis of detrend_data.m:23 (nk > 1, method 'spline'): the filtered trace
  * loses its projection on them first; NULL / 0 = no detrending.  sig: the threshold factor (the reference's is 3).
- * Frames [frame0, frame0 + nframes) with frame0 == 0 and 64 <= nframes <= min(T, 20400) (the LDS-resident GetSn); anything else, and a derived (bg_ssub) patch,
- * is CNMFE_EUNSUPPORTED.  The block is filtered whole (the reference's 500^3-sample sub-patch split of :50-59 is a memory workaround and is not reproduced).
+ * Frames [frame0, frame0 + nframes) with frame0 == 0 and 64 <= nframes <= min(T, 147456) (WELCH_TMAX, the longest trace the Welch estimator takes); anything
+ * else, and a derived (bg_ssub) patch, is CNMFE_EUNSUPPORTED.  Up to 20416 frames a pixel's trace and its Welch transform share one workgroup's LDS; beyond, the
+ * statistics kernel keeps the trace in a row of the context's scratch (at most 1024 rows of 4 * ceil4(nframes) bytes, 256 from 36869 frames on: <= 151 MB, plus
+ * 12 * nfft bytes of transform tables per row from there on), which stays with the context.  The block is filtered whole (the reference's 500^3-sample sub-patch split of :50-59 is a memory workaround and is not reproduced).
  * Scratch: the filtered block, 16 * ceil(nframes / 4) * d_b bytes, allocated for the call and released before it returns (CNMFE_ENOMEM names the bytes);
  * no resident state of the patch is read or written except the centred video.  Two calls return bit-identical images.  A pixel without a neighbour inside the
  * block (a 1 x 1 block) has Cn = 0 / 0 = NaN, as in the reference; a constant trace (Sn = 0) has PNR = NaN likewise.  Outputs: d_b floats each, the patch's
@@ -180,7 +182,7 @@ int cnmfe_seed_images(cnmfe_ctx *ctx, int patch_id, const float *psf, int32_t ps
  * with Ysig the resident residual of cnmfe_residual / cnmfe_residual_ssub (called with the block's current neurons; CNMFE_ESTATE without one, a recorded or
  * pending one is realised first, as for cnmfe_get_sn).  A: d x Ksel CSC over the PATCH rows (empty columns are legal: a neuron that only touches the halo), C as
  * for cnmfe_residual; Ksel = 0 searches Ysig itself.  Per pixel the stored neurons are summed in fp64 in ascending column order and the difference is rounded
- * once to fp32; Ysig is only read.  All T frames are used (64 <= T <= 20400), there is no detrending (M = 0), y_bg takes no pixel mean (the residual carries its
+ * once to fp32; Ysig is only read.  All T frames are used (64 <= T <= 147456, as cnmfe_seed_images), there is no detrending (M = 0), y_bg takes no pixel mean (the residual carries its
  * own), and extract / apply take the seed 0-BASED in the PATCH and clip their boxes at the patch (tmp_options.d1 / d2, :176-177).  Cn_patch / PNR_patch /
  * Sn_patch: d floats (Sn may be NULL); Yres_out (may be NULL): exactly the fp32 video the session searches, d x T frame-major like cnmfe_residual's output, to
  * host or device memory (out_memspace).  The session keeps 2 x 16 * ceil(T / 4) * d bytes (HY and Yw, which starts as Yres; CNMFE_ENOMEM names them).  The
@@ -359,11 +361,13 @@ int cnmfe_traces_load(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *C, cons
  * pipe with the fp64 mean subtracted from every operand.  A row without variance gives NaN in its row and column (MATLAB's 0 / 0).  K = 0 is legal. */
 int cnmfe_trace_corr(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, int raw, double *out);
 /* merge_high_corr.m:57-66, the branch without S:  S_ = diff(X, 1, 2);  S_(:, end + 1) = 0;  S_(S_ < 2 * GetSn(S_)) = 0  with GetSn per row (fp32 differences, the Welch
- * estimator of the traces).  The result stays in the context as the source CNMFE_RES_DIFF; sn_out (K floats) and S_out (K x T ROW-MAJOR) may be NULL.  64 <= T <= 20400. */
+ * estimator of the traces).  The result stays in the context as the source CNMFE_RES_DIFF; sn_out (K floats) and S_out (K x T ROW-MAJOR) may be NULL.  64 <= T <= 147456
+ * (WELCH_TMAX; beyond 20416 frames the difference trace lives in its output row, not in LDS: the long flavour, bit-equal where both run). */
 int cnmfe_trace_diff_spikes(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, float *sn_out, float *S_out);
 /* tag_neurons_parallel's per-trace quantities (Sources2D.m:1700-1709) of the context's C, C_raw, S, one workgroup per trace, one pass:
  * out[4 k + 0] = max(C(k, :)), [1] = std(C_raw(k, :) - C(k, :), 0) in fp64, [2] = GetSn(C_raw(k, :)), [3] = |{t >= 2 : S(k, t) > 0}| (-1 without an S).
- * K must be the bound matrix'; the bit arithmetic (and nnz(A(:, k)) < min_pixel) is the host's.  64 <= T <= 20400. */
+ * K must be the bound matrix'; the bit arithmetic (and nnz(A(:, k)) < min_pixel) is the host's.  64 <= T <= 147456 (WELCH_TMAX; beyond 20416 frames
+ * C_raw's row is read in place). */
 int cnmfe_trace_tags(cnmfe_ctx *ctx, int32_t K, double *out /* 4 K */);
 /* The K-changing step of the three merges and of obj.delete, in place on the context's matrices (K rows before, nkeep after):
  *   group g = rows grp_idx[grp_ptr[g] .. grp_ptr[g + 1]) with weights w[...] (same positions): ci = w' C_raw(IDs, :) summed in fp64 in that order and rounded to fp32
@@ -564,7 +568,9 @@ int cnmfe_synchronize(cnmfe_ctx *ctx);
  *   prealloc          default 1: cnmfe_fit_reserve may allocate the fit's large buffers ahead of the first fit
  * A deployment short of HBM sets win_i8 = proj_tiled = 0 (and solve_packed = 0) or leaves it to the engine, which falls back by itself.
  * Diagnostics (scripts/): solve_probe, r1_probe (phase probes: results are NOT the product's), deconv_trace, host_trace (1: host-side phase times of every call on
- * stderr, 2: + slow launch calls), debug (1: NaN-poison never-computed table entries).
+ * stderr, 2: + slow launch calls), debug (1: NaN-poison never-computed table entries), trace_long (default 0: the seed-statistics, peel-trace, trace-difference and
+ * trace-tag kernels keep the trace in LDS while it fits beside the Welch transform, T <= 20416, and in global memory beyond; 1: the long flavour at every T --
+ * results are bit-equal, tests/test_gpu_long_flavour.py).
  * Round 6 removed the retired names rounds 2-5 still accepted and ignored (gram_mode, gram_flush, solve_defer, solve_mode, solve_gfill, gram_kernel, r1_arc_d,
  * r1_arc_bias, r1_duo_ord) and the experiment switches tile_order, gram_probe, r1_nseg.
  * Every option can be preset for a process with CNMFE_OPTS="name=value,..." (logged once on stderr). */
