@@ -517,21 +517,11 @@ cnmfe_ctx::~cnmfe_ctx() {
     if (ev_fork) (void)hipEventDestroy(ev_fork);
 }
 
-// ---- execution lanes (common.hpp, cnmfe_lane) ----
-void cnmfe_ctx::swap_lane(cnmfe_lane &L) {
-    std::swap(stream_, L.stream_); std::swap(pseg, L.pseg); std::swap(npseg, L.npseg); pin.swap(L.pin); std::swap(spatial_nnz, L.spatial_nnz);
-    for (int i = 0; i < 32; ++i) vp[i].swap(L.vp[i]);          // (the high-water sizes hw_* stay with the context: what one lane's patches needed, the other lanes' buffers get at once)
-    std::swap(last_ldc, L.last_ldc);
-    ysig_low.swap(L.ysig_low); up_tmp.swap(L.up_tmp); bgs_r.swap(L.bgs_r); bgs_b.swap(L.bgs_b); bgs_upr.swap(L.bgs_upr); bgs_upc.swap(L.bgs_upc);
-    std::swap(bgs_patch, L.bgs_patch); std::swap(bgs_d1s, L.bgs_d1s); std::swap(bgs_dF, L.bgs_dF);
-    bf.swap(L.bf); dig_smax.swap(L.dig_smax); dig_rspart.swap(L.dig_rspart); dig_scale.swap(L.dig_scale); tdig.swap(L.tdig); tscale.swap(L.tscale); gk.swap(L.gk);
-    win_items.swap(L.win_items); bf2.swap(L.bf2); outl_cnt.swap(L.outl_cnt); outl_sel.swap(L.outl_sel); cov.swap(L.cov); rowsum.swap(L.rowsum);
-    for (int i = 0; i < 16; ++i) tmp[i].swap(L.tmp[i]);
-    for (int i = 0; i < 7; ++i) inc[i].swap(L.inc[i]);
-    for (int i = 0; i < 4; ++i) stg[i].swap(L.stg[i]);
-    wcodes.swap(L.wcodes); solve_fill.swap(L.solve_fill); stage.swap(L.stage);
-    for (int i = 0; i < 24; ++i) scr[i].swap(L.scr[i]);
-    dscr.swap(L.dscr);
+// ---- execution lanes (common.hpp, LaneState) ----
+void cnmfe_ctx::patches_changed() {                          // (they may name the patch that just went)
+    early.valid = false;
+    kept.patch_gone();
+    for (cnmfe_lane *L : lanes) L->state.kept.patch_gone();
 }
 int cnmfe_ctx::activate(int lane) {
     if (lanes.empty() || lane == cur_lane) {
@@ -543,8 +533,8 @@ int cnmfe_ctx::activate(int lane) {
     }
     if (lane < 0 || lane >= (int)lanes.size()) return fail(CNMFE_ESTATE, "lane %d of %d", lane, (int)lanes.size());
     if (npseg) flush_copies();                               // an inactive lane holds no held-back uploads: whoever reads their targets from another lane finds them queued
-    swap_lane(*lanes[cur_lane]);                             // the active lane's members into its storage ...
-    swap_lane(*lanes[lane]);                                 // ... and this lane's out of its own
+    lanes[cur_lane]->store(*this);                           // the active lane's state into its storage ...
+    lanes[lane]->load(*this);                                // ... and this lane's out of its own
     cur_lane = lane;
     if (lane != 0) {
         if (lanes[lane]->fork_seen != fork_gen) { CK(hipStreamWaitEvent(stream_, ev_fork, 0)); lanes[lane]->fork_seen = fork_gen; }
@@ -572,23 +562,41 @@ int cnmfe_ctx::fork_mark() {
     ++fork_gen;
     return 0;
 }
-static int lanes_set(cnmfe_ctx *ctx, int64_t n) {
-    if (n < 1 || n > 4) return fail(CNMFE_EINVAL, "option lanes = %lld: 1 .. 4", (long long)n);
-    if (!ctx->patches.empty() && (int)std::max<size_t>(1, ctx->lanes.size()) != n) return fail(CNMFE_ESTATE, "option lanes is set before the first patch is created");
-    if (n == 1 || (int)ctx->lanes.size() == n) return 0;
-    CK(hipSetDevice(ctx->device));
+// Option "lanes", before the first patch: the lanes are built as a whole and committed only when every stream, event and arena exists; a different count replaces
+// them, lanes = 1 drops them, the count in force does nothing.
+static void lanes_delete(std::vector<cnmfe_lane *> &v) { for (cnmfe_lane *L : v) delete L; v.clear(); }
+static int lanes_build(int n, std::vector<cnmfe_lane *> &v) {
     for (int l = 0; l < n; ++l) {
         cnmfe_lane *L = new cnmfe_lane();
-        ctx->lanes.push_back(L);
+        v.push_back(L);
         CK(hipEventCreateWithFlags(&L->ev, hipEventDisableTiming));
         if (l == 0) continue;                                // (lane 0 is the active one: its members are the context's own)
-        CK(hipStreamCreate(&L->stream_));
-        hipLaunchKernelGGL(k_scratch_warm, dim3(1), dim3(64), 0, L->stream_, (int *)nullptr, 3);       // (its hardware queue now, not inside the first update)
-        CK(hipStreamSynchronize(L->stream_));
-        if (L->pin.init(size_t(64) << 20) != 0) return fail(CNMFE_EHIP, "pinned staging arena (64 MB) of lane %d could not be allocated", l);
+        CK(hipStreamCreate(&L->state.stream_));
+        hipLaunchKernelGGL(k_scratch_warm, dim3(1), dim3(64), 0, L->state.stream_, (int *)nullptr, 3);       // (its hardware queue now, not inside the first update)
+        CK(hipStreamSynchronize(L->state.stream_));
+        if (L->state.pin.init(size_t(64) << 20) != 0) return fail(CNMFE_EHIP, "pinned staging arena (64 MB) of lane %d could not be allocated", l);
     }
-    CK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-    CK(hipEventRecord(ctx->ev_fork, ctx->st()));
+    return 0;
+}
+static int lanes_set(cnmfe_ctx *ctx, int64_t n) {
+    if (n < 1 || n > 4) return fail(CNMFE_EINVAL, "option lanes = %lld: 1 .. 4", (long long)n);
+    const int live = (int)std::max<size_t>(1, ctx->lanes.size());
+    if (!ctx->patches.empty() && live != n) return fail(CNMFE_ESTATE, "option lanes is set before the first patch is created");
+    if (live == n) return 0;
+    CK(hipSetDevice(ctx->device));
+    if (!ctx->lanes.empty()) {                               // (no patch yet: lane 0 is active and the stored lanes have been given nothing that anybody waits for)
+        RET(ctx->join_lanes());
+        CK(hipStreamSynchronize(ctx->st()));
+        lanes_delete(ctx->lanes);
+        ctx->cur_lane = 0; ctx->spatial_lane = 0; ctx->patches_created = 0;
+    }
+    if (n == 1) return 0;
+    if (!ctx->ev_fork) CK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+    std::vector<cnmfe_lane *> built;
+    int rc = lanes_build((int)n, built);
+    if (!rc && hipEventRecord(ctx->ev_fork, ctx->st()) != hipSuccess) rc = fail(CNMFE_EHIP, "the fork event of the lanes could not be recorded");
+    if (rc) { lanes_delete(built); return rc; }
+    ctx->lanes.swap(built);
     return 0;
 }
 
@@ -681,8 +689,8 @@ int cnmfe_set_option(cnmfe_ctx *ctx, const char *name, int64_t value) {
 int cnmfe_get_option(cnmfe_ctx *ctx, const char *name, int64_t *value) {
     if (!ctx || !name || !value) return fail(CNMFE_EINVAL, "null argument");
     const struct { const char *n; int64_t v; } counters[] = {{"temporal_early_hits", ctx->early_hits}, {"temporal_early_drops", ctx->early_drops}, {"temporal_early_declined", ctx->early_declined},
-                                                              {"temporal_early_entries", ctx->early_nent}, {"temporal_proj_entries", ctx->last_nent}, {"temporal_nowait", ctx->sweep_nowait},
-                                                              {"merge_trace_uploads", ctx->merge_uploads},
+                                                              {"temporal_early_entries", ctx->early.nent}, {"temporal_proj_entries", ctx->last_nent}, {"temporal_nowait", ctx->sweep_nowait},
+                                                              {"merge_trace_uploads", ctx->merge_uploads}, {"lanes_live", (int64_t)std::max<size_t>(1, ctx->lanes.size())},
                                                               {"bound_K", ctx->bound_valid ? (int64_t)ctx->bound_K : 0}, {"bound_T", ctx->bound_valid ? ctx->bound_T : 0}};
     for (const auto &c : counters) if (!strcmp(c.n, name)) { *value = c.v; return 0; }
     auto it = ctx->opts.find(name);
@@ -700,7 +708,7 @@ int cnmfe_patch_create(cnmfe_ctx *ctx, int patch_id, const int32_t pr[4], const 
                     pr[0], pr[1], pr[2], pr[3], br[0], br[1], br[2], br[3], d1, d2);
     CK(hipSetDevice(ctx->device));
     if (ctx->patches.count(patch_id)) { delete ctx->patches[patch_id]; ctx->patches.erase(patch_id); }
-    ctx->early.valid = false; ctx->spatial_patch = nullptr;  // (they may name the patch that just went)
+    ctx->patches_changed();
     Patch *P = new Patch();
     P->lane = ctx->lanes.empty() ? 0 : (ctx->patches_created++ % (int)ctx->lanes.size());
     memcpy(P->prect, pr, sizeof(P->prect)); memcpy(P->brect, br, sizeof(P->brect));
@@ -1190,9 +1198,9 @@ int cnmfe_update_spatial_fetch_async(cnmfe_ctx *ctx, float *A_out_pinned, int64_
     if (!A_out_pinned && nnz) return fail(CNMFE_EINVAL, "null A_out");
     CK(hipSetDevice(ctx->device));
     RET(ctx->activate(ctx->spatial_lane));
-    if (ctx->spatial_nnz < 0 || nnz != ctx->spatial_nnz) return fail(CNMFE_ESTATE, "no deferred spatial update of %lld values (last one: %lld)", (long long)nnz, (long long)ctx->spatial_nnz);
+    RET(require_kept_spatial(ctx, nnz, false));
     // A_out_pinned: PINNED host memory (cnmfe_host_alloc) of at least nnz floats rounded up to 16 bytes -- the copy is a kernel writing through the mapping
-    return ticket_record(ctx, ticket, ctx->scr[6].p, A_out_pinned, (size_t)nnz * sizeof(float));
+    return ticket_record(ctx, ticket, ctx->scr[kept::SCR_AVAL].p, A_out_pinned, (size_t)nnz * sizeof(float));
 }
 
 int cnmfe_ticket_wait(cnmfe_ctx *ctx, int64_t ticket) {
@@ -1384,7 +1392,7 @@ int cnmfe_stitch_add(cnmfe_ctx *ctx, int32_t K_m, const int32_t *ind_m) {
     if (!ctx->stitch_open) return fail(CNMFE_ESTATE, "cnmfe_stitch_begin has not been called");
     if (K_m == 0) return 0;
     if (K_m < 0 || !ind_m) return fail(CNMFE_EINVAL, "bad K_m / null ind_m");
-    if (!ctx->last_t_valid || ctx->last_t_K != K_m || ctx->last_t_T != ctx->stitch_T)
+    if (!ctx->last_t.valid || ctx->last_t.K != K_m || ctx->last_t.T != ctx->stitch_T)
         return fail(CNMFE_ESTATE, "no temporal result of %d rows x %lld frames on the device (the last cnmfe_hals_temporal / cnmfe_fast_temporal call)", K_m, (long long)ctx->stitch_T);
     std::vector<char> seen((size_t)ctx->stitch_K, 0);
     for (int32_t j = 0; j < K_m; ++j) {
@@ -1395,10 +1403,10 @@ int cnmfe_stitch_add(cnmfe_ctx *ctx, int32_t K_m, const int32_t *ind_m) {
     CK(hipSetDevice(ctx->device));
     GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;          // (lanes: lane 0, behind the other lanes; they wait for what this queues)
     RET(to_dev(ctx, ctx->scr[23], ind_m, (size_t)K_m));
-    LAUNCH(ctx, "stitch_add", k_stitch_add, dim3((unsigned)((ctx->stitch_T + 255) / 256), (unsigned)K_m), dim3(256), 0, ctx->last_craw.as<float>(), ctx->last_t_ldc,
-           ctx->last_aa.as<float>(), ctx->scr[23].as<int>(), ctx->stitch.as<float>(), ctx->stitch_ld, ctx->stitch_T);
+    LAUNCH(ctx, "stitch_add", k_stitch_add, dim3((unsigned)((ctx->stitch_T + 255) / 256), (unsigned)K_m), dim3(256), 0, ctx->last_t.craw.as<float>(), ctx->last_t.ldc,
+           ctx->last_t.aa.as<float>(), ctx->scr[23].as<int>(), ctx->stitch.as<float>(), ctx->stitch_ld, ctx->stitch_T);
     // (ind_m went through the pinned arena; the call returns with the accumulation queued behind the patch's HALS sweeps)
-    ctx->last_t_valid = false;
+    ctx->last_t.valid = false;
     return 0;
 }
 

@@ -741,8 +741,9 @@ int bg_reserve(cnmfe_ctx *ctx, Patch *P) {
     if (planes) { RET(reserve(P->dig, (size_t)nblk * g.Tpad * BLKPX * sizeof(float))); RET(P->dig_sc.ensure((size_t)nblk * BLKPX * sizeof(double))); }
     if (ctx->opt("r1_virtual", 1) != 0) {
         // the temporal projection on the int8 pipe reads pixel-major planes instead of the read-order copy
-        if (planes && ctx->opt("proj_i8", 1) != 0) RET(reserve(P->digp, (size_t)nblk * g.Tpad * BLKPX * sizeof(float)));
-        else if (ctx->opt("proj_tiled", 1) != 0) RET(reserve(P->yt4, (size_t)nblk * ((P->Tc + 15) >> 4) * 64 * 64 * sizeof(float4)));
+        const kept::ProjOpts po = proj_opts(ctx);
+        if (planes && po.i8 != 0) RET(reserve(P->digp, (size_t)nblk * g.Tpad * BLKPX * sizeof(float)));
+        else if (po.tiled != 0) RET(reserve(P->yt4, (size_t)nblk * ((P->Tc + 15) >> 4) * 64 * 64 * sizeof(float4)));
     }
     return 0;
 }

@@ -15,6 +15,7 @@
 #include "../../include/cnmfe.h"
 #include "ring_plan.hpp"
 #include "residual_plan.hpp"
+#include "kept_results.hpp"
 
 namespace cnmfe {
 
@@ -46,6 +47,12 @@ struct DevBuf {
     ~DevBuf() { if (p) { pin_flush_range(p, cap); (void)hipFree(p); } }
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
+    // a move steals the allocation and leaves the source empty; what the target held is released first (nothing, wherever two buffers change places)
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) { if (p) { pin_flush_range(p, cap); (void)hipFree(p); } p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
     int ensure(size_t bytes) {
         if (bytes <= cap) return 0;
         // a buffer that GROWS gets half as much again: index lists and value arrays follow nnz(A) / nnz(IND), which creep up over the first iterations, and every
@@ -261,9 +268,7 @@ struct Patch {
 };
 
 // device scratch of the OASIS kernels (deconv.hip): pool / task tables, grown on demand and kept with the context
-struct DeconvScratch { DevBuf pv, pw, pt, pl, tkp, tko, tkl, tkv, pnum, list, ybuf, obuf, tbuf;
-    void swap(DeconvScratch &o) { DevBuf *a[] = {&pv, &pw, &pt, &pl, &tkp, &tko, &tkl, &tkv, &pnum, &list, &ybuf, &obuf, &tbuf}, *b[] = {&o.pv, &o.pw, &o.pt, &o.pl, &o.tkp, &o.tko, &o.tkl, &o.tkv, &o.pnum, &o.list, &o.ybuf, &o.obuf, &o.tbuf};
-        for (int i = 0; i < 13; ++i) a[i]->swap(*b[i]); } };
+struct DeconvScratch { DevBuf pv, pw, pt, pl, tkp, tko, tkl, tkv, pnum, list, ybuf, obuf, tbuf; };      // (moves member by member: DevBuf)
 
 // One patch's temporal update set up but not swept (cnmfe_hals_temporal_job): its projections, A'A lists and traces in buffers of its own, its
 // Gauss-Seidel level schedule on the host.  cnmfe_temporal_jobs_sweep then runs level l of EVERY job of the context in one launch -- the patches of a
@@ -289,9 +294,17 @@ namespace cnmfe {
 // the arena and enqueues the transfer from there, so (a) the source may go away as soon as to_dev returns and (b) the call does not have to
 // drain the stream for that -- the host prepares the next patch while the GPU still works on this one.  Two halves: before allocating in a
 // half again, the host waits for the event that marks the last transfer enqueued out of it.
-struct PinArena {
-    char *p = nullptr; size_t cap = 0, off = 0; int half = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr}; bool ev_set[2] = {false, false};
+struct PinArenaFields { char *p = nullptr; size_t cap = 0, off = 0; int half = 0; hipEvent_t ev[2] = {nullptr, nullptr}; bool ev_set[2] = {false, false}; };
+struct PinArena : PinArenaFields {
+    PinArena() = default;
+    PinArena(const PinArena &) = delete; PinArena &operator=(const PinArena &) = delete;
+    // a move steals the arena and its events and leaves the source empty (the fields as a whole: no list of them here)
+    PinArena(PinArena &&o) noexcept : PinArenaFields(o) { static_cast<PinArenaFields &>(o) = PinArenaFields(); }
+    PinArena &operator=(PinArena &&o) noexcept {
+        if (this != &o) { release(); static_cast<PinArenaFields &>(*this) = o; static_cast<PinArenaFields &>(o) = PinArenaFields(); }
+        return *this;
+    }
+    void release() { if (p) (void)hipHostFree(p); for (int i = 0; i < 2; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]); static_cast<PinArenaFields &>(*this) = PinArenaFields(); }
     int init(size_t bytes) {
         if (p) return 0;
         if (hipHostMalloc((void **)&p, bytes, hipHostMallocDefault) != hipSuccess) { p = nullptr; return -1; }
@@ -311,8 +324,7 @@ struct PinArena {
         }
         void *r = p + off; off += n; return r;
     }
-    void swap(PinArena &o) { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(off, o.off); std::swap(half, o.half); for (int i = 0; i < 2; ++i) { std::swap(ev[i], o.ev[i]); std::swap(ev_set[i], o.ev_set[i]); } }
-    ~PinArena() { if (p) (void)hipHostFree(p); for (int i = 0; i < 2; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]); }
+    ~PinArena() { release(); }
 };
 }  // namespace cnmfe
 
@@ -329,30 +341,59 @@ struct PinSegs { const uint4 *src[PIN_NSEG]; uint4 *dst[PIN_NSEG]; unsigned n16[
 
 // Execution lanes (option "lanes", round 6).  The patches of a rank are independent inside each of the three updates (the reference's parfor), and most of a small
 // patch's kernels are a few workgroups with 8-10 us of dispatch latency between two dependent ones: on ONE stream sixteen 128 x 128 patches leave the chip idle for a
-// sixth of the iteration.  A lane is a stream + a full set of the context's per-call scratch (+ its own pinned upload arena and held-back uploads); a patch belongs to
-// lane (creation order) mod lanes, every call with a patch id ACTIVATES the patch's lane first (get_patch), and the members below are swapped in and out of the
-// context, so that no code path knows about lanes.  Calls without a patch id that touch what all patches share (the bound traces, the stitch accumulator, the
-// temporal jobs' sweep, post-processing) run on lane 0 after lane 0 has been made to wait for the other lanes (join), and leave an event the other lanes wait for
-// at their next activation (fork) -- cnmfe::GlobalScope.  lanes = 1 (the default): none of this does anything.
+// sixth of the iteration.  A lane is a stream + a full set of the context's per-call scratch (+ its own pinned upload arena and held-back uploads): LaneState, THE list
+// of what a lane owns.  The context derives from it -- its own LaneState is the active lane's -- and a stored lane (cnmfe_lane) holds one; a patch belongs to lane
+// (creation order) mod lanes, every call with a patch id ACTIVATES the patch's lane first (get_patch), and the two states change places as a whole (cnmfe_lane::store / load: moves), so that no
+// code path knows about lanes and a member added here is a member of every lane.  Calls without a patch id that touch what all patches share (the bound traces, the
+// stitch accumulator, the temporal jobs' sweep, post-processing) run on lane 0 after lane 0 has been made to wait for the other lanes (join), and leave an event the
+// other lanes wait for at their next activation (fork) -- cnmfe::GlobalScope.  lanes = 1 (the default): none of this does anything.  ("Lane state and kept results")
+namespace cnmfe {
+struct LaneState {
+    hipStream_t stream_ = nullptr;                         // the compute stream (owned by whoever holds the state: ~cnmfe_ctx the active one, ~cnmfe_lane a stored one)
+    PinSegs pseg{}; int npseg = 0;                         // the held-back small uploads (cnmfe_ctx::st)
+    PinArena pin;
+    DevBuf vp[32];            // scratch of the sweep-free projections (vproj.hip; [16..]: the bg_ssub > 1 forms)
+    int64_t last_ldc = 0;     // row stride of the centred traces the last residual_run left in tmp[1]
+    DevBuf ysig_low;          // bg_ssub > 1: residual sweep of the low-resolution patch
+    DevBuf up_tmp;            // bg_ssub > 1: column-upsampled W*(...) (low rows x block columns)
+    DevBuf bgs_r, bgs_b, bgs_upr, bgs_upc;   // bg_ssub > 1, reconstruct_background / compute_RSS: R_low, W*R_low, replication maps
+    int bgs_patch = -1, bgs_d1s = 0; int64_t bgs_dF = 0;   // the patch bgs_b belongs to (cnmfe_background_ssub)
+    DevBuf bf;                // tiled centred background residual  [blk][t'][256] fp32
+    DevBuf dig_smax;          // gram_i8.hpp: per block-region pixel max |Bf| (float bits) of the build in flight
+    DevBuf dig_rspart;        // gram_i8.hpp: per frame chunk the row sums of the build in flight (reduced in a fixed order by k_rs_reduce)
+    DevBuf dig_scale;         // gram_i8.hpp: per block-region pixel the scale of its 32-bit fixed-point trace (the int8-digit table build)
+    DevBuf tdig, tscale, gk, win_items;   // win_proj_i8.hpp: digit planes / scales of the centred traces, their K x K Gram matrix, the (block, trace group) work items
+    DevBuf bf2, outl_cnt, outl_sel;   // outlier branch of the ring fit: clipped copy of bf, outliers per frame, kept frames
+    DevBuf cov;               // block-pair covariances [pair][256][256] (fp64)
+    DevBuf rowsum;            // [blk][256] double
+    DevBuf tmp[16];           // small scratch
+    DevBuf inc[7];            // incremental ring regression: block footprint lists, U~, trace sums
+    DevBuf stg[4];            // ring_solve_staged.hpp: per-neuron window metadata, per-list-position metadata, the windows of U~ and of A
+    DevBuf wcodes, solve_fill;   // ring solve: the block-pair codes per window origin (k_win_codes); the fill values {0, 1} in global memory (ring_solve.hpp)
+    DevBuf stage;             // upload staging
+    // per-call device scratch of the factor updates (factor.hip, deconv.hip): grown on demand, NEVER freed between calls -- a hipMalloc /
+    // hipFree pair per buffer and call cost more than the small kernels they serve, and hipFree drains the device
+    DevBuf scr[24];
+    DeconvScratch dscr;
+    kept::KeptSpatial kept;   // what the last deferred spatial update of this lane left in scr[SCR_COLPTR | SCR_EROW | SCR_AVAL | SCR_KEEP] (kept_results.hpp)
+    LaneState() = default;
+    LaneState(LaneState &&) = default; LaneState &operator=(LaneState &&) = default;
+};
+}  // namespace cnmfe
+
 struct cnmfe_lane {
-    hipStream_t stream_ = nullptr; cnmfe::PinSegs pseg{}; int npseg = 0; cnmfe::PinArena pin; int64_t spatial_nnz = -1;
-    cnmfe::DevBuf vp[32]; size_t hw_vp[32] = {}; int64_t last_ldc = 0;
-    cnmfe::DevBuf ysig_low, up_tmp, bgs_r, bgs_b, bgs_upr, bgs_upc; int bgs_patch = -1, bgs_d1s = 0; int64_t bgs_dF = 0;
-    cnmfe::DevBuf bf, dig_smax, dig_rspart, dig_scale, tdig, tscale, gk, win_items, bf2, outl_cnt, outl_sel, cov, rowsum, tmp[16];
-    size_t hw_cc = 0, hw_cm = 0, hw_wa[3] = {0, 0, 0};
-    cnmfe::DevBuf inc[7], stg[4], wcodes, solve_fill, stage, scr[24]; cnmfe::DeconvScratch dscr;
-    hipEvent_t ev = nullptr; int64_t fork_seen = 0; bool dirty = false;      // (these three describe the lane itself and are never swapped)
-    ~cnmfe_lane() { if (stream_) (void)hipStreamDestroy(stream_); if (ev) (void)hipEventDestroy(ev); }
+    cnmfe::LaneState state;                                                  // this lane's members while another lane is the active one (empty while it is active)
+    // a lane switch is two moves of a whole state (two std::swaps cost three moves each: 1.0 us per switch on the host against 0.32)
+    void store(cnmfe::LaneState &active) { state = std::move(active); }
+    void load(cnmfe::LaneState &active) { active = std::move(state); state.stream_ = nullptr; }   // (the stream is a raw handle: the move copied it, and ~cnmfe_lane destroys what it finds here)
+    hipEvent_t ev = nullptr; int64_t fork_seen = 0; bool dirty = false;      // (these three describe the lane itself and never change places)
+    ~cnmfe_lane() { if (state.stream_) (void)hipStreamDestroy(state.stream_); if (ev) (void)hipEventDestroy(ev); }
 };
 
-struct cnmfe_ctx {
+struct cnmfe_ctx : cnmfe::LaneState {
     int device = 0;
-    hipStream_t stream_ = nullptr;
-    cnmfe::PinSegs pseg; int npseg = 0;
     void flush_copies();                                   // api.hip
     hipStream_t st() { if (npseg) flush_copies(); return stream_; }   // the compute stream, every held-back upload enqueued first (npseg: written by this context's own thread only, pin_flush_range)
-    cnmfe::PinArena pin;
-    int64_t spatial_nnz = -1;                              // values of the last cnmfe_update_spatial still in scr[6] (deferred fetch)
     hipStream_t copy_stream = nullptr;                     // device -> pinned host downloads that should not hold up the compute stream
     // option fit_side (bg.hip, SideScope): the second stream a steady-state ring fit queues its set-up on, beside the window projection; created at its first use at
     // the compute stream's priority, with the event the side stream waits for (fork) and the one the compute stream waits for (join)
@@ -368,51 +409,24 @@ struct cnmfe_ctx {
     static constexpr size_t TICKET_FLAGS = 1024;
     cnmfe::Profiler prof;
     std::map<int, cnmfe::Patch *> patches;
-    // scratch shared by all patches of this context (sized for the largest)
+    // shared by all patches and all lanes of this context
     cnmfe::DevBuf bound;      // trace matrix bound with cnmfe_traces_bind (K x ldc fp32), passed as c_order = CNMFE_BOUND
     int32_t bound_K = 0; int64_t bound_T = 0; int bound_order = 1; bool bound_valid = false;
     int64_t bound_gen = 0;    // counts the changes of the bound matrix' CONTENT (cnmfe_traces_bind, the stitch, deconvTemporal on it): what a table derived from its rows is valid for
-    cnmfe::DevBuf vp[32];     // scratch of the sweep-free projections (vproj.hip; [16..]: the bg_ssub > 1 forms)
-    size_t hw_vp[32] = {};
-    int64_t last_ldc = 0;     // row stride of the centred traces the last residual_run left in tmp[1]
-    cnmfe::DevBuf ysig_low;   // bg_ssub > 1: residual sweep of the low-resolution patch
-    cnmfe::DevBuf up_tmp;     // bg_ssub > 1: column-upsampled W*(...) (low rows x block columns)
-    cnmfe::DevBuf bgs_r, bgs_b, bgs_upr, bgs_upc;   // bg_ssub > 1, reconstruct_background / compute_RSS: R_low, W*R_low, replication maps
-    int bgs_patch = -1, bgs_d1s = 0; int64_t bgs_dF = 0;   // the patch bgs_b belongs to (cnmfe_background_ssub)
-    cnmfe::DevBuf bf;         // tiled centred background residual  [blk][t'][256] fp32
-    cnmfe::DevBuf dig_smax;   // gram_i8.hpp: per block-region pixel max |Bf| (float bits) of the build in flight
-    cnmfe::DevBuf dig_rspart; // gram_i8.hpp: per frame chunk the row sums of the build in flight (reduced in a fixed order by k_rs_reduce)
-    cnmfe::DevBuf dig_scale;  // gram_i8.hpp: per block-region pixel the scale of its 32-bit fixed-point trace (the int8-digit table build)
-    cnmfe::DevBuf tdig, tscale, gk, win_items;   // win_proj_i8.hpp: digit planes / scales of the centred traces, their K x K Gram matrix, the (block, trace group) work items
-    cnmfe::DevBuf bf2, outl_cnt, outl_sel;   // outlier branch of the ring fit: clipped copy of bf, outliers per frame, kept frames
-    cnmfe::DevBuf cov;        // block-pair covariances [pair][256][256] (fp64)
-    cnmfe::DevBuf rowsum;     // [blk][256] double
-    cnmfe::DevBuf tmp[16];    // small scratch
-    size_t hw_cc = 0, hw_cm = 0, hw_wa[3] = {0, 0, 0};     // high-water sizes of the buffers that rotate through tmp[1], tmp[2], tmp[8..10] (DevBuf::ensure_hw)
-    cnmfe::DevBuf inc[7];     // incremental ring regression: block footprint lists, U~, trace sums
-    cnmfe::DevBuf stg[4];     // ring_solve_staged.hpp: per-neuron window metadata, per-list-position metadata, the windows of U~ and of A
-    cnmfe::DevBuf wcodes, solve_fill;   // ring solve: the block-pair codes per window origin (k_win_codes); the fill values {0, 1} in global memory (ring_solve.hpp)
-    cnmfe::DevBuf stage;      // upload staging
-    // per-call device scratch of the factor updates (factor.hip, deconv.hip): grown on demand, NEVER freed between calls -- a hipMalloc /
-    // hipFree pair per buffer and call cost more than the small kernels they serve, and hipFree drains the device
-    cnmfe::DevBuf scr[24];
-    cnmfe::DeconvScratch dscr;
-    // the traces the last cnmfe_hals_temporal[_deconv] / cnmfe_fast_temporal left on the device (C_raw rows, row stride last_t_ldc, and aa): what
-    // cnmfe_stitch_add folds into the stitch accumulator without a host round trip
-    cnmfe::DevBuf last_craw, last_aa;
+    // high-water sizes of the buffers that change hands between the scratch and the patches (DevBuf::ensure_hw): vp[], and what rotates through tmp[1], tmp[2],
+    // tmp[8..10].  They stay with the context: what one lane's patches needed, the other lanes' buffers get at once
+    size_t hw_vp[32] = {}, hw_cc = 0, hw_cm = 0, hw_wa[3] = {0, 0, 0};
+    // the traces the last cnmfe_hals_temporal[_deconv] / cnmfe_fast_temporal left on the device (C_raw rows of stride ldc, and aa): what cnmfe_stitch_add folds
+    // into the stitch accumulator without a host round trip.  Written by the non-job temporal updates only, void while one runs, consumed by the stitch
+    struct LastTemporal { cnmfe::DevBuf craw, aa; int32_t K = 0; int64_t ldc = 0, T = 0; bool valid = false;
+        void set(int32_t K_, int64_t ldc_, int64_t T_) { K = K_; ldc = ldc_; T = T_; valid = true; } } last_t;
     // The temporal projection queued behind the connectivity kernel (option temporal_early, factor.hip: temporal_early_project; DESIGN.md section 3, "the hand-over").
-    // early_a: keep ? value : 0 on the mask's pattern; early_u: U = B' Yc of exactly those values.  Nothing else writes either.  The tag says what early_u is valid
+    // a: keep ? value : 0 on the mask's pattern; u: U = B' Yc of exactly those values.  Nothing else writes either.  The tag (kept_results.hpp) says what u is valid
     // for; temporal_run takes it only when the caller claimed the token (its A IS that spatial result) and every field still holds, and drops it otherwise.
-    struct EarlyU {
-        bool valid = false; int64_t token = 0, claimed = 0;
-        cnmfe::Patch *P = nullptr; int32_t K = 0; int64_t ldc = 0, T = 0, spatial_gen = 0, request_gen = 0;      // request_gen (ResidualState::gen): W, b0 and the video only change in front of a new residual request
-        int64_t proj_i8 = 0, proj_i8_planes = 0, proj_tiled = 0;                                             // the options that select the projection kernel
-    } early;
-    cnmfe::DevBuf early_a, early_u;
-    cnmfe::Patch *spatial_patch = nullptr; int32_t spatial_K = 0;        // what spatial_run recorded: the patch and K of the result in scr[6]
-    int64_t spatial_gen = 0, conn_gen = -1;                              // spatial results so far; the one whose keep flags lie in scr[14] with its pattern still in scr[0], scr[1] (-1: none)
+    struct EarlyU : cnmfe::kept::EarlyTag { cnmfe::DevBuf a, u; int64_t nent = 0; } early;      // nent: (block, neuron) entries of that projection (a counter)
+    int64_t spatial_gen = 0;                                             // spatial results so far, over all lanes (KeptSpatial::gen, EarlyTag::spatial_gen)
     int64_t last_nent = 0;                                               // (block, neuron) entries of the last vproj_temporal
-    int64_t early_seq = 0, early_hits = 0, early_drops = 0, early_declined = 0, early_nent = 0, sweep_nowait = 0;   // counters (cnmfe_get_option)
+    int64_t early_seq = 0, early_hits = 0, early_drops = 0, early_declined = 0, sweep_nowait = 0;   // counters (cnmfe_get_option)
     std::vector<cnmfe::TemporalJob *> tjobs; int tjobs_used = 0;          // cnmfe_hals_temporal_job: kept (with their buffers) from update to update, counted from cnmfe_stitch_begin
     cnmfe::DevBuf dcv_c, dcv_s, dcv_pars, dcv_sn;          // cnmfe_deconv_temporal_bound: C_raw - b (after the swap with `bound`), S, kernel_pars, sn -- read by the copy stream, so not shared scratch
     // merging (merge.hpp): dcv_c / dcv_s / dcv_pars / dcv_sn are the C_raw, S, kernel_pars, sn that belong to the bound matrix C while residents_gen == bound_gen
@@ -421,7 +435,6 @@ struct cnmfe_ctx {
     cnmfe::DevBuf mrg[23];                                 // [0] an uploaded source, [1] the result of cnmfe_trace_diff_spikes (diff_K x diff_T), [2..5] moments / K x K / sn, [6..22] cnmfe_merge_apply
     int32_t diff_K = 0; int64_t diff_T = 0;
     int64_t merge_uploads = 0;                             // counter merge_trace_uploads: K x T matrices the merge / tag entry points took from the host
-    int32_t last_t_K = 0; int64_t last_t_ldc = 0, last_t_T = 0; bool last_t_valid = false;
     // overlap-region stitch of update_temporal_parallel.m:264-280: acc[k][0..T) = sum_m aa_m(k) C_raw_m(k,:), acc[k][ld-1..] ... see cnmfe_stitch_begin
     cnmfe::DevBuf stitch;     // K rows of stitch_ld floats: [0, T) the weighted sum, column stitch_ld - 4 the sum of the weights
     int32_t stitch_K = 0; int64_t stitch_T = 0, stitch_ld = 0; bool stitch_open = false;
@@ -430,15 +443,26 @@ struct cnmfe_ctx {
     std::map<std::string, int64_t> opts;
     int trace_level = 0;                                   // opts["host_trace"], read by every LAUNCH
     int64_t opt(const char *n, int64_t dflt) const { auto it = opts.find(n); return it == opts.end() ? dflt : it->second; }
-    // lanes (see cnmfe_lane): lanes[k] holds lane k's members while another lane is active; empty = one lane
-    std::vector<cnmfe_lane *> lanes; int cur_lane = 0, patches_created = 0, spatial_lane = 0;
+    // lanes (see LaneState): lanes[k] holds lane k's state while another lane is active; empty = one lane
+    std::vector<cnmfe_lane *> lanes; int cur_lane = 0, patches_created = 0;
+    int spatial_lane = 0;                                  // the lane of the last cnmfe_update_spatial (the fetch calls carry no patch id)
     hipEvent_t ev_fork = nullptr; int64_t fork_gen = 0;
-    void swap_lane(cnmfe_lane &L);                         // api.hip
     int activate(int lane);                                // api.hip: make `lane` the active one (its stream behind st(), its scratch behind the members)
     int join_lanes();                                      // api.hip: lane 0 active and waiting for everything the other lanes have been given
     int fork_mark();                                       // api.hip: the other lanes wait for what lane 0 has been given up to here, at their next activation
+    void patches_changed();                                // api.hip: a patch was created or replaced -- no lane's record and no queued projection names a patch any more
     ~cnmfe_ctx();
 };
+
+namespace cnmfe {
+// the options that select the kernel of the temporal projection, with their defaults: the one place that names them
+inline kept::ProjOpts proj_opts(const cnmfe_ctx *ctx) { return {ctx->opt("proj_i8", 1), ctx->opt("proj_i8_planes", 3), ctx->opt("proj_tiled", 1)}; }
+// the guard of the three fetch calls: the active lane still holds the deferred result of nnz values (connected: and its pattern)
+inline int require_kept_spatial(const cnmfe_ctx *ctx, int64_t nnz, bool connected) {
+    if (connected ? ctx->kept.fetchable_connected(nnz) : ctx->kept.fetchable(nnz)) return 0;
+    return fail(CNMFE_ESTATE, "no deferred spatial update of %lld values (last one: %lld)", (long long)nnz, (long long)ctx->kept.nnz);
+}
+}  // namespace cnmfe
 
 namespace cnmfe {
 // option "host_trace" = 1: wall-clock marks of the host-side phases of a call on stderr (scripts/host_timeline.py)

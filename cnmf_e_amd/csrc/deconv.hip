@@ -1202,8 +1202,8 @@ int deconv_all_run(cnmfe_ctx *ctx, int32_t K, int64_t T, float *C_raw, int c_ord
     RET(deconv_setup(opts, T, 0, c, shmem));
     c.trace = (int)ctx->opt("deconv_trace", 0);
     DevBuf *S_ = ctx->scr;
-    DevBuf &dCraw = S_[0], &dC = S_[1], &dS = S_[2], &dPars = S_[3], &dSn = S_[4], &dB = S_[20], &dList = S_[5]; DeconvScratch &scr = ctx->dscr;
-    ctx->conn_gen = -1;                                      // (scr[0], scr[1] change hands)
+    DevBuf &dCraw = S_[kept::SCR_COLPTR], &dC = S_[kept::SCR_EROW], &dS = S_[2], &dPars = S_[3], &dSn = S_[4], &dB = S_[20], &dList = S_[5]; DeconvScratch &scr = ctx->dscr;
+    ctx->kept.drop_pattern();                                // (the pattern slots serve as trace buffers here; the values of a deferred spatial update stay)
     int64_t ldc;
     RET(upload_traces(ctx, dCraw, C_raw, K, T, c_order, &ldc));
     RET(dC.ensure((size_t)K * ldc * sizeof(float))); RET(dS.ensure((size_t)K * ldc * sizeof(float)));

@@ -525,13 +525,12 @@ int spatial_run(cnmfe_ctx *ctx, Patch *P, int algorithm, int32_t K, const int64_
                 const float *A_val, const float *C, int c_order, const int64_t *IND_colptr, const int32_t *IND_rowidx,
                 const float *sn, int32_t param, float *A_out) {
     const int64_t T = P->T, d = P->d, nnz = IND_colptr[K];
-    ctx->spatial_nnz = nnz == 0 ? 0 : -1;
-    ++ctx->spatial_gen; ctx->spatial_patch = P; ctx->spatial_K = K; ctx->conn_gen = -1; ctx->early.valid = false;      // (a new result: what was queued ahead for the last one is void)
-    if (nnz == 0) return 0;
+    ctx->kept.drop(); ++ctx->spatial_gen; ctx->early.valid = false;      // (a new result: the last one, and what was queued ahead for it, are void)
+    if (nnz == 0) { ctx->kept.record(0, P, K, ctx->spatial_gen); return 0; }
     if (nnz >= (int64_t(1) << 31)) return fail(CNMFE_EUNSUPPORTED, "nnz(IND) too large");
     DevBuf &dC = ctx->tmp[0], &dCc = ctx->tmp[1], &dCm = ctx->tmp[2];
     DevBuf *S_ = ctx->scr;
-    DevBuf &dColptr = S_[0], &dErow = S_[1], &dEcol = S_[2], &dRptr = S_[3], &dRcol = S_[4], &dRsrc = S_[5], &dAval = S_[6], &dU = S_[7], &dPart = S_[8], &dV = S_[9], &dPairs = S_[10], &dSn = S_[11], &dLvl = S_[12];
+    DevBuf &dColptr = S_[kept::SCR_COLPTR], &dErow = S_[kept::SCR_EROW], &dEcol = S_[2], &dRptr = S_[3], &dRcol = S_[4], &dRsrc = S_[5], &dAval = S_[kept::SCR_AVAL], &dU = S_[7], &dPart = S_[8], &dV = S_[9], &dPairs = S_[10], &dSn = S_[11], &dLvl = S_[12];
     HostTrace ht(ctx, "spatial");
     int64_t ldc;
     RET(upload_centered(ctx, dC, C, K, T, c_order, dCc, dCm, &ldc));
@@ -630,15 +629,15 @@ int spatial_run(cnmfe_ctx *ctx, Patch *P, int algorithm, int32_t K, const int64_
                        dSn.as<float>(), algorithm == CNMFE_SPATIAL_HALS_THRESH ? 1 : 0, dAval.as<float>());
     }
     ht.mark("sweep launches");
-    ctx->spatial_nnz = nnz;                                  // the result stays in scr[6] until the next spatial update (cnmfe_update_spatial_fetch)
+    ctx->kept.record(nnz, P, K, ctx->spatial_gen);           // the result stays in this lane's slots until a call takes them (cnmfe_update_spatial_fetch)
     if (!A_out) return 0;                                    // deferred: the caller does other host work under the sweeps and fetches afterwards
     CK(hipMemcpyAsync(A_out, dAval.p, (size_t)nnz * sizeof(float), hipMemcpyDeviceToHost, ctx->st()));
     return ctx_check_errflag(ctx);                           // the wait, and what the kernels queued since the last one had to report
 }
 
 int spatial_fetch(cnmfe_ctx *ctx, float *A_out, int64_t nnz) {
-    if (ctx->spatial_nnz < 0 || nnz != ctx->spatial_nnz) return fail(CNMFE_ESTATE, "no deferred spatial update of %lld values (last one: %lld)", (long long)nnz, (long long)ctx->spatial_nnz);
-    if (nnz) CK(hipMemcpyAsync(A_out, ctx->scr[6].p, (size_t)nnz * sizeof(float), hipMemcpyDeviceToHost, ctx->st()));
+    RET(require_kept_spatial(ctx, nnz, false));
+    if (nnz) CK(hipMemcpyAsync(A_out, ctx->scr[kept::SCR_AVAL].p, (size_t)nnz * sizeof(float), hipMemcpyDeviceToHost, ctx->st()));
     return ctx_check_errflag(ctx);
 }
 
@@ -676,8 +675,8 @@ int fast_temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colp
         aa[k] = (float)s; inv[k] = s > 0.0 ? (float)(1.0 / s) : 0.f;
     }
     DevBuf *S_ = ctx->scr;
-    DevBuf &dColptr = S_[0], &dErow = S_[1], &dAval = S_[6], &dU = ctx->last_craw, &dInv = S_[13];
-    ctx->conn_gen = -1;                                      // (scr[0], scr[1], scr[6] change hands)
+    DevBuf &dColptr = S_[kept::SCR_COLPTR], &dErow = S_[kept::SCR_EROW], &dAval = S_[kept::SCR_AVAL], &dU = ctx->last_t.craw, &dInv = S_[13];
+    ctx->kept.drop();
     const int64_t ldc = (T + 3) & ~int64_t(3);
     RET(to_dev(ctx, dColptr, A_colptr, (size_t)K + 1));
     RET(to_dev(ctx, dErow, A_rowidx, (size_t)nnz));
@@ -692,8 +691,8 @@ int fast_temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colp
         LAUNCH(ctx, "temporal_proj_U", k_proj_temporal, dim3(K, nchunk), dim3(256), 0, P->ysig.as<float4>(), d, T, dColptr.as<int64_t>(),
                dErow.as<int>(), dAval.as<float>(), tchunk, dU.as<float>(), ldc);
     LAUNCH(ctx, "temporal_scale_rows", k_scale_rows, dim3((unsigned)((T + 255) / 256), (unsigned)K), dim3(256), 0, dU.as<float>(), ldc, T, dInv.as<float>());
-    RET(to_dev(ctx, ctx->last_aa, aa.data(), (size_t)K));
-    ctx->last_t_K = K; ctx->last_t_ldc = ldc; ctx->last_t_T = T; ctx->last_t_valid = true;      // for cnmfe_stitch_add
+    RET(to_dev(ctx, ctx->last_t.aa, aa.data(), (size_t)K));
+    ctx->last_t.set(K, ldc, T);                              // for cnmfe_stitch_add
     RET(download_traces(ctx, dU.as<float>(), ldc, C_raw_out, K, T, c_order));
     if (aa_out) memcpy(aa_out, aa.data(), (size_t)K * sizeof(float));
     return 0;
@@ -707,10 +706,10 @@ int temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, c
     // a job (cnmfe_hals_temporal_job) works in buffers of its own and stops in front of the sweeps: temporal_sweep_jobs runs them for all jobs together
     DevBuf *S_ = ctx->scr;
     DevBuf &dC = job ? job->dC : ctx->tmp[0];
-    DevBuf &dColptr = job ? job->dColptr : S_[0], &dErow = job ? job->dErow : S_[1], &dAval = job ? job->dAval : S_[6], &dU_scr = job ? job->dU : S_[7],
-           &dCraw = job ? job->dCraw : ctx->last_craw, &dNk = job ? job->dNk : S_[14], &dNidx = job ? job->dNidx : S_[15], &dNval = job ? job->dNval : S_[16],
-           &dNptr = job ? job->dNptr : S_[17], &dAa = job ? job->dAa : ctx->last_aa, &dLvl = S_[12], &dOvf = job ? job->dOvf : S_[18];
-    if (!job) ctx->last_t_valid = false;
+    DevBuf &dColptr = job ? job->dColptr : S_[kept::SCR_COLPTR], &dErow = job ? job->dErow : S_[kept::SCR_EROW], &dAval = job ? job->dAval : S_[kept::SCR_AVAL], &dU_scr = job ? job->dU : S_[7],
+           &dCraw = job ? job->dCraw : ctx->last_t.craw, &dNk = job ? job->dNk : S_[kept::SCR_KEEP], &dNidx = job ? job->dNidx : S_[15], &dNval = job ? job->dNval : S_[16],
+           &dNptr = job ? job->dNptr : S_[17], &dAa = job ? job->dAa : ctx->last_t.aa, &dLvl = S_[12], &dOvf = job ? job->dOvf : S_[18];
+    if (!job) ctx->last_t.valid = false;
     HostTrace ht(ctx, "temporal");
     int64_t ldc;
     RET(upload_traces(ctx, dC, C_in, K, T, c_order, &ldc));
@@ -721,16 +720,14 @@ int temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, c
     if (!job) {
         cnmfe_ctx::EarlyU &E = ctx->early;
         if (E.valid) {
-            early_hit = (te_mode == 1 || te_mode == 2) && E.claimed == E.token && E.P == P && E.K == K && E.ldc == ldc && E.T == T && E.spatial_gen == ctx->spatial_gen
-                        && E.request_gen == P->residual.gen && nnz > 0 && P->residual.is_virtual() && P->residual.source == rplan::SRC_FULL && ctx->lanes.empty()
-                        && rplan::terms_match_stride(P->residual.terms(), ldc)                                          // (the term would be folded into Ysig below: no virtual residual then)
-                        && E.proj_i8 == ctx->opt("proj_i8", 1) && E.proj_i8_planes == ctx->opt("proj_i8_planes", 3) && E.proj_tiled == ctx->opt("proj_tiled", 1);
+            early_hit = kept::early_takes(E, {te_mode, P, K, ldc, T, ctx->spatial_gen, P->residual.gen, nnz, P->residual.is_virtual(), P->residual.source == rplan::SRC_FULL,
+                                              ctx->lanes.empty(), rplan::terms_match_stride(P->residual.terms(), ldc), proj_opts(ctx)});
             E.valid = false;                                 // consumed either way
             ++(early_hit ? ctx->early_hits : ctx->early_drops);
         }
-        ctx->conn_gen = -1;                                  // (scr[0], scr[1], scr[6], scr[14] change hands below)
+        ctx->kept.drop();
     }
-    DevBuf &dU = early_hit ? ctx->early_u : dU_scr;
+    DevBuf &dU = early_hit ? ctx->early.u : dU_scr;
     RET(to_dev(ctx, dColptr, A_colptr, (size_t)K + 1));
     RET(to_dev(ctx, dErow, A_rowidx, (size_t)nnz));
     RET(to_dev(ctx, dAval, A_val, (size_t)nnz));
@@ -888,7 +885,7 @@ int temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, c
             CK(hipStreamSynchronize(ctx->st()));
         }
     }
-    ctx->last_t_K = K; ctx->last_t_ldc = ldc; ctx->last_t_T = T; ctx->last_t_valid = true;      // C_raw rows + aa stay on the device for cnmfe_stitch_add
+    ctx->last_t.set(K, ldc, T);                              // C_raw rows + aa stay on the device for cnmfe_stitch_add
     RET(download_traces(ctx, dC.as<float>(), ldc, C_out, K, T, c_order));
     RET(download_traces(ctx, dCraw.as<float>(), ldc, C_raw_out, K, T, c_order));
     if (aa_out && nowait) {                                     // (a caller that wants aa on the host waits for it here, behind the queued levels)
@@ -977,17 +974,17 @@ int temporal_sweep_jobs(cnmfe_ctx *ctx) {
 
 static int postproc_boxes(int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, std::vector<int4> &box);
 
-// The connectivity constraint on the result of a deferred spatial update WHERE IT LIES (scr[0], scr[1], scr[6]: the mask's CSC pattern and the new
+// The connectivity constraint on the result of a deferred spatial update WHERE IT LIES (SCR_COLPTR, SCR_EROW, SCR_AVAL: the mask's CSC pattern and the new
 // values, explicit zeros included -- they are zero pixels of the footprint image either way): valid when the patch is the whole field of view, so
 // that patch rows are FOV pixels.  One wait, one download of values + keep flags; no second upload of A.
 int spatial_fetch_connected(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *IND_colptr, const int32_t *IND_rowidx, float *A_out, uint8_t *keep, bool wait) {
     const int64_t nnz = IND_colptr[K];
-    if (ctx->spatial_nnz < 0 || nnz != ctx->spatial_nnz) return fail(CNMFE_ESTATE, "no deferred spatial update of %lld values (last one: %lld)", (long long)nnz, (long long)ctx->spatial_nnz);
+    RET(require_kept_spatial(ctx, nnz, true));
     if (nnz == 0) return 0;
     std::vector<int4> box;
     RET(postproc_boxes(d1, d2, K, IND_colptr, IND_rowidx, box));
     DevBuf *S_ = ctx->scr;
-    DevBuf &dColptr = S_[0], &dErow = S_[1], &dAval = S_[6], &dBox = S_[13], &dKeep = S_[14];
+    DevBuf &dColptr = S_[kept::SCR_COLPTR], &dErow = S_[kept::SCR_EROW], &dAval = S_[kept::SCR_AVAL], &dBox = S_[13], &dKeep = S_[kept::SCR_KEEP];
     RET(to_dev(ctx, dBox, box.data(), box.size()));
     RET(dKeep.ensure((size_t)nnz));
     CK(hipMemsetAsync(dKeep.p, 0, (size_t)nnz, ctx->st()));
@@ -995,41 +992,40 @@ int spatial_fetch_connected(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, c
            dBox.as<int4>(), d1, d2, dKeep.as<unsigned char>());
     CK(hipMemcpyAsync(A_out, dAval.p, (size_t)nnz * sizeof(float), hipMemcpyDeviceToHost, ctx->st()));
     CK(hipMemcpyAsync(keep, dKeep.p, (size_t)nnz, hipMemcpyDeviceToHost, ctx->st()));
-    ctx->conn_gen = ctx->spatial_gen;                        // (pattern, values and keep flags of this result lie in scr[0], scr[1], scr[6], scr[14]: temporal_early_project)
+    ctx->kept.flags_written();                               // (pattern, values and keep flags of this result lie in its four slots: temporal_early_project)
     return wait ? ctx_check_errflag(ctx) : 0;                // (no wait: the caller records a ticket behind the copies, cnmfe_update_spatial_fetch_connected_async)
 }
 
 // The hand-over (option temporal_early): the temporal update's projection U = B' Yc, B = A - W'A, queued on the stream right behind the
-// connectivity kernel, before the host has seen the new A.  Everything it needs is on the device: the mask's CSC pattern (scr[0], scr[1]), the new values
-// (scr[6]) and the keep flags (scr[14]); the block lists come from the mask's host pattern, a superset of A's whose extra entries are stored zeros.  The result
-// waits in ctx->early_u under a tag; *token = 0 when the request is declined (several lanes, a patch that is not the field of view, no virtual residual,
+// connectivity kernel, before the host has seen the new A.  Everything it needs is on the device: the mask's CSC pattern (SCR_COLPTR, SCR_EROW), the new values
+// (SCR_AVAL) and the keep flags (SCR_KEEP); the block lists come from the mask's host pattern, a superset of A's whose extra entries are stored zeros.  The result
+// waits in ctx->early.u under a tag; *token = 0 when the request is declined (several lanes, a patch that is not the field of view, no virtual residual,
 // bg_ssub > 1, a projection that cannot serve it).  Same stream, no event.
 int temporal_early_project(cnmfe_ctx *ctx, int32_t K, const int64_t *IND_colptr, const int32_t *IND_rowidx, int64_t *token) {
     *token = 0;
     ctx->early.valid = false;
-    const int64_t mode = ctx->opt("temporal_early", 1);
-    if ((mode != 1 && mode != 2) || !ctx->lanes.empty()) return 0;
-    Patch *P = ctx->spatial_patch;
+    Patch *P = const_cast<Patch *>(ctx->kept.patch);         // (the record names a patch of this context: patch_gone)
     const int64_t nnz = IND_colptr[K];
     // (no virtual residual: also what a spatial update leaves whose own table lists were too long -- they are the lists of the masks grown by the ring, the
     //  very lists built below, so vproj_temporal's own limit of 64 masks over a block is met there first and the residual realised)
-    if (!P || ctx->spatial_K != K || nnz == 0 || ctx->spatial_nnz != nnz || ctx->conn_gen != ctx->spatial_gen
-        || P->d != (int64_t)P->d1 * P->d2 || !P->residual.is_virtual() || P->residual.source != rplan::SRC_FULL) { ++ctx->early_declined; return 0; }
+    const kept::Serve sv = kept::early_serves(ctx->kept, {ctx->opt("temporal_early", 1), ctx->lanes.empty(), K, nnz, ctx->spatial_gen,
+                                                          P && P->d == (int64_t)P->d1 * P->d2, P && P->residual.is_virtual(), P && P->residual.source == rplan::SRC_FULL});
+    if (sv != kept::SERVE_YES) { if (sv == kept::SERVE_DECLINED) ++ctx->early_declined; return 0; }
     HostTrace ht(ctx, "temporal_early");
     const int64_t T = P->T, ldc = (T + 3) & ~int64_t(3);    // (the row stride upload_traces gives the traces of this T)
     DevBuf *S_ = ctx->scr;
-    RET(ctx->early_a.ensure((size_t)nnz * sizeof(float)));
-    RET(ctx->early_u.ensure((size_t)K * ldc * sizeof(float)));
-    LAUNCH(ctx, "temporal_early_values", k_keep_values, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, S_[6].as<float>(), S_[14].as<unsigned char>(), nnz, ctx->early_a.as<float>());
+    RET(ctx->early.a.ensure((size_t)nnz * sizeof(float)));
+    RET(ctx->early.u.ensure((size_t)K * ldc * sizeof(float)));
+    LAUNCH(ctx, "temporal_early_values", k_keep_values, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, S_[kept::SCR_AVAL].as<float>(), S_[kept::SCR_KEEP].as<unsigned char>(), nnz, ctx->early.a.as<float>());
     // (k_vp_reduce writes every column of every row of U, the padded tail included: no memset)
-    const int rcv = vproj_temporal(ctx, P, K, IND_colptr, IND_rowidx, nullptr, S_[0].as<int64_t>(), S_[1].as<int>(), ctx->early_a.as<float>(), ctx->early_u.as<float>(), ldc);
+    const int rcv = vproj_temporal(ctx, P, K, IND_colptr, IND_rowidx, nullptr, S_[kept::SCR_COLPTR].as<int64_t>(), S_[kept::SCR_EROW].as<int>(), ctx->early.a.as<float>(), ctx->early.u.as<float>(), ldc);
     if (rcv < 0) return rcv;
     if (rcv > 0) { ++ctx->early_declined; return 0; }        // more than 64 masks over one block, too large a partial buffer: the temporal update projects as before
     cnmfe_ctx::EarlyU &E = ctx->early;
     E.P = P; E.K = K; E.ldc = ldc; E.T = T; E.spatial_gen = ctx->spatial_gen; E.request_gen = P->residual.gen;
-    E.proj_i8 = ctx->opt("proj_i8", 1); E.proj_i8_planes = ctx->opt("proj_i8_planes", 3); E.proj_tiled = ctx->opt("proj_tiled", 1);
+    E.proj = proj_opts(ctx);
     E.token = ++ctx->early_seq; E.claimed = 0; E.valid = true;
-    ctx->early_nent = ctx->last_nent;
+    E.nent = ctx->last_nent;
     *token = E.token;
     return 0;
 }
@@ -1055,22 +1051,11 @@ int postproc_run(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_
                  const float *A_val, uint8_t *keep) {
     const int64_t nnz = A_colptr[K];
     if (nnz == 0) return 0;
-    std::vector<int4> box(K);
-    for (int k = 0; k < K; ++k) {
-        int rmin = d1, rmax = -1, cmin = d2, cmax = -1;
-        for (int64_t e = A_colptr[k]; e < A_colptr[k + 1]; ++e) {
-            int r = A_rowidx[e] % d1, c = A_rowidx[e] / d1;
-            rmin = std::min(rmin, r); rmax = std::max(rmax, r); cmin = std::min(cmin, c); cmax = std::max(cmax, c);
-        }
-        if (rmax < 0) { box[k] = make_int4(0, 0, 0, 0); continue; }
-        int h = rmax - rmin + 5, w = cmax - cmin + 5;
-        if (h > PP_MAX || w > PP_MAX)
-            return fail(CNMFE_EUNSUPPORTED, "footprint %d spans %dx%d pixels; post-processing supports %dx%d", k, h - 4, w - 4, PP_MAX - 4, PP_MAX - 4);
-        box[k] = make_int4(rmin - 2, cmin - 2, h, w);
-    }
+    std::vector<int4> box;
+    RET(postproc_boxes(d1, d2, K, A_colptr, A_rowidx, box));
     DevBuf *S_ = ctx->scr;
-    DevBuf &dColptr = S_[0], &dErow = S_[1], &dAval = S_[6], &dBox = S_[13], &dKeep = S_[14];
-    ctx->conn_gen = -1;                                      // (scr[0], scr[1], scr[6], scr[14] change hands)
+    DevBuf &dColptr = S_[kept::SCR_COLPTR], &dErow = S_[kept::SCR_EROW], &dAval = S_[kept::SCR_AVAL], &dBox = S_[13], &dKeep = S_[kept::SCR_KEEP];
+    ctx->kept.drop();
     RET(to_dev(ctx, dColptr, A_colptr, (size_t)K + 1));
     RET(to_dev(ctx, dErow, A_rowidx, (size_t)nnz));
     RET(to_dev(ctx, dAval, A_val, (size_t)nnz));

@@ -465,7 +465,8 @@ int vproj_temporal(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr,
         LAUNCH(ctx, "temporal_build_B", k_vp_build_b, dim3((unsigned)nent), dim3(256), 0, dEb.as<int>(), dEk.as<int>(), dEs.as<int>(), dG16.as<int>(), g, R, dColptr, dErow, dAval,
                P->ring_dr.as<int>(), P->ring_dc.as<int>(), P->W.as<float>(), dBt.as<double>());
     // round 5 (late): on the int8 pipe out of the video's digit planes when the fit left them resident (vproj_i8.hpp) -- their pixel-major copy is made once per upload
-    bool i8 = !P->derived && P->dig_valid && ctx->opt("proj_i8", 1) != 0 && nent > 0 && P->dig_T16 * 16 >= ldu;
+    const kept::ProjOpts po = proj_opts(ctx);
+    bool i8 = !P->derived && P->dig_valid && po.i8 != 0 && nent > 0 && P->dig_T16 * 16 >= ldu;
     if (i8 && !P->digp_valid) {
         const size_t dbytes = (size_t)nblk * P->dig_T16 * 16 * 64 * sizeof(uint4);
         RET(fits_leaving(P->digp, dbytes, &i8));
@@ -495,7 +496,7 @@ int vproj_temporal(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr,
             const size_t shmem = (size_t)(t + 1) * 1024 * sizeof(uint4);
 #define VP_GO8(NT_, V0_) LAUNCH(ctx, "temporal_proj_B", (k_vp_proj_i8<NT_, V0_>), dim3((unsigned)(nb_ * nsg)), dim3(256), shmem, P->digp.as<uint4>(), T16, ctx->vp[11].as<int>() + off, \
                            ctx->vp[5].as<int>(), ctx->vp[4].as<int>(), dBd.as<uint4>(), dBs.as<double>(), nsg, dPart.as<double>(), ldp)
-            if (ctx->opt("proj_i8_planes", 3) >= 4) { if (t == 0) VP_GO8(1, 0); else if (t == 1) VP_GO8(2, 0); else if (t == 2) VP_GO8(3, 0); else VP_GO8(4, 0); }
+            if (po.i8_planes >= 4) { if (t == 0) VP_GO8(1, 0); else if (t == 1) VP_GO8(2, 0); else if (t == 2) VP_GO8(3, 0); else VP_GO8(4, 0); }
             else { if (t == 0) VP_GO8(1, 1); else if (t == 1) VP_GO8(2, 1); else if (t == 2) VP_GO8(3, 1); else VP_GO8(4, 1); }
 #undef VP_GO8
             off += nb_;
@@ -503,7 +504,7 @@ int vproj_temporal(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr,
     } else {
     // the block-tiled copy of the centred video (k_tile_video), built at the first projection of a patch when the memory allows
     bool tiled = false;
-    if (!P->derived && ctx->opt("proj_tiled", 1) != 0) {
+    if (!P->derived && po.tiled != 0) {
         const int64_t ncg_t = (P->Tc + 15) >> 4;
         const size_t ybytes = (size_t)nblk * ncg_t * 64 * 64 * sizeof(float4);
         if (!P->yt4_valid) {

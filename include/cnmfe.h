@@ -267,7 +267,10 @@ int cnmfe_get_sn(cnmfe_ctx *ctx, int patch_id, float *sn_out);
  * (HALS_THRESH only).  param = maxIter (HALS*) or maxN (NNLS).  The result has exactly
  * the IND pattern: A_out[nnz(IND)] in IND's CSC order (entries may be 0).
  * A_out == NULL defers the download: the call returns with the sweeps queued and cnmfe_update_spatial_fetch(ctx, A_out, nnz(IND)) collects the
- * values later (valid until the next spatial update of this context) -- the host mirror sets up the temporal update's residual in between. */
+ * values later -- the host mirror sets up the temporal update's residual in between.  The deferred result is valid until the next spatial, temporal
+ * (cnmfe_hals_temporal[_deconv]), fast-temporal or post-processing call on the same lane (option lanes; one lane: of this context): those calls reuse the scratch
+ * it lies in, and a fetch after one of them returns CNMFE_ESTATE.  cnmfe_deconv_temporal reuses the mask's pattern only: cnmfe_update_spatial_fetch[_async] still
+ * serve after it, the connected fetches below do not.  cnmfe_hals_temporal_job works in buffers of its own and leaves the result alone. */
 int cnmfe_update_spatial(cnmfe_ctx *ctx, int patch_id, int algorithm, int32_t K,
                          const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
                          const float *C, int c_order,
@@ -550,7 +553,8 @@ int cnmfe_synchronize(cnmfe_ctx *ctx);
  *   proj_tiled / proj_i8   default 1 / 1: the temporal projection on the int8 pipe out of a pixel-major copy of the digit planes (needs win_i8), else out of a copy of
  *                     the centred video in its own read order (one video's worth either, same rule); 0 / 0: the frame-major video on the fp64 pipe.  The tables over ALL frames
  *                     (spatial update, temporal projection) sum inside frame segments of at most 24576 frames, recordings up to 16 x 24576 frames
- *   lanes             default 1; 2 .. 4 (set BEFORE the first patch is created): the patches alternate between that many execution lanes -- a HIP stream + a set of the
+ *   lanes             default 1; 2 .. 4 (set BEFORE the first patch is created; until then a further call replaces the lanes, 1 drops them, the count in force does
+ *                     nothing -- read-only counter lanes_live): the patches alternate between that many execution lanes -- a HIP stream + a set of the
  *                     context's scratch each -- so that the small kernels of independent patches overlap (update_*_parallel.m: parfor); calls on what the patches share
  *                     (bound traces, stitch, the temporal jobs' sweep, post-processing) join the lanes.  Results are bit-equal to lanes = 1 (tests/test_gpu_lanes.py)
  *   sweep_dag         default 1: the maxIter Gauss-Seidel sweeps of a HALS update (HALS_spatial.m:36-44, HALS_temporal.m:59-68, with or without the in-sweep
@@ -580,7 +584,7 @@ int cnmfe_set_option(cnmfe_ctx *ctx, const char *name, int64_t value);
  * (requests the projection could not serve), temporal_early_entries / temporal_proj_entries ((block, neuron) entries of the last early / of the last projection),
  * temporal_nowait (temporal updates whose levels were queued without the host wait), and merge_trace_uploads (K x T matrices the merge / tag entry points and
  * cnmfe_traces_load took from the host: 0 while they work on the context's own matrices), and bound_K / bound_T (the shape of the bound trace matrix, 0 without
- * one: what a gateway sizes the outputs of cnmfe_merge_apply with). */
+ * one: what a gateway sizes the outputs of cnmfe_merge_apply with), and lanes_live (the execution lanes in force, 1 without option lanes). */
 int cnmfe_get_option(cnmfe_ctx *ctx, const char *name, int64_t *value);
 
 /* The hand-over between the spatial and the temporal update (option temporal_early).  After cnmfe_update_spatial_fetch_connected[_async] of a patch that is the
