@@ -148,6 +148,14 @@ PROTOTYPES = {
     "cnmfe_trace_diff_spikes": (C.c_int, [c_ctx, C.c_int32, C.c_int64, f32p, C.c_int, f32p, f32p]),
     "cnmfe_trace_tags": (C.c_int, [c_ctx, C.c_int32, f64p]),
     "cnmfe_merge_apply": (C.c_int, [c_ctx, C.c_int32, i32p, i32p, f64p, C.c_int32, i32p, C.POINTER(DeconvOpts), f32p, f32p, f32p, f32p, f32p]),
+    "cnmfe_df_begin": (C.c_int, [c_ctx, C.c_int32, C.c_int64]),
+    "cnmfe_df_add_frames": (C.c_int, [c_ctx, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int32, i64p, i32p, f32p, i32p]),
+    "cnmfe_df_add_background": (C.c_int, [c_ctx, C.c_int, f32p, f32p, C.c_int32, i64p, i32p, f32p, i32p]),
+    "cnmfe_df_add_background_ssub": (C.c_int, [c_ctx, C.c_int, f32p, C.c_int32, i64p, i32p, f32p, i32p]),
+    "cnmfe_df_dims": (C.c_int, [c_ctx, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "cnmfe_df_fetch": (C.c_int, [c_ctx, f64p]),
+    "cnmfe_df_load": (C.c_int, [c_ctx, C.c_int32, C.c_int64, f64p]),
+    "cnmfe_df_finish": (C.c_int, [c_ctx, f64p, C.c_double, C.c_int64, f32p, C.c_int, f32p, C.c_int, f32p, f32p, f64p, f64p]),
 }
 # exports younger than the oldest build CNMFE_LIB is used with (A/B runs against the parent commit's library)
 OPTIONAL = {"cnmfe_get_option", "cnmfe_temporal_early_project", "cnmfe_temporal_early_claim"}

@@ -515,6 +515,7 @@ cnmfe_ctx::~cnmfe_ctx() {
     if (stream_) (void)hipStreamDestroy(stream_);
     for (auto *L : lanes) delete L;                           // (the inactive lanes' streams, events and scratch)
     if (ev_fork) (void)hipEventDestroy(ev_fork);
+    if (ev_df) (void)hipEventDestroy(ev_df);
 }
 
 // ---- execution lanes (common.hpp, LaneState) ----
@@ -1839,6 +1840,118 @@ int cnmfe_merge_apply(cnmfe_ctx *ctx, int32_t ngroups, const int32_t *grp_ptr, c
     CK(hipSetDevice(ctx->device));
     GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
     return merge_apply_run(ctx, ngroups, grp_ptr, grp_idx, w, nkeep, keep, opts, C_out, C_raw_out, S_out, kernel_pars_out, sn_out);
+}
+
+// ---- dF/F (dff.hpp) ----
+// everything k_df_project indexes with, checked on the host: A's rows in [0, d) (check_csc), the accumulator rows in [0, K) and distinct
+static int df_check_add(cnmfe_ctx *ctx, int32_t Km, int64_t d, const int64_t *cp, const int32_t *ri, const float *va, const int32_t *ind) {
+    if (!ctx->df_open) return fail(CNMFE_ESTATE, "cnmfe_df_begin has not been called");
+    if (Km < 0 || d <= 0) return fail(CNMFE_EINVAL, "bad Km / d");
+    if (Km == 0) return 0;
+    RET(check_csc("A", Km, d, cp, ri));
+    if ((!va && cp[Km] > 0) || !ind) return fail(CNMFE_EINVAL, "null A_val / ind_m");
+    std::vector<char> seen((size_t)ctx->df_K, 0);
+    for (int32_t j = 0; j < Km; ++j) {
+        if (ind[j] < 0 || ind[j] >= ctx->df_K) return fail(CNMFE_EINVAL, "row %d outside the %d-row accumulator", ind[j], ctx->df_K);
+        if (seen[ind[j]]) return fail(CNMFE_EINVAL, "row %d listed twice", ind[j]);
+        seen[ind[j]] = 1;
+    }
+    return 0;
+}
+int cnmfe_df_begin(cnmfe_ctx *ctx, int32_t K, int64_t T) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    if (K < 0 || T < 64 || T > 147456) return fail(CNMFE_EINVAL, "bad K, or T outside 64 .. 147456");
+    if (ctx->df_open) return fail(CNMFE_ESTATE, "a dF/F accumulator of %d x %lld is open (cnmfe_df_finish closes it)", ctx->df_K, (long long)ctx->df_T);
+    CK(hipSetDevice(ctx->device));
+    GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
+    return df_begin_run(ctx, K, T);
+}
+int cnmfe_df_add_frames(cnmfe_ctx *ctx, int64_t d, int64_t frame0, int64_t nframes, const float *Ybg, int memspace, int32_t Km, const int64_t *A_colptr,
+                        const int32_t *A_rowidx, const float *A_val, const int32_t *ind_m) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    RET(df_check_add(ctx, Km, d, A_colptr, A_rowidx, A_val, ind_m));
+    if (frame0 < 0 || nframes <= 0 || frame0 + nframes > ctx->df_T || nframes > INT32_MAX) return fail(CNMFE_EINVAL, "frames [%lld, %lld) outside [0, %lld)", (long long)frame0, (long long)(frame0 + nframes), (long long)ctx->df_T);
+    if (!Ybg || (memspace != CNMFE_HOST && memspace != CNMFE_DEVICE)) return fail(CNMFE_EINVAL, "null Ybg / bad memspace");
+    if (Km == 0) return 0;
+    CK(hipSetDevice(ctx->device));
+    GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
+    return df_add_frames_run(ctx, d, frame0, nframes, Ybg, memspace, Km, A_colptr, A_rowidx, A_val, ind_m);
+}
+// all T frames of one patch: a chunk of the background is reconstructed into the lane's scratch (cnmfe_reconstruct_background[_ssub], device output) and projected at once
+static int df_add_patch(cnmfe_ctx *ctx, int patch_id, const float *b0_block /* nullptr: bg_ssub > 1 */, const float *b0_new, int32_t Km, const int64_t *cp, const int32_t *ri,
+                        const float *va, const int32_t *ind) {
+    Patch *P = get_patch(ctx, patch_id);                     // (the patch's lane from here on)
+    if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
+    RET(df_check_add(ctx, Km, P->d, cp, ri, va, ind));
+    if (P->T != ctx->df_T) return fail(CNMFE_EINVAL, "patch %d has %lld frames, the accumulator %lld", patch_id, (long long)P->T, (long long)ctx->df_T);
+    if (b0_block) RET(require_residual_full(P, patch_id, "cnmfe_df_add_background"));
+    else if (ctx->bgs_patch != patch_id) return fail(CNMFE_ESTATE, "cnmfe_background_ssub has not been run for patch %d", patch_id);
+    if (!b0_new) return fail(CNMFE_EINVAL, "null b0_new");
+    if (Km == 0) return 0;
+    CK(hipSetDevice(ctx->device));
+    int64_t nch;
+    RET(df_chunk_frames(P->d, P->T, &nch));
+    float *chunk = df_chunk_buf(ctx, P->d, nch);
+    if (!chunk) return CNMFE_ENOMEM;
+    RET(df_stage_a(ctx, Km, cp, ri, va, ind));
+    for (int64_t t0 = 0; t0 < P->T; t0 += nch) {
+        const int64_t n = std::min(nch, P->T - t0);
+        if (b0_block) RET(cnmfe_reconstruct_background(ctx, patch_id, b0_block, b0_new, t0, n, chunk, CNMFE_DEVICE));
+        else RET(cnmfe_reconstruct_background_ssub(ctx, patch_id, b0_new, t0, n, chunk, CNMFE_DEVICE));
+        RET(df_project_run(ctx, Km, P->d, t0, n, chunk));
+    }
+    return 0;
+}
+int cnmfe_df_add_background(cnmfe_ctx *ctx, int patch_id, const float *b0_block, const float *b0_new, int32_t Km, const int64_t *A_colptr, const int32_t *A_rowidx,
+                            const float *A_val, const int32_t *ind_m) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    if (!b0_block) return fail(CNMFE_EINVAL, "null b0_block");
+    return df_add_patch(ctx, patch_id, b0_block, b0_new, Km, A_colptr, A_rowidx, A_val, ind_m);
+}
+int cnmfe_df_add_background_ssub(cnmfe_ctx *ctx, int patch_id, const float *b0_new, int32_t Km, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
+                                 const int32_t *ind_m) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    return df_add_patch(ctx, patch_id, nullptr, b0_new, Km, A_colptr, A_rowidx, A_val, ind_m);
+}
+int cnmfe_df_dims(cnmfe_ctx *ctx, int32_t *K, int64_t *T) {
+    if (!ctx || !K || !T) return fail(CNMFE_EINVAL, "null argument");
+    if (!ctx->df_open) return fail(CNMFE_ESTATE, "cnmfe_df_begin has not been called");
+    *K = ctx->df_K; *T = ctx->df_T;
+    return 0;
+}
+int cnmfe_df_fetch(cnmfe_ctx *ctx, double *Yf_out) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    if (!ctx->df_open) return fail(CNMFE_ESTATE, "cnmfe_df_begin has not been called");
+    if (!Yf_out && ctx->df_K > 0) return fail(CNMFE_EINVAL, "null output");
+    CK(hipSetDevice(ctx->device));
+    GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
+    return df_fetch_run(ctx, Yf_out);
+}
+int cnmfe_df_load(cnmfe_ctx *ctx, int32_t K, int64_t T, const double *Yf) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    if (K < 0 || T < 64 || T > 147456 || (!Yf && K > 0)) return fail(CNMFE_EINVAL, "bad K, T outside 64 .. 147456, or null Yf");
+    if (ctx->df_open && (K != ctx->df_K || T != ctx->df_T)) return fail(CNMFE_EINVAL, "the open accumulator is %d x %lld", ctx->df_K, (long long)ctx->df_T);
+    CK(hipSetDevice(ctx->device));
+    GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
+    return df_load_run(ctx, K, T, Yf);
+}
+int cnmfe_df_finish(cnmfe_ctx *ctx, const double *inv_norm, double df_prctile, int64_t df_window, const float *C, int c_src, const float *C_raw, int raw_src,
+                    float *C_df_out, float *C_raw_df_out, double *Df_out, double *Yf_out) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    if (!ctx->df_open) return fail(CNMFE_ESTATE, "cnmfe_df_begin has not been called");
+    if (!(df_prctile >= 0.0 && df_prctile <= 100.0) || df_window < 0) return fail(CNMFE_EINVAL, "df_prctile outside [0, 100] or negative df_window");
+    if (df_window > ctx->df_T) df_window = 0;                // (Sources2D.m:546: a window longer than the recording means none)
+    if (df_window > 16384) return fail(CNMFE_EUNSUPPORTED, "df_window = %lld: windows of up to 16384 frames are served", (long long)df_window);
+    if (ctx->df_K > 0) {
+        if (!inv_norm) return fail(CNMFE_EINVAL, "null inv_norm");
+        if (C_df_out) RET(merge_src_check(ctx->df_K, ctx->df_T, C, c_src));
+        if (C_raw_df_out) RET(merge_src_check(ctx->df_K, ctx->df_T, C_raw, raw_src));
+        if ((C_df_out && (c_src == CNMFE_RES_S || c_src == CNMFE_RES_DIFF)) || (C_raw_df_out && (raw_src == CNMFE_RES_S || raw_src == CNMFE_RES_DIFF)))
+            return fail(CNMFE_EINVAL, "C / C_raw come from the host, the bound matrix or the resident C_raw");
+    }
+    CK(hipSetDevice(ctx->device));
+    GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
+    return df_finish_run(ctx, inv_norm, df_prctile, df_window, C, c_src, C_raw, raw_src, C_df_out, C_raw_df_out, Df_out, Yf_out);
 }
 
 int cnmfe_post_process_spatial(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr,

@@ -371,6 +371,7 @@ struct LaneState {
     DevBuf stg[4];            // ring_solve_staged.hpp: per-neuron window metadata, per-list-position metadata, the windows of U~ and of A
     DevBuf wcodes, solve_fill;   // ring solve: the block-pair codes per window origin (k_win_codes); the fill values {0, 1} in global memory (ring_solve.hpp)
     DevBuf stage;             // upload staging
+    DevBuf dfl[5];            // dff.hpp: [0] the frame chunk of the reconstructed background (<= 256 MB), [1..4] the call's A (colptr, rowidx, val) and accumulator rows
     // per-call device scratch of the factor updates (factor.hip, deconv.hip): grown on demand, NEVER freed between calls -- a hipMalloc /
     // hipFree pair per buffer and call cost more than the small kernels they serve, and hipFree drains the device
     DevBuf scr[24];
@@ -435,6 +436,11 @@ struct cnmfe_ctx : cnmfe::LaneState {
     cnmfe::DevBuf mrg[23];                                 // [0] an uploaded source, [1] the result of cnmfe_trace_diff_spikes (diff_K x diff_T), [2..5] moments / K x K / sn, [6..22] cnmfe_merge_apply
     int32_t diff_K = 0; int64_t diff_T = 0;
     int64_t merge_uploads = 0;                             // counter merge_trace_uploads: K x T matrices the merge / tag entry points took from the host
+    // dF/F (dff.hpp): the K x T fp64 accumulator of cnmfe_df_begin .. cnmfe_df_finish (row stride df_T), and [0] 1 / sum(A.^2), [1] the rows that are not finite, [2] Df,
+    // [3] a divided matrix on its way out.  ev_df chains the projections of different lanes in call order (df_chain: one has been queued since cnmfe_df_begin)
+    cnmfe::DevBuf df_acc, df_buf[4];
+    int32_t df_K = 0; int64_t df_T = 0; bool df_open = false, df_chain = false;
+    hipEvent_t ev_df = nullptr;
     // overlap-region stitch of update_temporal_parallel.m:264-280: acc[k][0..T) = sum_m aa_m(k) C_raw_m(k,:), acc[k][ld-1..] ... see cnmfe_stitch_begin
     cnmfe::DevBuf stitch;     // K rows of stitch_ld floats: [0, T) the weighted sum, column stitch_ld - 4 the sum of the weights
     int32_t stitch_K = 0; int64_t stitch_T = 0, stitch_ld = 0; bool stitch_open = false;
@@ -573,6 +579,19 @@ int fast_temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colp
 int deconv_bound_run(cnmfe_ctx *ctx, const cnmfe_deconv_opts *opts, float *C_out, float *C_raw_out, float *S_out, float *pars_out, float *sn_out);
 int deconv_all_run(cnmfe_ctx *ctx, int32_t K, int64_t T, float *C_raw, int c_order, const cnmfe_deconv_opts *opts,
                    float *C_out, float *S_out, float *pars_out, float *sn_out);
+// dff.hpp (deconv.hip)
+int df_begin_run(cnmfe_ctx *ctx, int32_t K, int64_t T);
+int df_stage_a(cnmfe_ctx *ctx, int32_t Km, const int64_t *cp, const int32_t *ri, const float *va, const int32_t *ind);
+int df_project_run(cnmfe_ctx *ctx, int32_t Km, int64_t d, int64_t frame0, int64_t nframes, const float *dY);
+int df_add_frames_run(cnmfe_ctx *ctx, int64_t d, int64_t frame0, int64_t nframes, const float *Ybg, int memspace, int32_t Km, const int64_t *cp, const int32_t *ri,
+                      const float *va, const int32_t *ind);
+int df_chunk_frames(int64_t d, int64_t T, int64_t *nch);
+float *df_chunk_buf(cnmfe_ctx *ctx, int64_t d, int64_t nch);
+int df_fetch_run(cnmfe_ctx *ctx, double *out);
+int df_load_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const double *Yf);
+int df_source_check(cnmfe_ctx *ctx, int32_t K, int64_t T, int src);
+int df_finish_run(cnmfe_ctx *ctx, const double *inv_norm, double p, int64_t w, const float *C, int c_src, const float *C_raw, int raw_src, float *C_df_out,
+                  float *C_raw_df_out, double *Df_out, double *Yf_out);
 // merge.hpp (deconv.hip)
 int trace_corr_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, int raw, double *out);
 int trace_diff_spikes_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, float *sn_out, float *S_out);

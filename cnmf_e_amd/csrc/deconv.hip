@@ -1284,6 +1284,7 @@ int deconv_bound_run(cnmfe_ctx *ctx, const cnmfe_deconv_opts *opts, float *C_out
 
 }  // namespace cnmfe
 #include "merge.hpp"      // (h) merging: trace correlations, tags and the merged rows (its kernels need get_sn and block_sum, its merged row the launcher above)
+#include "dff.hpp"        // (i) dF/F: the background projected onto the footprints, its baselines and the division (its order statistics are peel.hpp's, its trace sources merge.hpp's)
 namespace cnmfe {
 
 // loads this translation unit's code object now (HIP loads it at the first launch of one of its kernels -- milliseconds each that would otherwise fall into the first iteration): cnmfe_create

@@ -62,6 +62,13 @@
 //   [sn, S_] = cnmfe_mex('trace_diff_spikes', h, source...)                the S-less branch (:57-66); the result stays on the device as the source 'diff'
 //   q = cnmfe_mex('trace_tags', h, K)                                      K x 4: max(C), std(C_raw - C), GetSn(C_raw), spikes after frame 1
 //   [C, C_raw, S, pars, sn] = cnmfe_mex('merge_apply', h, grp_ptr, grp_idx, w, keep, T, smin, max_tau)   merged traces, their deconvolution, obj.delete: on the device
+// dF/F (Sources2D.m:540-570, extract_DF_F_endoscope; the loop over the patches is the caller's, as in cnmf_e_amd/sources2d.py -- no .m twin is written):
+//   cnmfe_mex('df_begin', h, K, T)                                         the K x T fp64 accumulator of (A ./ sum(A.^2, 1))' * Ybg, zeroed
+//   cnmfe_mex('df_add_background', h, pid, b0_block, b0_new_patch, A_patch, ind)   all frames of one patch, after 'residual' (as 'reconstruct_background'); ind: 1-based rows
+//   cnmfe_mex('df_add_background_ssub', h, pid, b0_new_patch, A_patch, ind)        the same after 'background_ssub'
+//   cnmfe_mex('df_add_frames', h, Ybg, frame0, A, ind)                     a d x nframes slab of a background the caller holds
+//   Yf = cnmfe_mex('df_fetch', h);  cnmfe_mex('df_load', h, Yf)            the accumulator to / from the host (a sharded run's all-reduce goes in between)
+//   [C_df, C_raw_df, Df, Yf] = cnmfe_mex('df_finish', h, inv_norm, df_prctile, df_window, C, C_raw)   C, C_raw: K x T matrices or 'bound' / 'craw'; df_window 0 / []: none
 #include "mex.h"
 #include "matrix.h"
 #include <string.h>
@@ -144,6 +151,15 @@ static Traces traces_of(const mxArray *C, int32_t K) {
     if ((int32_t)mxGetM(C) != K) FAIL("trace matrix has %d rows for %d footprints", (int)mxGetM(C), (int)K);
     t.ptr = f32_of(C, NULL);
     return t;
+}
+static int32_t *ind_of(const mxArray *I, size_t *n_out) {      // 1-based rows (double or int32) -> 0-based int32
+    const size_t n = mxGetNumberOfElements(I);
+    int32_t *ind = (int32_t *)mxMalloc((n + 1) * sizeof(int32_t));
+    if (mxIsInt32(I)) { const int32_t *s = (const int32_t *)mxGetData(I); for (size_t i = 0; i < n; ++i) ind[i] = s[i] - 1; }
+    else if (mxIsDouble(I)) { const double *s = mxGetPr(I); for (size_t i = 0; i < n; ++i) ind[i] = (int32_t)s[i] - 1; }
+    else FAIL("row lists must be double or int32");
+    *n_out = n;
+    return ind;
 }
 static mxArray *to_double(const float *v, size_t r, size_t c) {
     mxArray *o = mxCreateDoubleMatrix(r, c, mxREAL);
@@ -310,6 +326,83 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
         }
         if (nout > 3) pout[3] = to_double(kp, nk, 1);
         if (nout > 4) pout[4] = to_double(sn, nk, 1);
+        return;
+    }
+    // ---- dF/F (cnmfe.h section (i)): the accumulator's K x T is the context's (cnmfe_df_dims) -- every output is sized from it, never from the caller
+    if (!strcmp(cmd, "df_begin")) {                             // cnmfe_mex('df_begin', h, K, T)
+        if (nin != 4) FAIL("df_begin: 4 inputs required (h, K, T)");
+        CHECK(cnmfe_df_begin(c, (int32_t)mxGetScalar(pin[2]), (int64_t)mxGetScalar(pin[3])));
+        return;
+    }
+    if (!strcmp(cmd, "df_add_frames")) {                        // cnmfe_mex('df_add_frames', h, Ybg, frame0, A, ind): Ybg d x nframes (a slab of reconstruct_background), frame0 0-based, ind 1-based rows
+        if (nin != 6) FAIL("df_add_frames: 6 inputs required (h, Ybg, frame0, A, ind)");
+        const size_t d = mxGetM(pin[2]), nf = mxGetN(pin[2]);
+        Csc A = csc_of(pin[4]);
+        if (A.K && mxGetM(pin[4]) != d) FAIL("df_add_frames: A has %d rows, Ybg %d", (int)mxGetM(pin[4]), (int)d);
+        size_t n = 0;
+        int32_t *ind = ind_of(pin[5], &n);
+        if (n != (size_t)A.K) FAIL("df_add_frames: one accumulator row per column of A");
+        CHECK(cnmfe_df_add_frames(c, (int64_t)d, (int64_t)mxGetScalar(pin[3]), (int64_t)nf, f32_of(pin[2], NULL), CNMFE_HOST, A.K, A.cp, A.ri, A.v, ind));
+        return;
+    }
+    if (!strcmp(cmd, "df_fetch")) {                             // Yf = cnmfe_mex('df_fetch', h): the K x T accumulator (double)
+        if (nin != 2) FAIL("df_fetch: 2 inputs required");
+        int32_t Kd = 0; int64_t Td = 0;
+        CHECK(cnmfe_df_dims(c, &Kd, &Td));
+        const size_t K = (size_t)Kd, T = (size_t)Td;
+        double *buf = (double *)mxCalloc(K * T + 1, sizeof(double));
+        CHECK(cnmfe_df_fetch(c, buf));
+        pout[0] = mxCreateDoubleMatrix(K, T, mxREAL);
+        for (size_t k = 0; k < K; ++k) for (size_t t = 0; t < T; ++t) mxGetPr(pout[0])[k + t * K] = buf[k * T + t];
+        return;
+    }
+    if (!strcmp(cmd, "df_load")) {                              // cnmfe_mex('df_load', h, Yf): a K x T double matrix becomes the accumulator (after the caller's all-reduce)
+        if (nin != 3) FAIL("df_load: 3 inputs required (h, Yf)");
+        if (!mxIsDouble(pin[2]) || mxIsSparse(pin[2])) FAIL("df_load: Yf must be a full double matrix");
+        const size_t K = mxGetM(pin[2]), T = mxGetN(pin[2]);
+        double *buf = (double *)mxCalloc(K * T + 1, sizeof(double));
+        for (size_t k = 0; k < K; ++k) for (size_t t = 0; t < T; ++t) buf[k * T + t] = mxGetPr(pin[2])[k + t * K];
+        CHECK(cnmfe_df_load(c, (int32_t)K, (int64_t)T, buf));
+        return;
+    }
+    if (!strcmp(cmd, "df_finish")) {
+        // [C_df, C_raw_df, Df, Yf] = cnmfe_mex('df_finish', h, inv_norm, df_prctile, df_window, C, C_raw): C and C_raw are K x T matrices (uploaded) or the names
+        // 'bound' / 'craw' (the context's own); df_window = 0 or [] for none.  C_df, C_raw_df single, Df (K x 1, or K x T with a window) and Yf double
+        if (nin != 7) FAIL("df_finish: 7 inputs required (h, inv_norm, df_prctile, df_window, C, C_raw)");
+        int32_t Kd = 0; int64_t Td = 0;
+        CHECK(cnmfe_df_dims(c, &Kd, &Td));
+        const size_t K = (size_t)Kd, T = (size_t)Td;
+        if (!mxIsDouble(pin[2]) || mxGetNumberOfElements(pin[2]) != K) FAIL("df_finish: inv_norm must hold %d doubles", (int)K);
+        const int64_t w = mxIsEmpty(pin[4]) ? 0 : (int64_t)mxGetScalar(pin[4]);
+        const float *X[2] = {NULL, NULL}; int src[2] = {CNMFE_COLMAJOR, CNMFE_COLMAJOR};
+        for (int a = 0; a < 2; ++a) {
+            const mxArray *M = pin[5 + a];
+            if (mxIsChar(M)) {
+                char nm[16];
+                if (mxGetString(M, nm, sizeof(nm))) FAIL("df_finish: bad source name");
+                src[a] = !strcmp(nm, "bound") ? CNMFE_BOUND : !strcmp(nm, "craw") ? CNMFE_RES_CRAW : -1;
+                if (src[a] < 0) FAIL("df_finish: unknown source '%s' (bound, craw)", nm);
+            } else {
+                if (mxGetM(M) != K || mxGetN(M) != T) FAIL("df_finish: C and C_raw must be %d x %d", (int)K, (int)T);
+                if (K) X[a] = f32_of(M, NULL);
+            }
+        }
+        const int win = w > 0 && w <= Td;
+        float *o0 = (float *)mxCalloc(K * T + 1, sizeof(float)), *o1 = (float *)mxCalloc(K * T + 1, sizeof(float));
+        double *df = (double *)mxCalloc((win ? K * T : K) + 1, sizeof(double)), *yf = nout > 3 ? (double *)mxCalloc(K * T + 1, sizeof(double)) : NULL;
+        CHECK(cnmfe_df_finish(c, mxGetPr(pin[2]), mxGetScalar(pin[3]), w, X[0], src[0], X[1], src[1], o0, o1, df, yf));
+        float *o[2] = {o0, o1};
+        for (int j = 0; j < 2 && j < (nout > 0 ? nout : 1); ++j) {
+            pout[j] = mxCreateNumericMatrix(K, T, mxSINGLE_CLASS, mxREAL);
+            float *p = (float *)mxGetData(pout[j]);
+            for (size_t k = 0; k < K; ++k) for (size_t t = 0; t < T; ++t) p[k + t * K] = o[j][k * T + t];
+        }
+        if (nout > 2) {
+            pout[2] = mxCreateDoubleMatrix(K, win ? T : 1, mxREAL);
+            if (win) { for (size_t k = 0; k < K; ++k) for (size_t t = 0; t < T; ++t) mxGetPr(pout[2])[k + t * K] = df[k * T + t]; }
+            else for (size_t k = 0; k < K; ++k) mxGetPr(pout[2])[k] = df[k];
+        }
+        if (nout > 3) { pout[3] = mxCreateDoubleMatrix(K, T, mxREAL); for (size_t k = 0; k < K; ++k) for (size_t t = 0; t < T; ++t) mxGetPr(pout[3])[k + t * K] = yf[k * T + t]; }
         return;
     }
     if (!strcmp(cmd, "postprocess")) {
@@ -533,6 +626,20 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
         if (nf <= 0) FAIL("reconstruct_background: nframes must be positive");
         pout[0] = mxCreateNumericMatrix(nn, (size_t)nf, mxSINGLE_CLASS, mxREAL);
         CHECK(cnmfe_reconstruct_background(c, pid, bb, bn, f0, nf, (float *)mxGetData(pout[0]), CNMFE_HOST));
+    } else if (!strcmp(cmd, "df_add_background")) {            // cnmfe_mex('df_add_background', h, pid, b0_block, b0_new_patch, A_patch, ind): all frames of the patch, after 'residual'
+        if (nin != 7) FAIL("df_add_background: 7 inputs required (h, pid, b0_block, b0_new, A_patch, ind)");
+        Csc A = csc_of(pin[5]);
+        size_t n = 0;
+        int32_t *ind = ind_of(pin[6], &n);
+        if (n != (size_t)A.K) FAIL("df_add_background: one accumulator row per column of A");
+        CHECK(cnmfe_df_add_background(c, pid, f32_of(pin[3], NULL), f32_of(pin[4], NULL), A.K, A.cp, A.ri, A.v, ind));
+    } else if (!strcmp(cmd, "df_add_background_ssub")) {       // cnmfe_mex('df_add_background_ssub', h, pid, b0_new_patch, A_patch, ind): after 'background_ssub'
+        if (nin != 6) FAIL("df_add_background_ssub: 6 inputs required (h, pid, b0_new, A_patch, ind)");
+        Csc A = csc_of(pin[4]);
+        size_t n = 0;
+        int32_t *ind = ind_of(pin[5], &n);
+        if (n != (size_t)A.K) FAIL("df_add_background_ssub: one accumulator row per column of A");
+        CHECK(cnmfe_df_add_background_ssub(c, pid, f32_of(pin[3], NULL), A.K, A.cp, A.ri, A.v, ind));
     } else if (!strcmp(cmd, "set_noise")) {                    // cnmfe_mex('set_noise', h, pid, sn_block): read by the outlier branch of the ring fit
         if (nin != 4) FAIL("set_noise: 4 inputs required");
         CHECK(cnmfe_set_noise(c, pid, f32_of(pin[3], NULL)));

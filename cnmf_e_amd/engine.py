@@ -934,6 +934,90 @@ class Engine:
         self._res = (Cn, Rn, Sn) if n else None
         return Cn, Rn, Sn, kp, sn
 
+    # ---- dF/F (cnmfe.h section (i)): extract_DF_F_endoscope without the d x T background (Sources2D.m:540-570) ----
+    def df_begin(self, K, T):
+        """the K x T float64 accumulator of Yf = (A ./ sum(A.^2, 1))' * Ybg, zeroed (cnmfe_df_begin)"""
+        L.check(L.lib.cnmfe_df_begin(self._ctx, int(K), int(T)))
+
+    @staticmethod
+    def _df_a(A, nrow, ind):
+        Km, cp, ri, va = _csc(A, nrow)
+        ind = np.ascontiguousarray(ind, dtype=np.int32)
+        if ind.size != Km:
+            raise ValueError("%d accumulator rows for %d columns of A" % (ind.size, Km))
+        return Km, cp, ri, va, ind
+
+    def df_add_frames(self, Ybg, frame0, A, ind):
+        """acc[ind, frame0 + t] += A' * Ybg[t]: Ybg (nframes, d) float32 (frame-major), A d x len(ind) sparse (cnmfe_df_add_frames)"""
+        Y = np.ascontiguousarray(Ybg, dtype=np.float32)
+        n, d = Y.shape
+        Km, cp, ri, va, ind = self._df_a(A, d, ind)
+        L.check(L.lib.cnmfe_df_add_frames(self._ctx, d, int(frame0), n, Y.ctypes.data_as(C.c_void_p), L.HOST, Km, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p),
+                                          _p(ind, L.i32p)))
+
+    def df_add_background(self, pid, b0_block, b0_new_patch, A_patch, ind):
+        """the same for all frames of one patch, the background taken from the resident residual of (A_prev, C_prev) as reconstruct_background takes it"""
+        info = self._patch[pid]
+        Km, cp, ri, va, ind = self._df_a(A_patch, info["d"], ind)
+        bb = np.ascontiguousarray(b0_block, dtype=np.float32).ravel(); bn = np.ascontiguousarray(b0_new_patch, dtype=np.float32).ravel()
+        if bb.size != info["d_b"] or bn.size != info["d"]:
+            raise ValueError("b0_block / b0_new have %d / %d entries, expected %d / %d" % (bb.size, bn.size, info["d_b"], info["d"]))
+        L.check(L.lib.cnmfe_df_add_background(self._ctx, pid, _p(bb, L.f32p), _p(bn, L.f32p), Km, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p), _p(ind, L.i32p)))
+
+    def df_add_background_ssub(self, pid, b0_new_patch, A_patch, ind):
+        """bg_ssub > 1: after background_ssub of that patch, as reconstruct_background_ssub takes it"""
+        info = self._patch[pid]
+        Km, cp, ri, va, ind = self._df_a(A_patch, info["d"], ind)
+        bn = np.ascontiguousarray(b0_new_patch, dtype=np.float32).ravel()
+        if bn.size != info["d"]:
+            raise ValueError("b0_new has %d entries, expected %d" % (bn.size, info["d"]))
+        L.check(L.lib.cnmfe_df_add_background_ssub(self._ctx, pid, _p(bn, L.f32p), Km, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p), _p(ind, L.i32p)))
+
+    def df_dims(self):
+        K = C.c_int32(0); T = C.c_int64(0)
+        L.check(L.lib.cnmfe_df_dims(self._ctx, C.byref(K), C.byref(T)))
+        return K.value, T.value
+
+    def df_close(self):
+        """drop an open accumulator (a finish without outputs); nothing happens when none is open"""
+        K = C.c_int32(0); T = C.c_int64(0)
+        if L.lib.cnmfe_df_dims(self._ctx, C.byref(K), C.byref(T)) != 0:
+            return
+        inv = np.ones(max(K.value, 1), dtype=np.float64)
+        L.lib.cnmfe_df_finish(self._ctx, _p(inv, L.f64p), 50.0, 0, None, L.ROWMAJOR, None, L.ROWMAJOR, None, None, None, None)
+
+    def df_fetch(self):
+        """the accumulator as a K x T float64 array"""
+        K, T = self.df_dims()
+        out = np.empty((K, T), dtype=np.float64)
+        L.check(L.lib.cnmfe_df_fetch(self._ctx, _p(out, L.f64p)))
+        return out
+
+    def df_load(self, Yf):
+        """a K x T float64 array becomes the accumulator (opens one if none is open)"""
+        Yf = np.ascontiguousarray(Yf, dtype=np.float64)
+        L.check(L.lib.cnmfe_df_load(self._ctx, Yf.shape[0], Yf.shape[1], _p(Yf, L.f64p)))
+
+    def df_finish(self, inv_norm, df_prctile, df_window, Cm, C_raw, want_Yf=False):
+        """scale by inv_norm = 1 / sum(A.^2, 1) (float64), take the baseline, divide: (C_df, C_raw_df, Df[, Yf]); Df is (K,) without a window, (K, T) with one.
+        Cm / C_raw that are the engine's bound matrix / resident C_raw are read where they lie (no upload)."""
+        K, T = self.df_dims()
+        inv = np.ascontiguousarray(inv_norm, dtype=np.float64).ravel()
+        if inv.size != K:
+            raise ValueError("inv_norm has %d entries, expected %d" % (inv.size, K))
+        w = 0 if df_window is None else int(df_window)
+        win = 0 < w <= T
+        cptr, csrc, _, _, _k1 = self._tsrc(Cm) if K else (None, L.ROWMAJOR, 0, T, None)
+        rptr, rsrc, _, _, _k2 = self._tsrc(C_raw) if K else (None, L.ROWMAJOR, 0, T, None)
+        if K and (tuple(Cm.shape) != (K, T) or tuple(C_raw.shape) != (K, T)):
+            raise ValueError("C / C_raw are not %d x %d" % (K, T))
+        C_df = np.empty((K, T), dtype=np.float32); R_df = np.empty((K, T), dtype=np.float32)
+        Df = np.empty((K, T) if win else (K,), dtype=np.float64)
+        Yf = np.empty((K, T), dtype=np.float64) if want_Yf else None
+        L.check(L.lib.cnmfe_df_finish(self._ctx, _p(inv, L.f64p), float(df_prctile), w, cptr, csrc, rptr, rsrc, _p(C_df, L.f32p), _p(R_df, L.f32p), _p(Df, L.f64p),
+                                      _p(Yf, L.f64p)))
+        return (C_df, R_df, Df, Yf) if want_Yf else (C_df, R_df, Df)
+
     def _mark_batch(self, *lazies):
         """the asynchronous call just made queued one batch of downloads: its generation number goes to the buffers it fills"""
         g = C.c_int64(0)

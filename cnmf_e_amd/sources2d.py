@@ -18,6 +18,7 @@ collective on the data path, the temporal update does ONE all-reduce of ``aa .* 
 from __future__ import annotations
 
 from dataclasses import dataclass, field
+from typing import Optional
 
 import ctypes
 import os
@@ -78,6 +79,9 @@ class Options:
     merge_thr: object = 0.85         # :70 / :260   scalar, or [A overlap, corr(C), corr(S)] (+ a fourth entry: the largest difference of the decay times)
     dmin: object = 1.0               # :110 / :299  largest distance of two neuron centres that may merge (merge_close_neighbors: + a second entry, decay times)
     method_dist: str = "max"         # :111 / :300  'max' (the footprint's brightest pixel) | 'mean' / 'center' (its centre of mass)
+    # dF/F (extract_DF_F_endoscope): CNMFSetParms.m:73-74
+    df_prctile: float = 50           # :73   percentile of the projected background that is the baseline
+    df_window: Optional[int] = None  # :74   length of the running window in frames; None = [] (or longer than the recording): one baseline per neuron
 
 
 def _mround(x):
@@ -1905,6 +1909,71 @@ class Sources2D:
                 else:
                     Ybg[pp, t0 - (f0 - 1):t0 - (f0 - 1) + n] = self.engine.reconstruct_background(v.pid[idx], b0_[bp], b0_new_[pp], t0, n).T
         return Ybg.reshape(v.d1, v.d2, -1, order="F")
+
+    def extract_DF_F_endoscope(self, Ybg=None, want_Yf=False):
+        """[C_df, C_raw_df, Df] = extract_DF_F_endoscope(obj, Ybg)  (@Sources2D/Sources2D.m:540-570): the background projected onto every footprint,
+        Yf = (A ./ sum(A.^2, 1))' * Ybg (:545); its baseline Df = median / prctile(Yf, df_prctile, 2) (:549-553), or with options.df_window <= T
+        medfilt1(Yf, w, [], 2, 'truncate') / running_percentile(Yf(k, :), w, df_prctile) (:559, :563); C_df = C ./ Df, C_raw_df = C_raw ./ Df.  Sets nothing on the
+        object, like the reference.  Df is (K,) float64 without a window and (K, T) with one; C_df, C_raw_df are float32.
+
+        Ybg = None: the background is never assembled.  Per owned patch the residual of (A_prev, C_prev) is requested as reconstruct_background requests it, and the
+        engine reconstructs and projects frame chunks on the device (df_add_background[_ssub]); a sharded run all-reduces the K x T projection once.
+        Ybg given (d1 x d2 x T or d x T, the reference's argument): it goes up in frame chunks against the full-FOV A (df_add_frames).  Nothing is computed on the host.
+        Raises RuntimeError where reconstruct_background would (no data, no background fit yet).
+
+        Deviations: a row of Yf with a non-finite value (an empty footprint: 0 * Inf) has NaN throughout its Df row -- the reference's three estimators disagree with
+        each other on NaN; Df is float64, C_df and C_raw_df are (float)((double)C / Df).  medfilt1 and prctile are MathWorks functions restated from their
+        documentation (parity unpinned).  want_Yf = True appends Yf (K x T float64) to the result."""
+        self._need_data()
+        v, o, eng = self.video, self.options, self.engine
+        K, T = self.C.shape
+        p = float(o.df_prctile)
+        w = 0 if o.df_window is None else int(o.df_window)
+        if not (0.0 <= p <= 100.0) or w < 0:
+            raise ValueError("df_prctile must lie in [0, 100] and df_window must not be negative")
+        A = self.A if sp.isspmatrix_csc(self.A) else sp.csc_matrix(self.A)
+        C_raw = self.C_raw if (self.C_raw is not None and self.C_raw.shape[0] == K) else self.C
+        if Ybg is None:
+            b0_ = self.reconstruct_b0().reshape(-1, order="F")                                       # :1292 (a collective when sharded)
+            b0_new_ = np.asarray(self.b0_new, dtype=np.float64).reshape(-1, order="F")               # :1293
+        else:
+            Y = np.asarray(Ybg)
+            Y = Y.reshape(-1, Y.shape[-1], order="F")
+            if Y.shape != (v.d1 * v.d2, T):
+                raise ValueError("Ybg has %s samples, expected %d x %d" % (Y.shape, v.d1 * v.d2, T))
+        eng.df_begin(K, T)
+        try:
+            if Ybg is None:
+                for idx in v.owned:
+                    pp, bp = v.patch_pix[idx], v.block_pix[idx]
+                    indp, A_prev_b = self._prev_block_of(idx)                                            # :1317-1320
+                    if self.ssub != 1:
+                        eng.background_ssub(v.pid[idx], self.pid_fit[idx], self.ssub, A_prev_b if indp.size else None,
+                                            self._rows(self.C_prev, indp) if indp.size else None, b0_[bp])
+                    else:
+                        self._residual(idx, A_prev_b if indp.size else None, self._rows(self.C_prev, indp) if indp.size else None)
+                    ind, A_pp = self._slice(A, idx, "patch")
+                    if self.ssub != 1:
+                        eng.df_add_background_ssub(v.pid[idx], b0_new_[pp], A_pp, ind)
+                    else:
+                        eng.df_add_background(v.pid[idx], b0_[bp], b0_new_[pp], A_pp, ind)
+                if self.dist is not None and (v.world_size > 1 or self.force_collectives):               # every rank holds the sum over its own patches
+                    eng.df_load(self._allreduce(eng.df_fetch()))
+            elif K:
+                step = max(4, min(4096, ((64 << 20) // (4 * Y.shape[0])) & ~3))
+                allk = np.arange(K, dtype=np.int32)
+                for t0 in range(0, T, step):
+                    eng.df_add_frames(np.ascontiguousarray(Y[:, t0:t0 + step].T, dtype=np.float32), t0, A, allk)
+        except Exception:
+            eng.df_close()                                           # (a refused call must not leave the accumulator open)
+            raise
+        with np.errstate(divide="ignore"):
+            inv = 1.0 / np.asarray(A.astype(np.float64).power(2).sum(axis=0)).ravel() if K else np.zeros(0)     # :545 (an empty footprint: Inf)
+        try:
+            return eng.df_finish(inv, p, w, self.C, C_raw, want_Yf=want_Yf)
+        except Exception:
+            eng.df_close()
+            raise
 
     # -- temporal -----------------------------------------------------------------------
     def update_temporal_parallel(self, use_parallel=True, use_c_hat=True):

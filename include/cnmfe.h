@@ -500,6 +500,47 @@ int cnmfe_reconstruct_background_ssub(cnmfe_ctx *ctx, int patch_id, const float 
 int cnmfe_compute_rss_ssub(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx,
                            const float *A_val, const float *C, int c_order, const float *b0_new /* d */, double *rss_out);
 
+/* ---- (i) dF/F: [C_df, C_raw_df, Df] = extract_DF_F_endoscope(obj, Ybg)   @Sources2D/Sources2D.m:540-570, CNMFSetParms.m:73-74 (df_prctile 50, df_window [])
+ *   Yf = (A ./ sum(A.^2, 1))' * Ybg  (:545);  Df = median(Yf, 2) / prctile(Yf, df_prctile, 2) without a window (:549-553), medfilt1(Yf, w, [], 2, 'truncate') /
+ *   running_percentile(Yf(k, :), w, df_prctile) with one (:559, :563; utilities/running_percentile.m:74-121);  C_df = C ./ Df,  C_raw_df = C_raw ./ Df  (:554-555, :567-568).
+ * Ybg = reconstruct_background() never exists as a whole: Yf is accumulated in a K x T fp64 matrix of the context, patch by patch and frame chunk by frame chunk.
+ *   cnmfe_df_begin(ctx, K, T)                 the accumulator, zeroed.  64 <= T <= 147456, K = 0 is legal; CNMFE_ESTATE while one is open.
+ *   cnmfe_df_add_frames(...)                  acc[ind_m[j], frame0 + t] += sum_i A(i, j) Ybg(i, t), t in [0, nframes): Ybg d x nframes frame-major fp32 in host or device
+ *                                             memory (what cnmfe_reconstruct_background writes), A d x Km CSC over those d rows (empty columns are legal), ind_m the
+ *                                             Km distinct accumulator rows.  The product of two fp32 values is formed and summed in fp64, in a fixed order.
+ *   cnmfe_df_add_background[_ssub](...)       the same for all T frames of one patch with Ybg taken from the patch exactly as cnmfe_reconstruct_background[_ssub] takes
+ *                                             it (same arguments, same preconditions: CNMFE_ESTATE without the residual / without cnmfe_background_ssub; a recorded or
+ *                                             pending residual is realised first); A over the PATCH rows.  Frame chunks (a multiple of 4 frames, at most 256 MB of
+ *                                             scratch kept with the patch's lane) are reconstructed and projected in turn: nothing of d x T is allocated.  Runs on the
+ *                                             patch's lane; the projections of different lanes follow each other in call order, so the bits do not depend on the lanes.
+ *   cnmfe_df_fetch / cnmfe_df_load            the accumulator to / from the host, K x T ROW-MAJOR doubles (a sharded run: fetch, all-reduce, load -- one K x T collective
+ *                                             per session); load opens an accumulator if none is open.  cnmfe_df_dims: its K x T (CNMFE_ESTATE if none is open).
+ *   cnmfe_df_finish(...)                      scales row k by inv_norm[k] = 1 / sum(A(:, k).^2) (K doubles, computed by the host in float64), takes the baseline, divides,
+ *                                             writes the host outputs (ROW-MAJOR; each may be NULL) and closes the accumulator.  df_window = 0 or > T: no window, Df_out
+ *                                             receives K doubles; else K x T doubles.  0 < df_window <= 16384 (DF_WINDOW_MAX: a longer window that is not longer than the
+ *                                             recording is CNMFE_EUNSUPPORTED -- every output sample selects over its whole window); df_prctile outside [0, 100] or
+ *                                             df_window < 0 is CNMFE_EINVAL.  (C, c_src) and (C_raw, raw_src) are trace SOURCES of section (h): a host pointer with its
+ *                                             order (counted by merge_trace_uploads), CNMFE_BOUND or CNMFE_RES_CRAW.  Yf_out (may be NULL): the scaled K x T projection.
+ *                                             With every output NULL the accumulator is only closed (what a caller does whose own session failed half way).
+ * Deviations: a row of Yf that holds any non-finite value (a neuron with an empty footprint: 0 * Inf) gives NaN throughout its Df row (the reference's three
+ * estimators disagree with each other on NaN); Df is float64, C_df and C_raw_df are float32, each (float)((double)C / Df).
+ * medfilt1 and prctile are MathWorks functions, restated from their documentation (PARITY UNPINNED); running_percentile is in the reference tree.
+ * Traces of up to 20346 frames (windowed: 20480) are staged in LDS by the baseline kernels, longer ones are read where they lie (option trace_long = 1 forces that: equal bits).
+ * Every index is checked on the host before anything is launched: CNMFE_EINVAL for a row of A outside [0, d), an ind_m outside [0, K) or repeated, frames beyond T. */
+int cnmfe_df_begin(cnmfe_ctx *ctx, int32_t K, int64_t T);
+int cnmfe_df_add_frames(cnmfe_ctx *ctx, int64_t d, int64_t frame0, int64_t nframes, const float *Ybg /* d x nframes */, int memspace, int32_t Km,
+                        const int64_t *A_colptr, const int32_t *A_rowidx /* in [0, d) */, const float *A_val, const int32_t *ind_m /* Km */);
+int cnmfe_df_add_background(cnmfe_ctx *ctx, int patch_id, const float *b0_block /* d_b */, const float *b0_new /* d */, int32_t Km, const int64_t *A_colptr,
+                            const int32_t *A_rowidx, const float *A_val, const int32_t *ind_m);
+int cnmfe_df_add_background_ssub(cnmfe_ctx *ctx, int patch_id, const float *b0_new /* d */, int32_t Km, const int64_t *A_colptr, const int32_t *A_rowidx,
+                                 const float *A_val, const int32_t *ind_m);
+int cnmfe_df_dims(cnmfe_ctx *ctx, int32_t *K, int64_t *T);
+int cnmfe_df_fetch(cnmfe_ctx *ctx, double *Yf_out /* K x T */);
+int cnmfe_df_load(cnmfe_ctx *ctx, int32_t K, int64_t T, const double *Yf /* K x T */);
+int cnmfe_df_finish(cnmfe_ctx *ctx, const double *inv_norm /* K */, double df_prctile, int64_t df_window /* 0: none */, const float *C, int c_src,
+                    const float *C_raw, int raw_src, float *C_df_out /* K x T */, float *C_raw_df_out /* K x T */, double *Df_out /* K, or K x T with a window */,
+                    double *Yf_out /* K x T or NULL */);
+
 /* ---- S6: post_process_spatial (connected = true, circular = false)
  * @Sources2D/post_process_spatial.m:19-32 -> endoscope/connectivity_constraint.m:1-18.
  * A is the whole-FOV d1*d2 x K CSC; keep[nnz] receives 1 for entries that survive. */
@@ -574,7 +615,7 @@ int cnmfe_synchronize(cnmfe_ctx *ctx);
  * Diagnostics (scripts/): solve_probe, r1_probe (phase probes: results are NOT the product's), deconv_trace, host_trace (1: host-side phase times of every call on
  * stderr, 2: + slow launch calls), debug (1: NaN-poison never-computed table entries), trace_long (default 0: the seed-statistics, peel-trace, trace-difference and
  * trace-tag kernels keep the trace in LDS while it fits beside the Welch transform, T <= 20416, and in global memory beyond; 1: the long flavour at every T --
- * results are bit-equal, tests/test_gpu_long_flavour.py).
+ * results are bit-equal, tests/test_gpu_long_flavour.py; the dF/F baselines of section (i) follow the same option with their own limits of 20346 / 20480 frames, tests/test_gpu_dff.py).
  * Round 6 removed the retired names rounds 2-5 still accepted and ignored (gram_mode, gram_flush, solve_defer, solve_mode, solve_gfill, gram_kernel, r1_arc_d,
  * r1_arc_bias, r1_duo_ord) and the experiment switches tile_order, gram_probe, r1_nseg.
  * Every option can be preset for a process with CNMFE_OPTS="name=value,..." (logged once on stderr). */
