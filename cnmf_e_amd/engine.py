@@ -190,8 +190,105 @@ for _op in ("add", "sub", "mul", "truediv", "radd", "rsub", "rmul", "rtruediv", 
 LazyHostTraces.__hash__ = object.__hash__
 
 
+class SpatialResult:
+    """The spatial update of one patch that update_spatial(defer=True) queued: the sweeps are in flight, the caller does other host work under them and calls this
+    object for the values (before the next spatial update).  r() is the updated A as a CSC matrix with exactly IND's pattern (explicit zeros kept).
+    connected_fov = (d1, d2): the patch is the whole field of view -- also apply the connectivity constraint on the device and return (A_raw, A) instead of A_raw.
+    compact: without the stored zeros of the mask pattern (rows sorted); with connected_fov, A_raw then comes as a callable that builds it on first use."""
+    def __init__(self, eng, d, K, icp, iri, out):
+        self._eng, self._d, self._K, self._icp, self._iri, self._out = eng, d, K, icp, iri, out
+        self._pend = None                                 # the queued download: None, or (ticket, pinned block, its bytes, True: the keep flags come with the values)
+
+    def _queue(self, nbytes, keep, call):
+        """a download into a pooled pinned block (by size class), queued by call(block, ticket)"""
+        if self._out.size == 0 or self._pend is not None:
+            return
+        nb = 1 << max(12, int(nbytes - 1).bit_length())
+        ptr = self._eng._pinned_take(nb)
+        tk = C.c_int64(0)
+        try:
+            L.check(call(ptr, C.byref(tk)))
+        except Exception:
+            self._eng._pinned_give(ptr, nb)
+            raise
+        self._pend = (tk.value, ptr, nb, keep)
+
+    def _collect(self, keep=None):
+        """the queued download (keep: the one with the keep flags): wait for its ticket, copy out of the pinned block, give the block back.  False: none of that kind"""
+        if self._pend is None or self._pend[3] != (keep is not None):
+            return False
+        (tk, ptr, nb, _), self._pend, out = self._pend, None, self._out
+        try:
+            L.check(L.lib.cnmfe_ticket_wait(self._eng._ctx, tk))
+            C.memmove(out.ctypes.data, ptr, out.size * 4)
+            if keep is not None:
+                C.memmove(keep.ctypes.data, ptr + out.size * 4, out.size)
+        finally:
+            self._eng._pinned_give(ptr, nb)
+        return True
+
+    def start(self):
+        """queue the download into pinned memory right behind the sweeps: r() then waits for that point of the stream only, so the caller may queue the next patch first"""
+        n = int(self._out.size)
+        self._queue(n * 4, False, lambda ptr, tk: L.lib.cnmfe_update_spatial_fetch_async(self._eng._ctx, ptr, n, tk))
+
+    def start_connected(self, connected_fov):
+        """queue the connectivity constraint + the downloads of (values, keep flags) into pinned memory now; r(connected_fov=...) then only waits for them"""
+        n = int(self._out.size)
+        self._queue(n * 5, True, lambda ptr, tk: L.lib.cnmfe_update_spatial_fetch_connected_async(
+            self._eng._ctx, int(connected_fov[0]), int(connected_fov[1]), self._K, _p(self._icp, L.i64p), _p(self._iri, L.i32p), ptr, ptr + n * 4, tk))
+
+    def temporal_early(self):
+        """behind start_connected: queue the temporal update's projection of the post-processed result where it lies (cnmfe_temporal_early_project).
+        Returns a token for temporal_early_claim, 0 when the engine declines"""
+        if self._pend is None or not self._pend[3] or not hasattr(L.lib, "cnmfe_temporal_early_project"):
+            return 0
+        tk = C.c_int64(0)
+        L.check(L.lib.cnmfe_temporal_early_project(self._eng._ctx, self._K, _p(self._icp, L.i64p), _p(self._iri, L.i32p), C.byref(tk)))
+        return tk.value
+
+    def compacted(self, vals, keep=None):
+        """CSC of the non-zero values (keep: and flagged entries) on IND's pattern, rows sorted: one pass in the library's host helper --
+        scipy's eliminate_zeros() on the 250 k-entry mask pattern was the longest host step between the spatial and the temporal update"""
+        K, icp, iri = self._K, self._icp, self._iri
+        optr = np.empty(K + 1, dtype=np.int64); orow = np.empty(max(1, vals.size), dtype=np.int32); oval = np.empty(max(1, vals.size), dtype=np.float32)
+        n = C.c_int64(0)
+        L.check(L.lib.cnmfe_csc_drop_zeros(K, icp.ctypes.data, iri.ctypes.data, vals.ctypes.data, None if keep is None else keep.ctypes.data,
+                                           optr.ctypes.data, orow.ctypes.data, oval.ctypes.data, C.byref(n)))
+        M = sp.csc_matrix((oval[:n.value], orow[:n.value], optr), shape=(self._d, K))
+        M.has_canonical_format = True                            # (sorted rows, no duplicates: the mask's pattern was canonical)
+        return M
+
+    def _on_pattern(self, vals):
+        return sp.csc_matrix((vals, self._iri.copy(), self._icp.copy()), shape=(self._d, self._K))
+
+    def __call__(self, connected_fov=None, compact=False):
+        eng, out = self._eng, self._out
+        if connected_fov is None:
+            if not self._collect():
+                L.check(L.lib.cnmfe_update_spatial_fetch(eng._ctx, _p(out, L.f32p), int(out.size)))
+            return self.compacted(out) if compact else self._on_pattern(out)
+        keep = np.zeros(out.size, dtype=np.uint8)
+        if not self._collect(keep):
+            L.check(L.lib.cnmfe_update_spatial_fetch_connected(eng._ctx, int(connected_fov[0]), int(connected_fov[1]), self._K, _p(self._icp, L.i64p),
+                                                               _p(self._iri, L.i32p), _p(out, L.f32p), _p(keep, L.u8p)))
+        if compact:                                  # the raw update (obj.A before post-processing) is compacted when somebody reads it: nothing in the iteration does
+            return (lambda: self.compacted(out)), self.compacted(out, keep)
+        return self._on_pattern(out), self._on_pattern(out * keep)
+
+
 class Engine:
-    supports_lazy_traces = True
+    # what this engine offers beyond the blocking calls.  Sources2D asks these flags, where it decides, and nothing else; every stand-in for an engine declares them
+    supports_lazy_traces = True       # update_spatial(defer=True) -> SpatialResult, stitch_finish(want="lazy")
+    supports_temporal_jobs = True     # hals_temporal_job / temporal_jobs_sweep / stitch_add_job: several patches' temporal updates swept together
+    supports_queued_fetch = True      # SpatialResult.start() and r(compact=True): a patch's result collected late
+    supports_connected_start = True   # SpatialResult.start_connected()
+    supports_temporal_early = True    # SpatialResult.temporal_early(), temporal_early_claim(), hals_temporal(want_aa=False)
+    supports_bound_traces = True      # bind_traces()
+    supports_bound_deconv = True      # deconv_temporal_bound()
+    supports_fit_reserve = True       # fit_reserve()
+    supports_synchronize = True       # synchronize()
+
     # pinned buffers of LazyHostTraces, recycled by size (page-locking 20 MB costs milliseconds)
     def _pinned_take(self, nbytes):
         pool = self.__dict__.setdefault("_pinned_pool", {})
@@ -339,22 +436,7 @@ class Engine:
         """[Cn, PNR] = correlation_image_endoscope(Ypatch, options) of the BLOCK of a patch (correlation_image_endoscope.m:36-96) over the first `nframes`
         frames (default all): psf = the spatial filter (sources2d.seed_psf; None = no filter), Q = nframes x M orthonormal detrend basis (None = none),
         sig = the threshold factor.  Two float32 arrays of d_b pixels, column-major in the block."""
-        info = self._patch[pid]
-        n = info["T"] if nframes is None else int(nframes)
-        psf_a, psf_n = None, 0
-        if psf is not None and np.size(psf):
-            psf = np.asarray(psf, dtype=np.float32)
-            if psf.ndim != 2 or psf.shape[0] != psf.shape[1]:
-                raise ValueError("psf must be square, got %s" % (psf.shape,))
-            psf_n = int(psf.shape[0])
-            psf_a = np.ascontiguousarray(psf.T)                            # column-major
-        Q_a, M = None, 0
-        if Q is not None and np.size(Q):
-            Q = np.asarray(Q, dtype=np.float64)
-            if Q.ndim != 2 or Q.shape[0] != n:
-                raise ValueError("Q must be (%d, M), got %s" % (n, Q.shape))
-            M = int(Q.shape[1])
-            Q_a = np.ascontiguousarray(Q.T)                                # column-major
+        info, n, psf_a, psf_n, Q_a, M = self._seed_args(pid, psf, nframes, Q)
         Cn = np.empty(info["d_b"], dtype=np.float32); PNR = np.empty(info["d_b"], dtype=np.float32)
         L.check(L.lib.cnmfe_seed_images(self._ctx, pid, _p(psf_a, L.f32p), psf_n, int(frame0), n, _p(Q_a, L.f64p), M, float(sig),
                                         _p(Cn, L.f32p), _p(PNR, L.f32p)))
@@ -519,8 +601,8 @@ class Engine:
         return out
 
     def update_spatial(self, pid, algorithm, A_patch, C_patch, IND_patch, sn=None, param=3, defer=False):
-        """Returns the updated A as a CSC matrix with exactly IND's pattern (explicit zeros kept).  defer=True returns a callable instead that
-        fetches it: the sweeps are queued, the caller does other host work under them and calls it afterwards (before the next spatial update)."""
+        """Returns the updated A as a CSC matrix with exactly IND's pattern (explicit zeros kept).  defer=True returns with the sweeps
+        queued, and a SpatialResult that fetches it."""
         info = self._patch[pid]
         alg = {"hals": L.SPATIAL_HALS, "hals_thresh": L.SPATIAL_HALS_THRESH, "nnls": L.SPATIAL_NNLS}[algorithm]
         K, cp, ri, va = _csc(A_patch, info["d"])
@@ -535,89 +617,7 @@ class Engine:
         L.check(L.lib.cnmfe_update_spatial(self._ctx, pid, alg, K, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p), cptr, cord,
                                            _p(icp, L.i64p), _p(iri, L.i32p), _p(snf, L.f32p), int(param), None if defer else _p(out, L.f32p)))
         if defer:
-            pend = {}
-            def start():
-                """queue the download into pinned memory right behind the sweeps (cnmfe_update_spatial_fetch_async): fetch() then waits for that point of
-                the stream only, so the caller may queue the next patch's kernels first"""
-                if out.size == 0 or "t" in pend:
-                    return
-                nb = 1 << max(12, int(out.size * 4 - 1).bit_length())          # pooled by size class
-                ptr = self._pinned_take(nb)
-                tk = C.c_int64(0)
-                try:
-                    L.check(L.lib.cnmfe_update_spatial_fetch_async(self._ctx, ptr, int(out.size), C.byref(tk)))
-                except Exception:
-                    self._pinned_give(ptr, nb)
-                    raise
-                pend["t"] = (tk.value, ptr, nb)
-            def compacted(vals, keep=None):
-                """CSC of the non-zero values (keep: and flagged entries) on IND's pattern, rows sorted: one pass in the library's host helper --
-                scipy's eliminate_zeros() on the 250 k-entry mask pattern was the longest host step between the spatial and the temporal update"""
-                optr = np.empty(K + 1, dtype=np.int64); orow = np.empty(max(1, vals.size), dtype=np.int32); oval = np.empty(max(1, vals.size), dtype=np.float32)
-                n = C.c_int64(0)
-                L.check(L.lib.cnmfe_csc_drop_zeros(K, icp.ctypes.data, iri.ctypes.data, vals.ctypes.data, None if keep is None else keep.ctypes.data,
-                                                   optr.ctypes.data, orow.ctypes.data, oval.ctypes.data, C.byref(n)))
-                M = sp.csc_matrix((oval[:n.value], orow[:n.value], optr), shape=(info["d"], K))
-                M.has_canonical_format = True                            # (sorted rows, no duplicates: the mask's pattern was canonical)
-                return M
-            def start_connected(connected_fov):
-                """queue the connectivity constraint + the downloads of (values, keep flags) into pinned memory now; fetch(connected_fov=...) then only waits for them"""
-                if out.size == 0 or "c" in pend or "t" in pend:
-                    return
-                nb = 1 << max(12, int(out.size * 5 - 1).bit_length())
-                ptr = self._pinned_take(nb)
-                tk = C.c_int64(0)
-                try:
-                    L.check(L.lib.cnmfe_update_spatial_fetch_connected_async(self._ctx, int(connected_fov[0]), int(connected_fov[1]), K, _p(icp, L.i64p), _p(iri, L.i32p),
-                                                                             ptr, ptr + out.size * 4, C.byref(tk)))
-                except Exception:
-                    self._pinned_give(ptr, nb)
-                    raise
-                pend["c"] = (tk.value, ptr, nb)
-            def fetch(connected_fov=None, compact=False):
-                """connected_fov = (d1, d2): the patch is the whole field of view -- also apply the connectivity constraint on the device and
-                return (A_raw, A) instead of A_raw.  compact: without the stored zeros of the mask pattern (rows sorted); with connected_fov, A_raw then comes as a
-                callable that builds it on first use"""
-                if connected_fov is None:
-                    if "t" in pend:
-                        tk, ptr, nb = pend.pop("t")
-                        try:
-                            L.check(L.lib.cnmfe_ticket_wait(self._ctx, tk))
-                            C.memmove(out.ctypes.data, ptr, out.size * 4)
-                        finally:
-                            self._pinned_give(ptr, nb)
-                    else:
-                        L.check(L.lib.cnmfe_update_spatial_fetch(self._ctx, _p(out, L.f32p), int(out.size)))
-                    return compacted(out) if compact else sp.csc_matrix((out, iri.copy(), icp.copy()), shape=(info["d"], K))
-                keep = np.zeros(out.size, dtype=np.uint8)
-                if "c" in pend:
-                    tk, ptr, nb = pend.pop("c")
-                    try:
-                        L.check(L.lib.cnmfe_ticket_wait(self._ctx, tk))
-                        C.memmove(out.ctypes.data, ptr, out.size * 4)
-                        C.memmove(keep.ctypes.data, ptr + out.size * 4, out.size)
-                    finally:
-                        self._pinned_give(ptr, nb)
-                else:
-                    L.check(L.lib.cnmfe_update_spatial_fetch_connected(self._ctx, int(connected_fov[0]), int(connected_fov[1]), K, _p(icp, L.i64p), _p(iri, L.i32p),
-                                                                       _p(out, L.f32p), _p(keep, L.u8p)))
-                if compact:                                  # the raw update (obj.A before post-processing) is compacted when somebody reads it: nothing in the iteration does
-                    return (lambda: compacted(out)), compacted(out, keep)
-                A_raw = sp.csc_matrix((out, iri.copy(), icp.copy()), shape=(info["d"], K))
-                A_pp = sp.csc_matrix((out * keep, iri.copy(), icp.copy()), shape=(info["d"], K))
-                return A_raw, A_pp
-            def temporal_early():
-                """behind start_connected: queue the temporal update's projection of the post-processed result where it lies (cnmfe_temporal_early_project).
-                Returns a token for temporal_early_claim, 0 when the engine declines"""
-                if "c" not in pend or not hasattr(L.lib, "cnmfe_temporal_early_project"):
-                    return 0
-                tk = C.c_int64(0)
-                L.check(L.lib.cnmfe_temporal_early_project(self._ctx, K, _p(icp, L.i64p), _p(iri, L.i32p), C.byref(tk)))
-                return tk.value
-            fetch.start = start
-            fetch.start_connected = start_connected
-            fetch.temporal_early = temporal_early
-            return fetch
+            return SpatialResult(self, info["d"], K, icp, iri, out)
         return sp.csc_matrix((out, iri.copy(), icp.copy()), shape=(info["d"], K))
 
     def hals_temporal(self, pid, A_patch, C_patch, maxIter=5, want_C=True, want_raw=True, want_aa=True):
@@ -710,8 +710,6 @@ class Engine:
         self._stitch_shape = (int(K), int(T))
 
     # ---- several patches per context: set the patches' temporal updates up, sweep them together, add each to the stitch (cnmfe_hals_temporal_job) ----
-    supports_temporal_jobs = True
-
     def hals_temporal_job(self, pid, A_patch, C_patch, maxIter, deconv_options=None, kernel_pars=None):
         """everything of hals_temporal / hals_temporal_deconv up to the Gauss-Seidel sweeps; returns the job number (for stitch_add_job)"""
         info = self._patch[pid]

@@ -743,6 +743,20 @@ class Sources2D:
         # test hook: take the collective (sharded) branches even with one rank, so that a single-GPU box can run the all-gather of A, the
         # device-side stitch of C_raw and the lazy all-reduces over RCCL exactly as an N-rank job does (scripts/nccl_smoke.py)
         self.force_collectives = False
+        # what one update call leaves for the next (each: who writes it; what voids it)
+        self._resid_tag = {}            # patch -> who asked for its resident residual (_residual; None = anybody); a background fit of the patch drops the entry
+        self._cur_blocks = {}           # patch -> (ind, A(block, ind)), cut by update_temporal_parallel under its sweeps; serves the next fit while _cur_blocks_src is self.A
+        self._cur_blocks_src = None     # the A they were cut from
+        self._prev_blocks = {}          # patch -> (ind, A_prev(block, ind)): filled by update_background_parallel, completed by _prev_block_of, which empties it ...
+        self._prev_csr_src = None       # ... when this, the A_prev they were cut from, is no longer self.A_prev
+        self._early_u = None            # (token, A): the temporal projection queued for the one-patch spatial result A; reset by every spatial launch and its taker
+        self._prefetch_wanted = False   # _spatial_finish: the next search masks are to start under the temporal update's sweep call; _start_wanted_prefetch clears it
+        self._ind_future = None         # (A, future of A's search masks) of _prefetch_search_location; taken by _search_location_csc, ignored unless A is self.A
+        self._pool = None               # the mask thread's executor, made on first use
+        self._gather_cap = 0            # _gather_sparse: entries per rank its padded block holds; grows with the gathered counts
+        self._cmean_of = None           # the C whose row means _cmean holds; any other self.C voids them
+        self._init_observer = None      # tests: set to a function the two initialisations call at every step; never reset
+        self._bbox_cache = ()           # _bbox_of: (matrix, bounding boxes of its columns) of the last four matrices, by identity
         self._bind_C()
         self.ssub = int(options.bg_ssub)
         npatch = len(video.order)
@@ -757,10 +771,19 @@ class Sources2D:
                 self.engine.patch_derive(video.pid[idx], self.pid_res[idx], self.ssub, "bicubic")
                 self.engine.ring_init(self.pid_fit[idx], rr, options.num_neighbors)
                 self.engine.ring_init(self.pid_res[idx], rr, options.num_neighbors)
-            if hasattr(self.engine, "fit_reserve"):                       # the fit's large buffers now, not inside the first update_background_parallel
+            if self._can("fit_reserve"):                          # the fit's large buffers now, not inside the first update_background_parallel
                 self.engine.fit_reserve(video.pid[idx] if self.ssub == 1 else self.pid_fit[idx])
             self.P["Ymean"][idx] = self.engine.ymean(video.pid[idx])[video.ind_patch[idx]]      # :338-339, patch part
         self._ymean_full = None
+
+    def _can(self, what):
+        """the engine's class-level flag supports_<what> (engine.Engine lists them), read where the decision is made; an engine that does not declare it does not offer it"""
+        return getattr(self.engine, "supports_" + what, False)
+
+    @property
+    def _sharded(self):
+        """the collective branches are taken: the patches are spread over the ranks of a group (or the test hook says so)"""
+        return self.dist is not None and (self.video.world_size > 1 or self.force_collectives)
 
     # -- accessors ------------------------------------------------------------------
     def get_W(self, idx):
@@ -768,47 +791,43 @@ class Sources2D:
 
     def _slice(self, A, idx, kind, cols=None):
         """(ind, A(pixels of idx's block / patch / halo, ind)): the reference's `mask` selections (update_*_parallel.m) without a CSR of A"""
-        t, n, span = self.video.lut(idx, kind)
-        cand = None
-        if cols is None and sp.isspmatrix_csc(A) and A.has_sorted_indices:
-            # columns whose bounding box meets the rectangle (block for 'block' / 'halo', patch for 'patch'): with 4 x 4 patches the first / last
-            # stored row test of rows_of alone passes every neuron of the patch's COLUMN band; the boxes are found once per matrix
-            bb = self._bbox_of(A)
-            if bb is not None:
-                v = self.video
-                r0, r1, c0, c1 = [int(x) - 1 for x in (v.patch_pos[idx] if kind == "patch" else v.block_pos[idx])]
-                nz, rmin, rmax, cmin, cmax = bb
-                cand = nz[(rmax >= r0) & (rmin <= r1) & (cmax >= c0) & (cmin <= c1)]
+        v = self.video
+        t, n, span = v.lut(idx, kind)
+        cand = self._box_candidates(A, v.patch_pos[idx] if kind == "patch" else v.block_pos[idx]) if cols is None else None
         return rows_of(A, t, n, cols=cols, span=span, cand=cand)
+
+    def _box_candidates(self, A, rect):
+        """the columns of A whose bounding box meets the rectangle (block for 'block' / 'halo', patch for 'patch'): with 4 x 4 patches the first / last stored row
+        test of rows_of alone passes every neuron of the patch's COLUMN band; the boxes are found once per matrix.  None: A is not a sorted CSC matrix"""
+        bb = self._bbox_of(A) if sp.isspmatrix_csc(A) and A.has_sorted_indices else None
+        if bb is None:
+            return None
+        r0, r1, c0, c1 = [int(x) - 1 for x in rect]
+        nz, rmin, rmax, cmin, cmax = bb
+        return nz[(rmax >= r0) & (rmin <= r1) & (cmax >= c0) & (cmin <= c1)]
 
     def _slice_block_patch(self, A, idx):
         """(ind, A(block, ind), A(patch, ind)) = _slice(A, idx, "block") followed by _slice(A, idx, "patch", cols=ind), in one pass over the candidates"""
-        if sp.isspmatrix_csc(A) and A.has_sorted_indices:
-            bb = self._bbox_of(A)
-            if bb is not None:
-                v = self.video
-                tb, nb, _ = v.lut(idx, "block"); tp, npx, _ = v.lut(idx, "patch")
-                r0, r1, c0, c1 = [int(x) - 1 for x in v.block_pos[idx]]
-                nz, rmin, rmax, cmin, cmax = bb
-                got = _select_block_patch_native(A, tb, nb, tp, npx, nz[(rmax >= r0) & (rmin <= r1) & (cmax >= c0) & (cmin <= c1)])
-                if got is not None:
-                    return got
+        v = self.video
+        cand = self._box_candidates(A, v.block_pos[idx])
+        if cand is not None:
+            tb, nb, _ = v.lut(idx, "block"); tp, npx, _ = v.lut(idx, "patch")
+            got = _select_block_patch_native(A, tb, nb, tp, npx, cand)
+            if got is not None:
+                return got
         ind, A_blk = self._slice(A, idx, "block")
         return ind, A_blk, (self._slice(A, idx, "patch", cols=ind)[1] if ind.size else None)
 
     def _bbox_of(self, A):
         """(non-empty columns, their first / last image row and column), cached for the last few matrices by identity"""
-        cache = self.__dict__.setdefault("_bbox_cache", [])
-        for M, bb in cache:
+        for M, bb in self._bbox_cache:
             if M is A:
                 return bb
         bb = _bbox_native(A, self.video.d1)
         nz = np.nonzero(np.diff(A.indptr) > 0)[0] if bb is None else None
-        if bb is not None:
-            pass
-        elif nz.size == 0:
+        if bb is None and nz.size == 0:
             bb = (nz, nz, nz, nz, nz)
-        else:
+        elif bb is None:
             d1 = self.video.d1
             rr = A.indices % d1
             starts = A.indptr[nz]
@@ -816,8 +835,7 @@ class Sources2D:
             cmin = A.indices[starts] // d1; cmax = A.indices[A.indptr[nz + 1] - 1] // d1
             rmin = np.minimum.reduceat(rr, starts); rmax = np.maximum.reduceat(rr, starts)
             bb = (nz, rmin, rmax, cmin, cmax)
-        cache.append((A, bb))
-        del cache[:-4]
+        self._bbox_cache = (self._bbox_cache + ((A, bb),))[-4:]
         return bb
 
     @staticmethod
@@ -828,17 +846,51 @@ class Sources2D:
 
     def _bind_C(self):
         """one upload of obj.C per iteration instead of one per engine call (cnmfe_traces_bind)"""
-        if hasattr(self.engine, "bind_traces"):
+        if self._can("bound_traces"):
             self.engine.bind_traces(self.C)
 
-    def _residual(self, idx, A_prev_b, C_prev_b, tag=None):
+    # -- the engine calls that come in two forms, bg_ssub = 1 and > 1: the one place that chooses --
+    def _residual(self, idx, A_prev_b, C_prev_b, tag=None, want=False):
         """the background-subtraction expression of update_spatial_parallel.m:162-178 / update_temporal_parallel.m:149-165.
         tag: who asked (see _temporal_residual_early); any other request replaces it"""
-        self.__dict__.setdefault("_resid_tag", {})[idx] = tag
+        self._resid_tag[idx] = tag
         if self.ssub == 1:
-            self.engine.residual(self.video.pid[idx], A_prev_b, C_prev_b)
+            return self.engine.residual(self.video.pid[idx], A_prev_b, C_prev_b, want=want)
+        return self.engine.residual_ssub(self.video.pid[idx], self.pid_res[idx], self.ssub, A_prev_b, C_prev_b, want=want)
+
+    def _fit(self, idx, A_block, C_block):
+        o, pid = self.options, self.video.pid[idx]
+        if self.ssub == 1:
+            return self.engine.fit_ring_model(pid, A_block, C_block, o.thresh_outlier, o.bg_acceleration, want_b0=False)         # update_background_parallel.m:218
+        return self.engine.fit_ring_model_ssub(pid, self.pid_fit[idx], self.pid_res[idx], self.ssub, A_block, C_block, o.thresh_outlier, o.bg_acceleration)   # :219-230
+
+    def _background_resident(self, idx, b0_):
+        """the background of patch idx where the three readers below take it: the residual of (A_prev, C_prev) on its block (Sources2D.m:1317-1320) -- the one the
+        temporal update asks for, so right after it this costs nothing --, with bg_ssub > 1 W times its 'nearest' reduction (:1325-1334), kept on the fit patch"""
+        A_prev_b, C_prev_b = self._prev_block_args(idx)
+        if self.ssub == 1:
+            self._residual(idx, A_prev_b, C_prev_b)
         else:
-            self.engine.residual_ssub(self.video.pid[idx], self.pid_res[idx], self.ssub, A_prev_b, C_prev_b)
+            self.engine.background_ssub(self.video.pid[idx], self.pid_fit[idx], self.ssub, A_prev_b, C_prev_b, b0_[self.video.block_pix[idx]])
+
+    def _reconstruct(self, idx, b0_, b0_new_, t0, n):
+        v, eng = self.video, self.engine
+        if self.ssub == 1:
+            return eng.reconstruct_background(v.pid[idx], b0_[v.block_pix[idx]], b0_new_[v.patch_pix[idx]], t0, n)
+        return eng.reconstruct_background_ssub(v.pid[idx], b0_new_[v.patch_pix[idx]], t0, n)
+
+    def _rss(self, idx, A_pp, C_p, b0_, b0_new_):
+        v, eng = self.video, self.engine
+        if self.ssub == 1:
+            return eng.compute_rss(v.pid[idx], A_pp, C_p, b0_[v.block_pix[idx]], b0_new_[v.patch_pix[idx]])
+        return eng.compute_rss_ssub(v.pid[idx], A_pp, C_p, b0_new_[v.patch_pix[idx]])
+
+    def _df_add_background(self, idx, b0_, b0_new_, A_pp, ind):
+        v, eng = self.video, self.engine
+        if self.ssub == 1:
+            eng.df_add_background(v.pid[idx], b0_[v.block_pix[idx]], b0_new_[v.patch_pix[idx]], A_pp, ind)
+        else:
+            eng.df_add_background_ssub(v.pid[idx], b0_new_[v.patch_pix[idx]], A_pp, ind)
 
     def init_residual(self, idx):
         """@Sources2D/initComponents_residual_parallel.m:106-121,186-217 (ring model): the video greedyROI_endoscope searches for missed
@@ -849,14 +901,9 @@ class Sources2D:
         (T, d_patch) float32 array (frame-major == the reference's d x T in MATLAB order).  greedyROI_endoscope itself is host code
         outside this engine (initialisation is out of scope)."""
         self._need_data()
-        v = self.video
         ind, A_blk = self._slice(self.A, idx, "block")                                               # :116-117
         C_blk = self._rows(self.C, ind) if ind.size else None                                        # :120
-        pid = v.pid[idx]
-        if self.ssub == 1:
-            out = self.engine.residual(pid, A_blk if ind.size else None, C_blk, want=True)
-        else:
-            out = self.engine.residual_ssub(pid, self.pid_res[idx], self.ssub, A_blk if ind.size else None, C_blk, want=True)
+        out = self._residual(idx, A_blk if ind.size else None, C_blk, want=True)
         if ind.size:
             A_pp = self._slice(self.A, idx, "patch", cols=ind)[1].tocsr()
             Cb = np.asarray(C_blk, dtype=np.float32)
@@ -883,6 +930,7 @@ class Sources2D:
     # how many patches' spatial results may be outstanding before the oldest is collected: the host queues that many patches ahead of the device (each
     # result waits in a pinned buffer of its size; a lag of 1 tied the host to the device's pace and left the device idle whenever a patch's host work ran long)
     spatial_lag = 16
+    _bbox_cache = ()                # (before __init__ has run, as on an object made with __new__: nothing cached yet)
 
     def _need_data(self):
         if self.video is None:
@@ -952,7 +1000,7 @@ class Sources2D:
         Returns (A d x K csc, C, C_raw, S (K x n float32), kernel_pars, center (K x 2, 1-based FOV))."""
         v, o = self.video, self.options
         d = v.d1 * v.d2
-        sharded = self.dist is not None and (v.world_size > 1 or self.force_collectives)
+        sharded = self._sharded
         counts = np.zeros(len(v.order), dtype=np.int64)
         for i, idx in enumerate(v.order):
             if idx in per_patch:
@@ -996,7 +1044,6 @@ class Sources2D:
         the given pixels of its block ONCE, in the given order -- the one deviation: the reference asks for another round of clicks until none is valid.
         Not built (NotImplementedError): ssub / tsub other than 1, detrend_method 'local_min', a frame range that does not start at 1, use_prev, save_avi /
         debug_on."""
-        from . import hostops
         self._need_data()
         v, o = self.video, self.options
         if int(o.ssub) != 1 or int(o.tsub) != 1:
@@ -1025,7 +1072,7 @@ class Sources2D:
         d = v.d1 * v.d2
         Cn = np.zeros(d, dtype=np.float64); PNR = np.zeros(d, dtype=np.float64)
         per_patch = {}
-        observer = getattr(self, "_init_observer", None)                  # tests: called with (patch idx, kind, data) at every extract / apply
+        observer = self._init_observer                                     # tests: called with (patch idx, kind, data) at every extract / apply
         for idx in v.owned:
             pid = v.pid[idx]
             pp, bp = v.patch_pos[idx], v.block_pos[idx]
@@ -1058,7 +1105,7 @@ class Sources2D:
             self.set_components(A, Cm, Craw)                              # :470-472
         else:                                                             # (traces of the first n frames only: kept, but not bound for the updates)
             self.A, self.C, self.C_raw = A, Cm, Craw
-            if hasattr(self.engine, "bind_traces"):
+            if self._can("bound_traces"):
                 self.engine.bind_traces(None)
         if o.deconv_flag:                                                 # :473-480
             self.S = Sm; self.P["kernel_pars"] = kp
@@ -1080,7 +1127,6 @@ class Sources2D:
         min_corr, min_pnr, seed_method: when given they overwrite the options and stay overwritten (:47-55) -- first of all, as in the reference, so a call that is
         then refused (seed_method = 'manual' without seeds) has changed them all the same.  seeds: as in initComponents_parallel, tried by the
         patch that holds them.  Not built (NotImplementedError): ssub / tsub other than 1, save_avi."""
-        from . import hostops
         self._need_data()
         v, o = self.video, self.options
         if int(o.ssub) != 1 or int(o.tsub) != 1:
@@ -1104,7 +1150,7 @@ class Sources2D:
         d = v.d1 * v.d2
         Cn = np.zeros(d, dtype=np.float64); PNR = np.zeros(d, dtype=np.float64)
         per_patch = {}
-        observer = getattr(self, "_init_observer", None)                  # tests (the hook of initComponents_parallel): (patch idx, kind, data) at every open /
+        observer = self._init_observer                                     # tests (the hook of initComponents_parallel): (patch idx, kind, data) at every open /
         want_video = observer is not None                                 # extract / apply; an observer is also handed the video every session was opened on
         for idx in v.owned:
             pid = v.pid[idx]
@@ -1177,7 +1223,7 @@ class Sources2D:
         return self._ymean_full
 
     def _allreduce(self, arr):
-        if self.dist is None or (self.video.world_size == 1 and not self.force_collectives):
+        if not self._sharded:
             return arr
         import torch
         import torch.distributed as td
@@ -1189,7 +1235,7 @@ class Sources2D:
 
     def _cmean(self):
         """mean(obj.C, 2), cached per C object (K x T can be hundreds of MB when many ranks share one FOV)"""
-        if getattr(self, "_cmean_of", None) is not self.C:
+        if self._cmean_of is not self.C:
             self._cmean_val = self.C.mean(axis=1, dtype=np.float64)
             self._cmean_of = self.C
         return self._cmean_val
@@ -1466,7 +1512,7 @@ class Sources2D:
             return self.C_raw.copy()
         v = self.video
         rows = np.arange(K)[v.rank::v.world_size] if (self.dist is not None and v.world_size > 1) else np.arange(K)
-        if rows.size == K and hasattr(self.engine, "deconv_temporal_bound") and self.C_raw is getattr(self.engine, "_bound", None):
+        if rows.size == K and self._can("bound_deconv") and self.C_raw is getattr(self.engine, "_bound", None):
             # the stitched C_raw is the engine's bound matrix: deconvolved where it lies; C, C_raw - b, S come back lazily (pinned copies behind the kernels)
             C, Craw, S, kp, sn = self.engine.deconv_temporal_bound(self.options.deconv_options)
             self.C, self.C_raw, self.S = C, Craw, S
@@ -1502,9 +1548,8 @@ class Sources2D:
         self._need_data()
         v, o = self.video, self.options
         # the block slices of the current A: prepared by the temporal update under its GPU work when A has not changed since
-        cached = getattr(self, "_cur_blocks_src", None) is self.A
-        infos = {}
-        prefetched = False
+        cached = self._cur_blocks_src is self.A
+        infos, prefetched = {}, False
         flag_first = self._first_run()                                     # :143, from patch 1 for EVERY patch (a collective when sharded)
         self._prev_blocks = {}                                             # (ind, A_block) per patch: what the temporal update's residual needs
         for idx in v.owned:
@@ -1518,7 +1563,7 @@ class Sources2D:
             # first-run test on W{m}(1,:) exactly like :143; an empty A_block on a later run keeps W, b0.
             if A_block.shape[1] == 0 and not flag_first:
                 continue
-            getattr(self, "_resid_tag", {}).pop(idx, None)                 # W, b0 of this patch change: its resident residual goes with them
+            self._resid_tag.pop(idx, None)                                # W, b0 of this patch change: its resident residual goes with them
             if not prefetched:                                             # host thread under the first blocking (GIL-free) fit call
                 self._prefetch_search_location(); prefetched = True
             if not np.isnan(o.thresh_outlier):                             # :131-138: sn of the block, resized for bg_ssub > 1
@@ -1530,13 +1575,7 @@ class Sources2D:
                     nr_b, nc_b = int(b[1] - b[0] + 1), int(b[3] - b[2] + 1)
                     low = sn_block.reshape(nr_b, nc_b, order="F")[np.ix_(nearest_rows(nr_b, self.ssub), nearest_rows(nc_b, self.ssub))] * self.ssub
                     self.engine.set_noise(self.pid_fit[idx], low.reshape(-1, order="F"))
-            if self.ssub == 1:
-                _, infos[idx] = self.engine.fit_ring_model(v.pid[idx], A_block if A_block.shape[1] else None, C_block,
-                                                           o.thresh_outlier, o.bg_acceleration, want_b0=False)   # :218
-            else:                                                                                                # :219-230
-                _, infos[idx] = self.engine.fit_ring_model_ssub(v.pid[idx], self.pid_fit[idx], self.pid_res[idx], self.ssub,
-                                                                A_block if A_block.shape[1] else None, C_block,
-                                                                o.thresh_outlier, o.bg_acceleration)
+            _, infos[idx] = self._fit(idx, A_block if A_block.shape[1] else None, C_block)
         # :315, evaluated on first read (b0 only changes in this method), so the call returns with the fit still running on the GPU.
         # Sharded: that first read is a collective (all-reduce of the stitched image) -- like every method of this class it must then be
         # made by all ranks at the same point of the program; nobody reading it costs nothing (update_spatial_parallel replaces it).
@@ -1550,18 +1589,16 @@ class Sources2D:
         """update_temporal_parallel.m:149-152 asks for the residual of (A_prev, C_prev) on the block -- both known since the background update.
         The engine only RECORDS that request while the resident Ysig still serves the spatial update (pending footprint term), so
         the host-side part of it is done here, under the spatial sweeps that were just queued; the temporal update then finds it in place."""
-        indp, A_prev_b = self._prev_block_of(idx)
-        self._residual(idx, A_prev_b if indp.size else None, self._rows(self.C_prev, indp) if indp.size else None,
-                       tag=("temporal", self.A_prev, self.C_prev))
+        self._residual(idx, *self._prev_block_args(idx), tag=("temporal", self.A_prev, self.C_prev))
 
     def _temporal_residual_done(self, idx):
-        t = getattr(self, "_resid_tag", {}).get(idx)
+        t = self._resid_tag.get(idx)
         return t is not None and t[0] == "temporal" and t[1] is self.A_prev and t[2] is self.C_prev
 
     def _prev_block_of(self, idx):
         """(ind, A_prev(block rows, ind)) for the neurons of A_prev that touch the block (update_temporal_parallel.m:90-91); cached by
         update_background_parallel when A_prev is the A it fitted against"""
-        if getattr(self, "_prev_csr_src", None) is not self.A_prev:
+        if self._prev_csr_src is not self.A_prev:
             self._prev_csr_src = self.A_prev
             self._prev_blocks = {}
         hit = self._prev_blocks.get(idx)
@@ -1569,178 +1606,179 @@ class Sources2D:
             hit = self._prev_blocks[idx] = self._slice(self.A_prev, idx, "block")
         return hit
 
+    def _prev_block_args(self, idx):
+        """(A_prev(block, ind), C_prev(ind, :)) as the residual calls take them; (None, None) when no neuron of A_prev touches the block"""
+        indp, A_prev_b = self._prev_block_of(idx)
+        return (A_prev_b, self._rows(self.C_prev, indp)) if indp.size else (None, None)
+
     def _first_run(self):
         """flag_first = (length(unique(W{1}(1,:)))==2)  (update_background_parallel.m:143): the value test on patch 1's W decides the
         "nothing changed here, keep W" skip (:188-199) of EVERY patch.  Sharded: the rank that owns patch 1 evaluates it, one
         all-reduce of a flag hands it to the others (fit_ring_model's own first-run test, :25, stays per patch inside the engine)."""
         v = self.video
         idx1 = v.order[0]
-        flag = 0.0
-        if idx1 in v.owned:
-            flag = float(self.engine.ring_first_run(v.pid[idx1] if self.ssub == 1 else self.pid_fit[idx1]))
+        flag = float(self.engine.ring_first_run(v.pid[idx1] if self.ssub == 1 else self.pid_fit[idx1])) if idx1 in v.owned else 0.0
         return bool(self._allreduce(np.array([flag], dtype=np.float64))[0] > 0)
 
     # -- spatial ----------------------------------------------------------------------
     def update_spatial_parallel(self, use_parallel=True, update_sn=False):
-        """@Sources2D/update_spatial_parallel.m:61-100,116-216,320-351."""
+        """@Sources2D/update_spatial_parallel.m:61-100,116-216,320-351.  Per owned patch: _spatial_inputs cuts what it reads (for every patch but the first under the
+        sweeps of the patch before), _spatial_launch queues it, its values are collected at once or, from an engine that queues downloads, `spatial_lag` patches
+        late (_spatial_drain); _spatial_finish stitches them into obj.A."""
         self._need_data()
-        v, o = self.video, self.options
+        v, o, eng = self.video, self.options, self.engine
         sn_new = np.zeros(v.d1 * v.d2, dtype=np.float64) if update_sn else None                  # :101-102
         if o.search_method not in ("ellipse", "dilate"):
             raise NotImplementedError("search_method must be 'ellipse' or 'dilate'")
-        K = self.A.shape[1]
-        rows, cols, vals = [], [], []
-        whole_result = whole_pp = None
-        IND = None
+        d, K = v.d1 * v.d2, self.A.shape[1]
         se_now = o.se                                                      # :56 copies the options, :63-65 clears obj.options.se: once per update, here
         if o.search_method == "dilate":
             o.se = None
-
-        def prev_of(idx):
-            # A_prev restricted to neurons that touch the HALO only (mask==1 after the patch is set to 2, :84-85,96)
-            if v.halo_pix(idx).size:
-                indp, _ = self._slice(self.A_prev, idx, "halo")
-            else:
-                indp = np.zeros(0, dtype=np.int64)
-            A_prev_b = self._slice(self.A_prev, idx, "block", cols=indp)[1] if indp.size else None   # :97
-            C_prev_b = self._rows(self.C_prev, indp) if indp.size else None                         # :98
-            return A_prev_b, C_prev_b
-
-        def masks_of(idx):
-            ind, IND_patch = self._slice(IND, idx, "patch")                                          # :87, :89
-            if ind.size == 0:
-                return ind, IND_patch, None, None
-            return ind, IND_patch, self._slice(self.A, idx, "patch", cols=ind)[1], self._rows(self.C, ind)   # :88,199 / :91
-
-        in_flight = []                                                     # (fetch, patch pixels, neurons) of deferred updates not collected yet
-
-        def collect(fetch, pp, ind):
-            coo = (fetch(compact=True) if hasattr(fetch, "start") else fetch()).tocoo()
-            rows.append(pp[coo.row]); cols.append(ind[coo.col]); vals.append(coo.data)             # :324-334 (patches are disjoint)
-
-        ahead = None                                                       # the next patch's slices, cut while this patch's sweeps run
+        trip = ([], [], [])                                                # (rows, columns, values) of the patches collected so far
+        whole_raw = whole_pp = None                                        # one patch over the whole FOV, every neuron: already A_ (and its post-processed form)
+        in_flight = []                                                     # (result, patch pixels, neurons) of queued downloads not collected yet
+        IND = ahead = None
         for i, idx in enumerate(v.owned):
-            pp = v.patch_pix[idx]
-            launched = IND is None
-            if launched:
+            if IND is None:
                 # the residual sweep (:162-166) does not depend on the search mask: start it (the call returns with
                 # the kernel in flight) and build IND (:66) on the host underneath it
-                A_prev_b, C_prev_b = prev_of(idx)
-                self._residual(idx, A_prev_b, C_prev_b)
+                prev = self._spatial_prev(idx)
+                self._residual(idx, *prev)
                 IND = self._search_location_csc(se_now)
-                ind, IND_patch, A_patch, C_patch = masks_of(idx)
+                job = self._spatial_launch(idx, prev + self._spatial_masks(idx, IND), True, sn_new)
             else:
-                (A_prev_b, C_prev_b), (ind, IND_patch, A_patch, C_patch) = ahead
-            ahead = None
-            nxt = v.owned[i + 1] if i + 1 < len(v.owned) else None
-            if ind.size == 0 and not update_sn:
-                if nxt is not None:
-                    ahead = (prev_of(nxt), masks_of(nxt))
-                continue                                                                             # :121-124
-            if not launched:
-                self._residual(idx, A_prev_b, C_prev_b)                                # :162-166
-            sn_patch = self.P["sn"][pp]                                                             # :90,154
-            if update_sn:
-                sn_patch = self.engine.get_sn(v.pid[idx])                                           # :191-194  sn_patch = GetSn(Ypatch)
-                sn_new[pp] = sn_patch
-            if ind.size == 0:
-                if nxt is not None:
-                    ahead = (prev_of(nxt), masks_of(nxt))
-                continue                                                                             # :196-199
-            param = 20 if o.spatial_algorithm == "nnls" else 3                                      # :203,205,211
-            if getattr(self.engine, "supports_lazy_traces", False):
-                fetch = self.engine.update_spatial(v.pid[idx], o.spatial_algorithm, A_patch, C_patch, IND_patch,
-                                                   sn_patch if o.spatial_algorithm == "hals_thresh" else None, param, defer=True)
-                whole = pp.size == v.d1 * v.d2 and ind.size == K
-                late = not whole and hasattr(fetch, "start")
-                whole_conn = (whole and o.spatial_constraints.get("connected", True) and (self.dist is None or (v.world_size == 1 and not self.force_collectives)))
-                if late:
-                    # several patches: the download is queued right behind the sweeps and collected `spatial_lag` patches LATE -- a patch's values are assembled
-                    # on the host while the next patch's kernels, queued first, keep the device busy (a fetch per patch drained the stream 16 times per update)
-                    fetch.start()
-                elif whole_conn and hasattr(fetch, "start_connected"):
-                    # one patch = the field of view: the connectivity kernel and the downloads are queued NOW, so that what the temporal update's residual request
-                    # starts on the device (the deferred half of the ring solve, the W*A_prev tables) runs behind them, under the host's assembly of A
-                    fetch.start_connected((v.d1, v.d2))
-                self._temporal_residual_early(idx)                       # host work under the sweeps
-                self._early_u = None
-                if (whole_conn and hasattr(fetch, "temporal_early") and not update_sn and not o.spatial_constraints.get("circular", False)
-                        and not o.deconv_flag and self.ssub == 1 and len(v.owned) == 1):
-                    # the hand-over: the temporal update's projection of this result, queued behind the connectivity kernel and the residual request above,
-                    # before the host has seen the values (engine option temporal_early); update_temporal_parallel claims it when self.A is still this result
-                    self._early_u = fetch.temporal_early()
-                if nxt is not None:
-                    ahead = (prev_of(nxt), masks_of(nxt))                # ... and the slices of the next patch
-                if whole_conn:
-                    # one patch = the field of view: post_process_spatial's connectivity constraint (:341) runs on the result where it lies
-                    # (the engine's fetch: A without stored zeros, rows sorted, and the raw update as a recipe -- see the early return below)
-                    Anew, whole_pp = fetch(connected_fov=(v.d1, v.d2), **({"compact": True} if hasattr(fetch, "start") else {}))
-                    if getattr(self, "_early_u", None):
-                        self._early_u = (self._early_u, whole_pp)
-                elif late:
-                    in_flight.append((fetch, pp, ind))
-                    while len(in_flight) > self.spatial_lag:
-                        collect(*in_flight.pop(0))
-                    continue
-                else:
-                    Anew = fetch()
-            else:
-                Anew = self.engine.update_spatial(v.pid[idx], o.spatial_algorithm, A_patch, C_patch, IND_patch,
-                                                  sn_patch if o.spatial_algorithm == "hals_thresh" else None, param)
-                if nxt is not None:
-                    ahead = (prev_of(nxt), masks_of(nxt))
-            if pp.size == v.d1 * v.d2 and ind.size == K:
-                whole_result = Anew                                                                  # one patch over the whole FOV, every neuron: already A_
+                job = self._spatial_launch(idx, ahead, False, sn_new)
+            ahead = self._spatial_inputs(v.owned[i + 1], IND) if i + 1 < len(v.owned) else None     # the next patch's slices, cut while this patch's sweeps run
+            if job is None:
                 continue
-            collect(lambda Anew=Anew: Anew, pp, ind)
+            r, ind, late, whole_conn, token = job
+            pp = v.patch_pix[idx]
+            if late:
+                in_flight.append((r, pp, ind))
+                self._spatial_drain(trip, in_flight, self.spatial_lag)
+                continue
+            if whole_conn:
+                # one patch = the field of view: post_process_spatial's connectivity constraint (:341) runs on the result where it lies
+                # (an engine that queues downloads: A without stored zeros, rows sorted, and the raw update as a recipe -- see _spatial_finish)
+                Anew, whole_pp = r(connected_fov=(v.d1, v.d2), **({"compact": True} if self._can("queued_fetch") else {}))
+                if token:
+                    self._early_u = (token, whole_pp)
+            else:
+                Anew = r() if self._can("lazy_traces") else r
+            if pp.size == d and ind.size == K:
+                whole_raw = Anew
+            else:
+                self._spatial_collect(trip, Anew, pp, ind)
         late_any = bool(in_flight)
-        while in_flight:
-            collect(*in_flight.pop(0))
-        if late_any and hasattr(self.engine, "synchronize"):
+        self._spatial_drain(trip, in_flight, 0)
+        if late_any and self._can("synchronize"):
             # the late-collected results waited for their own point of the stream only (cnmfe_ticket_wait): what the kernels had to report (a ring over too many
             # footprints, an inconsistent table) must be heard BEFORE obj.A is replaced by what they computed
-            self.engine.synchronize()
-        d = v.d1 * v.d2
-        if whole_result is not None and callable(whole_result):
-            self.A_raw = whole_result                                                                # (not sharded: nothing to gather; assembled on first read)
-            if update_sn:
-                self.P["sn"] = self._allreduce(sn_new).astype(np.float32)
-            self.A = whole_pp
-            if o.spatial_constraints.get("circular", False):
-                from . import hostops
-                self.A = hostops.circular_constraints_columns(self.A, v.d1, v.d2)
-            self._update_b0_new()
-            # the NEXT spatial update's masks depend on this A only: their thread starts under the temporal update's blocking (GIL-free) sweep call, not here, where its
-            # Python would share the GIL with the temporal set-up the device is waiting for (CNMFE_PREFETCH_EARLY=1: at once, as until round 6)
-            if os.environ.get("CNMFE_PREFETCH_EARLY", "0") == "1":
-                self._prefetch_search_location()
-            else:
-                self._prefetch_wanted = True
-            return
-        if whole_result is not None:
-            A_ = whole_result
-        elif rows:
-            A_ = _csc_from_triplets(np.concatenate(rows), np.concatenate(cols), np.concatenate(vals), (d, K))
-        else:
-            A_ = sp.csc_matrix((d, K), dtype=np.float32)
-        A_ = self._gather_sparse(A_)
+            eng.synchronize()
+        if whole_raw is None:
+            whole_raw = (_csc_from_triplets(np.concatenate(trip[0]), np.concatenate(trip[1]), np.concatenate(trip[2]), (d, K)) if trip[0]
+                         else sp.csc_matrix((d, K), dtype=np.float32))
+        self._spatial_finish(whole_raw, whole_pp, sn_new)
+
+    def _spatial_prev(self, idx):
+        """(A_prev(block, indp), C_prev(indp, :)) of the neurons a patch's residual subtracts, (None, None) without one"""
+        # A_prev restricted to neurons that touch the HALO only (mask==1 after the patch is set to 2, :84-85,96)
+        indp = self._slice(self.A_prev, idx, "halo")[0] if self.video.halo_pix(idx).size else np.zeros(0, dtype=np.int64)
+        A_prev_b = self._slice(self.A_prev, idx, "block", cols=indp)[1] if indp.size else None   # :97
+        C_prev_b = self._rows(self.C_prev, indp) if indp.size else None                         # :98
+        return A_prev_b, C_prev_b
+
+    def _spatial_masks(self, idx, IND):
+        """(ind, IND(patch, ind), A(patch, ind), C(ind, :)) of the neurons whose search mask meets the patch"""
+        ind, IND_patch = self._slice(IND, idx, "patch")                                          # :87, :89
+        if ind.size == 0:
+            return ind, IND_patch, None, None
+        return ind, IND_patch, self._slice(self.A, idx, "patch", cols=ind)[1], self._rows(self.C, ind)   # :88,199 / :91
+
+    def _spatial_inputs(self, idx, IND):
+        """everything patch idx's update reads, in the order _spatial_launch takes it"""
+        return self._spatial_prev(idx) + self._spatial_masks(idx, IND)
+
+    def _spatial_launch(self, idx, inputs, residual_queued, sn_new):
+        """queue patch idx's update: its residual (unless the caller has), GetSn (sn_new given: update_sn), the sweeps; with an engine that defers its results also the
+        download and, under the sweeps, the temporal update's residual request.  None: no neuron in the patch.  Else (r, ind, late, whole_conn, token): r the SpatialResult
+        (a blocking engine: the matrix); late: its download is queued, to be collected later; whole_conn: the patch is the field of view and the fetch applies the
+        connectivity constraint; token: of the temporal projection queued behind that (0: none)."""
+        v, o, eng = self.video, self.options, self.engine
+        A_prev_b, C_prev_b, ind, IND_patch, A_patch, C_patch = inputs
+        update_sn = sn_new is not None
+        if ind.size == 0 and not update_sn:
+            return None                                                                              # :121-124
+        if not residual_queued:
+            self._residual(idx, A_prev_b, C_prev_b)                                                  # :162-166
+        pp = v.patch_pix[idx]
+        sn_patch = self.P["sn"][pp]                                                                  # :90,154
         if update_sn:
+            sn_patch = eng.get_sn(v.pid[idx])                                                        # :191-194  sn_patch = GetSn(Ypatch)
+            sn_new[pp] = sn_patch
+        if ind.size == 0:
+            return None                                                                              # :196-199
+        args = (v.pid[idx], o.spatial_algorithm, A_patch, C_patch, IND_patch, sn_patch if o.spatial_algorithm == "hals_thresh" else None,
+                20 if o.spatial_algorithm == "nnls" else 3)                                          # :203,205,211
+        if not self._can("lazy_traces"):
+            return eng.update_spatial(*args), ind, False, False, 0
+        r = eng.update_spatial(*args, defer=True)
+        whole = pp.size == v.d1 * v.d2 and ind.size == self.A.shape[1]
+        late = not whole and self._can("queued_fetch")
+        whole_conn = whole and o.spatial_constraints.get("connected", True) and not self._sharded
+        if late:
+            # several patches: the download is queued right behind the sweeps and collected `spatial_lag` patches LATE -- a patch's values are assembled
+            # on the host while the next patch's kernels, queued first, keep the device busy (a fetch per patch drained the stream 16 times per update)
+            r.start()
+        elif whole_conn and self._can("connected_start"):
+            # one patch = the field of view: the connectivity kernel and the downloads are queued NOW, so that what the temporal update's residual request
+            # starts on the device (the deferred half of the ring solve, the W*A_prev tables) runs behind them, under the host's assembly of A
+            r.start_connected((v.d1, v.d2))
+        self._temporal_residual_early(idx)                       # host work under the sweeps
+        self._early_u, token = None, 0
+        if (whole_conn and self._can("temporal_early") and not update_sn and not o.spatial_constraints.get("circular", False)
+                and not o.deconv_flag and self.ssub == 1 and len(v.owned) == 1):
+            # the hand-over: the temporal update's projection of this result, queued behind the connectivity kernel and the residual request above,
+            # before the host has seen the values (engine option temporal_early); update_temporal_parallel claims it when self.A is still this result
+            token = r.temporal_early()
+        return r, ind, late, whole_conn, token
+
+    def _spatial_collect(self, trip, A_p, pp, ind):
+        coo = A_p.tocoo()
+        trip[0].append(pp[coo.row]); trip[1].append(ind[coo.col]); trip[2].append(coo.data)         # :324-334 (patches are disjoint)
+
+    def _spatial_drain(self, trip, in_flight, lag):
+        """collect queued results, oldest first, until `lag` are left outstanding"""
+        while len(in_flight) > lag:
+            r, pp, ind = in_flight.pop(0)
+            self._spatial_collect(trip, r(compact=True), pp, ind)
+
+    def _spatial_finish(self, A_raw, A_pp, sn_new):
+        """:336-351 with the update of all owned patches.  A_raw: the matrix, or -- one patch, not sharded, from an engine that compacts -- the recipe of it,
+        assembled on first read (nothing in the iteration reads obj.A_raw).  A_pp: its post-processed form when the fetch applied the connectivity constraint."""
+        v, o = self.video, self.options
+        recipe = callable(A_raw)                                                                     # (then nothing to gather, no stored zero in A_pp)
+        if not recipe:
+            A_raw = self._gather_sparse(A_raw)
+        if sn_new is not None:
             self.P["sn"] = self._allreduce(sn_new).astype(np.float32)                               # :336-337 (patches are disjoint)
-        A_.eliminate_zeros()
-        A_.sort_indices()
-        self.A_raw = A_
-        if whole_pp is not None:
-            whole_pp.eliminate_zeros(); whole_pp.sort_indices()
-            self.A = whole_pp                                                                        # :341, done with the fetch
-        else:
-            self.A = self._post_process(A_) if o.spatial_constraints.get("connected", True) else A_                          # :341, :24-26
+        if not recipe:
+            A_raw.eliminate_zeros(); A_raw.sort_indices()
+            if A_pp is not None:
+                A_pp.eliminate_zeros(); A_pp.sort_indices()
+        self.A_raw = A_raw
+        if A_pp is None:
+            A_pp = self._post_process(A_raw) if o.spatial_constraints.get("connected", True) else A_raw      # :341, :24-26
+        self.A = A_pp                                                                                # :341 (A_pp given: done with the fetch)
         if o.spatial_constraints.get("circular", False):                                            # post_process_spatial.m:28-30
-            from . import hostops
             self.A = hostops.circular_constraints_columns(self.A, v.d1, v.d2)
         self._update_b0_new()                                                                        # :347-351
-        # (several patches: the mask thread is NOT started here -- its Python would share the GIL with the temporal update's set-up, on the hand-over where the device
-        # waits for the host (0.4 ms of a rank's 4.3 at c4); update_temporal_parallel starts it under its sweep call, update_background_parallel otherwise)
-        self._prefetch_wanted = True
+        # the NEXT spatial update's masks depend on this A only: their thread starts under the temporal update's blocking (GIL-free) sweep call (or the next fit call), not
+        # here, where its Python would share the GIL with the temporal set-up the device waits for (0.4 ms of a rank's 4.3 at c4).  CNMFE_PREFETCH_EARLY=1, one patch: at once
+        if recipe and os.environ.get("CNMFE_PREFETCH_EARLY", "0") == "1":
+            self._prefetch_search_location()
+        else:
+            self._prefetch_wanted = True
 
     def _post_process(self, A_):
         """obj.post_process_spatial() (:341) works on whole footprints, which only exist after the gather.  Sharded, every rank holds the whole gathered A and
@@ -1751,7 +1789,7 @@ class Sources2D:
         return self.engine.post_process_spatial(A_, v.d1, v.d2)
 
     def _start_wanted_prefetch(self):
-        if getattr(self, "_prefetch_wanted", False):
+        if self._prefetch_wanted:
             self._prefetch_wanted = False
             self._prefetch_search_location()
 
@@ -1761,10 +1799,10 @@ class Sources2D:
         if self.options.search_method != "ellipse":
             return
         import concurrent.futures as cf
-        if getattr(self, "_pool", None) is None:
+        if self._pool is None:
             self._pool = cf.ThreadPoolExecutor(max_workers=1)
         A = self.A
-        fut = getattr(self, "_ind_future", None)
+        fut = self._ind_future
         if fut is not None and fut[0] is A:
             return                                                         # (already on its way: requested at the end of the spatial update that made this A)
         self._ind_future = (A, self._pool.submit(lambda: self._as_mask_csc(self._search_location_owned(A))))
@@ -1776,8 +1814,7 @@ class Sources2D:
         return M
 
     def _search_location_csc(self, se=_UNSET):
-        fut = getattr(self, "_ind_future", None)
-        self._ind_future = None
+        fut, self._ind_future = self._ind_future, None
         if fut is not None and fut[0] is self.A:
             return fut[1].result()
         return self._as_mask_csc(self._search_location_owned(se=se))
@@ -1793,7 +1830,6 @@ class Sources2D:
             # update_spatial_parallel.m:56 copies the options BEFORE :63-65 clears obj.options.se: an update uses the element it finds and the
             # next one strel('disk', bSiz, 0) (determine_search_location.m:42-44).  The element is only READ here (prefetches and measurement
             # helpers call this too); update_spatial_parallel clears it once per update.  Host work on every rank (off in every demo).
-            from . import hostops
             se = o.se if se is _UNSET else se
             se = hostops.strel_disk(4) if isinstance(se, str) else hostops.strel_disk(o.bSiz) if se is None else se
             return hostops.search_location_dilate(A, v.d1, v.d2, se, o.nb, o.nrgthr)
@@ -1822,7 +1858,7 @@ class Sources2D:
         rank sends a padded int32 [3, cap + 1] block (row, column, value bits; the last column carries its count) with cap = the largest count of the previous
         gather + a quarter; a rank that outgrew cap is seen by everybody in the gathered counts, and everybody repeats the round with the capacity those counts ask
         for (the first call of a run costs two rounds: it starts from cap = 0)."""
-        if self.dist is None or (self.video.world_size == 1 and not self.force_collectives):
+        if not self._sharded:
             return A_
         import torch
         import torch.distributed as td
@@ -1831,7 +1867,7 @@ class Sources2D:
         dev = torch.device("cuda", torch.cuda.current_device()) if nccl else torch.device("cpu")
         W = td.get_world_size(self.dist)                                  # (= video.world_size in a run; scripts/rank_load.py times one rank's share behind a group of one)
         n = int(coo.nnz)
-        cap = int(getattr(self, "_gather_cap", 0))
+        cap = self._gather_cap
         while True:
             # the padded block is put together by NumPy, not by torch CPU kernels: a torch fill / copy of this size opens an OpenMP region over every core of
             # the host, whose threads then spin -- inside a CPU-quota'd container that throttled the whole process for ~40 ms of every 100-ms scheduler period
@@ -1869,17 +1905,10 @@ class Sources2D:
         b0_new_ = np.asarray(self.b0_new, dtype=np.float64).reshape(-1, order="F")                   # :1399
         RSS = {}
         for idx in v.owned:
-            pp, bp = v.patch_pix[idx], v.block_pix[idx]
             ind, _ = self._slice(self.A, idx, "block")                                              # :1423
-            indp, A_prev_b = self._prev_block_of(idx)                                                # :1427-1428
             A_pp = self._slice(self.A, idx, "patch", cols=ind)[1] if ind.size else None              # A_patch(ind_patch, :)  (:1467)
-            if self.ssub != 1:                                                                       # :1479-1486 ('nearest' both ways)
-                self.engine.background_ssub(v.pid[idx], self.pid_fit[idx], self.ssub, A_prev_b if indp.size else None,
-                                            self._rows(self.C_prev, indp) if indp.size else None, b0_[bp])
-                RSS[idx] = self.engine.compute_rss_ssub(v.pid[idx], A_pp, self._rows(self.C, ind) if ind.size else None, b0_new_[pp])
-                continue
-            self._residual(idx, A_prev_b if indp.size else None, self._rows(self.C_prev, indp) if indp.size else None)
-            RSS[idx] = self.engine.compute_rss(v.pid[idx], A_pp, self._rows(self.C, ind) if ind.size else None, b0_[bp], b0_new_[pp])
+            self._background_resident(idx, b0_)                                                      # :1427-1428, :1479-1486 ('nearest' both ways)
+            RSS[idx] = self._rss(idx, A_pp, self._rows(self.C, ind) if ind.size else None, b0_, b0_new_)
         total = float(self._allreduce(np.array([sum(RSS.values())], dtype=np.float64))[0])           # :1507-1508
         self.P["RSS"] = total                                                                        # :1509
         return total, RSS
@@ -1895,19 +1924,11 @@ class Sources2D:
         b0_new_ = np.asarray(self.b0_new, dtype=np.float64).reshape(-1, order="F")                   # :1293
         Ybg = np.zeros((v.d1 * v.d2, f1 - f0 + 1), dtype=np.float32)                                 # :1297
         for idx in v.owned:
-            pp, bp = v.patch_pix[idx], v.block_pix[idx]
-            indp, A_prev_b = self._prev_block_of(idx)                                                # :1317-1320
-            if self.ssub != 1:                                                                       # :1325-1334
-                self.engine.background_ssub(v.pid[idx], self.pid_fit[idx], self.ssub, A_prev_b if indp.size else None,
-                                            self._rows(self.C_prev, indp) if indp.size else None, b0_[bp])
-            else:
-                self._residual(idx, A_prev_b if indp.size else None, self._rows(self.C_prev, indp) if indp.size else None)
+            pp = v.patch_pix[idx]
+            self._background_resident(idx, b0_)                                                      # :1317-1320, :1325-1334
             for t0 in range(f0 - 1, f1, 4096):                                                       # (the ABI hands out at most 65535 frames per call)
                 n = min(4096, f1 - t0)
-                if self.ssub != 1:
-                    Ybg[pp, t0 - (f0 - 1):t0 - (f0 - 1) + n] = self.engine.reconstruct_background_ssub(v.pid[idx], b0_new_[pp], t0, n).T
-                else:
-                    Ybg[pp, t0 - (f0 - 1):t0 - (f0 - 1) + n] = self.engine.reconstruct_background(v.pid[idx], b0_[bp], b0_new_[pp], t0, n).T
+                Ybg[pp, t0 - (f0 - 1):t0 - (f0 - 1) + n] = self._reconstruct(idx, b0_, b0_new_, t0, n).T
         return Ybg.reshape(v.d1, v.d2, -1, order="F")
 
     def extract_DF_F_endoscope(self, Ybg=None, want_Yf=False):
@@ -1945,34 +1966,21 @@ class Sources2D:
         try:
             if Ybg is None:
                 for idx in v.owned:
-                    pp, bp = v.patch_pix[idx], v.block_pix[idx]
-                    indp, A_prev_b = self._prev_block_of(idx)                                            # :1317-1320
-                    if self.ssub != 1:
-                        eng.background_ssub(v.pid[idx], self.pid_fit[idx], self.ssub, A_prev_b if indp.size else None,
-                                            self._rows(self.C_prev, indp) if indp.size else None, b0_[bp])
-                    else:
-                        self._residual(idx, A_prev_b if indp.size else None, self._rows(self.C_prev, indp) if indp.size else None)
+                    self._background_resident(idx, b0_)                                                  # :1317-1320
                     ind, A_pp = self._slice(A, idx, "patch")
-                    if self.ssub != 1:
-                        eng.df_add_background_ssub(v.pid[idx], b0_new_[pp], A_pp, ind)
-                    else:
-                        eng.df_add_background(v.pid[idx], b0_[bp], b0_new_[pp], A_pp, ind)
-                if self.dist is not None and (v.world_size > 1 or self.force_collectives):               # every rank holds the sum over its own patches
+                    self._df_add_background(idx, b0_, b0_new_, A_pp, ind)
+                if self._sharded:                                                                        # every rank holds the sum over its own patches
                     eng.df_load(self._allreduce(eng.df_fetch()))
             elif K:
                 step = max(4, min(4096, ((64 << 20) // (4 * Y.shape[0])) & ~3))
                 allk = np.arange(K, dtype=np.int32)
                 for t0 in range(0, T, step):
                     eng.df_add_frames(np.ascontiguousarray(Y[:, t0:t0 + step].T, dtype=np.float32), t0, A, allk)
-        except Exception:
-            eng.df_close()                                           # (a refused call must not leave the accumulator open)
-            raise
-        with np.errstate(divide="ignore"):
-            inv = 1.0 / np.asarray(A.astype(np.float64).power(2).sum(axis=0)).ravel() if K else np.zeros(0)     # :545 (an empty footprint: Inf)
-        try:
+            with np.errstate(divide="ignore"):
+                inv = 1.0 / np.asarray(A.astype(np.float64).power(2).sum(axis=0)).ravel() if K else np.zeros(0)     # :545 (an empty footprint: Inf)
             return eng.df_finish(inv, p, w, self.C, C_raw, want_Yf=want_Yf)
         except Exception:
-            eng.df_close()
+            eng.df_close()                                           # (a refused call must not leave the accumulator open)
             raise
 
     # -- temporal -----------------------------------------------------------------------
@@ -1981,26 +1989,24 @@ class Sources2D:
         aa .* C_raw is added to the engine's stitch accumulator (:269-278), sharded runs all-reduce that buffer in place (the
         overlap-region stitch, ONE collective), and :279-286 run on the device; one K x T copy comes back for obj.C_raw / obj.C."""
         self._need_data()
-        v, o = self.video, self.options
-        eng = self.engine
+        v, o, eng = self.video, self.options, self.engine
         K, T = self.C.shape
         launched_any = False
-        sharded = self.dist is not None and (v.world_size > 1 or self.force_collectives)
+        sharded = self._sharded
         eng.stitch_begin(K, T)
         # several patches on this rank: every patch's update is set up first and the Gauss-Seidel sweeps run level by level ACROSS the patches (they are
         # independent: the reference's parfor, :112-186) -- one patch's level is a few workgroups as long as one trace's work
-        batch = use_c_hat and len(v.owned) > 1 and getattr(eng, "supports_temporal_jobs", False)
+        batch = use_c_hat and len(v.owned) > 1 and self._can("temporal_jobs")
         jobs = []
         for idx in v.owned:
             pp, bp = v.patch_pix[idx], v.block_pix[idx]
-            indp, A_prev_b = self._prev_block_of(idx)                                                # :90-91
-            C_prev_b = self._rows(self.C_prev, indp) if indp.size else None
+            A_prev_b, C_prev_b = self._prev_block_args(idx)                                          # :90-91
             launched = not launched_any
             whole = bp.size == v.d1 * v.d2                                 # this block is the whole field of view (then so is the patch): no row slicing
             if launched:
                 # the sweep (:149-152) only needs (A_prev, C_prev): start it, slice the current A underneath it
                 if not self._temporal_residual_done(idx):
-                    self._residual(idx, A_prev_b if indp.size else None, C_prev_b)
+                    self._residual(idx, A_prev_b, C_prev_b)
                 launched_any = True
                 self._cur_blocks, self._cur_blocks_src = {}, self.A
             if whole:
@@ -2015,7 +2021,7 @@ class Sources2D:
             if ind.size == 0:
                 continue                                                                              # :123
             if not launched and not self._temporal_residual_done(idx):
-                self._residual(idx, A_prev_b if indp.size else None, C_prev_b)          # :149-152
+                self._residual(idx, A_prev_b, C_prev_b)          # :149-152
             C_patch = self._rows(self.C, ind)                                                        # :86
             if not use_c_hat:                                                                         # :174-175
                 eng.fast_temporal(v.pid[idx], A_pp, want_raw=False)
@@ -2027,12 +2033,12 @@ class Sources2D:
                 eng.hals_temporal_deconv(v.pid[idx], A_pp, C_patch, o.maxIter, o.deconv_options, want_all=None)
             else:
                 self._start_wanted_prefetch()
-                early, self._early_u = getattr(self, "_early_u", None), None
-                if (isinstance(early, tuple) and whole and A_pp is early[1] and self.A is early[1] and ind.size == K and not sharded and len(v.owned) == 1
-                        and hasattr(eng, "temporal_early_claim")):
+                early, self._early_u = self._early_u, None
+                if (early is not None and whole and A_pp is early[1] and self.A is early[1] and ind.size == K and not sharded and len(v.owned) == 1
+                        and self._can("temporal_early")):
                     eng.temporal_early_claim(early[0])       # (A is exactly the spatial result the projection was queued for: hand-over)
                 eng.hals_temporal(v.pid[idx], A_pp, C_patch, o.maxIter, want_C=False, want_raw=False,
-                                  **({"want_aa": False} if hasattr(eng, "temporal_early_claim") else {}))  # :180-181
+                                  **({"want_aa": False} if self._can("temporal_early") else {}))            # :180-181
             eng.stitch_add(ind)                                                                       # :274-275
         if jobs:
             self._start_wanted_prefetch()                                  # host thread under the (GIL-free) sweep / stitch / fit calls that follow
@@ -2043,13 +2049,9 @@ class Sources2D:
             eng.stitch_allreduce(self.dist)
         # without deconvolution nobody needs the values on the host right away: the engine keeps the matrix bound and streams a copy into pinned
         # memory behind the kernels (LazyHostTraces); the next background fit is set up while the temporal sweep is still running
-        lazy = (not o.deconv_flag) and getattr(eng, "supports_lazy_traces", False)
-        bound_deconv = o.deconv_flag and not sharded and hasattr(eng, "deconv_temporal_bound") and getattr(eng, "supports_lazy_traces", False)
+        lazy = (not o.deconv_flag) and self._can("lazy_traces")
+        bound_deconv = o.deconv_flag and not sharded and self._can("bound_deconv") and self._can("lazy_traces")
         C_raw = eng.stitch_finish(subtract_min=not o.deconv_flag, want="lazy" if lazy else ("bound" if bound_deconv else True))       # :279-280, :285
-        if o.deconv_flag:                                                                             # :282-283  obj.C = obj.deconvTemporal()
-            self.C_raw = C_raw
-            self.C = self.deconvTemporal()
-        else:
-            self.C_raw = C_raw
-            self.C = self.C_raw                                                                       # :286 (already the engine's bound matrix)
+        self.C_raw = C_raw
+        self.C = self.deconvTemporal() if o.deconv_flag else C_raw        # :282-283 obj.C = obj.deconvTemporal() / :286 (already the engine's bound matrix)
         self._update_b0_new()                                                                         # :291-295

@@ -43,7 +43,8 @@ for name in dir(eng):
     if not name.startswith("__") and callable(getattr(eng, name)) and name not in ("close",):
         wrap(eng, name)
 for name in ("update_background_parallel", "update_spatial_parallel", "update_temporal_parallel", "_slice", "_post_process", "_search_location_csc", "_prefetch_search_location", "_update_b0_new",
-             "_gather_sparse", "_rows", "_residual", "_allreduce", "_first_run", "ymean_full", "_csc_of_patches"):
+             "_gather_sparse", "_rows", "_residual", "_allreduce", "_first_run", "ymean_full", "_csc_of_patches",
+             "_spatial_inputs", "_spatial_launch", "_spatial_drain", "_spatial_finish"):
     if hasattr(s, name):
         wrap(s, name)
 def step():

@@ -13,7 +13,9 @@ from cnmf_e_amd.sources2d import PatchedVideo, Sources2D, Options
 
 
 class NullEngine:
-    supports_lazy_traces = True
+    supports_lazy_traces = supports_bound_traces = True
+    supports_temporal_jobs = supports_queued_fetch = supports_connected_start = supports_temporal_early = False
+    supports_bound_deconv = supports_fit_reserve = supports_synchronize = False
     def __init__(self): self.K = self.T = 0; self.bound = None
     def create_patch(self, *x, **k): pass
     def ring_init(self, *x, **k): pass

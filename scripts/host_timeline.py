@@ -69,7 +69,7 @@ if os.environ.get("TRACE_SLOW_PY") == "1":               # which Python-side hel
             return r_
         setattr(obj, name, staticmethod(w) if static else w)
     for nm in ("_slice", "_rows", "_prev_block_of", "_residual", "_temporal_residual_done", "_temporal_residual_early", "_gather_sparse", "_allreduce", "_post_process", "_first_run",
-               "_search_location_csc", "_update_b0_new", "ymean_full", "_prefetch_search_location"):
+               "_search_location_csc", "_update_b0_new", "ymean_full", "_prefetch_search_location", "_spatial_inputs", "_spatial_launch", "_spatial_drain", "_spatial_finish"):
         if hasattr(Sources2D, nm): _wrap_slow(Sources2D, nm)
     for nm in ("rows_of", "_select_rows_native", "_csc_from_triplets", "determine_search_location"):
         if hasattr(_s2, nm): _wrap_slow(_s2, nm)

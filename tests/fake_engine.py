@@ -10,6 +10,10 @@ import cnmfe_oracle as orc
 
 
 class FakeEngine:
+    # the flags Sources2D asks (cnmf_e_amd.engine.Engine): this double has the blocking calls only
+    supports_lazy_traces = supports_temporal_jobs = supports_queued_fetch = supports_connected_start = supports_temporal_early = False
+    supports_bound_traces = supports_bound_deconv = supports_fit_reserve = supports_synchronize = False
+
     def __init__(self):
         self.p = {}
 
@@ -182,6 +186,8 @@ class LazyFakeEngine(FakeEngine):
 class LateFakeEngine(LazyFakeEngine):
     """... and with the real engine's queued download: fetch.start() (cnmfe_update_spatial_fetch_async) and fetch(compact=True) (no stored zeros; with
     connected_fov the raw update comes as a recipe) -- the surface behind which sources2d collects a patch's result one patch late"""
+    supports_queued_fetch = True
+
     def update_spatial(self, pid, algorithm, A_patch, C_patch, IND_patch, sn=None, param=3, defer=False):
         inner = super().update_spatial(pid, algorithm, A_patch, C_patch, IND_patch, sn, param, defer)
         if not defer:

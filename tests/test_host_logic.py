@@ -316,8 +316,15 @@ def test_noise_image_bookkeeping_and_nearest_rows_match_the_oracle():
             assert (M.max(axis=1) == 1).all() and np.array_equal(M.argmax(axis=1), nearest_rows(n, s_)), (n, s_)
 
 
-@pytest.mark.parametrize("pdims,update_sn", [([20, 22], False), ([20, 22], True), (None, False)])
-def test_asynchronous_engine_orderings_give_the_same_iteration(pdims, update_sn):
+_CIRCULAR = {"connected": True, "circular": True}
+
+
+@pytest.mark.parametrize("pdims,update_sn,constraints", [
+    pytest.param([20, 22], False, None, id="pdims0-False"), pytest.param([20, 22], True, None, id="pdims1-True"), pytest.param(None, False, None, id="None-False"),
+    # both tails of the spatial update from both sides: the whole FOV with update_sn, and the circular constraint on one patch and on several
+    pytest.param(None, True, None, id="None-True"), pytest.param(None, False, _CIRCULAR, id="None-False-circular"),
+    pytest.param([20, 22], False, _CIRCULAR, id="pdims-False-circular")])
+def test_asynchronous_engine_orderings_give_the_same_iteration(pdims, update_sn, constraints):
     """with an engine that defers its results (the real one) sources2d reorders host work: the temporal update's residual is requested under the
     spatial sweeps, the next patch's slices are cut before this patch's fetch, a whole-FOV patch gets its connectivity constraint with the fetch.
     Two iterations with the deferring test double = two iterations with the blocking one, exactly; and the call order is the intended one."""
@@ -331,7 +338,10 @@ def test_asynchronous_engine_orderings_give_the_same_iteration(pdims, update_sn)
     def run(engine):
         v = PatchedVideo(d1, d2, T, pdims or [d1, d2], r, engine)
         v.upload_from_full(Y)
-        s = Sources2D(v, Options(ring_radius=r, spatial_algorithm="hals", maxIter=3), f.A_init, f.C_init, f.sn)
+        o = Options(ring_radius=r, spatial_algorithm="hals", maxIter=3)
+        if constraints is not None:
+            o.spatial_constraints = dict(constraints)
+        s = Sources2D(v, o, f.A_init, f.C_init, f.sn)
         for _ in range(2):
             s.update_background_parallel(); s.update_spatial_parallel(update_sn=update_sn); s.update_temporal_parallel()
         return s, v
@@ -404,6 +414,23 @@ def test_late_collection_of_spatial_results_gives_the_same_iteration(pdims, lag)
             expect.append(("fetch", pids[i - 1]))
     expect.append(("fetch", pids[-1]))
     assert calls == expect, calls
+
+
+def test_hand_over_state_of_a_fresh_object_answers_before_any_update():
+    """the state the update calls hand to each other is declared by the constructor: before any update no patch has the temporal update's residual in place, and
+    there is no search-mask prefetch to start"""
+    from fake_engine import FakeEngine
+    from cnmf_e_amd import synth
+    from cnmf_e_amd.sources2d import PatchedVideo, Sources2D, Options
+    d1, d2, T, K, r = 40, 44, 120, 6, 4
+    f = synth.make_factors(d1, d2, T, K, 31, gSig=1.5, gSiz=7, min_sep=5)
+    eng = FakeEngine()
+    v = PatchedVideo(d1, d2, T, [20, 22], r, eng)
+    s = Sources2D(v, Options(ring_radius=r), f.A_init, f.C_init, f.sn)
+    for idx in v.owned:
+        assert s._temporal_residual_done(idx) is False
+    assert s._start_wanted_prefetch() is None
+    assert s._ind_future is None and s._pool is None and s._early_u is None        # nothing was started, nothing is queued
 
 
 def test_sparse_row_selection_matches_scipy_on_random_matrices():
