@@ -131,6 +131,7 @@ int upload_traces(cnmfe_ctx *ctx, DevBuf &dst, const float *C, int32_t K, int64_
         LAUNCH(ctx, "gather_rows", k_gather_rows, dim3((unsigned)K), dim3(256), 0, ctx->bound.as<float4>(), ldc >> 2, dIdx.as<int>(), dst.as<float4>());
         return 0;                                          // (the index array went through the pinned arena: the caller may drop it)
     }
+    ++ctx->trace_uploads;
     CK(hipMemsetAsync(dst.p, 0, (size_t)K * ldc * sizeof(float), ctx->st()));
     if (order == CNMFE_ROWMAJOR) {
         CK(hipMemcpy2DAsync(dst.p, ldc * sizeof(float), C, T * sizeof(float), T * sizeof(float), K, hipMemcpyDefault, ctx->st()));
@@ -691,7 +692,7 @@ int cnmfe_get_option(cnmfe_ctx *ctx, const char *name, int64_t *value) {
     if (!ctx || !name || !value) return fail(CNMFE_EINVAL, "null argument");
     const struct { const char *n; int64_t v; } counters[] = {{"temporal_early_hits", ctx->early_hits}, {"temporal_early_drops", ctx->early_drops}, {"temporal_early_declined", ctx->early_declined},
                                                               {"temporal_early_entries", ctx->early.nent}, {"temporal_proj_entries", ctx->last_nent}, {"temporal_nowait", ctx->sweep_nowait},
-                                                              {"merge_trace_uploads", ctx->merge_uploads}, {"lanes_live", (int64_t)std::max<size_t>(1, ctx->lanes.size())},
+                                                              {"merge_trace_uploads", ctx->merge_uploads}, {"trace_matrix_uploads", ctx->trace_uploads}, {"init_temporal_levels", ctx->last_nlevels}, {"lanes_live", (int64_t)std::max<size_t>(1, ctx->lanes.size())},
                                                               {"bound_K", ctx->bound_valid ? (int64_t)ctx->bound_K : 0}, {"bound_T", ctx->bound_valid ? ctx->bound_T : 0}};
     for (const auto &c : counters) if (!strcmp(c.n, name)) { *value = c.v; return 0; }
     auto it = ctx->opts.find(name);
@@ -1356,11 +1357,53 @@ int cnmfe_hals_temporal_job(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64
     CK(hipSetDevice(ctx->device));
     if (ctx->tjobs_used == (int)ctx->tjobs.size()) ctx->tjobs.push_back(new TemporalJob());
     TemporalJob *job = ctx->tjobs[ctx->tjobs_used];
-    job->K = 0; job->swept = false;
+    job->K = 0; job->swept = false; job->has_w = false; job->has_off = false;
     RET(temporal_run(ctx, P, K, A_colptr, A_rowidx, A_val, C_in, c_order, maxIter, nullptr, nullptr, nullptr, opts, const_cast<float *>(kernel_pars), nullptr, nullptr, job));
     *job_out = ctx->tjobs_used++;
     return 0;
 }
+// ---- (f) known footprints: initTemporal.m:156-168 of one patch (init_temporal.hpp) ----
+static int init_temporal_args(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, int32_t iters_plain, int32_t iters_last,
+                              const cnmfe_deconv_opts *opts, Patch *&P) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    P = get_patch(ctx, patch_id);
+    if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
+    if (P->derived) return fail(CNMFE_EUNSUPPORTED, "init_temporal: patch %d is a low-resolution (bg_ssub) patch; the reference's ring branch multiplies W with the full-resolution block", patch_id);
+    if (!P->ring_ready) return fail(CNMFE_ESTATE, "ring of patch %d not initialised", patch_id);
+    if (K <= 0) return fail(CNMFE_EINVAL, "K=%d", K);
+    if (!A_colptr || !A_rowidx) return fail(CNMFE_EINVAL, "null A");
+    RET(check_csc("A", K, P->d_b, A_colptr, A_rowidx));
+    if (!A_val && A_colptr[K] > 0) return fail(CNMFE_EINVAL, "null A_val");
+    if (iters_plain < 0 || iters_last < 0 || iters_plain + iters_last <= 0) return fail(CNMFE_EINVAL, "iters_plain = %d, iters_last = %d", iters_plain, iters_last);
+    if (opts && iters_last <= 0) return fail(CNMFE_EINVAL, "deconvolution options need iters_last > 0");
+    if (opts && (opts->type != 1 || opts->method != 1)) return fail(CNMFE_EUNSUPPORTED, "only deconvolution type 'ar1' with method 'foopsi' is built");
+    return 0;
+}
+int cnmfe_init_temporal(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, int32_t iters_plain, int32_t iters_last,
+                        const cnmfe_deconv_opts *opts, float *C_out, float *C_raw_out, float *S_out, float *kernel_pars_out, float *sn_out, float *AA_out, int c_order) {
+    Patch *P = nullptr;
+    RET(init_temporal_args(ctx, patch_id, K, A_colptr, A_rowidx, A_val, iters_plain, iters_last, opts, P));
+    if (c_order != CNMFE_COLMAJOR && c_order != CNMFE_ROWMAJOR) return fail(CNMFE_EINVAL, "c_order must be CNMFE_COLMAJOR or CNMFE_ROWMAJOR (there is no input matrix to be bound)");
+    if (!opts && (S_out || kernel_pars_out || sn_out)) return fail(CNMFE_EINVAL, "S / kernel_pars / sn exist with deconvolution options only");
+    CK(hipSetDevice(ctx->device));
+    return init_temporal_run(ctx, P, K, A_colptr, A_rowidx, A_val, iters_plain, iters_last, opts, C_out, C_raw_out, S_out, kernel_pars_out, sn_out, AA_out, c_order);
+}
+int cnmfe_init_temporal_job(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, int32_t iters_plain, int32_t iters_last,
+                            const cnmfe_deconv_opts *opts, float *AA_out, int32_t *job_out) {
+    Patch *P = nullptr;
+    RET(init_temporal_args(ctx, patch_id, K, A_colptr, A_rowidx, A_val, iters_plain, iters_last, opts, P));
+    if (!job_out) return fail(CNMFE_EINVAL, "null job_out");
+    if (iters_last <= 0) return fail(CNMFE_EINVAL, "a job needs iters_last > 0 (those sweeps are what cnmfe_temporal_jobs_sweep runs)");
+    if (!ctx->stitch_open) return fail(CNMFE_ESTATE, "cnmfe_stitch_begin has not been called (it opens a round of temporal jobs)");
+    CK(hipSetDevice(ctx->device));
+    if (ctx->tjobs_used == (int)ctx->tjobs.size()) ctx->tjobs.push_back(new TemporalJob());
+    TemporalJob *job = ctx->tjobs[ctx->tjobs_used];
+    job->K = 0; job->swept = false; job->has_w = false; job->has_off = false;
+    RET(init_temporal_run(ctx, P, K, A_colptr, A_rowidx, A_val, iters_plain, iters_last, opts, nullptr, nullptr, nullptr, nullptr, nullptr, AA_out, CNMFE_ROWMAJOR, job));
+    *job_out = ctx->tjobs_used++;
+    return 0;
+}
+
 int cnmfe_temporal_jobs_sweep(cnmfe_ctx *ctx) {
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
     CK(hipSetDevice(ctx->device));
@@ -1384,7 +1427,7 @@ int cnmfe_stitch_add_job(cnmfe_ctx *ctx, int32_t job_id, int32_t K_m, const int3
     GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;          // (lanes: lane 0, behind the other lanes; they wait for what this queues)
     RET(to_dev(ctx, ctx->scr[23], ind_m, (size_t)K_m));
     LAUNCH(ctx, "stitch_add", k_stitch_add, dim3((unsigned)((ctx->stitch_T + 255) / 256), (unsigned)K_m), dim3(256), 0, job->dCraw.as<float>(), job->ldc,
-           job->dAa.as<float>(), ctx->scr[23].as<int>(), ctx->stitch.as<float>(), ctx->stitch_ld, ctx->stitch_T);
+           (job->has_w ? job->dW : job->dAa).as<float>(), ctx->scr[23].as<int>(), ctx->stitch.as<float>(), ctx->stitch_ld, ctx->stitch_T);
     return 0;
 }
 

@@ -284,6 +284,11 @@ struct TemporalJob {
     // for all jobs and finishes each: aa = diag(A'A) against the host-side column test, the projection again if a footprint term overflowed its list
     std::vector<int> diag; std::vector<char> upd; bool term_applied = false, finished = false; int nn = 0;
     float *pin = nullptr; size_t pin_cap = 0;             // nn floats of A'A values + one int (the term-projection overflow word)
+    // initTemporal (init_temporal.hpp): the stitch weights are NOT the regression's aa (dAa, the squared norms of the ring-filtered footprints) but AA of the
+    // original footprints on the patch rows (initTemporal.m:160,285): cnmfe_stitch_add_job takes dW when has_w
+    DevBuf dW; bool has_w = false;
+    // ... and its deconvolution sweeps run on the CENTRED video's U: dOff (K doubles) is what the raw video adds to each row, which GetSn alone sees (deconv.hip, DeconvIO::off)
+    DevBuf dOff; bool has_off = false;
     ~TemporalJob() { if (pin) (void)hipHostFree(pin); }
 };
 
@@ -375,6 +380,7 @@ struct LaneState {
     // per-call device scratch of the factor updates (factor.hip, deconv.hip): grown on demand, NEVER freed between calls -- a hipMalloc /
     // hipFree pair per buffer and call cost more than the small kernels they serve, and hipFree drains the device
     DevBuf scr[24];
+    DevBuf itp[30];           // init_temporal.hpp: the block's footprints, the ring-filtered footprints and their rough-start selection (fp64), their lists, U | C0 of the projection
     DeconvScratch dscr;
     kept::KeptSpatial kept;   // what the last deferred spatial update of this lane left in scr[SCR_COLPTR | SCR_EROW | SCR_AVAL | SCR_KEEP] (kept_results.hpp)
     LaneState() = default;
@@ -435,6 +441,8 @@ struct cnmfe_ctx : cnmfe::LaneState {
     int64_t residents_gen = -1; bool res_has_s = false;
     cnmfe::DevBuf mrg[23];                                 // [0] an uploaded source, [1] the result of cnmfe_trace_diff_spikes (diff_K x diff_T), [2..5] moments / K x K / sn, [6..22] cnmfe_merge_apply
     int32_t diff_K = 0; int64_t diff_T = 0;
+    int64_t trace_uploads = 0;                             // counter trace_matrix_uploads: K x T matrices ANY entry point took through a pointer (upload_traces; a bound matrix or rows of it do not count)
+    int64_t last_nlevels = 0;                              // counter init_temporal_levels: launches of level kernels the last cnmfe_init_temporal queued itself (the depth of its schedule)
     int64_t merge_uploads = 0;                             // counter merge_trace_uploads: K x T matrices the merge / tag entry points took from the host
     // dF/F (dff.hpp): the K x T fp64 accumulator of cnmfe_df_begin .. cnmfe_df_finish (row stride df_T), and [0] 1 / sum(A.^2), [1] the rows that are not finite, [2] Df,
     // [3] a divided matrix on its way out.  ev_df chains the projections of different lanes in call order (df_chain: one has been queued since cnmfe_df_begin)
@@ -545,7 +553,7 @@ bool bound_rows_of(const cnmfe_ctx *ctx, const float *C, int c_order, int32_t K,
 int vproj_spatial(cnmfe_ctx *ctx, Patch *P, int32_t K, const float *C, int c_order, const int64_t *IND_colptr, const int32_t *IND_rowidx,
                   const int *dErow, const int *dEcol, const float *dCc, int64_t ldc, float *dU, double *dQ = nullptr);
 int vproj_temporal(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
-                   const int64_t *dColptr, const int *dErow, const float *dAval, float *dU, int64_t ldu);
+                   const int64_t *dColptr, const int *dErow, const float *dAval, float *dU, int64_t ldu, const double *dAval64 = nullptr, bool add_const = true);
 // the same for a residual of cnmfe_residual_ssub (source 2): through the resampling maps, DESIGN.md section 3 bg_ssub
 int vproj_spatial_ssub(cnmfe_ctx *ctx, Patch *M, int32_t K, const float *C, int c_order, const int64_t *IND_colptr, const int32_t *IND_rowidx,
                        const int *dErow, const int *dEcol, const float *dCc, int64_t ldc, float *dU);
@@ -562,6 +570,10 @@ int spatial_run(cnmfe_ctx *ctx, Patch *P, int algorithm, int32_t K, const int64_
 int temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
                  const float *C_in, int c_order, int32_t maxIter, float *C_out, float *C_raw_out, float *aa_out,
                  const cnmfe_deconv_opts *dopts, float *kernel_pars, float *S_out, float *sn_out, TemporalJob *job = nullptr);
+// init_temporal.hpp (factor.hip): initTemporal.m:156-168 of one patch -- A: d_b x K CSC over BLOCK rows
+int init_temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, int32_t iters_plain, int32_t iters_last,
+                      const cnmfe_deconv_opts *dopts, float *C_out, float *C_raw_out, float *S_out, float *pars_out, float *sn_out, float *AA_out, int c_order, TemporalJob *job = nullptr);
+int vproj_pass_plan(Patch *P, int32_t K, const int64_t *colptr, const int32_t *rowidx, int per, std::vector<int> &pass_of);   // vproj.hip
 int temporal_sweep_jobs(cnmfe_ctx *ctx);                  // factor.hip: the level sweeps of every job set up since cnmfe_stitch_begin, level by level across the jobs
 #ifdef __HIPCC__
 // LDS-DMA: 64 lanes x 16 B, global (uniform base + per-lane 32-bit byte offset) -> LDS [lds_dst + lane*16].  Invisible to

@@ -28,13 +28,14 @@ struct DeconvCfg {
 };
 
 // the per-job part of DeconvIO when one launch serves several temporal jobs (factor.hip, temporal_sweep_jobs): workgroup -> jlist[slot] = (job, neuron)
-struct DeconvJobDev { float *C, *Craw, *S; int64_t ldc; const float *U; const int *nptr, *nidx; const float *nval, *aa; float *pars, *sn_out, *b_out; };
+struct DeconvJobDev { float *C, *Craw, *S; int64_t ldc; const float *U; const int *nptr, *nidx; const float *nval, *aa; float *pars, *sn_out, *b_out; const double *off; };
 struct DeconvIO {
     const DeconvJobDev *jobs = nullptr; const int2 *jlist = nullptr;
     const int *list;                   // neuron ids handled by this launch
     float *C; float *Craw; float *S; int64_t ldc;
     const float *U; const int *nptr; const int *nidx; const float *nval; const float *aa;   // HALS inputs
     float *pars; float *sn_out; float *b_out;
+    const double *off = nullptr;       // HALS, initTemporal: U is the CENTRED video's, the raw video's row is off[k] higher -- a constant that only GetSn sees (k_deconv)
     double *pv, *pw; int *pt, *pl;     // pool scratch, T entries per trace slot
     int *tk_pool, *tk_off, *tk_len;    // task scratch, 2*T per trace slot
     double *tk_val;
@@ -149,6 +150,10 @@ __device__ void fft_lds(float *re, float *im, const float2 *tw, int n, int logn)
 struct Ysig4Acc {                                    // frame t of one pixel of a [T/4][npix] float4 video (+ a constant): no LDS copy of the trace
     const float4 *base; int64_t npix; float add;
     __device__ __forceinline__ float operator[](int t) const { return reinterpret_cast<const float *>(base + (int64_t)(t >> 2) * npix)[t & 3] + add; }
+};
+struct RowAdd {                                      // a row in LDS or global memory plus a constant, added in fp64 and rounded once (add = 0: the row itself)
+    const float *y; double add;
+    __device__ __forceinline__ float operator[](int t) const { return (float)((double)y[t] + add); }
 };
 // `y` is anything indexable by the frame (a pointer into LDS or global memory, or an accessor of the 4-frame-interleaved video: Ysig4Acc below).
 // `tabs`: where the twiddle (nfft / 2 floats) and window (nfft floats) tables live -- nullptr: behind re | im in scr; a global buffer for recordings whose
@@ -635,7 +640,7 @@ __global__ void __launch_bounds__(DECONV_NT) k_deconv(DeconvCfg c, DeconvIO io) 
         const DeconvJobDev j = io.jobs[e.x];
         k = e.y;
         io.C = j.C; io.Craw = j.Craw; io.S = j.S; io.ldc = j.ldc; io.U = j.U; io.nptr = j.nptr; io.nidx = j.nidx; io.nval = j.nval; io.aa = j.aa;
-        io.pars = j.pars; io.sn_out = j.sn_out; io.b_out = j.b_out;
+        io.pars = j.pars; io.sn_out = j.sn_out; io.b_out = j.b_out; io.off = j.off;
     } else k = io.list[slot];
     // bit 30 of a list entry: this item belongs to the LAST sweep of the update (HALS_temporal.m:99-102 keeps S and C_raw of that one) -- the sweeps of one update are
     // scheduled as ONE dependency graph over (sweep, trace) items (factor.hip, dag_schedule), so a launch can hold items of different sweeps
@@ -724,7 +729,10 @@ __global__ void __launch_bounds__(DECONV_NT) k_deconv(DeconvCfg c, DeconvIO io) 
     __syncthreads();
     lap(1);
     // ---- noise level (GetSn on the raw trace: HALS_temporal.m:79, deconvTemporal.m:45) ----
-    const double sn = get_sn<decltype(y), 17, SPLIT>(y, c, scr, red, true, tabs);
+    // (io.off: the row the reference holds is y + off[k].  Every other use of y below is y - bsub, and bsub moves with the row: the constant stays out of the
+    //  fp32 row -- 3000 + signal would cost the trace 1e-5 of its norm -- and goes into the samples GetSn windows, where Welch's side lobes leak it into the band)
+    const double yoff = io.off ? io.off[k] : 0.0;
+    const double sn = get_sn<RowAdd, 17, SPLIT>(RowAdd{y, yoff}, c, scr, red, true, tabs);
     lap(2);
     // ---- time constant (deconvolveCa.m:73-89) ----
     double g = (double)io.pars[k];
@@ -772,7 +780,8 @@ __global__ void __launch_bounds__(DECONV_NT) k_deconv(DeconvCfg c, DeconvIO io) 
         if (!optimize_g) break;                      // :113-115
         const double g0 = g;
         if (g > c.gmax) {                            // :104-108
-            const double sn2 = get_sn<decltype(y), 17, SPLIT>(y, c, scr, red, true, tabs);
+            // (foopsi_oasisAR1.m:105 sees the row AFTER HALS_temporal.m:88 took b off: with io.off that is y - bsub; without, y is the residual-based row and stays as it was)
+            const double sn2 = get_sn<RowAdd, 17, SPLIT>(RowAdd{y, io.off ? -bsub : 0.0}, c, scr, red, true, tabs);
             const double g2 = est_g(y, bsub, T, sn2, red);
             if (g2 >= -1.0) g = g2;
             if (tid < 64) { oasis_first(y, bsub + b, T, g, lam, smin, P, scr, nc_pools); const int nt = build_tasks(P, io, base2); if (tid == 0) { sh_i[0] = P.n; sh_i[1] = nt; } }
@@ -1153,14 +1162,14 @@ int deconv_launch(cnmfe_ctx *ctx, DeconvCfg &c, size_t shmem, DeconvIO io, const
 
 int temporal_deconv_sweeps(cnmfe_ctx *ctx, const cnmfe_deconv_opts *dopts, int64_t T, int K, int maxIter, const std::vector<std::vector<int>> &levels,
                            const int *dLvl, const std::vector<int> &off, float *dC, float *dCraw, float *dS, int64_t ldc, const float *dU,
-                           const int *dNptr, const int *dNidx, const float *dNval, const float *dAa, float *dPars, float *dSn) {
+                           const int *dNptr, const int *dNidx, const float *dNval, const float *dAa, float *dPars, float *dSn, const double *dOff) {
     DeconvCfg c; size_t shmem;
     RET(deconv_setup(dopts, T, 1, c, shmem));
     DeconvScratch &scr = ctx->dscr; DevBuf &dB = ctx->scr[20];
     RET(dB.ensure((size_t)K * sizeof(float)));
     DeconvIO io;
     io.C = dC; io.Craw = dCraw; io.S = dS; io.ldc = ldc; io.U = dU; io.nptr = dNptr; io.nidx = dNidx; io.nval = dNval; io.aa = dAa;
-    io.pars = dPars; io.sn_out = dSn; io.b_out = dB.as<float>();
+    io.pars = dPars; io.sn_out = dSn; io.b_out = dB.as<float>(); io.off = dOff;
     // maxIter < 0: `levels` are the levels of the dependency graph over the items of ALL sweeps (factor.hip, dag_schedule): one pass, the last sweep's items carry bit 30
     for (int it = 0; it < (maxIter < 0 ? 1 : maxIter); ++it) {
         c.last = maxIter >= 0 && it == maxIter - 1;
@@ -1179,7 +1188,7 @@ int temporal_deconv_sweeps_jobs(cnmfe_ctx *ctx, const cnmfe_deconv_opts *dopts, 
     for (size_t ji = 0; ji < jobs.size(); ++ji) {
         TemporalJob *j = jobs[ji];
         tab[ji] = DeconvJobDev{j->dC.as<float>(), j->dCraw.as<float>(), j->dS.as<float>(), j->ldc, j->dU.as<float>(), j->dNptr.as<int>(), j->dNidx.as<int>(),
-                               j->dNval.as<float>(), j->dAa.as<float>(), j->dPars.as<float>(), j->dSn.as<float>(), j->dB.as<float>()};
+                               j->dNval.as<float>(), j->dAa.as<float>(), j->dPars.as<float>(), j->dSn.as<float>(), j->dB.as<float>(), j->has_off ? j->dOff.as<double>() : nullptr};
     }
     RET(to_dev(ctx, dTab, tab.data(), tab.size()));
     DeconvIO io;

@@ -645,7 +645,7 @@ int spatial_fetch(cnmfe_ctx *ctx, float *A_out, int64_t nnz) {
 struct DeconvCfg; struct DeconvIO; struct DeconvScratch;
 int temporal_deconv_sweeps(cnmfe_ctx *ctx, const cnmfe_deconv_opts *dopts, int64_t T, int K, int maxIter, const std::vector<std::vector<int>> &levels,
                            const int *dLvl, const std::vector<int> &off, float *dC, float *dCraw, float *dS, int64_t ldc, const float *dU,
-                           const int *dNptr, const int *dNidx, const float *dNval, const float *dAa, float *dPars, float *dSn);
+                           const int *dNptr, const int *dNidx, const float *dNval, const float *dAa, float *dPars, float *dSn, const double *dOff = nullptr);
 
 // ---- fast_temporal (use_c_hat = false): C_raw = (A .* [A >= max(A)/2])' * Y ./ aa   (update_temporal_parallel.m:314-337)
 __global__ void k_scale_rows(float *__restrict__ U, int64_t ldc, int64_t T, const float *__restrict__ inv) {
@@ -971,6 +971,8 @@ int temporal_sweep_jobs(cnmfe_ctx *ctx) {
     ht.mark("launches");
     return 0;
 }
+
+#include "init_temporal.hpp"      // (f) known footprints: initTemporal's per-patch regression (its sweeps are the level kernels and the schedule above)
 
 static int postproc_boxes(int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, std::vector<int4> &box);
 

@@ -55,6 +55,10 @@
 //   [Cn_patch, PNR_patch, Sn_patch, Yres] = cnmfe_mex('peel_open_residual', h, pid, A_patch, C_or_rows, psf)   the second pass (initComponents_residual_parallel.m:186-220):
 //                                                                          the session on the PATCH and on Ysig - A_patch C, after 'residual' / 'residual_ssub'; the images are
 //                                                                          nr x nc of the patch, Yres (asked for as 4th output) d x T single; extract / apply then take the seed in the patch
+// Known footprints (@Sources2D/initTemporal.m:156-168 per patch; the loop over the patches, the stitch and deconvTemporal are the caller's, as in cnmf_e_amd/sources2d.py -- no .m twin is written):
+//   [C, C_raw, AA, S, pars, sn] = cnmfe_mex('init_temporal', h, pid, A_block, iters_plain, iters_last, smin, max_tau)   A_block: sparse, BLOCK rows x K; without smin and
+//                                                                          max_tau the last sweeps are plain too (three outputs).  C_raw and AA also stay on the device:
+//                                                                          cnmfe_mex('stitch_add', h, ind) then adds AA .* C_raw (:285)
 // Merging (merge_high_corr.m:50-85,172-196,236 and its two siblings, Sources2D.m:1683-1715; the K x K criteria and the groups are the caller's).  A trace SOURCE is the
 // last argument: a K x T matrix (uploaded), or 'bound' | 'craw' | 's' | 'diff' followed by K, T -- the context's own C, C_raw, S, the last 'trace_diff_spikes':
 //   cnmfe_mex('traces_load', h, C, C_raw, S, kernel_pars)                  the object's matrices become the context's ([] for what it lacks); not needed after 'deconv' on the bound matrix
@@ -640,6 +644,29 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
         int32_t *ind = ind_of(pin[5], &n);
         if (n != (size_t)A.K) FAIL("df_add_background_ssub: one accumulator row per column of A");
         CHECK(cnmfe_df_add_background_ssub(c, pid, f32_of(pin[3], NULL), A.K, A.cp, A.ri, A.v, ind));
+    } else if (!strcmp(cmd, "init_temporal")) {                // [C, C_raw, AA, S, pars, sn] = cnmfe_mex('init_temporal', h, pid, A_block, iters_plain, iters_last, smin, max_tau)   initTemporal.m:160-168
+        if (nin != 6 && nin != 8) FAIL("init_temporal: 6 inputs required, 8 with deconvolution (h, pid, A_block, iters_plain, iters_last[, smin, max_tau])");
+        int slot = 0;
+        while (slot < g_ndims && !(g_dims[slot].c == c && g_dims[slot].pid == pid)) ++slot;
+        if (slot == g_ndims) FAIL("init_temporal: patch %d was not created through this gateway", pid);
+        if (!mxIsSparse(pin[3])) FAIL("init_temporal: A_block must be sparse (block rows x K)");
+        Csc A = csc_of(pin[3]);
+        const size_t K = (size_t)A.K, T = (size_t)g_dims[slot].T;
+        const int dec = nin == 8;
+        if (!dec && nout > 3) FAIL("init_temporal: S, pars and sn exist with deconvolution only (give smin and max_tau)");
+        cnmfe_deconv_opts o;
+        if (dec) deconv_opts_of(&o, mxGetScalar(pin[6]), mxGetScalar(pin[7]));
+        float *Co = (float *)mxMalloc((K * T + 1) * sizeof(float)), *Cr = nout > 1 ? (float *)mxMalloc((K * T + 1) * sizeof(float)) : NULL;
+        float *AA = (float *)mxMalloc((K + 1) * sizeof(float));
+        float *S = nout > 3 ? (float *)mxMalloc((K * T + 1) * sizeof(float)) : NULL, *kp = nout > 4 ? (float *)mxMalloc((K + 1) * sizeof(float)) : NULL;
+        float *sn = nout > 5 ? (float *)mxMalloc((K + 1) * sizeof(float)) : NULL;
+        CHECK(cnmfe_init_temporal(c, pid, A.K, A.cp, A.ri, A.v, (int32_t)mxGetScalar(pin[4]), (int32_t)mxGetScalar(pin[5]), dec ? &o : NULL, Co, Cr, S, kp, sn, AA, CNMFE_COLMAJOR));
+        pout[0] = to_double(Co, K, T);
+        if (nout > 1) pout[1] = to_double(Cr, K, T);
+        if (nout > 2) pout[2] = to_double(AA, K, 1);
+        if (nout > 3) pout[3] = to_double(S, K, T);
+        if (nout > 4) pout[4] = to_double(kp, K, 1);
+        if (nout > 5) pout[5] = to_double(sn, K, 1);
     } else if (!strcmp(cmd, "set_noise")) {                    // cnmfe_mex('set_noise', h, pid, sn_block): read by the outlier branch of the ring fit
         if (nin != 4) FAIL("set_noise: 4 inputs required");
         CHECK(cnmfe_set_noise(c, pid, f32_of(pin[3], NULL)));

@@ -195,14 +195,16 @@ int vproj_spatial(cnmfe_ctx *ctx, Patch *P, int32_t K, const float *C, int c_ord
 #define VP_WG_TARGET 2048
 #endif
 constexpr int VP_WS = 64;                                   // window side: 16 + 2 * 24
+// (TV: the footprint values' type -- float for A of the updates, double for the ring-filtered footprints of initTemporal, init_temporal.hpp)
+template <class TV>
 __global__ void __launch_bounds__(256) k_vp_build_b(const int *__restrict__ ent_blk, const int *__restrict__ ent_k, const int *__restrict__ ent_slot, const int *__restrict__ g16,
-                                                    BgGeom g, int R, const int64_t *__restrict__ colptr, const int *__restrict__ erow, const float *__restrict__ aval,
+                                                    BgGeom g, int R, const int64_t *__restrict__ colptr, const int *__restrict__ erow, const TV *__restrict__ aval,
                                                     const int *__restrict__ dr, const int *__restrict__ dc, const float *__restrict__ W, double *__restrict__ Bt) {
-    __shared__ float win[VP_WS * VP_WS];
+    __shared__ TV win[VP_WS * VP_WS];
     const int b = ent_blk[blockIdx.x], k = ent_k[blockIdx.x], slot = ent_slot[blockIdx.x];
     const int bi = b % g.nbr, bj = b / g.nbr;
     const int wr0 = bi * 16 - R, wc0 = bj * 16 - R, ws = 16 + 2 * R;
-    for (int i = threadIdx.x; i < ws * ws; i += 256) win[i] = 0.f;
+    for (int i = threadIdx.x; i < ws * ws; i += 256) win[i] = TV(0);
     __syncthreads();
     for (int64_t e = colptr[k] + threadIdx.x; e < colptr[k + 1]; e += 256) {
         const int m = erow[e];
@@ -216,8 +218,8 @@ __global__ void __launch_bounds__(256) k_vp_build_b(const int *__restrict__ ent_
         double acc = 0.0;
         for (int i = 0; i < g.p; ++i) {
             const int rm = rb - dr[i], cm = cb - dc[i];                     // the centre pixel whose i-th ring neighbour is this pixel
-            const float a = win[(cm - wc0) * ws + (rm - wr0)];
-            if (a != 0.f) acc += (double)W[(int64_t)i * g.d + (int64_t)(cm - g.coff) * g.nr + (rm - g.roff)] * (double)a;      // (a != 0: a patch pixel)
+            const TV a = win[(cm - wc0) * ws + (rm - wr0)];
+            if (a != TV(0)) acc += (double)W[(int64_t)i * g.d + (int64_t)(cm - g.coff) * g.nr + (rm - g.roff)] * (double)a;      // (a != 0: a patch pixel)
         }
         v = (double)win[(cb - wc0) * ws + (rb - wr0)] - acc;
     }
@@ -433,7 +435,7 @@ static int vp_launch_proj(cnmfe_ctx *ctx, Patch *V, const BgGeom &g, const VpLis
 }
 
 int vproj_temporal(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
-                   const int64_t *dColptr, const int *dErow, const float *dAval, float *dU, int64_t ldu) {
+                   const int64_t *dColptr, const int *dErow, const float *dAval, float *dU, int64_t ldu, const double *dAval64, bool add_const) {
     HostTrace ht(ctx, "vproj_temporal");
     const BgGeom g = bg_geom(P);
     const int nblk = g.nbr * g.nbc, R = g.p_radius;
@@ -461,8 +463,11 @@ int vproj_temporal(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr,
     RET(dCst.ensure_hw((size_t)K * sizeof(double), ctx->hw_vp[7]));
     RET(dPart.ensure_hw((size_t)std::max<int64_t>(1, nent) * ldp * sizeof(double), ctx->hw_vp[8]));
     CK(hipMemsetAsync(dBt.p, 0, bt_bytes, ctx->st()));      // (the padding slots of a group must be 0)
-    if (nent > 0)
-        LAUNCH(ctx, "temporal_build_B", k_vp_build_b, dim3((unsigned)nent), dim3(256), 0, dEb.as<int>(), dEk.as<int>(), dEs.as<int>(), dG16.as<int>(), g, R, dColptr, dErow, dAval,
+    if (nent > 0 && dAval64)                                // (fp64 footprint values: initTemporal's ring-filtered footprints, never rounded before their panels)
+        LAUNCH(ctx, "temporal_build_B", k_vp_build_b<double>, dim3((unsigned)nent), dim3(256), 0, dEb.as<int>(), dEk.as<int>(), dEs.as<int>(), dG16.as<int>(), g, R, dColptr, dErow, dAval64,
+               P->ring_dr.as<int>(), P->ring_dc.as<int>(), P->W.as<float>(), dBt.as<double>());
+    else if (nent > 0)
+        LAUNCH(ctx, "temporal_build_B", k_vp_build_b<float>, dim3((unsigned)nent), dim3(256), 0, dEb.as<int>(), dEk.as<int>(), dEs.as<int>(), dG16.as<int>(), g, R, dColptr, dErow, dAval,
                P->ring_dr.as<int>(), P->ring_dc.as<int>(), P->W.as<float>(), dBt.as<double>());
     // round 5 (late): on the int8 pipe out of the video's digit planes when the fit left them resident (vproj_i8.hpp) -- their pixel-major copy is made once per upload
     const kept::ProjOpts po = proj_opts(ctx);
@@ -476,7 +481,8 @@ int vproj_temporal(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr,
             P->digp_valid = true;
         }
     }
-    LAUNCH(ctx, "temporal_const", k_vp_const, dim3((unsigned)K), dim3(256), 0, dColptr, dErow, dAval, g, P->ymean_d.as<double>(), P->b0.as<double>(), dCst.as<double>());
+    if (add_const) LAUNCH(ctx, "temporal_const", k_vp_const, dim3((unsigned)K), dim3(256), 0, dColptr, dErow, dAval, g, P->ymean_d.as<double>(), P->b0.as<double>(), dCst.as<double>());
+    else CK(hipMemsetAsync(dCst.p, 0, (size_t)K * sizeof(double), ctx->st()));      // (U = B' Yc alone: initTemporal's rows end in "minus the minimum", a constant changes nothing)
     if (i8) {
         const int ngrp = L.g16[nblk];
         std::vector<int> grp_blk((size_t)std::max(1, ngrp), 0);
@@ -524,6 +530,34 @@ int vproj_temporal(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr,
            dCst.as<double>(), P->T, dU, ldu);
     ht.mark("launches");
     return 0;
+}
+
+// initTemporal (init_temporal.hpp) projects `per` columns per neuron -- the ring-filtered footprint and its rough-start selection share one pattern -- and a
+// column of (E - W)' At reaches two ring widths beyond the footprint: one 16 x 16 block can meet more than the WIN_NLB list slots.  The neurons are therefore
+// dealt into PASSES, each a projection of its own: a neuron goes into the first pass in which every block it meets still has `per` free slots (first fit, in
+// ascending k: a fixed assignment).  pass_of[k] = its pass; returns the number of passes (1 unless a block is that crowded), 0 when the ring is wider than the
+// panel builder's window.
+int vproj_pass_plan(Patch *P, int32_t K, const int64_t *colptr, const int32_t *rowidx, int per, std::vector<int> &pass_of) {
+    const BgGeom g = bg_geom(P);
+    const int nblk = g.nbr * g.nbc, R = g.p_radius;
+    pass_of.assign((size_t)K, 0);
+    if (16 + 2 * R > VP_WS || per > WIN_NLB) return 0;
+    std::vector<int> lo(g.nbc, 0), hi(g.nbc, -1), need;
+    std::vector<std::vector<int>> fill;
+    for (int32_t k = 0; k < K; ++k) {
+        need.clear();
+        reach_blocks(P, g, R, rowidx, colptr[k], colptr[k + 1], lo, hi, need);
+        size_t p = 0;
+        for (;; ++p) {
+            if (p == fill.size()) fill.emplace_back((size_t)nblk, 0);
+            bool ok = true;
+            for (int b : need) if (fill[p][b] + per > WIN_NLB) { ok = false; break; }
+            if (ok) break;
+        }
+        for (int b : need) fill[p][b] += per;
+        pass_of[k] = (int)p;
+    }
+    return (int)std::max<size_t>(1, fill.size());
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------

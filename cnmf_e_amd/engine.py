@@ -288,6 +288,7 @@ class Engine:
     supports_bound_deconv = True      # deconv_temporal_bound()
     supports_fit_reserve = True       # fit_reserve()
     supports_synchronize = True       # synchronize()
+    supports_init_temporal = True     # init_temporal() / init_temporal_job()
 
     # pinned buffers of LazyHostTraces, recycled by size (page-locking 20 MB costs milliseconds)
     def _pinned_take(self, nbytes):
@@ -722,6 +723,38 @@ class Engine:
         job = C.c_int32(-1)
         L.check(L.lib.cnmfe_hals_temporal_job(self._ctx, pid, K, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p), cptr, cord, int(maxIter),
                                               None if opts is None else C.byref(opts), _p(pars, L.f32p), C.byref(job)))
+        return job.value
+
+    # ---- (f) known footprints: initTemporal.m:156-168 of one patch (cnmfe_init_temporal in include/cnmfe.h) ----
+    def init_temporal(self, pid, A_block, iters_plain=10, iters_last=2, deconv_options=None, want=True):
+        """the traces of the footprints A_block (d_b x K, BLOCK rows) under the patch's resident W on its resident video: the rough start of
+        HALS_temporal.m:34-41, iters_plain plain sweeps and iters_last more (with deconv_options: the in-sweep AR(1) FOOPSI, kernel parameters estimated fresh).
+        Returns (C, C_raw, S, kernel_pars, sn, AA); want=False downloads nothing but AA (C_raw and AA stay on the device for stitch_add)."""
+        info = self._patch[pid]
+        K, cp, ri, va = _csc(A_block, info["d_b"])
+        T = info["T"]
+        opts = None if deconv_options is None else self._dopts(deconv_options)
+        Cout = np.empty((K, T), dtype=np.float32) if want else None
+        Craw = np.empty((K, T), dtype=np.float32) if want else None
+        dec = want and opts is not None
+        S = np.empty((K, T), dtype=np.float32) if dec else None
+        pars = np.zeros(K, dtype=np.float32) if dec else None
+        sn = np.zeros(K, dtype=np.float32) if dec else None
+        AA = np.empty(K, dtype=np.float32)
+        L.check(L.lib.cnmfe_init_temporal(self._ctx, pid, K, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p), int(iters_plain), int(iters_last),
+                                          None if opts is None else C.byref(opts), _p(Cout, L.f32p), _p(Craw, L.f32p), _p(S, L.f32p), _p(pars, L.f32p),
+                                          _p(sn, L.f32p), _p(AA, L.f32p), L.ROWMAJOR))
+        return Cout, Craw, S, pars, sn, AA
+
+    def init_temporal_job(self, pid, A_block, iters_plain=10, iters_last=2, deconv_options=None):
+        """init_temporal for several patches per engine: the plain sweeps run at once, the last ones with the other jobs' in temporal_jobs_sweep; returns
+        the job number (for stitch_add_job, which adds AA .* C_raw)"""
+        info = self._patch[pid]
+        K, cp, ri, va = _csc(A_block, info["d_b"])
+        opts = None if deconv_options is None else self._dopts(deconv_options)
+        job = C.c_int32(-1)
+        L.check(L.lib.cnmfe_init_temporal_job(self._ctx, pid, K, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p), int(iters_plain), int(iters_last),
+                                              None if opts is None else C.byref(opts), None, C.byref(job)))
         return job.value
 
     def temporal_jobs_sweep(self):

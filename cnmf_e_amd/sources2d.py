@@ -914,6 +914,39 @@ class Sources2D:
     def get_b0(self, idx):
         return self.engine.b0(self.video.pid[idx])
 
+    # -- a known background on a fresh object: W{m}, b0{m} of another recording of the same field of view (there is get_W / get_b0; these are the way in) --
+    def set_W(self, idx, values):
+        """obj.W{idx} = values: a d x d_b sparse matrix on the ring pattern (what get_W returns; entries off the pattern are refused) or the pattern's values in
+        CSR order.  The patch's resident residual goes with the old W.  The reference's first-run test (fit_ring_model.m:25: two distinct values in row 1 of
+        W{m}, also update_background_parallel.m:143) then sees a FITTED W: the next update_background_parallel of this object refits from it as a later run
+        and takes the "nothing changed here" skip of :188-199 for patches without neurons."""
+        pat = self.get_W(idx)
+        if sp.issparse(values):
+            V = sp.csr_matrix(values)
+            if V.shape != pat.shape:
+                raise ValueError("W{%s} is %s, got %s" % (idx, pat.shape, V.shape))
+            rows = np.repeat(np.arange(pat.shape[0]), np.diff(pat.indptr))
+            vals = np.asarray(V[rows, pat.indices]).ravel().astype(np.float32)
+            if np.count_nonzero(vals) != V.count_nonzero():
+                raise ValueError("W{%s} has entries off the ring pattern" % (idx,))
+        else:
+            vals = np.ascontiguousarray(values, dtype=np.float32).ravel()
+            if vals.size != pat.nnz:
+                raise ValueError("W{%s} has %d entries on its ring pattern, got %d values" % (idx, pat.nnz, vals.size))
+        for pid in ([self.video.pid[idx]] if self.ssub == 1 else [self.pid_fit[idx], self.pid_res[idx]]):
+            self.engine.ring_set_values(pid, vals)
+        self._resid_tag.pop(idx, None)
+
+    def set_b0(self, idx, b0):
+        """obj.b0{idx} = b0 (the patch's pixels, column-major).  Beside a W from set_W this completes a transplanted background: the first-run test of
+        fit_ring_model.m:25 looks at W alone and then sees a fitted one.  The patch's resident residual goes with the old b0; b0_new is re-read from b0."""
+        b0 = np.ascontiguousarray(b0, dtype=np.float32).ravel()
+        if b0.size != self.video.patch_pix[idx].size:
+            raise ValueError("b0{%s} has %d pixels, got %d" % (idx, self.video.patch_pix[idx].size, b0.size))
+        self.engine.set_b0(self.video.pid[idx], b0)
+        self._resid_tag.pop(idx, None)
+        self._b0_new_src = "b0"
+
     # obj.A_raw: the spatial update before post-processing.  Nothing in the iteration reads it, so the one-patch path stores the recipe (a callable) and
     # the matrix is assembled on first read
     @property
@@ -1982,6 +2015,56 @@ class Sources2D:
         except Exception:
             eng.df_close()                                           # (a refused call must not leave the accumulator open)
             raise
+
+    # -- known footprints ---------------------------------------------------------------
+    def initTemporal(self, frame_range=None, use_parallel=True):
+        """@Sources2D/initTemporal.m:89-168,270-292 (ring model): the traces of the footprints obj.A under the background obj.W / obj.b0 (set_W / set_b0, or an
+        earlier fit) on the recording that is uploaded -- the second session of an animal, the next temporal batch (initComponents_batch.m:65), a curated A.  No C
+        is read.  Per owned patch: the neurons with any weight in the BLOCK (:106-111), Engine.init_temporal[_job] (the rough start, ten plain sweeps, two more
+        with deconv_flag's options) and P.Ymean (:152-153); the stitch weighs every patch's rows with AA of the ORIGINAL footprints on its pixels (:160,276-290; one
+        all-reduce when sharded); then obj.deconvTemporal() under deconv_flag (:292), else C = C_raw as :290 leaves it.  Sets C, C_raw (and S, P.kernel_pars,
+        P.neuron_sn under deconv_flag); the new traces are the engine's bound matrix, so the update_background_parallel that follows uploads no K x T matrix.
+        W and b0 stay as they are (:270).  frame_range: the frames that were uploaded, None or (1, T).
+        Not built (NotImplementedError): bg_ssub > 1 (the reference's ring branch multiplies W with the full-resolution block), other frame ranges."""
+        self._need_data()
+        v, o, eng = self.video, self.options, self.engine
+        if self.ssub > 1:
+            raise NotImplementedError("initTemporal: bg_ssub > 1 is not built (initTemporal.m:165-166 multiplies W with the full-resolution block)")
+        if frame_range is not None and len(frame_range) and (int(frame_range[0]) != 1 or int(frame_range[1]) != v.T):
+            raise NotImplementedError("initTemporal works on the frames that were uploaded, [1, %d] (frame_range = [%d, %d])" % (v.T, int(frame_range[0]), int(frame_range[1])))
+        K, T = self.A.shape[1], v.T
+        if K == 0:
+            raise ValueError("initTemporal needs footprints: obj.A has no columns")
+        if not self._can("init_temporal"):
+            raise NotImplementedError("this engine has no init_temporal")
+        dopt = o.deconv_options if o.deconv_flag else None
+        sharded = self._sharded
+        eng.stitch_begin(K, T)
+        batch = len(v.owned) > 1 and self._can("temporal_jobs")
+        jobs = []
+        for idx in v.owned:
+            self.P["Ymean"][idx] = eng.ymean(v.pid[idx])[v.ind_patch[idx]]                           # :152-153
+            ind, A_blk = self._slice(self.A, idx, "block")                                           # :106-111
+            self._resid_tag.pop(idx, None)
+            if ind.size == 0:
+                continue                                                                              # :156-159
+            if batch:
+                jobs.append((eng.init_temporal_job(v.pid[idx], A_blk, 10, 2, dopt), ind))             # :167-168
+                continue
+            eng.init_temporal(v.pid[idx], A_blk, 10, 2, dopt, want=False)                            # :167-168
+            eng.stitch_add(ind)                                                                       # :285-286
+        if jobs:
+            eng.temporal_jobs_sweep()
+            for job, ind in jobs:
+                eng.stitch_add_job(job, ind)                                                          # :285-286
+        if sharded:
+            eng.stitch_allreduce(self.dist)
+        self._ymean_full = None
+        lazy = (not o.deconv_flag) and self._can("lazy_traces")
+        bound_deconv = o.deconv_flag and not sharded and self._can("bound_deconv") and self._can("lazy_traces")
+        self.C_raw = eng.stitch_finish(subtract_min=False, want="lazy" if lazy else ("bound" if bound_deconv else True))      # :289-290
+        self.C = self.deconvTemporal() if o.deconv_flag else self.C_raw                               # :292
+        return self.C
 
     # -- temporal -----------------------------------------------------------------------
     def update_temporal_parallel(self, use_parallel=True, use_c_hat=True):

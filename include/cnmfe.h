@@ -410,6 +410,32 @@ int cnmfe_hals_temporal_job(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64
                             const float *C_in, int c_order, int32_t maxIter, const cnmfe_deconv_opts *opts, const float *kernel_pars, int32_t *job_out);
 int cnmfe_temporal_jobs_sweep(cnmfe_ctx *ctx);
 int cnmfe_stitch_add_job(cnmfe_ctx *ctx, int32_t job, int32_t K_m, const int32_t *ind_m);
+
+/* ---- (f) known footprints: the traces of given footprints and a given ring background on ANOTHER recording
+ * @Sources2D/initTemporal.m:89-168 (ring branch) -> utilities/HALS_temporal.m:34-41 (the rough start without a C), :48-68, :70-104:
+ *     AA = sum(A(patch, :).^2, 1)                                                                  (:160, the stitch weight)
+ *     Yt = Y(patch, :) - W Y(block, :);   At = A(patch, :) - W A                                   (:165-166: the raw video; no b0, no mean, no previous factors)
+ *     [~, C] = HALS_temporal(Yt, At, [], iters_plain);   [C, C_raw, deconv] = HALS_temporal(Yt, At, C, iters_last, deconv_options)       (:167-168; 10 and 2)
+ * Y = the resident block, W = the resident W{m} (cnmfe_ring_set_values / a fit; b0 is not read).  A is d_b x K CSC over BLOCK rows (the neurons with any weight in
+ * the block, :106-111; columns that are empty or zero on the patch are legal).  opts == NULL: the last sweeps are plain too (S_out, kernel_pars_out, sn_out must
+ * be NULL); else they are the in-sweep AR(1) FOOPSI of cnmfe_hals_temporal_deconv with kernel parameters estimated fresh.  At and V = At' At are formed in fp64
+ * from the fp32 A and W; U = At' Yt and the rough start come out of ONE block-tiled pass over the centred video (a constant per row of U or of the starting C
+ * changes no output of the plain sweeps: every row update ends in "minus its minimum"; the deconvolution sweeps take GetSn before their baseline goes,
+ * HALS_temporal.m:79, and get the raw video's constant At' (E - W) Ymean / aa per row in fp64, for GetSn alone) -- several passes only where a 16 x 16 block meets more than 32
+ * neurons' (E - W)' At; all sweeps run on the dependency graph of the non-zeros of V, nothing K x T crosses PCIe in between.  Outputs K x T in c_order
+ * (CNMFE_COLMAJOR / CNMFE_ROWMAJOR), K floats; each may be NULL: C_raw and AA also stay on the device, and cnmfe_stitch_add then adds AA .* C_raw (:285 --
+ * NOT the regression's own aa).  A row with At(:, k) = 0 keeps its rough start (0) and C_raw = 0.  Every reduction has a fixed order: two calls are bit-identical.
+ * CNMFE_ESTATE without a ring, CNMFE_EUNSUPPORTED for a derived (bg_ssub) patch or a ring radius above 24; a refused call changes nothing.  No residual of the
+ * patch is read, written or invalidated.
+ * cnmfe_init_temporal_job: the same for several patches per context, alongside cnmfe_hals_temporal_job (after cnmfe_stitch_begin): the iters_plain sweeps run at
+ * once on the patch's lane, the iters_last (> 0) sweeps are job *job_out of cnmfe_temporal_jobs_sweep; cnmfe_stitch_add_job adds AA .* C_raw.
+ * Read-only counters (cnmfe_get_option): init_temporal_levels, the level-kernel launches the last call queued itself (the depth of its schedule);
+ * trace_matrix_uploads, the K x T matrices any entry point of the context took through a pointer (a bound matrix or rows of it do not count). */
+int cnmfe_init_temporal(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx /* BLOCK rows */, const float *A_val,
+                        int32_t iters_plain /* 10 */, int32_t iters_last /* 2 */, const cnmfe_deconv_opts *opts /* NULL: plain */,
+                        float *C_out, float *C_raw_out, float *S_out, float *kernel_pars_out, float *sn_out, float *AA_out, int c_order);
+int cnmfe_init_temporal_job(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, int32_t iters_plain,
+                            int32_t iters_last, const cnmfe_deconv_opts *opts, float *AA_out, int32_t *job_out);
 int cnmfe_stitch_buffer(cnmfe_ctx *ctx, float **dev_acc, int64_t *ld);
 /* cnmfe_stitch_buffer without the drain of the stream: also hands out the hipStream_t the additions are queued on.  A collective enqueued ON that stream (torch:
  * `with torch.cuda.stream(torch.cuda.ExternalStream(ptr)): all_reduce(...)` -- RCCL orders itself behind and in front of the current stream with events) needs
