@@ -343,9 +343,13 @@ int ctx_side_stream(cnmfe_ctx *ctx) {
     hipError_t e = hipStreamSynchronize(s);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_side_fork, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_side_join, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_ring_solved, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_ring_join, hipEventDisableTiming);
     if (e != hipSuccess) {
         (void)hipStreamDestroy(s);
         if (ctx->ev_side_fork) { (void)hipEventDestroy(ctx->ev_side_fork); ctx->ev_side_fork = nullptr; }
+        if (ctx->ev_side_join) { (void)hipEventDestroy(ctx->ev_side_join); ctx->ev_side_join = nullptr; }
+        if (ctx->ev_ring_solved) { (void)hipEventDestroy(ctx->ev_ring_solved); ctx->ev_ring_solved = nullptr; }
         return fail(CNMFE_EHIP, "side stream of option fit_side: %s", hipGetErrorString(e));
     }
     ctx->side_stream = s;
@@ -522,6 +526,7 @@ cnmfe_ctx::~cnmfe_ctx() {
 // ---- execution lanes (common.hpp, LaneState) ----
 void cnmfe_ctx::patches_changed() {                          // (they may name the patch that just went)
     early.valid = false;
+    rs_ahead.valid = false;                                  // (the tables built ahead name a patch too)
     kept.patch_gone();
     for (cnmfe_lane *L : lanes) L->state.kept.patch_gone();
 }
@@ -666,12 +671,16 @@ void cnmfe_destroy(cnmfe_ctx *ctx) {
     if (ctx->side_stream) { (void)hipStreamSynchronize(ctx->side_stream); (void)hipStreamDestroy(ctx->side_stream); ctx->side_stream = nullptr; }
     if (ctx->ev_side_fork) { (void)hipEventDestroy(ctx->ev_side_fork); ctx->ev_side_fork = nullptr; }
     if (ctx->ev_side_join) { (void)hipEventDestroy(ctx->ev_side_join); ctx->ev_side_join = nullptr; }
+    if (ctx->ev_ring_solved) { (void)hipEventDestroy(ctx->ev_ring_solved); ctx->ev_ring_solved = nullptr; }
+    if (ctx->ev_ring_join) { (void)hipEventDestroy(ctx->ev_ring_join); ctx->ev_ring_join = nullptr; }
+    if (ctx->rs_pin) { (void)hipHostFree(ctx->rs_pin); ctx->rs_pin = nullptr; ctx->rs_pin_cap = 0; }
     delete ctx;
 }
 
 int cnmfe_synchronize(cnmfe_ctx *ctx) {
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
     RET(ctx->join_lanes());                                  // (every lane's work in front of lane 0's stream)
+    RET(ctx->ring_side_join());
     CK(hipStreamSynchronize(ctx->st()));
     if (ctx->copy_stream) CK(hipStreamSynchronize(ctx->copy_stream));
     return ctx_check_errflag(ctx);
@@ -680,7 +689,7 @@ int cnmfe_synchronize(cnmfe_ctx *ctx) {
 int cnmfe_set_option(cnmfe_ctx *ctx, const char *name, int64_t value) {
     if (!ctx || !name) return fail(CNMFE_EINVAL, "null argument");
     // behaviour switches (include/cnmfe.h) and, behind them, the probes of scripts/ (diagnostics: solve_probe, r1_probe, deconv_trace, trace_long, host_trace, debug)
-    static const char *known[] = {"r1_variant", "r1_delta", "r1_lazy", "r1_defer", "r1_virtual", "gram_incremental", "prealloc", "solve_packed", "sweep_dag", "win_i8_planes", "solve_staged", "solve_inv", "solve_inv_terms", "gram_i8", "win_i8", "proj_tiled", "proj_i8", "proj_i8_planes", "ssub_virtual", "temporal_early", "fit_side",
+    static const char *known[] = {"r1_variant", "r1_delta", "r1_lazy", "r1_defer", "r1_virtual", "gram_incremental", "prealloc", "solve_packed", "sweep_dag", "win_i8_planes", "solve_staged", "solve_inv", "solve_inv_terms", "gram_i8", "win_i8", "proj_tiled", "proj_i8", "proj_i8_planes", "ssub_virtual", "temporal_early", "fit_side", "ring_side",
                                   "solve_probe", "r1_probe", "deconv_trace", "trace_long", "host_trace", "debug", nullptr};
     if (!strcmp(name, "lanes")) { RET(lanes_set(ctx, value)); ctx->opts[name] = value; return 0; }
     for (int i = 0; known[i]; ++i) if (!strcmp(known[i], name)) { ctx->opts[name] = value; if (!strcmp(name, "host_trace")) ctx->trace_level = (int)value; return 0; }
@@ -709,6 +718,7 @@ int cnmfe_patch_create(cnmfe_ctx *ctx, int patch_id, const int32_t pr[4], const 
         return fail(CNMFE_EINVAL, "patch [%d %d %d %d] must lie inside block [%d %d %d %d] inside the %dx%d FOV",
                     pr[0], pr[1], pr[2], pr[3], br[0], br[1], br[2], br[3], d1, d2);
     CK(hipSetDevice(ctx->device));
+    if (ctx->ring_side_join() != 0) return CNMFE_EHIP;       // (option ring_side: the side stream may still read the W of the patch that goes)
     if (ctx->patches.count(patch_id)) { delete ctx->patches[patch_id]; ctx->patches.erase(patch_id); }
     ctx->patches_changed();
     Patch *P = new Patch();
@@ -794,6 +804,7 @@ int cnmfe_ring_init(cnmfe_ctx *ctx, int patch_id, int32_t radius, int32_t num_ne
     if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
     if (radius < 1 || radius > 64) return fail(CNMFE_EINVAL, "ring radius %d out of range", radius);
     CK(hipSetDevice(ctx->device));
+    RET(ctx->ring_side_join());                              // (option ring_side: the side stream may still read the W and the offsets that go)
     // validate on locals first: a rejected call leaves the patch's ring (offsets, p, W) exactly as it was
     std::vector<int32_t> ndr, ndc;
     ring_offsets(radius, num_neighbors, ndr, ndc);
@@ -871,6 +882,7 @@ int cnmfe_ring_set_values(cnmfe_ctx *ctx, int patch_id, const float *val) {
     Patch *P = get_patch(ctx, patch_id);
     if (!P || !P->ring_ready) return fail(CNMFE_ESTATE, "ring of patch %d not initialised", patch_id);
     CK(hipSetDevice(ctx->device));
+    RET(ctx->ring_side_join());                              // (option ring_side: the side stream may still read the W this call overwrites)
     std::vector<float> W((size_t)P->p * P->d, 0.f);
     int64_t e = 0;
     for (int64_t m = 0; m < P->d; ++m) {
@@ -967,7 +979,9 @@ int cnmfe_fit_ring_model(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64_t 
     RET(ensure_ymean(ctx, P));
     int64_t dummy[4];
     int rc = bg_fit_ring(ctx, P, K, A_colptr, A_rowidx, A_val, C, c_order, with_projection, b0_out, info ? info : dummy, 0, thresh_outlier);
+    const bool marked = rc == 0 && P->residual.solve_marked;  // (option ring_side: the fit's own mark outlives this invalidation, which is of the fit's making too)
     P->residual.invalidate();
+    P->residual.solve_marked = marked;
     return rc;
 }
 

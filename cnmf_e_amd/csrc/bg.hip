@@ -867,28 +867,7 @@ static void fit_lists(RingFit &f) {
 // fit_side = 1: fork, projection on the compute stream, enter .. leave -- the set-up runs under the projection.  2: fork, enter .. leave, THEN the projection: the same
 // streams and code with nothing concurrent (tests; a wrong stream shows in both, a hazard of the overlap in 1 only).  0: one stream, the order of before.
 // Between fork and leave the compute stream is given the projection's launches and nothing else: no upload, no event of the arena.
-struct SideScope {
-    cnmfe_ctx *ctx; bool inside = false;
-    explicit SideScope(cnmfe_ctx *c) : ctx(c) {}
-    int fork() {
-        int *dErr = nullptr;
-        RET(ctx_errflag(ctx, &dErr));                            // (allocated and cleared on the compute stream, before anything can raise it from the other one)
-        RET(ctx_side_stream(ctx));
-        CK(hipEventRecord(ctx->ev_side_fork, ctx->st()));
-        CK(hipStreamWaitEvent(ctx->side_stream, ctx->ev_side_fork, 0));
-        return 0;
-    }
-    int enter() { (void)ctx->st(); std::swap(ctx->stream_, ctx->side_stream); inside = true; return 0; }
-    int leave() {
-        if (!inside) return 0;
-        const hipError_t e = hipEventRecord(ctx->ev_side_join, ctx->st());
-        std::swap(ctx->stream_, ctx->side_stream); inside = false;
-        CK(e);
-        CK(hipStreamWaitEvent(ctx->stream_, ctx->ev_side_join, 0));
-        return 0;
-    }
-    ~SideScope() { if (inside) (void)leave(); }                  // (an error inside the scope: the streams go back, and the compute stream still waits for what was queued)
-};
+// (the scope itself: common.hpp, SideScope -- fork / enter / leave here; its second way to start, behind a recorded event, serves option ring_side in resid.hip)
 // which way this fit goes (0: no side scope).  lanes > 1: every lane is a stream of its own already, and the patches' fits overlap each other
 static int fit_side_mode(const RingFit &f) {
     const int64_t m = f.ctx->opt("fit_side", 1);
@@ -1274,6 +1253,7 @@ int bg_fit_ring(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, co
     RingFit f(ctx, P);
     f.K = K; f.A_colptr = A_colptr; f.A_rowidx = A_rowidx; f.A_val = A_val; f.C = C; f.c_order = c_order; f.b0_only = b0_only; f.thresh_outlier = thresh_outlier; f.T = P->T;
     f.outl = thresh_outlier == thresh_outlier; f.has_a = K > 0 && A_colptr[K] > 0; f.a_empty = K == 0;
+    RET(ctx->ring_side_join());                              // (option ring_side: the last fit's side work reads the W this fit will write)
     if (f.outl && !P->sn_ready && !(b0_only & 1)) return fail(CNMFE_ESTATE, "fit_ring_model with thresh_outlier needs the noise levels of the block (cnmfe_set_noise)");
     RET(fit_traces_up(f));
     f.ht.mark("traces");
@@ -1303,7 +1283,24 @@ int bg_fit_ring(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, co
     if (f.incr) RET(fit_corrections(f, C, c_order));
     f.ht.mark("base / correction launches");
     RET(fit_solve(f));
-    RET(ring_stats_enqueue(ctx, P));                         // what the NEXT fit of this patch asks of the W being written now
+    // option ring_side: W is final behind this point -- what the NEXT fit asks of it (ring_stats_enqueue) and the W*A tables of the residual request that follows
+    // this fit wait for THIS event on the side stream, not for what the compute stream is given after it (resid.hip, ring_side_ahead).  Not the outlier branch, not
+    // with lanes, one patch per context
+    bool solve_marked = false;
+    { const int64_t m = ctx->opt("ring_side", 1);
+      if ((m == 1 || m == 2) && !f.outl && ctx->lanes.empty() && ctx->patches.size() == 1) {
+          int *dErrAhead = nullptr;
+          RET(ctx_errflag(ctx, &dErrAhead));                  // (allocated and cleared in front of the event: the side stream's k_ring_wa may raise it)
+          RET(ctx_side_stream(ctx));
+          CK(hipEventRecord(ctx->ev_ring_solved, ctx->st()));
+          solve_marked = true;
+          // (the tables only where a request can be a recorded one at all: residual_plan.hpp -- r1_delta = 0 or r1_lazy = 0 sweep or fold at once, and such a
+          //  request builds its own)
+          const rplan::ResidualOpts ro = residual_opts(ctx);
+          const bool tables = f.has_a && !P->derived && ro.delta != 0 && ro.lazy != 0;
+          RET(ring_side_ahead(ctx, P, f.K, tables ? &f.csr : nullptr, A_colptr, A_rowidx, A_val, m == 2));
+      } }
+    if (!solve_marked) RET(ring_stats_enqueue(ctx, P));                         // what the NEXT fit of this patch asks of the W being written now
     f.ht.mark("solve launch");
     if (b0_out) {
         std::vector<double> tmp(P->d);
@@ -1315,6 +1312,7 @@ int bg_fit_ring(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, co
     // without b0_out the call returns with the fit in flight (every later engine call is stream-ordered behind it)
     if (info) { info[0] = f.first_run ? 1 : 0; info[1] = f.kstride; info[2] = f.nactive; info[3] = f.pmax; }
     P->residual.invalidate();
+    P->residual.solve_marked = solve_marked;
     return 0;
 }
 

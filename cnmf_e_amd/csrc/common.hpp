@@ -178,10 +178,12 @@ struct ResidualState {
     int source = rplan::SRC_NONE;      // who wrote it: 1 = cnmfe_residual, 2 = cnmfe_residual_ssub (compute_RSS / reconstruct_background serve 1 only)
     int64_t gen = 0;                   // counts the requests of this patch: what a projection queued ahead of its consumer is valid for
     bool has_pending = false;
+    bool solve_marked = false;         // option ring_side: W of this patch is final behind cnmfe_ctx::ev_ring_solved (the event a ring fit records right behind its
+                                       // solve) and nothing has invalidated since -- whatever changes W, b0 or the video goes through invalidate()
     FootTerm applied, pending;
     bool valid() const { return form != rplan::NONE; }
     bool is_virtual() const { return form == rplan::VIRTUAL; }
-    void invalidate() { form = rplan::NONE; source = rplan::SRC_NONE; has_pending = false; applied.ac = false; }      // frees nothing; gen keeps counting
+    void invalidate() { form = rplan::NONE; source = rplan::SRC_NONE; has_pending = false; solve_marked = false; applied.ac = false; }      // frees nothing; gen keeps counting
     rplan::TermsView terms() const { return {has_pending, applied.view(), pending.view()}; }
 };
 
@@ -405,6 +407,29 @@ struct cnmfe_ctx : cnmfe::LaneState {
     // option fit_side (bg.hip, SideScope): the second stream a steady-state ring fit queues its set-up on, beside the window projection; created at its first use at
     // the compute stream's priority, with the event the side stream waits for (fork) and the one the compute stream waits for (join)
     hipStream_t side_stream = nullptr; hipEvent_t ev_side_fork = nullptr, ev_side_join = nullptr;
+    // option ring_side (SideScope::fork_behind below; resid.hip, ring_side_ahead): ev_ring_solved is recorded right behind a ring fit's solve, and the fit
+    // queues the statistics of the new W and the W*A tables of the residual request that follows it on the side stream behind THAT event, beside whatever the compute
+    // stream is given next; ev_ring_join marks their end, and ring_side_join() makes the compute stream wait for it (ring_join_pending: not yet) -- in the next
+    // residual request, the next fit, the calls that write W, cnmfe_synchronize.  rsd: [0] the CSR rows of A, [1..3] the tables (they change hands with the
+    // patch's pending term as tmp[8..10] do); rs_pin: the pinned staging of [0], the scope's own (the shared arena's half-switch events assume one stream at a time)
+    hipEvent_t ev_ring_solved = nullptr, ev_ring_join = nullptr; bool ring_join_pending = false, ring_join_used = false;
+    cnmfe::DevBuf rsd[4]; void *rs_pin = nullptr; size_t rs_pin_cap = 0;
+    // the tables in rsd[1..3]: of which patch and which A (the fit's CSC arrays, compared with the request's before anything of the request is built)
+    struct RingAhead {
+        bool valid = false; const cnmfe::Patch *P = nullptr; int32_t K = 0; std::vector<int64_t> colptr; std::vector<int32_t> rowidx; std::vector<float> val;
+        void keep(const cnmfe::Patch *P_, int32_t K_, const int64_t *cp, const int32_t *ri, const float *va) {
+            P = P_; K = K_; colptr.assign(cp, cp + K_ + 1); rowidx.assign(ri, ri + cp[K_]); val.assign(va, va + cp[K_]); valid = true;
+        }
+        bool is(const cnmfe::Patch *P_, int32_t K_, const int64_t *cp, const int32_t *ri, const float *va) const {
+            return valid && P == P_ && K == K_ && memcmp(colptr.data(), cp, (size_t)(K_ + 1) * sizeof(int64_t)) == 0
+                   && memcmp(rowidx.data(), ri, rowidx.size() * sizeof(int32_t)) == 0 && memcmp(val.data(), va, val.size() * sizeof(float)) == 0;
+        }
+    } rs_ahead;
+    int ring_side_join() {
+        if (!ring_join_pending) return 0;
+        ring_join_pending = false;
+        return hipStreamWaitEvent(st(), ev_ring_join, 0) == hipSuccess ? 0 : cnmfe::fail(CNMFE_EHIP, "ring_side: the compute stream could not wait for the side stream");
+    }
     hipEvent_t ev_bound_ready = nullptr, ev_copy_done = nullptr; bool copy_pending = false;
     // every batch of downloads on the copy stream gets a generation number and an event of its own: a host buffer waits for ITS batch (cnmfe_copy_wait),
     // not for whatever was queued on the copy stream since (cnmfe_stitch_wait) -- releasing last iteration's traces must not wait for this iteration's
@@ -632,7 +657,38 @@ int ring_stats_enqueue(cnmfe_ctx *ctx, Patch *P);                    // after W 
 int ring_stats_get(cnmfe_ctx *ctx, Patch *P, int *pmax, bool *first); // waits for that event only (falls back to a fresh evaluation)
 int center_traces(cnmfe_ctx *ctx, const float *C, int64_t ldc, int32_t K, int64_t T, DevBuf &Cc, DevBuf &Cmean);
 int upload_centered(cnmfe_ctx *ctx, DevBuf &stage, const float *C, int32_t K, int64_t T, int order, DevBuf &Cc, DevBuf &Cmean, int64_t *ldc_out);
+int ring_side_ahead(cnmfe_ctx *ctx, Patch *P, int32_t K, const HostCSR *csr, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, bool join_now);   // resid.hip: behind a ring fit's solve, on the side stream (option ring_side)
 int ctx_side_stream(cnmfe_ctx *ctx);                    // api.hip: the side stream of option fit_side and its two events (created on first use)
 int ctx_errflag(cnmfe_ctx *ctx, int **dflag);            // the device error word (allocated and cleared on first use)
 int ctx_check_errflag(cnmfe_ctx *ctx);                   // after a stream sync: CNMFE_ESTATE if a kernel raised it (and clears it)
+// The context's side stream standing in for the compute stream (options fit_side, bg.hip, and ring_side, resid.hip): between enter() and leave() launches, held-back
+// uploads and the profiler's events follow it through cnmfe_ctx::st().  Two ways to start: fork() -- the side stream waits for the compute stream as it stands NOW,
+// and leave() makes the compute stream wait for the scope at once; fork_behind() -- it waits for an event recorded EARLIER (ev_ring_solved: a ring fit's solve) and
+// leave() only records ev_ring_join: the compute stream waits later, in cnmfe_ctx::ring_side_join().
+struct SideScope {
+    cnmfe_ctx *ctx; bool inside = false, deferred = false;
+    explicit SideScope(cnmfe_ctx *c) : ctx(c) {}
+    int fork() {
+        int *dErr = nullptr;
+        RET(ctx_errflag(ctx, &dErr));                            // (allocated and cleared on the compute stream, before anything can raise it from the other one)
+        RET(ctx_side_stream(ctx));
+        CK(hipEventRecord(ctx->ev_side_fork, ctx->st()));
+        CK(hipStreamWaitEvent(ctx->side_stream, ctx->ev_side_fork, 0));
+        return 0;
+    }
+    // (the caller has the error word in place from before `ev` was recorded, and the side stream exists: the event is one of its set)
+    int fork_behind(hipEvent_t ev) { deferred = true; CK(hipStreamWaitEvent(ctx->side_stream, ev, 0)); return 0; }
+    int enter() { (void)ctx->st(); std::swap(ctx->stream_, ctx->side_stream); inside = true; return 0; }   // (st(): the compute stream's held-back uploads go out on it)
+    int leave() {
+        if (!inside) return 0;
+        const hipError_t e = hipEventRecord(deferred ? ctx->ev_ring_join : ctx->ev_side_join, ctx->st());     // (st(): the scope's own uploads are sent first)
+        std::swap(ctx->stream_, ctx->side_stream); inside = false;
+        CK(e);
+        if (deferred) { ctx->ring_join_pending = ctx->ring_join_used = true; return 0; }
+        CK(hipStreamWaitEvent(ctx->stream_, ctx->ev_side_join, 0));
+        return 0;
+    }
+    // (an error inside the scope: the streams go back, and the compute stream still waits for what was queued)
+    ~SideScope() { if (inside) { (void)leave(); if (deferred) (void)ctx->ring_side_join(); } }
+};
 }  // namespace cnmfe

@@ -3,6 +3,7 @@
 // the sanitizers without a GPU.  The buffers stay where they are (cnmfe::LaneState::scr, cnmfe_ctx::EarlyU); the records here say what they hold, and every rule
 // that reads a record has ONE copy here ("Lane state and kept results").
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 namespace cnmfe {
@@ -66,6 +67,15 @@ inline Serve early_serves(const KeptSpatial &k, const ServeRequest &q) {
     if (!k.patch || k.K != q.K || q.nnz == 0 || k.nnz != q.nnz || !k.flags || k.gen != q.spatial_gen
         || !q.patch_is_fov || !q.is_virtual || !q.src_full) return SERVE_DECLINED;
     return SERVE_YES;
+}
+
+// ---- option ring_side: the W A tables of a residual request on the side stream, behind the event of the last ring fit's solve (resid.hip, residual_run) ----------
+// solve_marked: ResidualState -- the patch's W is final behind that event and nothing has invalidated since (the outlier branch and bg_ssub's fits do not mark);
+// foreign / tables_only / want_out: the request of a low-resolution patch, or one whose Ysig is read at once; recorded: the plan only records the request or
+// pends its term (the virtual request of the steady state) -- a sweep reads the tables on the compute stream right away
+struct RingSideRequest { int64_t mode; bool one_lane; size_t npatches; bool solve_marked, has_ac, foreign, tables_only, want_out, recorded; };
+inline bool ring_side_applies(const RingSideRequest &q) {
+    return (q.mode == 1 || q.mode == 2) && q.one_lane && q.npatches == 1 && q.solve_marked && q.has_ac && !q.foreign && !q.tables_only && !q.want_out && q.recorded;
 }
 
 }  // namespace kept

@@ -1102,46 +1102,119 @@ int residual_realize(cnmfe_ctx *ctx, Patch *P) {
     return 0;
 }
 
+// Option ring_side.  What depends on W, A and the ring geometry alone is queued by the ring fit itself, on the context's side stream behind the event recorded right
+// behind its solve: the statistics of W the next fit asks for (ring_stats_enqueue: k_ring_pmax, the row-1 copy, its event) and the W*A tables of the residual request
+// that follows the fit -- its A_prev IS the fit's A (the CSR rows are compared on the host when the request comes; another A builds its own tables as before).  The
+// device runs them beside the spatial update's kernels instead of between the solve and the spatial update / between the spatial and the temporal update.
+// The scope is SideScope's second way to start (common.hpp, fork_behind): the side stream waits for the event behind the SOLVE, not for a fork "now", and leave()
+// only records the join event.  The compute stream waits for it in cnmfe_ctx::ring_side_join() -- the residual request that takes the tables, the next fit,
+// whatever writes W, cnmfe_synchronize -- in front of the first reader of the tables and the first writer of W; a request that takes nothing (the spatial
+// update's own, without footprints) does not wait.  Inside the scope nothing goes through the shared pinned arena (its half-switch events assume one stream at a
+// time): the CSR rows are staged in pinned memory of the scope's own, into a buffer of its own (rsd[0]), and the tables are written to rsd[1..3].
+
+// the W*A tables of (W, A): ELL rows per patch pixel in cnt | k | v
+static int ring_wa_launch(cnmfe_ctx *ctx, Patch *P, int32_t K, const int *arow, const int *acol, const float *aval, int nnzA, DevBuf &dWaCnt, DevBuf &dWaK, DevBuf &dWaV, int *dErrWa) {
+    const int wa_cap = std::max(WA_CAP, std::min((int)K, WA_CAP_MAX));        // a ring cannot touch more footprints than there are
+    const size_t wa_stage = (size_t)nnzA * 8;
+    if (wa_stage <= 96 * 1024) {                               // (32 KB static + this: one workgroup per CU above ~48 KB, still every CU of a small patch's grid)
+        if (wa_stage > 32 * 1024)                                // (per device: set where it is needed, not once per process)
+            CK(hipFuncSetAttribute((const void *)k_ring_wa<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        LAUNCH(ctx, "r1_ring_wa", k_ring_wa<true>, dim3((unsigned)((P->d + 127) / 128)), dim3(128), wa_stage, P->W.as<float>(), P->d, P->nr, P->nr_b, P->nc_b,
+               P->roff, P->coff, P->p, P->ring_dr.as<int>(), P->ring_dc.as<int>(), arow, acol, aval, nnzA,
+               dWaCnt.as<int>(), dWaK.as<int>(), dWaV.as<float>(), dErrWa, wa_cap);
+    } else
+        LAUNCH(ctx, "r1_ring_wa", k_ring_wa<false>, dim3((unsigned)((P->d + 127) / 128)), dim3(128), 0, P->W.as<float>(), P->d, P->nr, P->nr_b, P->nc_b,
+               P->roff, P->coff, P->p, P->ring_dr.as<int>(), P->ring_dc.as<int>(), arow, acol, aval, nnzA,
+               dWaCnt.as<int>(), dWaK.as<int>(), dWaV.as<float>(), dErrWa, wa_cap);
+    return 0;
+}
+static int wa_ensure(cnmfe_ctx *ctx, Patch *P, int32_t K, DevBuf &dWaCnt, DevBuf &dWaK, DevBuf &dWaV) {
+    const int wa_cap = std::max(WA_CAP, std::min((int)K, WA_CAP_MAX));
+    RET(dWaCnt.ensure_hw(P->d * sizeof(int), ctx->hw_wa[0]));
+    RET(dWaK.ensure_hw((size_t)wa_cap * P->d * sizeof(int), ctx->hw_wa[1]));
+    return dWaV.ensure_hw((size_t)wa_cap * P->d * sizeof(float), ctx->hw_wa[2]);
+}
+// behind a ring fit's solve (bg_fit_ring, the event is recorded): the statistics of the new W and, with footprints, the tables of (W, A) -- csr: the fit's CSR
+// rows of A; its CSC arrays are kept on the host for the comparison with the request's
+int ring_side_ahead(cnmfe_ctx *ctx, Patch *P, int32_t K, const HostCSR *csr, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, bool join_now) {
+    cnmfe_ctx::RingAhead &ah = ctx->rs_ahead;
+    ah.valid = false;
+    int *dErrWa = nullptr;
+    RET(ctx_errflag(ctx, &dErrWa));                              // (in place since before the event was recorded: bg_fit_ring)
+    const int *arow = nullptr, *acol = nullptr; const float *aval = nullptr;
+    size_t bytes = 0;
+    if (csr) {
+        // the CSR rows in ONE buffer: rowptr | col | val, each padded to 16 bytes
+        const size_t nrp = (csr->rowptr.size() + 3) & ~size_t(3), nz4 = (csr->col.size() + 3) & ~size_t(3);
+        bytes = (nrp + 2 * nz4) * sizeof(int);
+        if (ctx->ring_join_used) CK(hipEventSynchronize(ctx->ev_ring_join));   // (the last scope's copy has left the staging: an event of the iteration before)
+        if (ctx->rs_pin_cap < bytes) {
+            if (ctx->rs_pin) { (void)hipHostFree(ctx->rs_pin); ctx->rs_pin = nullptr; ctx->rs_pin_cap = 0; }
+            const size_t want = bytes + bytes / 2;
+            if (hipHostMalloc(&ctx->rs_pin, want, hipHostMallocDefault) != hipSuccess) { ctx->rs_pin = nullptr; return fail(CNMFE_ENOMEM, "ring_side: %zu bytes of pinned staging", want); }
+            ctx->rs_pin_cap = want;
+        }
+        int *h = static_cast<int *>(ctx->rs_pin);
+        memset(h + nrp - 4, 0, 4 * sizeof(int)); memset(h + nrp + nz4 - 4, 0, 4 * sizeof(int)); memset(h + nrp + 2 * nz4 - 4, 0, 4 * sizeof(int));   // (the padding)
+        memcpy(h, csr->rowptr.data(), csr->rowptr.size() * sizeof(int));
+        memcpy(h + nrp, csr->col.data(), csr->col.size() * sizeof(int));
+        memcpy(h + nrp + nz4, csr->val.data(), csr->val.size() * sizeof(float));
+        RET(ctx->rsd[0].ensure(bytes));
+        arow = ctx->rsd[0].as<int>(); acol = arow + nrp; aval = reinterpret_cast<const float *>(acol + nz4);
+        RET(wa_ensure(ctx, P, K, ctx->rsd[1], ctx->rsd[2], ctx->rsd[3]));
+    }
+    SideScope sc(ctx);
+    RET(sc.fork_behind(ctx->ev_ring_solved));
+    RET(sc.enter());
+    RET(ring_stats_enqueue(ctx, P));
+    if (csr) {
+        RET(pinned_to_dev(ctx, ctx->rsd[0].p, ctx->rs_pin, bytes));
+        RET(ring_wa_launch(ctx, P, K, arow, acol, aval, (int)csr->col.size(), ctx->rsd[1], ctx->rsd[2], ctx->rsd[3], dErrWa));
+    }
+    RET(sc.leave());
+    if (join_now) RET(ctx->ring_side_join());
+    if (csr) ah.keep(P, K, A_colptr, A_rowidx, A_val);
+    return 0;
+}
+
 int residual_run(cnmfe_ctx *ctx, Patch *P, int pid, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx,
                  const float *A_val, const float *C, int c_order, float *Ysig_out, int out_memspace, DevBuf *outbuf, int tables_only) {
     const int64_t T = P->T;
     ResidualState &rs = P->residual;
     ++rs.gen;
     DevBuf &ysig = outbuf ? *outbuf : P->ysig;               // bg_ssub > 1 sweeps the low-resolution patch into its own buffer: the patch's own state stays as it is
-    DevBuf &dC = ctx->tmp[0], &dCc = ctx->tmp[1], &dCm = ctx->tmp[2], &dArow = ctx->tmp[3], &dAcol = ctx->tmp[4], &dAval = ctx->tmp[5],
-           &dWaCnt = ctx->tmp[8], &dWaK = ctx->tmp[9], &dWaV = ctx->tmp[10];
+    DevBuf &dC = ctx->tmp[0], &dCc = ctx->tmp[1], &dCm = ctx->tmp[2], &dArow = ctx->tmp[3], &dAcol = ctx->tmp[4], &dAval = ctx->tmp[5];
     int64_t ldc = 4;
     bool has_ac = Ksel > 0 && A_colptr[Ksel] > 0;
-    if (has_ac) {
-        RET(upload_centered(ctx, dC, C, Ksel, T, c_order, dCc, dCm, &ldc));
-        HostCSR csr; csc_to_csr(P->d_b, Ksel, A_colptr, A_rowidx, A_val, csr);
-        RET(to_dev(ctx, dArow, csr.rowptr.data(), csr.rowptr.size()));
-        RET(to_dev(ctx, dAcol, csr.col.data(), csr.col.size()));
-        RET(to_dev(ctx, dAval, csr.val.data(), csr.val.size()));
-        RET(dWaCnt.ensure_hw(P->d * sizeof(int), ctx->hw_wa[0]));
-        const int wa_cap = std::max(WA_CAP, std::min((int)Ksel, WA_CAP_MAX));        // a ring cannot touch more footprints than there are
-        RET(dWaK.ensure_hw((size_t)wa_cap * P->d * sizeof(int), ctx->hw_wa[1]));
-        RET(dWaV.ensure_hw((size_t)wa_cap * P->d * sizeof(float), ctx->hw_wa[2]));
-        // a ring that touches more than WA_CAP_MAX footprints raises the context's error flag (ctx_check_errflag at the next wait of this call chain: the
-        // spatial / temporal update's own download) instead of costing a drain of the stream here -- with several patches per context that drain
-        // was what kept the host from setting up patch m + 1 under patch m's kernels
-        int *dErrWa = nullptr;
-        RET(ctx_errflag(ctx, &dErrWa));
-        const int nnzA = (int)csr.col.size();
-        const size_t wa_stage = (size_t)nnzA * 8;
-        if (wa_stage <= 96 * 1024) {                               // (32 KB static + this: one workgroup per CU above ~48 KB, still every CU of a small patch's grid)
-            if (wa_stage > 32 * 1024)                                // (per device: set where it is needed, not once per process)
-                CK(hipFuncSetAttribute((const void *)k_ring_wa<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-            LAUNCH(ctx, "r1_ring_wa", k_ring_wa<true>, dim3((unsigned)((P->d + 127) / 128)), dim3(128), wa_stage, P->W.as<float>(), P->d, P->nr, P->nr_b, P->nc_b,
-                   P->roff, P->coff, P->p, P->ring_dr.as<int>(), P->ring_dc.as<int>(), dArow.as<int>(), dAcol.as<int>(), dAval.as<float>(), nnzA,
-                   dWaCnt.as<int>(), dWaK.as<int>(), dWaV.as<float>(), dErrWa, wa_cap);
-        } else
-            LAUNCH(ctx, "r1_ring_wa", k_ring_wa<false>, dim3((unsigned)((P->d + 127) / 128)), dim3(128), 0, P->W.as<float>(), P->d, P->nr, P->nr_b, P->nc_b,
-                   P->roff, P->coff, P->p, P->ring_dr.as<int>(), P->ring_dc.as<int>(), dArow.as<int>(), dAcol.as<int>(), dAval.as<float>(), nnzA,
-                   dWaCnt.as<int>(), dWaK.as<int>(), dWaV.as<float>(), dErrWa, wa_cap);
-    }
     const rplan::Plan plan = rplan::residual_plan({rs.form, rs.source, P->ysig.p != nullptr},
                                                   {rplan::SRC_FULL, has_ac, Ysig_out != nullptr, outbuf != nullptr, tables_only != 0, (double)P->d_b * (double)T}, residual_opts(ctx));
+    // option ring_side: the tables of a request that is only recorded, the first one behind a ring fit, may have been built by that fit already (ring_side_ahead: on the
+    // side stream behind its solve) -- they are taken when this request's A is the fit's, row for row
+    const bool side = kept::ring_side_applies({ctx->opt("ring_side", 1), ctx->lanes.empty(), ctx->patches.size(), rs.solve_marked, has_ac, outbuf != nullptr, tables_only != 0,
+                                               Ysig_out != nullptr, plan.action == rplan::PendOnly || plan.action == rplan::Record});
+    DevBuf *wa[3] = {&ctx->tmp[8], &ctx->tmp[9], &ctx->tmp[10]};
+    if (has_ac) {
+        RET(upload_centered(ctx, dC, C, Ksel, T, c_order, dCc, dCm, &ldc));
+        cnmfe_ctx::RingAhead &ah = ctx->rs_ahead;
+        if (side && (int64_t)ah.rowidx.size() == A_colptr[Ksel] && ah.is(P, Ksel, A_colptr, A_rowidx, A_val)) {
+            RET(ctx->ring_side_join());                          // (from here on the compute stream reads the tables: the term's readers all come behind this call)
+            for (int i = 0; i < 3; ++i) wa[i] = &ctx->rsd[1 + i];        // (they change hands with the patch's term below, as tmp[8..10] do)
+            ah.valid = false;
+        } else {
+            HostCSR csr; csc_to_csr(P->d_b, Ksel, A_colptr, A_rowidx, A_val, csr);
+            RET(to_dev(ctx, dArow, csr.rowptr.data(), csr.rowptr.size()));
+            RET(to_dev(ctx, dAcol, csr.col.data(), csr.col.size()));
+            RET(to_dev(ctx, dAval, csr.val.data(), csr.val.size()));
+            RET(wa_ensure(ctx, P, Ksel, *wa[0], *wa[1], *wa[2]));
+            // a ring that touches more than WA_CAP_MAX footprints raises the context's error flag (ctx_check_errflag at the next wait of this call chain: the
+            // spatial / temporal update's own download) instead of costing a drain of the stream here -- with several patches per context that drain
+            // was what kept the host from setting up patch m + 1 under patch m's kernels
+            int *dErrWa = nullptr;
+            RET(ctx_errflag(ctx, &dErrWa));
+            RET(ring_wa_launch(ctx, P, Ksel, dArow.as<int>(), dAcol.as<int>(), dAval.as<float>(), (int)csr.col.size(), *wa[0], *wa[1], *wa[2], dErrWa));
+        }
+    }
+    DevBuf &dWaCnt = *wa[0], &dWaK = *wa[1], &dWaV = *wa[2];
     if (plan.tables) { ctx->last_ldc = ldc; return 0; }      // bg_ssub: the caller only wants (W*A) and the centred traces (tmp[8..10], tmp[1])
     // the term of this call moves beside Ysig (the scratch buffers above change hands with the patch's)
     auto pend = [&](int32_t Kt) { rs.has_pending = true; rs.pending.take(has_ac, ldc, Kt, dWaCnt, dWaK, dWaV, dCc, dCm); };

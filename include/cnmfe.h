@@ -636,6 +636,14 @@ int cnmfe_synchronize(cnmfe_ctx *ctx);
  *                     sum(A, 2), ind_active, b0, slot_of, the staged windows' metadata -- on a second stream of the context, forked in front of the projection and joined
  *                     in front of k_win_fix, so the GPU runs it underneath the projection.  2: the same streams, joined in front of the projection (nothing overlaps:
  *                     tests).  0: one stream.  Inert with lanes > 1.  Results are bit-equal (tests/test_gpu_fit_side.py)
+ *   ring_side         default 1: a ring fit records an event right behind its solve and queues, on the context's side stream behind THAT event, what depends on the
+ *                     new W alone -- the statistics the next fit asks for (ring_pmax and its downloads) and, when the fit has footprints, the W*A tables (the CSR
+ *                     rows of A, r1_ring_wa, the error word) of the residual request that follows the fit, in buffers of their own -- so the GPU runs them beside
+ *                     the spatial update's kernels.  The first cnmfe_residual request behind the fit that is only recorded (no output, no sweep) takes the tables
+ *                     when its A is the fit's, entry for entry, and makes the compute stream wait for them first; any other request builds its own as before.
+ *                     2: the same streams and code, the wait directly behind the fit's launches (nothing overlaps: tests).  0: one stream.  Inert with lanes > 1,
+ *                     with more than one patch in the context, in a fit with thresh_outlier and for cnmfe_residual_ssub.  Results are bit-equal
+ *                     (tests/test_gpu_trace_ahead.py)
  *   prealloc          default 1: cnmfe_fit_reserve may allocate the fit's large buffers ahead of the first fit
  * A deployment short of HBM sets win_i8 = proj_tiled = 0 (and solve_packed = 0) or leaves it to the engine, which falls back by itself.
  * Diagnostics (scripts/): solve_probe, r1_probe (phase probes: results are NOT the product's), deconv_trace, host_trace (1: host-side phase times of every call on
