@@ -150,6 +150,8 @@ PROTOTYPES = {
     "cnmfe_trace_diff_spikes": (C.c_int, [c_ctx, C.c_int32, C.c_int64, f32p, C.c_int, f32p, f32p]),
     "cnmfe_trace_tags": (C.c_int, [c_ctx, C.c_int32, f64p]),
     "cnmfe_merge_apply": (C.c_int, [c_ctx, C.c_int32, i32p, i32p, f64p, C.c_int32, i32p, C.POINTER(DeconvOpts), f32p, f32p, f32p, f32p, f32p]),
+    "cnmfe_trace_energy": (C.c_int, [c_ctx, C.c_int32, C.c_int64, f32p, C.c_int, f64p]),
+    "cnmfe_traces_grow": (C.c_int, [c_ctx, C.c_int32]),
     "cnmfe_df_begin": (C.c_int, [c_ctx, C.c_int32, C.c_int64]),
     "cnmfe_df_add_frames": (C.c_int, [c_ctx, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int32, i64p, i32p, f32p, i32p]),
     "cnmfe_df_add_background": (C.c_int, [c_ctx, C.c_int, f32p, f32p, C.c_int32, i64p, i32p, f32p, i32p]),

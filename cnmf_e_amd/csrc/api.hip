@@ -1871,6 +1871,24 @@ int cnmfe_trace_corr(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int s
     GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
     return trace_corr_run(ctx, K, T, X, src, raw, out);
 }
+int cnmfe_trace_energy(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, double *out) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    RET(merge_src_check(K, T, X, src));
+    if (K == 0) return 0;
+    if (!out) return fail(CNMFE_EINVAL, "null output");
+    CK(hipSetDevice(ctx->device));
+    GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
+    return trace_energy_run(ctx, K, T, X, src, out);
+}
+int cnmfe_traces_grow(cnmfe_ctx *ctx, int32_t K_new) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    if (!ctx->bound_valid || ctx->bound_K <= 0) return fail(CNMFE_ESTATE, "no bound trace matrix to grow (cnmfe_traces_bind / cnmfe_stitch_finish)");
+    if (K_new < ctx->bound_K) return fail(CNMFE_EINVAL, "cnmfe_traces_grow: %d rows asked for, the bound matrix has %d", K_new, ctx->bound_K);
+    if (K_new == ctx->bound_K) return 0;
+    CK(hipSetDevice(ctx->device));
+    GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
+    return traces_grow_run(ctx, K_new);
+}
 int cnmfe_trace_diff_spikes(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, float *sn_out, float *S_out) {
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
     RET(merge_src_check(K, T, X, src));

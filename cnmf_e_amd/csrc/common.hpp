@@ -634,6 +634,8 @@ int trace_corr_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src
 int trace_diff_spikes_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, float *sn_out, float *S_out);
 int trace_tags_run(cnmfe_ctx *ctx, int32_t K, double *out);
 int traces_load_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *C, const float *C_raw, const float *S, const float *pars, int c_order);
+int trace_energy_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, double *out);
+int traces_grow_run(cnmfe_ctx *ctx, int32_t K_new);
 int merge_apply_run(cnmfe_ctx *ctx, int32_t ng, const int32_t *gptr, const int32_t *gidx, const double *w, int32_t nkeep, const int32_t *keep,
                     const cnmfe_deconv_opts *opts, float *C_out, float *C_raw_out, float *S_out, float *pars_out, float *sn_out);
 int postproc_run(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx,

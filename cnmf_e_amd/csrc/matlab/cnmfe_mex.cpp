@@ -66,6 +66,9 @@
 //   [sn, S_] = cnmfe_mex('trace_diff_spikes', h, source...)                the S-less branch (:57-66); the result stays on the device as the source 'diff'
 //   q = cnmfe_mex('trace_tags', h, K)                                      K x 4: max(C), std(C_raw - C), GetSn(C_raw), spikes after frame 1
 //   [C, C_raw, S, pars, sn] = cnmfe_mex('merge_apply', h, grp_ptr, grp_idx, w, keep, T, smin, max_tau)   merged traces, their deconvolution, obj.delete: on the device
+// Batch mode (demo_batch_1p.m:120-142; the batch methods are cnmf_e_amd/batch.py's -- no .m twin is written):
+//   e = cnmfe_mex('trace_energy', h, source...)                            sum(X.^2, 2) as K x 1 double: a batch's weights in the footprint average (update_spatial_batch.m:29)
+//   cnmfe_mex('traces_grow', h, K_new)                                     C = [C; zeros(K_new - K, T)] on the bound matrix (and the residents that belong to it), on the device
 // dF/F (Sources2D.m:540-570, extract_DF_F_endoscope; the loop over the patches is the caller's, as in cnmf_e_amd/sources2d.py -- no .m twin is written):
 //   cnmfe_mex('df_begin', h, K, T)                                         the K x T fp64 accumulator of (A ./ sum(A.^2, 1))' * Ybg, zeroed
 //   cnmfe_mex('df_add_background', h, pid, b0_block, b0_new_patch, A_patch, ind)   all frames of one patch, after 'residual' (as 'reconstruct_background'); ind: 1-based rows
@@ -302,6 +305,29 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
         CHECK(cnmfe_trace_tags(c, (int32_t)K, q));
         pout[0] = mxCreateDoubleMatrix(K, 4, mxREAL);
         for (size_t k = 0; k < K; ++k) for (int j = 0; j < 4; ++j) mxGetPr(pout[0])[k + j * K] = q[4 * k + j];
+        return;
+    }
+    if (!strcmp(cmd, "trace_energy")) {
+        // e = cnmfe_mex('trace_energy', h, X)  |  cnmfe_mex('trace_energy', h, name, K, T): sum(X.^2, 2) as K x 1 double (update_spatial_batch.m:29)
+        if (nin != 3 && nin != 5) FAIL("trace_energy: the source is a matrix, or a name followed by K, T");
+        size_t K, T; const float *X = NULL; int src = CNMFE_COLMAJOR;
+        if (mxIsChar(pin[2])) {
+            char nm[16];
+            if (nin != 5 || mxGetString(pin[2], nm, sizeof(nm))) FAIL("trace_energy: a named source needs K, T");
+            src = !strcmp(nm, "bound") ? CNMFE_BOUND : !strcmp(nm, "craw") ? CNMFE_RES_CRAW : !strcmp(nm, "s") ? CNMFE_RES_S : !strcmp(nm, "diff") ? CNMFE_RES_DIFF : -1;
+            if (src < 0) FAIL("trace_energy: unknown source '%s' (bound, craw, s, diff)", nm);
+            K = (size_t)mxGetScalar(pin[3]); T = (size_t)mxGetScalar(pin[4]);
+        } else {
+            if (nin != 3) FAIL("trace_energy: too many inputs behind a matrix source");
+            K = mxGetM(pin[2]); T = mxGetN(pin[2]); X = f32_of(pin[2], NULL);
+        }
+        pout[0] = mxCreateDoubleMatrix(K, 1, mxREAL);
+        CHECK(cnmfe_trace_energy(c, (int32_t)K, (int64_t)T, X, src, mxGetPr(pout[0])));
+        return;
+    }
+    if (!strcmp(cmd, "traces_grow")) {                          // cnmfe_mex('traces_grow', h, K_new): zero rows under the bound matrix and its residents, on the device
+        if (nin != 3) FAIL("traces_grow: 3 inputs required (h, K_new)");
+        CHECK(cnmfe_traces_grow(c, (int32_t)mxGetScalar(pin[2])));
         return;
     }
     if (!strcmp(cmd, "merge_apply")) {

@@ -11,6 +11,7 @@
 //                                    (both: the trace in LDS beside the Welch transform up to 20416 frames; k_trace_diff_spikes_long / k_trace_tags_long beyond, up
 //                                    to WELCH_TMAX = 147456 -- the difference trace in its output row, C_raw's row read in place, no scratch but the tables' slots)
 //   k_merge_rows + k_merge_compact   ci = w' C_raw(IDs, :) in fp64, rounded once; the rows that stay, gathered into new matrices that are swapped in
+//   k_trace_energy (+ _fin)          sum(X.^2, 2) in fp64, one pass: the weights of batch mode's footprint average (update_spatial_batch.m:29)
 // Every reduction runs in a fixed order: equal inputs give equal bits (on every rank of a sharded run).
 #pragma once
 
@@ -210,6 +211,44 @@ __global__ void __launch_bounds__(256) k_merge_compact(MergeMats mm, int64_t ldc
     if (y == 0 && threadIdx.x == 0) { pars_new[j] = g >= 0 ? pars_m[g] : pars_old[keep[j]]; sn_new[j] = g >= 0 ? sn_m[g] : sn_old[keep[j]]; }
 }
 
+// out[k] = sum_t X(k, t)^2 in fp64 (update_spatial_batch.m:29: cc = sum(neuron_k.C.^2, 2)).  One pass over the padded pitch with float4 loads, as k_merge_compact
+// reads it: workgroup (s, k) takes segment s of row k, TE_SEG4 float4 chunks = 4 per thread.  A thread sums its squares in chunk order (an fp32 square is exact in
+// fp64), block_sum adds the threads -- the wave's butterfly, then the four waves through LDS -- and k_trace_energy_fin the segments of a row, lane-strided in
+// segment order and through the same butterfly.  No atomics, nothing depends on the launch's timing: equal inputs give equal bits.  Frames behind T
+// contribute exact zeros whatever the padding holds.
+constexpr int TE_SEG4 = 1024;
+__global__ void __launch_bounds__(256) k_trace_energy(const float4 *__restrict__ X, int64_t ldc4, int64_t T, int nseg, double *__restrict__ part) {
+    __shared__ double red[4];
+    const int k = blockIdx.y, sg = blockIdx.x;
+    const float4 *row = X + (int64_t)k * ldc4;
+    const int64_t c0 = (int64_t)sg * TE_SEG4 + threadIdx.x;
+    float4 v[4]; int nv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int64_t c = c0 + 256 * u;
+        v[u] = make_float4(0.f, 0.f, 0.f, 0.f); nv[u] = 0;
+        if (c < ldc4) { v[u] = row[c]; const int64_t left = T - 4 * c; nv[u] = left > 4 ? 4 : (int)left; }      // (ldc4 = ceil(T / 4): left >= 1)
+    }
+    double a = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const double x = (double)v[u].x, y = (double)v[u].y, z = (double)v[u].z, w = (double)v[u].w;
+        if (nv[u] > 0) a += x * x;
+        if (nv[u] > 1) a += y * y;
+        if (nv[u] > 2) a += z * z;
+        if (nv[u] > 3) a += w * w;
+    }
+    a = block_sum(a, red);
+    if (threadIdx.x == 0) part[(int64_t)k * nseg + sg] = a;
+}
+__global__ void __launch_bounds__(64) k_trace_energy_fin(const double *__restrict__ part, int nseg, double *__restrict__ out) {
+    const double *p = part + (int64_t)blockIdx.x * nseg;
+    double a = 0;
+    for (int s = threadIdx.x; s < nseg; s += 64) a += p[s];
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+    if (threadIdx.x == 0) out[blockIdx.x] = a;
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------
 
 // (welch_cfg / WelchPlan, the one Welch set-up of these kernels and of seed.hpp / peel.hpp, sits in deconv.hip beside sn_pixels_launch, whose tier rule it follows)
@@ -256,6 +295,58 @@ int trace_corr_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src
     CK(hipMemcpyAsync(out, dG.p, (size_t)K * K * 8, hipMemcpyDeviceToHost, ctx->st()));
     CK(hipStreamSynchronize(ctx->st()));
     return ctx_check_errflag(ctx);
+}
+
+// cnmfe_trace_energy: the source where it lies (a host matrix through mrg[0], counted as an upload), the partial sums in mrg[2], the K results in mrg[3]
+int trace_energy_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, double *out) {
+    const int64_t ldc = (T + 3) & ~int64_t(3), ldc4 = ldc >> 2;
+    const int64_t nseg = (ldc4 + TE_SEG4 - 1) / TE_SEG4;
+    if (nseg > 65535 || K > 65535) return fail(CNMFE_EINVAL, "cnmfe_trace_energy: %d x %lld is beyond one launch (65535 rows, %lld frames)", K, (long long)T, (long long)65535 * TE_SEG4 * 4);
+    const float *dX;
+    RET(merge_source(ctx, K, T, X, src, &dX));
+    DevBuf &dPart = ctx->mrg[2], &dOut = ctx->mrg[3];
+    RET(dPart.ensure((size_t)K * nseg * 8)); RET(dOut.ensure((size_t)K * 8));
+    LAUNCH(ctx, "trace_energy", k_trace_energy, dim3((unsigned)nseg, (unsigned)K), dim3(256), 0, reinterpret_cast<const float4 *>(dX), ldc4, T, (int)nseg, dPart.as<double>());
+    LAUNCH(ctx, "trace_energy_fin", k_trace_energy_fin, dim3((unsigned)K), dim3(64), 0, (const double *)dPart.as<double>(), (int)nseg, dOut.as<double>());
+    CK(hipMemcpyAsync(out, dOut.p, (size_t)K * 8, hipMemcpyDeviceToHost, ctx->st()));
+    CK(hipStreamSynchronize(ctx->st()));
+    return ctx_check_errflag(ctx);
+}
+
+// cnmfe_traces_grow: K_new - K zero rows under the bound matrix and, while they belong to it, under the residents; zero entries behind kernel_pars and sn.  Every
+// matrix is rebuilt in a buffer of cnmfe_merge_apply (mrg[12..16]) -- the zero rows by a memset, the old rows by one device-to-device copy -- and swapped in, as
+// that call swaps its compacted matrices in: the old allocation stays alive for a download that still reads it.  Nothing crosses PCIe.
+int traces_grow_run(cnmfe_ctx *ctx, int32_t K_new) {
+    const int32_t K = ctx->bound_K; const int64_t T = ctx->bound_T, ldc = (T + 3) & ~int64_t(3);
+    const bool res = residents_valid(ctx);
+    if (ctx->copy_pending) { CK(hipStreamWaitEvent(ctx->st(), ctx->ev_copy_done, 0)); ctx->copy_pending = false; }   // the last downloads still read bound / dcv_*
+    const size_t ob = (size_t)K * ldc * 4, nb = (size_t)K_new * ldc * 4;
+    DevBuf *mats[3] = {&ctx->bound, &ctx->dcv_c, &ctx->dcv_s}, *vecs[2] = {&ctx->dcv_pars, &ctx->dcv_sn};
+    const int nm = res ? 3 : 1, nv = res ? 2 : 0;
+    // every check and every allocation first: a failure leaves the context as it was
+    for (int i = 0; i < nm; ++i)
+        if (mats[i]->cap < ob) return fail(CNMFE_ESTATE, "cnmfe_traces_grow: matrix %d of the context holds fewer than %d x %lld floats", i, K, (long long)ldc);
+    for (int i = 0; i < nv; ++i)
+        if (vecs[i]->cap < (size_t)K * 4) return fail(CNMFE_ESTATE, "cnmfe_traces_grow: vector %d of the context holds fewer than %d floats", i, K);
+    for (int i = 0; i < nm; ++i) RET(ctx->mrg[12 + i].ensure(nb));
+    for (int i = 0; i < nv; ++i) RET(ctx->mrg[15 + i].ensure((size_t)K_new * 4));
+    // the copies are queued into the side buffers, which nobody reads; only when all of them are queued do the buffers change places
+    for (int i = 0; i < nm; ++i) {
+        DevBuf &n = ctx->mrg[12 + i];
+        CK(hipMemcpyAsync(n.p, mats[i]->p, ob, hipMemcpyDeviceToDevice, ctx->st()));
+        CK(hipMemsetAsync((char *)n.p + ob, 0, nb - ob, ctx->st()));
+    }
+    for (int i = 0; i < nv; ++i) {
+        DevBuf &n = ctx->mrg[15 + i];
+        CK(hipMemcpyAsync(n.p, vecs[i]->p, (size_t)K * 4, hipMemcpyDeviceToDevice, ctx->st()));
+        CK(hipMemsetAsync((char *)n.p + (size_t)K * 4, 0, (size_t)(K_new - K) * 4, ctx->st()));
+    }
+    for (int i = 0; i < nm; ++i) mats[i]->swap(ctx->mrg[12 + i]);
+    for (int i = 0; i < nv; ++i) vecs[i]->swap(ctx->mrg[15 + i]);
+    ++ctx->bound_gen;                                        // (tables derived from the bound matrix' rows were sized for K of them)
+    if (res) ctx->residents_gen = ctx->bound_gen;
+    ctx->bound_K = K_new;
+    return 0;
 }
 
 int trace_diff_spikes_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, float *sn_out, float *S_out) {

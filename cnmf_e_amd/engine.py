@@ -185,9 +185,48 @@ class LazyHostTraces:
         return getattr(self.host(), name)
 
 
-for _op in ("add", "sub", "mul", "truediv", "radd", "rsub", "rmul", "rtruediv", "lt", "le", "gt", "ge", "eq", "ne", "neg", "abs", "matmul", "rmatmul"):
-    setattr(LazyHostTraces, "__%s__" % _op, (lambda op: lambda self, *a: getattr(self.host(), "__%s__" % op)(*a))(_op))
-LazyHostTraces.__hash__ = object.__hash__
+class GrownTraces:
+    """[X; zeros(n, T)] of a trace matrix X that Engine.traces_grow grew ON THE DEVICE: the host object that stands for the grown matrix (its identity is the
+    bound matrix' or a resident's from then on).  No value moves when it is made; X -- an array, or a LazyHostTraces whose rows may not even have arrived -- stays valid and
+    is read, below n zero rows, the first time somebody reads the values."""
+    def __init__(self, old, K_new):
+        self._old = old
+        self.shape = (int(K_new), int(old.shape[1])); self.dtype = np.dtype(np.float32); self.ndim = 2
+        self.flags = {"C_CONTIGUOUS": True}
+        self._arr = None
+    def host(self):
+        if self._arr is None:
+            a = np.zeros(self.shape, dtype=np.float32)
+            a[:self._old.shape[0]] = np.asarray(self._old)
+            self._arr, self._old = a, None
+        return self._arr
+    def __array__(self, dtype=None, copy=None):
+        a = self.host()
+        if dtype is not None and np.dtype(dtype) != a.dtype:
+            if copy is False:
+                raise ValueError("a float32 trace matrix cannot be viewed as %s without a copy" % np.dtype(dtype))
+            return a.astype(dtype)
+        return a.copy() if copy else a
+    def __getitem__(self, key):
+        return self.host()[key]
+    def __len__(self):
+        return self.shape[0]
+    def mean(self, *a, **k):
+        return self.host().mean(*a, **k)
+    def copy(self):
+        return self.host().copy()
+    def astype(self, *a, **k):
+        return self.host().astype(*a, **k)
+    def __getattr__(self, name):                      # everything else an ndarray has: the host copy's (as LazyHostTraces)
+        if name.startswith("_"):
+            raise AttributeError(name)
+        return getattr(self.host(), name)
+
+
+for _cls in (LazyHostTraces, GrownTraces):
+    for _op in ("add", "sub", "mul", "truediv", "radd", "rsub", "rmul", "rtruediv", "lt", "le", "gt", "ge", "eq", "ne", "neg", "abs", "matmul", "rmatmul"):
+        setattr(_cls, "__%s__" % _op, (lambda op: lambda self, *a: getattr(self.host(), "__%s__" % op)(*a))(_op))
+    _cls.__hash__ = object.__hash__
 
 
 class SpatialResult:
@@ -289,6 +328,7 @@ class Engine:
     supports_fit_reserve = True       # fit_reserve()
     supports_synchronize = True       # synchronize()
     supports_init_temporal = True     # init_temporal() / init_temporal_job()
+    supports_traces_grow = True       # traces_grow(): zero rows under the bound matrix and its residents, on the device
 
     # pinned buffers of LazyHostTraces, recycled by size (page-locking 20 MB costs milliseconds)
     def _pinned_take(self, nbytes):
@@ -926,6 +966,34 @@ class Engine:
         out = np.empty((K, K), dtype=np.float64)
         L.check(L.lib.cnmfe_trace_corr(self._ctx, K, T, ptr, src, int(bool(raw)), _p(out, L.f64p)))
         return out
+
+    def trace_energy(self, X):
+        """sum(X.^2, 2) of a K x T trace matrix as K float64 (update_spatial_batch.m:29) -- no upload when X is the bound matrix, a resident, or "diff" """
+        ptr, src, K, T, _keep = self._tsrc(X)
+        out = np.zeros(K, dtype=np.float64)
+        L.check(L.lib.cnmfe_trace_energy(self._ctx, K, T, ptr, src, _p(out, L.f64p)))
+        return out
+
+    def traces_grow(self, K_new):
+        """[C; zeros(K_new - K, T)] of the bound matrix and, while they belong to it, of the residents C_raw / S (kernel_pars, sn: zeros appended), on the device
+        (cnmfe_traces_grow).  Returns (C, C_raw, S): the host objects that stand for the grown matrices from here on -- GrownTraces over the old ones, whose values stay
+        valid; C_raw / S are None when the context holds no residents (or no S) for the bound matrix.  K_new == K returns the objects as they are."""
+        old = getattr(self, "_bound", None)
+        r = getattr(self, "_res", None)
+        live = r is not None and old is not None and r[0] is old
+        L.check(L.lib.cnmfe_traces_grow(self._ctx, int(K_new)))            # (refuses when nothing is bound, or K_new < K)
+        if old is None:                                                     # (bound through the C ABI behind this wrapper's back: no host object to stand for)
+            return None, None, None
+        if int(K_new) == old.shape[0]:
+            return old, (r[1] if live else None), (r[2] if live else None)
+        new = GrownTraces(old, K_new)
+        self._bound = new
+        if not live:
+            return new, None, None
+        raw = new if r[1] is old else GrownTraces(r[1], K_new)
+        s_ = None if r[2] is None else GrownTraces(r[2], K_new)
+        self._res = (new, raw, s_)
+        return new, raw, s_
 
     def trace_diff_spikes(self, X, want=False):
         """merge_high_corr.m:57-66 without S: the thresholded difference traces stay on the device as the source "diff"; want=True also returns (sn, S_)"""

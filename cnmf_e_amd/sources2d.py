@@ -1309,6 +1309,66 @@ class Sources2D:
         self._bind_C()
         self._update_b0_new()
 
+    # -- batch mode (cnmf_e_amd/batch.py): what a parent object does to one of its batches between two update calls --
+    def _set_A(self, A):
+        """neuron_k.A = obj.A (initComponents_batch.m:53,97, update_spatial_batch.m:41): the footprints are replaced as a spatial update replaces them (_spatial_finish),
+        the traces stay where they are -- nothing is bound or uploaded.  Everything cut from the old A is keyed by that matrix' identity (_cur_blocks_src, _ind_future,
+        _bbox_cache) and lapses with it; the queued projection of a spatial result (_early_u) is dropped, b0_new is due again once C has A's K, and the next
+        search masks may be prefetched.  A_prev, C_prev, W and b0 stay, as for set_components."""
+        A = sp.csc_matrix(A, dtype=np.float32)
+        if A.shape[0] != self.video.d1 * self.video.d2:
+            raise ValueError("A must have d1*d2 rows")
+        if not A.has_sorted_indices:
+            A = A.copy(); A.sort_indices()
+        self.A = A
+        self._early_u = None
+        if A.shape[1] == self.C.shape[0]:
+            self._update_b0_new()
+        self._prefetch_wanted = True
+
+    def _grow_K(self, K_new):
+        """neuron_k.C = [neuron_k.C; zeros(K - tmp_K, T)] (initComponents_batch.m:103-106, update_temporal_batch.m:24-27), after obj.A got its K_new columns: C, C_raw,
+        S grow by zero rows, P.kernel_pars / P.neuron_sn by zeros.  When C is the engine's bound matrix and the engine offers it (supports_traces_grow) the rows are
+        appended on the device (Engine.traces_grow: no K x T matrix moves, the resident C_raw / S follow); otherwise padded on the host and set_components."""
+        K, T = self.C.shape
+        K_new = int(K_new)
+        if K_new < K:
+            raise ValueError("_grow_K: %d rows asked for, C has %d" % (K_new, K))
+        if K_new == K:
+            return
+        if self.A.shape[1] != K_new:
+            raise ValueError("_grow_K: obj.A has %d columns, C is to grow to %d rows" % (self.A.shape[1], K_new))
+
+        def pad(X):
+            return np.concatenate([np.asarray(X, dtype=np.float32), np.zeros((K_new - K, T), dtype=np.float32)])
+        raw_is_c = self.C_raw is self.C or self.C_raw is None
+        S = getattr(self, "S", None)
+        has_S = S is not None and tuple(np.shape(S)) == (K, T)
+        if self._can("traces_grow") and self.C is getattr(self.engine, "_bound", None):
+            live = self.engine.residents_are(self.C, self.C_raw, S if has_S else None)
+            Cn, Rn, Sn = self.engine.traces_grow(K_new)
+            C_raw = Cn if raw_is_c else (Rn if live else pad(self.C_raw))
+            if has_S:
+                self.S = Sn if live else pad(S)
+            self.C, self.C_raw = Cn, C_raw
+            self._update_b0_new()
+        else:
+            if has_S:
+                self.S = pad(S)
+            self.set_components(self.A, pad(self.C), None if raw_is_c else pad(self.C_raw))
+        for name in ("kernel_pars", "neuron_sn"):
+            val = self.P.get(name)
+            if val is not None and len(val) == K:
+                val = np.asarray(val).ravel()
+                self.P[name] = np.concatenate([val, np.zeros(K_new - K, dtype=val.dtype)])
+
+    def _trace_energy(self):
+        """sum(obj.C.^2, 2) in float64 (update_spatial_batch.m:29), taken where C lies (Engine.trace_energy): no transfer while C is the engine's bound matrix (or a
+        resident), which is how every update method leaves it; any other C goes up once as a host matrix, counted by merge_trace_uploads AND trace_matrix_uploads"""
+        if self.C.shape[0] == 0:
+            return np.zeros(0, dtype=np.float64)
+        return self.engine.trace_energy(self.C)
+
     def delete(self, ind):
         """obj.delete(ind)  (@Sources2D/Sources2D.m:762-811): columns of A, rows of C / C_raw / S and of P.kernel_pars go; A_prev, C_prev stay"""
         K = self.A.shape[1]

@@ -383,6 +383,16 @@ int cnmfe_trace_tags(cnmfe_ctx *ctx, int32_t K, double *out /* 4 K */);
  * CNMFE_ESTATE without residents, CNMFE_EINVAL on an index out of range, a repeated kept row, an empty group or a group whose first member is not kept. */
 int cnmfe_merge_apply(cnmfe_ctx *ctx, int32_t ngroups, const int32_t *grp_ptr, const int32_t *grp_idx, const double *w, int32_t nkeep, const int32_t *keep,
                       const cnmfe_deconv_opts *opts, float *C_out, float *C_raw_out, float *S_out, float *kernel_pars_out, float *sn_out);
+/* Batch mode (demos/demo_batch_1p.m:120-142; cnmf_e_amd/batch.py): several recordings of one field of view, one context each, share the footprints.  Two calls keep a
+ * batch method from moving a K x T matrix that already lies in HBM.
+ * out[k] (K doubles) = sum_t X(k, t)^2, the weight of a batch in the footprint average (update_spatial_batch.m:29), of a trace SOURCE as above (CNMFE_RES_DIFF included).
+ * One pass, fp64 sums in a fixed order without atomics: the bits do not depend on the option lanes or on the call.  T >= 1 (no Welch estimate is taken); K = 0 is legal. */
+int cnmfe_trace_energy(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, double *out);
+/* obj.C = [obj.C; zeros(K_new - K, T)] (initComponents_batch.m:103-106, update_temporal_batch.m:24-27) on the BOUND matrix, on the device: K_new - K zero rows are
+ * appended; while the residents C_raw, S, kernel_pars, sn belong to it they grow the same way (zero rows / entries) and go on belonging to it.  The old rows keep their
+ * bits, the layout the matrix was bound in stays, nothing is uploaded (the counter trace_matrix_uploads does not move).  K_new == K does nothing.
+ * CNMFE_ESTATE without a bound matrix, CNMFE_EINVAL for K_new < K. */
+int cnmfe_traces_grow(cnmfe_ctx *ctx, int32_t K_new);
 
 /* ---- T5: the overlap-region stitch of the temporal update, on the device
  * @Sources2D/update_temporal_parallel.m:264-280:
