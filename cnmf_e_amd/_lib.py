@@ -46,6 +46,7 @@ i64p = C.POINTER(C.c_int64)
 f32p = C.POINTER(C.c_float)
 f64p = C.POINTER(C.c_double)
 u8p = C.POINTER(C.c_uint8)
+u16p = C.POINTER(C.c_uint16)
 
 class DeconvOpts(C.Structure):
     """struct cnmfe_deconv_opts (include/cnmfe.h)"""
@@ -160,6 +161,11 @@ PROTOTYPES = {
     "cnmfe_df_fetch": (C.c_int, [c_ctx, f64p]),
     "cnmfe_df_load": (C.c_int, [c_ctx, C.c_int32, C.c_int64, f64p]),
     "cnmfe_df_finish": (C.c_int, [c_ctx, f64p, C.c_double, C.c_int64, f32p, C.c_int, f32p, C.c_int, f32p, f32p, f64p, f64p]),
+    "cnmfe_trace_order_stats": (C.c_int, [c_ctx, C.c_int32, f64p]),
+    "cnmfe_demix_frames": (C.c_int, [c_ctx, C.c_int, f32p, f32p, C.c_int32, i64p, i32p, f32p, f32p, C.c_int, i32p, f32p, C.c_double, C.c_int64, C.c_int64, C.c_int64,
+                                     f32p, f32p, f32p, f32p, f32p, u16p, C.c_int]),
+    "cnmfe_demix_frames_ssub": (C.c_int, [c_ctx, C.c_int, f32p, C.c_int32, i64p, i32p, f32p, f32p, C.c_int, i32p, f32p, C.c_double, C.c_int64, C.c_int64, C.c_int64,
+                                          f32p, f32p, f32p, f32p, f32p, u16p, C.c_int]),
 }
 # exports younger than the oldest build CNMFE_LIB is used with (A/B runs against the parent commit's library)
 OPTIONAL = {"cnmfe_get_option", "cnmfe_temporal_early_project", "cnmfe_temporal_early_claim"}

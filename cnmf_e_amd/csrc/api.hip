@@ -1906,6 +1906,15 @@ int cnmfe_trace_tags(cnmfe_ctx *ctx, int32_t K, double *out) {
     GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
     return trace_tags_run(ctx, K, out);
 }
+int cnmfe_trace_order_stats(cnmfe_ctx *ctx, int32_t K, double *out) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    if (K < 0) return fail(CNMFE_EINVAL, "bad K");
+    if (K == 0) return 0;
+    if (!out) return fail(CNMFE_EINVAL, "null output");
+    CK(hipSetDevice(ctx->device));
+    GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
+    return trace_order_stats_run(ctx, K, out);
+}
 int cnmfe_merge_apply(cnmfe_ctx *ctx, int32_t ngroups, const int32_t *grp_ptr, const int32_t *grp_idx, const double *w, int32_t nkeep, const int32_t *keep,
                       const cnmfe_deconv_opts *opts, float *C_out, float *C_raw_out, float *S_out, float *kernel_pars_out, float *sn_out) {
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
@@ -2027,6 +2036,99 @@ int cnmfe_df_finish(cnmfe_ctx *ctx, const double *inv_norm, double df_prctile, i
     CK(hipSetDevice(ctx->device));
     GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
     return df_finish_run(ctx, inv_norm, df_prctile, df_window, C, c_src, C_raw, raw_src, C_df_out, C_raw_df_out, Df_out, Yf_out);
+}
+
+// ---- the demixed panels (demix.hpp) ----
+// Everything k_demix_panels indexes with is checked here: the frames in [0, T), A's rows in [0, d) (check_csc), the trace rows in [0, K of the source).
+static int demix_patch(cnmfe_ctx *ctx, int patch_id, const float *b0_block /* nullptr: bg_ssub > 1 */, const float *b0_new, int32_t Ksel, const int64_t *cp, const int32_t *ri,
+                       const float *va, const float *CC, int c_src, const int32_t *ind, const float *col, double mix_scale, int64_t frame0, int64_t stride, int64_t nframes,
+                       float *raw, float *bg, float *signal, float *denoised, float *residual, uint16_t *mixed, int out_memspace) {
+    Patch *P = get_patch(ctx, patch_id);                     // (the patch's lane from here on)
+    if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
+    if (stride < 1 || nframes < 0 || nframes > 65535 || frame0 < 0) return fail(CNMFE_EINVAL, "stride %lld < 1, frame0 %lld < 0, or nframes %lld outside 0 .. 65535", (long long)stride, (long long)frame0, (long long)nframes);
+    if (nframes > 0 && (frame0 >= P->T || (nframes > 1 && stride > (P->T - 1 - frame0) / (nframes - 1))))      // (no product that could overflow)
+        return fail(CNMFE_EINVAL, "displayed frames %lld + j * %lld, j < %lld, reach beyond the %lld frames of the patch", (long long)frame0, (long long)stride, (long long)nframes, (long long)P->T);
+    if (out_memspace != CNMFE_HOST && out_memspace != CNMFE_DEVICE) return fail(CNMFE_EINVAL, "bad out_memspace");
+    if (!b0_new) return fail(CNMFE_EINVAL, "null b0_new");
+    if (b0_block) RET(require_residual_full(P, patch_id, "cnmfe_demix_frames"));
+    else if (ctx->bgs_patch != patch_id) return fail(CNMFE_ESTATE, "cnmfe_background_ssub has not been run for patch %d", patch_id);
+    if (Ksel < 0) return fail(CNMFE_EINVAL, "Ksel=%d", Ksel);
+    const bool host_src = c_src == CNMFE_COLMAJOR || c_src == CNMFE_ROWMAJOR;
+    std::vector<int32_t> rows((size_t)std::max(Ksel, 1), 0);
+    int32_t Ksrc = Ksel;
+    if (Ksel > 0) {
+        RET(check_csc("A", Ksel, P->d, cp, ri));
+        if ((!va && cp[Ksel] > 0) || !col) return fail(CNMFE_EINVAL, "null A_val / col");
+        if (host_src) {
+            if (!CC) return fail(CNMFE_EINVAL, "null trace matrix");
+            for (int32_t k = 0; k < Ksel; ++k) rows[k] = k;
+        } else if (c_src == CNMFE_BOUND || c_src == CNMFE_RES_CRAW) {
+            if (!ind) return fail(CNMFE_EINVAL, "null ind: a resident trace source needs the rows of the call's neurons");
+            Ksrc = ctx->bound_K;
+            for (int32_t k = 0; k < Ksel; ++k) {
+                if (ind[k] < 0 || ind[k] >= Ksrc) return fail(CNMFE_EINVAL, "ind[%d] = %d outside the %d rows of the bound matrix", k, ind[k], Ksrc);
+                rows[k] = ind[k];
+            }
+        } else return fail(CNMFE_EINVAL, "the traces come from the host, the bound matrix or the resident C_raw (source %d)", c_src);
+    }
+    if (nframes == 0) return 0;
+    CK(hipSetDevice(ctx->device));
+    RET(ensure_ymean(ctx, P));
+    const float *dCC = nullptr;
+    if (Ksel > 0) {
+        RET(trace_source_dev(ctx, Ksrc, P->T, CC, c_src, &dCC));
+        RET(demix_stage(ctx, P, Ksel, cp, ri, va, rows.data(), col));
+    }
+    const int64_t ldc = (P->T + 3) & ~int64_t(3);
+    // the panels on the device: the caller's own, or a staging buffer that goes to the host at the end
+    const size_t np = (size_t)nframes * P->d;
+    float *hostf[5] = {raw, bg, signal, denoised, residual};
+    float *devf[5] = {raw, bg, signal, denoised, residual};
+    unsigned short *devm = mixed;
+    if (out_memspace != CNMFE_DEVICE) {
+        RET(ctx->dmx[5].ensure(np * 26 + 64));
+        char *base = (char *)ctx->dmx[5].p;
+        for (int i = 0; i < 5; ++i) devf[i] = hostf[i] ? reinterpret_cast<float *>(base + (size_t)i * np * 4) : nullptr;
+        devm = mixed ? reinterpret_cast<unsigned short *>(base + 5 * np * 4) : nullptr;
+    }
+    const DemixOut out{devf[0], devf[1], devf[2], devf[3], devf[4], devm};
+    if (b0_block) {
+        RET(demix_kappa(ctx, P, b0_block, b0_new));
+        RET(demix_launch(ctx, P, Ksel, dCC, ldc, mix_scale, frame0, stride, nframes, 0, nframes, nullptr, 0, out));
+    } else {
+        // bg_ssub > 1: the contiguous frames a run of displayed frames spans are reconstructed into the lane's chunk scratch (dff.hpp: at most 256 MB), then read
+        int64_t nch;
+        RET(df_chunk_frames(P->d, P->T, &nch));
+        float *chunk = df_chunk_buf(ctx, P->d, nch);
+        if (!chunk) return CNMFE_ENOMEM;
+        for (int64_t j0 = 0; j0 < nframes;) {
+            const int64_t nj = std::min<int64_t>(nframes - j0, (nch - 1) / stride + 1), t0 = frame0 + j0 * stride, span = (nj - 1) * stride + 1;
+            RET(cnmfe_reconstruct_background_ssub(ctx, patch_id, b0_new, t0, span, chunk, CNMFE_DEVICE));
+            RET(demix_launch(ctx, P, Ksel, dCC, ldc, mix_scale, frame0, stride, nframes, j0, nj, chunk, t0, out));
+            j0 += nj;
+        }
+    }
+    if (out_memspace != CNMFE_DEVICE) {
+        for (int i = 0; i < 5; ++i) if (hostf[i]) CK(hipMemcpyAsync(hostf[i], devf[i], np * 4, hipMemcpyDeviceToHost, ctx->st()));
+        if (mixed) CK(hipMemcpyAsync(mixed, devm, np * 6, hipMemcpyDeviceToHost, ctx->st()));
+    }
+    CK(hipStreamSynchronize(ctx->st()));                     // (the caller's buffers are written, the shared upload buffer of a host trace source is free again)
+    return ctx_check_errflag(ctx);
+}
+int cnmfe_demix_frames(cnmfe_ctx *ctx, int patch_id, const float *b0_block, const float *b0_new, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx,
+                       const float *A_val, const float *CC, int c_src, const int32_t *ind, const float *col, double mix_scale, int64_t frame0, int64_t stride,
+                       int64_t nframes, float *raw_out, float *bg_out, float *signal_out, float *denoised_out, float *residual_out, uint16_t *mixed_out, int out_memspace) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    if (!b0_block) return fail(CNMFE_EINVAL, "null b0_block");
+    return demix_patch(ctx, patch_id, b0_block, b0_new, Ksel, A_colptr, A_rowidx, A_val, CC, c_src, ind, col, mix_scale, frame0, stride, nframes, raw_out, bg_out, signal_out,
+                       denoised_out, residual_out, mixed_out, out_memspace);
+}
+int cnmfe_demix_frames_ssub(cnmfe_ctx *ctx, int patch_id, const float *b0_new, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
+                            const float *CC, int c_src, const int32_t *ind, const float *col, double mix_scale, int64_t frame0, int64_t stride, int64_t nframes,
+                            float *raw_out, float *bg_out, float *signal_out, float *denoised_out, float *residual_out, uint16_t *mixed_out, int out_memspace) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    return demix_patch(ctx, patch_id, nullptr, b0_new, Ksel, A_colptr, A_rowidx, A_val, CC, c_src, ind, col, mix_scale, frame0, stride, nframes, raw_out, bg_out, signal_out,
+                       denoised_out, residual_out, mixed_out, out_memspace);
 }
 
 int cnmfe_post_process_spatial(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr,

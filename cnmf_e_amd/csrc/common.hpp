@@ -379,6 +379,7 @@ struct LaneState {
     DevBuf wcodes, solve_fill;   // ring solve: the block-pair codes per window origin (k_win_codes); the fill values {0, 1} in global memory (ring_solve.hpp)
     DevBuf stage;             // upload staging
     DevBuf dfl[5];            // dff.hpp: [0] the frame chunk of the reconstructed background (<= 256 MB), [1..4] the call's A (colptr, rowidx, val) and accumulator rows
+    DevBuf dmx[6];            // demix.hpp: [0..2] the call's A as CSR over the patch pixels, [3] its trace rows, [4] its colours, [5] the six panels on their way to the host
     // per-call device scratch of the factor updates (factor.hip, deconv.hip): grown on demand, NEVER freed between calls -- a hipMalloc /
     // hipFree pair per buffer and call cost more than the small kernels they serve, and hipFree drains the device
     DevBuf scr[24];
@@ -629,7 +630,15 @@ int df_load_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const double *Yf);
 int df_source_check(cnmfe_ctx *ctx, int32_t K, int64_t T, int src);
 int df_finish_run(cnmfe_ctx *ctx, const double *inv_norm, double p, int64_t w, const float *C, int c_src, const float *C_raw, int raw_src, float *C_df_out,
                   float *C_raw_df_out, double *Df_out, double *Yf_out);
+// demix.hpp (resid.hip): the panels of show_demixed_video, device pointers to nframes x d each (mixed: three such planes), any may be null
+struct DemixOut { float *raw, *bg, *signal, *denoised, *residual; unsigned short *mixed; };
+int demix_stage(cnmfe_ctx *ctx, Patch *P, int32_t Ksel, const int64_t *cp, const int32_t *ri, const float *va, const int32_t *trow, const float *col);
+int demix_kappa(cnmfe_ctx *ctx, Patch *P, const float *b0_block, const float *b0_new);
+int demix_launch(cnmfe_ctx *ctx, Patch *P, int32_t Ksel, const float *dCC, int64_t ldc, double mix_scale, int64_t frame0, int64_t stride, int64_t nframes, int64_t j0,
+                 int64_t nj, const float *slab, int64_t slab0, const DemixOut &out);
 // merge.hpp (deconv.hip)
+int trace_source_dev(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, const float **dX);   // the K x ceil4(T) device matrix a trace SOURCE names (a host matrix: one counted upload)
+int trace_order_stats_run(cnmfe_ctx *ctx, int32_t K, double *out);
 int trace_corr_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, int raw, double *out);
 int trace_diff_spikes_run(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, float *sn_out, float *S_out);
 int trace_tags_run(cnmfe_ctx *ctx, int32_t K, double *out);

@@ -76,6 +76,10 @@
 //   cnmfe_mex('df_add_frames', h, Ybg, frame0, A, ind)                     a d x nframes slab of a background the caller holds
 //   Yf = cnmfe_mex('df_fetch', h);  cnmfe_mex('df_load', h, Yf)            the accumulator to / from the host (a sharded run's all-reduce goes in between)
 //   [C_df, C_raw_df, Df, Yf] = cnmfe_mex('df_finish', h, inv_norm, df_prctile, df_window, C, C_raw)   C, C_raw: K x T matrices or 'bound' / 'craw'; df_window 0 / []: none
+// Closing calls (Sources2D.m:573-653 orderROIs, show_demixed_video.m; the methods are cnmf_e_amd/sources2d.py's -- no .m twin is written):
+//   q = cnmfe_mex('trace_order_stats', h, K)                               K x 7: mean(C), var(C), var(C_raw - C), max(C), ||C_raw||_2, ||C_raw||_1, max(C_raw)
+//   [raw, bg, signal, denoised, residual, mixed] = cnmfe_mex('demix_frames', h, pid, b0_block, b0_new_patch, A_patch, CC, ind, col, mix_scale, frame0, stride, nframes)
+//   [...] = cnmfe_mex('demix_frames_ssub', h, pid, b0_new_patch, A_patch, CC, ind, col, mix_scale, frame0, stride, nframes)     the panels of the displayed frames of one patch
 #include "mex.h"
 #include "matrix.h"
 #include <string.h>
@@ -305,6 +309,15 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
         CHECK(cnmfe_trace_tags(c, (int32_t)K, q));
         pout[0] = mxCreateDoubleMatrix(K, 4, mxREAL);
         for (size_t k = 0; k < K; ++k) for (int j = 0; j < 4; ++j) mxGetPr(pout[0])[k + j * K] = q[4 * k + j];
+        return;
+    }
+    if (!strcmp(cmd, "trace_order_stats")) {                    // q = cnmfe_mex('trace_order_stats', h, K): K x 7 double = [mean(C), var(C), var(C_raw - C), max(C), norm(C_raw, 2), norm(C_raw, 1), max(C_raw)] per row
+        if (nin != 3) FAIL("trace_order_stats: 3 inputs required (h, K)");
+        const size_t K = (size_t)mxGetScalar(pin[2]);
+        double *q = (double *)mxCalloc(7 * K + 1, sizeof(double));
+        CHECK(cnmfe_trace_order_stats(c, (int32_t)K, q));
+        pout[0] = mxCreateDoubleMatrix(K, 7, mxREAL);
+        for (size_t k = 0; k < K; ++k) for (int j = 0; j < 7; ++j) mxGetPr(pout[0])[k + j * K] = q[7 * k + j];
         return;
     }
     if (!strcmp(cmd, "trace_energy")) {
@@ -670,6 +683,45 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
         int32_t *ind = ind_of(pin[5], &n);
         if (n != (size_t)A.K) FAIL("df_add_background_ssub: one accumulator row per column of A");
         CHECK(cnmfe_df_add_background_ssub(c, pid, f32_of(pin[3], NULL), A.K, A.cp, A.ri, A.v, ind));
+    } else if (!strcmp(cmd, "demix_frames") || !strcmp(cmd, "demix_frames_ssub")) {
+        // [raw, bg, signal, denoised, residual, mixed] = cnmfe_mex('demix_frames', h, pid, b0_block, b0_new_patch, A_patch, CC, ind, col, mix_scale, frame0, stride, nframes)
+        // ('demix_frames_ssub': without b0_block, after 'background_ssub').  CC: a Ksel x T matrix (uploaded; ind = []) or 'bound' / 'craw' with ind = the 1-based rows
+        // of A_patch's columns in the bound matrix; col: Ksel x 3; frame0 0-based.  The panels are d x nframes single, mixed d x (3 nframes) single holding the uint16 values
+        const int full = !strcmp(cmd, "demix_frames"), a0 = full ? 4 : 3;
+        if (nin != a0 + 9) FAIL("%s: %d inputs required (h, pid, %sb0_new, A_patch, CC, ind, col, mix_scale, frame0, stride, nframes)", cmd, a0 + 9, full ? "b0_block, " : "");
+        size_t nd = 0, ni = 0, ncol = 0;
+        float *bb = full ? f32_of(pin[3], NULL) : NULL, *bn = f32_of(pin[a0], &nd);
+        Csc A = csc_of(pin[a0 + 1]);
+        const float *CC = NULL; int src = CNMFE_COLMAJOR; int32_t *ind = NULL;
+        if (mxIsChar(pin[a0 + 2])) {
+            char nm[16];
+            if (mxGetString(pin[a0 + 2], nm, sizeof(nm))) FAIL("%s: bad source name", cmd);
+            src = !strcmp(nm, "bound") ? CNMFE_BOUND : !strcmp(nm, "craw") ? CNMFE_RES_CRAW : -1;
+            if (src < 0) FAIL("%s: unknown source '%s' (bound, craw)", cmd, nm);
+            ind = ind_of(pin[a0 + 3], &ni);
+            if (ni != (size_t)A.K) FAIL("%s: one row of the bound matrix per column of A", cmd);
+        } else if (A.K) {
+            if (mxGetM(pin[a0 + 2]) != (size_t)A.K) FAIL("%s: CC has %d rows for %d footprints", cmd, (int)mxGetM(pin[a0 + 2]), (int)A.K);
+            CC = f32_of(pin[a0 + 2], NULL);
+        }
+        float *col = f32_of(pin[a0 + 4], &ncol);
+        if (ncol != 3 * (size_t)A.K) FAIL("%s: col must be %d x 3", cmd, (int)A.K);
+        float *colr = (float *)mxMalloc((ncol + 1) * sizeof(float));       // column-major Ksel x 3 -> row-major
+        for (size_t k = 0; k < (size_t)A.K; ++k) for (int m = 0; m < 3; ++m) colr[3 * k + m] = col[k + (size_t)m * A.K];
+        const double scale = mxGetScalar(pin[a0 + 5]);
+        const int64_t f0 = (int64_t)mxGetScalar(pin[a0 + 6]), st = (int64_t)mxGetScalar(pin[a0 + 7]), nf = (int64_t)mxGetScalar(pin[a0 + 8]);
+        if (nf < 0 || nf > 65535) FAIL("%s: nframes outside 0 .. 65535", cmd);
+        const int no = nout > 0 ? (nout > 6 ? 6 : nout) : 1;
+        float *o[5] = {NULL, NULL, NULL, NULL, NULL};
+        for (int j = 0; j < 5 && j < no; ++j) { pout[j] = mxCreateNumericMatrix(nd, (size_t)nf, mxSINGLE_CLASS, mxREAL); o[j] = (float *)mxGetData(pout[j]); }
+        uint16_t *mix = no > 5 ? (uint16_t *)mxCalloc(3 * nd * (size_t)nf + 1, sizeof(uint16_t)) : NULL;
+        if (full) CHECK(cnmfe_demix_frames(c, pid, bb, bn, A.K, A.cp, A.ri, A.v, CC, src, ind, colr, scale, f0, st, nf, o[0], o[1], o[2], o[3], o[4], mix, CNMFE_HOST));
+        else CHECK(cnmfe_demix_frames_ssub(c, pid, bn, A.K, A.cp, A.ri, A.v, CC, src, ind, colr, scale, f0, st, nf, o[0], o[1], o[2], o[3], o[4], mix, CNMFE_HOST));
+        if (no > 5) {
+            pout[5] = mxCreateNumericMatrix(nd, 3 * (size_t)nf, mxSINGLE_CLASS, mxREAL);
+            float *p = (float *)mxGetData(pout[5]);
+            for (size_t i = 0; i < 3 * nd * (size_t)nf; ++i) p[i] = (float)mix[i];
+        }
     } else if (!strcmp(cmd, "init_temporal")) {                // [C, C_raw, AA, S, pars, sn] = cnmfe_mex('init_temporal', h, pid, A_block, iters_plain, iters_last, smin, max_tau)   initTemporal.m:160-168
         if (nin != 6 && nin != 8) FAIL("init_temporal: 6 inputs required, 8 with deconvolution (h, pid, A_block, iters_plain, iters_last[, smin, max_tau])");
         int slot = 0;

@@ -249,6 +249,42 @@ __global__ void __launch_bounds__(64) k_trace_energy_fin(const double *__restric
     if (threadIdx.x == 0) out[blockIdx.x] = a;
 }
 
+// orderROIs' per-trace statistics (Sources2D.m:599-637) and the max(CC, [], 2) of show_demixed_video.m:37, one workgroup per trace, fp64: out[7 k ..] = mean(C),
+// var(C, 0), var(C_raw - C, 0), max(C), ||C_raw||_2, ||C_raw||_1, max(C_raw).  Two passes (the means first), thread-strided partial sums and block_sum's tree: a
+// fixed order.  T is a loop bound: nothing of the trace lives in LDS.
+__global__ void __launch_bounds__(256) k_trace_order_stats(const float *__restrict__ Cm, const float *__restrict__ Craw, int64_t ldc, int64_t T, double *__restrict__ out) {
+    __shared__ double red[4];
+    __shared__ float mred[8];
+    const int tid = threadIdx.x;
+    const float *c = Cm + (int64_t)blockIdx.x * ldc, *r = Craw + (int64_t)blockIdx.x * ldc;
+    float mc = -INFINITY, mr = -INFINITY;
+    double sc = 0, sd = 0, s2 = 0, s1 = 0;
+    for (int64_t t = tid; t < T; t += 256) {
+        const float cv = c[t], rv = r[t];
+        mc = fmaxf(mc, cv); mr = fmaxf(mr, rv);
+        sc += (double)cv; sd += (double)rv - (double)cv; s2 += (double)rv * (double)rv; s1 += fabs((double)rv);
+    }
+    for (int o = 32; o > 0; o >>= 1) { mc = fmaxf(mc, __shfl_xor(mc, o)); mr = fmaxf(mr, __shfl_xor(mr, o)); }
+    if ((tid & 63) == 0) { mred[tid >> 6] = mc; mred[4 + (tid >> 6)] = mr; }
+    const double mean_c = block_sum(sc, red) / (double)T;      // (its barriers publish mred)
+    const double mean_d = block_sum(sd, red) / (double)T;
+    s2 = block_sum(s2, red); s1 = block_sum(s1, red);
+    double qc = 0, qd = 0;
+    for (int64_t t = tid; t < T; t += 256) {
+        const double cv = (double)c[t], a = cv - mean_c, b = ((double)r[t] - cv) - mean_d;
+        qc += a * a; qd += b * b;
+    }
+    qc = block_sum(qc, red); qd = block_sum(qd, red);
+    if (tid == 0) {
+        double *o = out + 7 * (int64_t)blockIdx.x;
+        const double n1 = (double)(T > 1 ? T - 1 : 1);
+        o[0] = mean_c; o[1] = qc / n1; o[2] = qd / n1;
+        o[3] = (double)fmaxf(fmaxf(mred[0], mred[1]), fmaxf(mred[2], mred[3]));
+        o[4] = sqrt(s2); o[5] = s1;
+        o[6] = (double)fmaxf(fmaxf(mred[4], mred[5]), fmaxf(mred[6], mred[7]));
+    }
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------
 
 // (welch_cfg / WelchPlan, the one Welch set-up of these kernels and of seed.hpp / peel.hpp, sits in deconv.hip beside sn_pixels_launch, whose tier rule it follows)
@@ -393,6 +429,20 @@ int trace_tags_run(cnmfe_ctx *ctx, int32_t K, double *out) {
         LAUNCH(ctx, "trace_tags", k_trace_tags, dim3((unsigned)K), dim3(256), w.shmem, w.c, ctx->bound.as<float>(), ctx->dcv_c.as<float>(), dS, ldc, dOut.as<double>());
     }
     CK(hipMemcpyAsync(out, dOut.p, (size_t)K * 4 * 8, hipMemcpyDeviceToHost, ctx->st()));
+    CK(hipStreamSynchronize(ctx->st()));
+    return ctx_check_errflag(ctx);
+}
+
+int trace_source_dev(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, const float **dX) { return merge_source(ctx, K, T, X, src, dX); }
+
+int trace_order_stats_run(cnmfe_ctx *ctx, int32_t K, double *out) {
+    if (!residents_valid(ctx) || ctx->bound_K != K) return fail(CNMFE_ESTATE, "the context holds no C, C_raw of %d traces (cnmfe_deconv_temporal_bound, cnmfe_traces_load)", K);
+    const int64_t T = ctx->bound_T, ldc = (T + 3) & ~int64_t(3);
+    DevBuf &dOut = ctx->mrg[4];
+    RET(dOut.ensure((size_t)K * 7 * 8));
+    LAUNCH(ctx, "trace_order_stats", k_trace_order_stats, dim3((unsigned)K), dim3(256), 0, (const float *)ctx->bound.as<float>(), (const float *)ctx->dcv_c.as<float>(), ldc, T,
+           dOut.as<double>());
+    CK(hipMemcpyAsync(out, dOut.p, (size_t)K * 7 * 8, hipMemcpyDeviceToHost, ctx->st()));
     CK(hipStreamSynchronize(ctx->st()));
     return ctx_check_errflag(ctx);
 }

@@ -996,8 +996,8 @@ __global__ void __launch_bounds__(256) k_bg_out(const float4 *__restrict__ yc4, 
     out[(int64_t)blockIdx.y * d + m] = y - s + cst;
 }
 
-int bg_reconstruct_run(cnmfe_ctx *ctx, Patch *P, const float *b0_block, const float *b0_new, int64_t frame0, int64_t nframes, float *out, int out_memspace) {
-    RET(residual_materialize(ctx, P));
+// kappa of the materialised residual for (b0_block, b0_new), into tmp[12]: what k_bg_out and k_demix_panels (demix.hpp) subtract
+static int bg_kappa(cnmfe_ctx *ctx, Patch *P, const float *b0_block, const float *b0_new) {
     const int64_t d = P->d;
     const FootTerm &ap = P->residual.applied;
     DevBuf &dB0b = ctx->tmp[6], &dB0n = ctx->tmp[7], &dKap = ctx->tmp[12];
@@ -1006,6 +1006,14 @@ int bg_reconstruct_run(cnmfe_ctx *ctx, Patch *P, const float *b0_block, const fl
     LAUNCH(ctx, "rss_const", k_rss_const, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, d, P->nr, P->nr_b, P->nc_b, P->roff, P->coff, P->p, P->ring_dr.as<int>(),
            P->ring_dc.as<int>(), P->W.as<float>(), P->ymean_f.as<float>(), P->b0.as<double>(), dB0b.as<float>(), dB0n.as<float>(),
            ap.ac ? ap.cnt.as<int>() : nullptr, ap.k.as<int>(), ap.v.as<float>(), ap.cm.as<double>(), dKap.as<float>());
+    return 0;
+}
+
+int bg_reconstruct_run(cnmfe_ctx *ctx, Patch *P, const float *b0_block, const float *b0_new, int64_t frame0, int64_t nframes, float *out, int out_memspace) {
+    RET(residual_materialize(ctx, P));
+    const int64_t d = P->d;
+    DevBuf &dKap = ctx->tmp[12];
+    RET(bg_kappa(ctx, P, b0_block, b0_new));
     float *dst = out;
     if (out_memspace != CNMFE_DEVICE) { RET(ctx->stage.ensure((size_t)d * nframes * sizeof(float))); dst = ctx->stage.as<float>(); }
     LAUNCH(ctx, "bg_reconstruct", k_bg_out, dim3((unsigned)((d + 255) / 256), (unsigned)nframes), dim3(256), 0, P->Yc4.as<float4>(), P->d_b, P->nr, P->nr_b, P->roff, P->coff,
@@ -1013,6 +1021,10 @@ int bg_reconstruct_run(cnmfe_ctx *ctx, Patch *P, const float *b0_block, const fl
     if (out_memspace != CNMFE_DEVICE) CK(hipMemcpyAsync(out, dst, (size_t)d * nframes * sizeof(float), hipMemcpyDeviceToHost, ctx->st()));
     return ctx_check_errflag(ctx);
 }
+
+}  // namespace cnmfe
+#include "demix.hpp"      // (f) closing calls: the panels of show_demixed_video (its background is k_bg_out's expression on bg_kappa's constant)
+namespace cnmfe {
 
 // The ring sweep itself: Ysig = Yc(patch) + (Ymean - b0) - W Yc_block [+ (W A_prev)(C_prev - mean) when `has_ac`: the ELL rows of W A_prev in tmp[8..10], the
 // centred traces in tmp[1]] into `ysig`.  can_defer: the caller can leave the footprint term PENDING beside Ysig instead (then *deferred is set and the sweep

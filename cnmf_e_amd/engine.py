@@ -1117,6 +1117,62 @@ class Engine:
                                       _p(Yf, L.f64p)))
         return (C_df, R_df, Df, Yf) if want_Yf else (C_df, R_df, Df)
 
+    # ---- closing calls (cnmfe.h section (f)): orderROIs' statistics and the panels of show_demixed_video ----
+    def trace_order_stats(self):
+        """per trace of the context's C, C_raw: [mean(C), var(C), var(C_raw - C), max(C), ||C_raw||_2, ||C_raw||_1, max(C_raw)] as K x 7 float64
+        (cnmfe_trace_order_stats)"""
+        K = self._res[0].shape[0]
+        out = np.empty((K, 7), dtype=np.float64)
+        L.check(L.lib.cnmfe_trace_order_stats(self._ctx, K, _p(out, L.f64p)))
+        return out
+
+    def _demix_traces(self, CC, ind, Ksel, T):
+        """(pointer, source, rows, keep-alive) of the traces of a demix call: CC as the bound matrix / the resident C_raw with the rows `ind`, or CC[ind] from the host"""
+        ind = np.ascontiguousarray(ind, dtype=np.int32)
+        if Ksel == 0:
+            return None, L.ROWMAJOR, None, None
+        r = getattr(self, "_res", None)
+        live = r is not None and r[0] is getattr(self, "_bound", None)
+        if CC is getattr(self, "_bound", None):
+            return None, L.BOUND, ind, None
+        if live and CC is r[1]:
+            return None, L.RES_CRAW, ind, None
+        a = _traces(np.asarray(CC)[ind], Ksel, T)
+        return _p(a, L.f32p), L.ROWMAJOR, None, a
+
+    def demix_frames(self, pid, b0_block, b0_new_patch, A_patch, CC, ind, col, mix_scale, frame0, stride, nframes, want=None):
+        """the six panels of show_demixed_video for the displayed frames frame0 + j stride (0-based), j < nframes, of one patch (cnmfe_demix_frames; b0_block = None:
+        cnmfe_demix_frames_ssub, after background_ssub).  A_patch: d x Ksel over the patch rows, ind: its columns' rows in CC (K x T; the bound matrix and the resident
+        C_raw are read where they lie), col: Ksel x 3.  Returns a dict of (nframes, d) float32 arrays raw, bg, signal, denoised, residual and mixed (3, nframes, d)
+        uint16; want: the names to compute (default all)."""
+        info = self._patch[pid]
+        d, T = info["d"], info["T"]
+        Ksel, cp, ri, va = _csc(A_patch, d) if A_patch is not None and A_patch.shape[1] else (0, np.zeros(1, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float32))
+        ind = np.zeros(0, np.int32) if ind is None else np.asarray(ind)
+        if ind.size != Ksel:
+            raise ValueError("%d trace rows for %d columns of A" % (ind.size, Ksel))
+        col = np.ascontiguousarray(col, dtype=np.float32).reshape(-1, 3)
+        if col.shape[0] != Ksel:
+            raise ValueError("col is %s, expected (%d, 3)" % (col.shape, Ksel))
+        cptr, csrc, rows, _keep = self._demix_traces(CC, ind, Ksel, T)
+        bn = np.ascontiguousarray(b0_new_patch, dtype=np.float32).ravel()
+        bb = None if b0_block is None else np.ascontiguousarray(b0_block, dtype=np.float32).ravel()
+        if bn.size != d or (bb is not None and bb.size != info["d_b"]):
+            raise ValueError("b0_block / b0_new do not have the block's / the patch's size")
+        nframes = int(nframes)
+        names = ("raw", "bg", "signal", "denoised", "residual", "mixed") if want is None else tuple(want)
+        n = max(nframes, 0)
+        out = {k: np.zeros((n, d), dtype=np.float32) for k in names if k != "mixed"}
+        if "mixed" in names:
+            out["mixed"] = np.zeros((3, n, d), dtype=np.uint16)
+        ptr = lambda k: _p(out[k], L.f32p) if k in out and out[k].size else None       # (zero frames: NULL, nothing is written)
+        mix = out["mixed"].ctypes.data_as(L.u16p) if "mixed" in out and out["mixed"].size else None
+        head = (self._ctx, pid) + (() if bb is None else (_p(bb, L.f32p),))
+        fn = L.lib.cnmfe_demix_frames_ssub if bb is None else L.lib.cnmfe_demix_frames
+        L.check(fn(*head, _p(bn, L.f32p), Ksel, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p), cptr, csrc, _p(rows, L.i32p) if rows is not None else None,
+                   _p(col, L.f32p), float(mix_scale), int(frame0), int(stride), nframes, ptr("raw"), ptr("bg"), ptr("signal"), ptr("denoised"), ptr("residual"), mix, L.HOST))
+        return out
+
     def _mark_batch(self, *lazies):
         """the asynchronous call just made queued one batch of downloads: its generation number goes to the buffers it fills"""
         g = C.c_int64(0)

@@ -7,6 +7,8 @@ Both are off in every demo (CNMFSetParms.m: search_method 'ellipse', circular fa
 stay on the host next to determine_search_location's ellipse branch ("host-side prerequisite; tiny").  The Image
 Processing Toolbox calls are written with scipy.ndimage under the toolbox's documented border rules: medfilt2 pads with zeros, imdilate
 with -Inf, imerode with +Inf; bwlabel(., 4) / bwlabeln(., 8) are 4- / 8-connected; strel('disk', R, 0) is the exact disc x^2 + y^2 <= R^2.
+
+Further down: the host halves of the greedy initialisation, of the merges and of the closing calls (orderROIs' sort rule, show_demixed_video's ranges and montage).
 """
 from __future__ import annotations
 
@@ -454,3 +456,73 @@ def merge_iterate(G, M, niter=10):
         Mg = M @ g
         w = Mg / (g @ Mg)
     return g, w
+
+
+# --------------------------------------------------------------------------------------
+# The closing calls of demo_large_data_1p.m: orderROIs (Sources2D.m:573-653) and show_demixed_video (@Sources2D/show_demixed_video.m).  What is K x T or d x T runs
+# on the engine (merge.hpp: k_trace_order_stats, demix.hpp: k_demix_panels); the sort, the display ranges and the montage are the host's.
+# --------------------------------------------------------------------------------------
+def matlab_sort_order(x, descend=False):
+    """[~, srt] = sort(x) / sort(x, 'descend'), 0-based: MATLAB's sort is stable -- ties keep their order --, 'ascend' puts NaN last and 'descend' puts NaN first
+    (among themselves the NaNs keep their order too).  The one statement of that rule."""
+    x = np.asarray(x, dtype=np.float64).ravel()
+    nan = np.flatnonzero(np.isnan(x))
+    rest = np.flatnonzero(~np.isnan(x))
+    if descend:
+        return np.concatenate([nan, rest[np.argsort(-x[rest], kind="stable")]]).astype(np.int64)
+    return np.concatenate([rest[np.argsort(x[rest], kind="stable")], nan]).astype(np.int64)
+
+
+def matlab_uint16(x):
+    """uint16(x) of a double array: round half away from zero, saturate to [0, 65535], NaN -> 0"""
+    x = np.asarray(x, dtype=np.float64)
+    r = np.where(np.isnan(x), 0.0, np.sign(x) * np.floor(np.abs(x) + 0.5))
+    return np.clip(r, 0.0, 65535.0).astype(np.uint16)
+
+
+def prism64():
+    """prism(64): MATLAB's prism colormap repeats red, orange, yellow, green, blue, violet"""
+    six = np.array([[1.0, 0.0, 0.0], [1.0, 0.5, 0.0], [1.0, 1.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0], [2.0 / 3.0, 0.0, 1.0]])
+    return six[np.arange(64) % 6]
+
+
+def demix_ranges(amp_ac, raw_samples=None, range_ac=None, range_Y=None, multi_factor=None):
+    """the display ranges of show_demixed_video.m:39-57 as a dict (range_ac, range_res, range_Y, multi_factor).  raw_samples: the values the default range_Y is
+    taken from (quantiles 0.01 and 0.98; with a given multi_factor the 0.01 quantile alone) -- needed only when range_Y is None"""
+    amp_ac = float(amp_ac)
+    range_ac = amp_ac * np.array([0.01, 1.01]) if range_ac is None else np.asarray(range_ac, dtype=np.float64).ravel()      # :39-41
+    range_res = range_ac - range_ac.mean()                                                                                    # :42
+    given_mf = multi_factor is not None
+    if range_Y is None:                                                                                                       # :43-52
+        if raw_samples is None:
+            raise ValueError("demix_ranges: the default range_Y needs samples of the raw video")
+        if not given_mf:
+            temp = matlab_quantile(raw_samples, [0.01, 0.98])
+            multi_factor = float(np.ceil((temp[1] - temp[0]) / (range_ac[1] - range_ac[0])))
+        else:
+            temp = matlab_quantile(raw_samples, [0.01])
+        center_Y = temp[0] + multi_factor * amp_ac / 2
+        range_Y = center_Y + range_res * multi_factor
+    else:
+        range_Y = np.asarray(range_Y, dtype=np.float64).ravel()
+    if not given_mf and multi_factor is None:                                                                                 # :54-57 (a given range_Y)
+        multi_factor = float(np.round((range_Y[1] - range_Y[0]) / (range_ac[1] - range_ac[0])))
+        range_Y = (range_res - range_res[0]) * multi_factor + range_Y[0]
+    return dict(range_ac=range_ac, range_res=range_res, range_Y=np.asarray(range_Y, dtype=np.float64), multi_factor=float(multi_factor))
+
+
+def imagesc_8bit(v, lo, hi):
+    """imagesc(v, [lo hi]) through a 256-entry grey map: floor(256 (v - lo) / (hi - lo)) clipped to 0 .. 255 (NaN -> 0)"""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        q = np.floor(256.0 * (np.asarray(v, dtype=np.float64) - lo) / (hi - lo))
+    return np.clip(np.nan_to_num(q, nan=0.0, posinf=255.0, neginf=0.0), 0, 255).astype(np.uint8)
+
+
+def demixed_montage(frame, ranges):
+    """one displayed frame as a (2 d1) x (3 d2) x 3 uint8 image in the positions of show_demixed_video.m:83-88 -- top: raw, raw - background, residual; bottom:
+    background, denoised, demixed.  frame: dict of d1 x d2 panels (mixed: d1 x d2 x 3 uint16, shown as truecolor: its high byte); no titles, no time stamp"""
+    rY, rac, rres = ranges["range_Y"], ranges["range_ac"], ranges["range_res"]
+    grey = lambda v, r: np.repeat(imagesc_8bit(v, r[0], r[1])[:, :, None], 3, axis=2)
+    top = np.concatenate([grey(frame["raw"], rY), grey(frame["signal"], rac), grey(frame["residual"], rres)], axis=1)
+    bottom = np.concatenate([grey(frame["bg"], rY), grey(frame["denoised"], rac), (np.asarray(frame["mixed"], dtype=np.uint16) >> 8).astype(np.uint8)], axis=1)
+    return np.concatenate([top, bottom], axis=0)

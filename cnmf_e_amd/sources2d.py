@@ -2076,6 +2076,176 @@ class Sources2D:
             eng.df_close()                                           # (a refused call must not leave the accumulator open)
             raise
 
+    # -- closing calls: demo_large_data_1p.m:185,216 (orderROIs) and :229 (show_demixed_video) -------------------------------
+    _ORDER_UNBUILT = {"circularity": "nnmf with a random start", "temporal_cluster": "linkage / optimalleaforder", "spatial_cluster": "linkage / optimalleaforder"}
+
+    def _order_stats(self):
+        """K x 7 per-trace statistics of (C, C_raw) where they lie (Engine.trace_order_stats): nothing moves when they are the engine's residents"""
+        self._traces_SRC()
+        return self.engine.trace_order_stats()
+
+    def _order_criterion(self, srt):
+        """(values, descend) of a named order, Sources2D.m:583-639; strcmpi where the reference uses it, strcmp elsewhere, anything unrecognised is 'snr' (:636)"""
+        K = self.A.shape[1]
+        low = srt.lower()
+        for name, why in self._ORDER_UNBUILT.items():
+            if srt == name or (name != "circularity" and low == name):
+                raise NotImplementedError("orderROIs(%r) is not built (%s)" % (srt, why))
+        A = sp.csc_matrix(self.A).astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if low == "decay_time":                                                                       # :584-596
+                kp = self.P.get("kernel_pars")
+                if kp is None or len(kp) != K:
+                    raise ValueError("orderROIs('decay_time') needs P['kernel_pars'] of the %d neurons (a deconvolving temporal update)" % K)
+                return hostops.decay_times(kp), False
+            if srt == "sparsity_spatial":                                                                 # :604-606
+                return np.sqrt(np.asarray(A.power(2).sum(axis=0)).ravel()) / np.asarray(abs(A).sum(axis=0)).ravel(), False
+            q = self._order_stats()
+            if srt == "mean":                                                                             # :597-603
+                val = q[:, 0] * np.asarray(A.sum(axis=0)).ravel()
+                if not self.options.deconv_flag:
+                    sn = self.P.get("neuron_sn")
+                    if sn is None or len(sn) != K:
+                        raise ValueError("orderROIs('mean') without deconv_flag divides by P['neuron_sn'], which this object does not hold")
+                    val = val / np.asarray(sn, dtype=np.float64).ravel()
+                return val, True
+            if srt == "sparsity_temporal":                                                                # :607-609
+                return q[:, 4] / q[:, 5], True
+            if low == "pnr":                                                                              # :620-622
+                return q[:, 3] / np.sqrt(q[:, 2]), True
+            return q[:, 1] / q[:, 2], True                                                                # :636-638 ('snr' and everything else)
+
+    def orderROIs(self, srt="srt"):
+        """srt = orderROIs(obj, srt)  (@Sources2D/Sources2D.m:573-653): sort the neurons by 'snr' (var(C) / var(C_raw - C), descending; also any unrecognised string, as
+        the reference's else), 'pnr' (max(C) / std(C_raw - C), descending), 'decay_time' (ascending), 'mean' (mean(C) * sum(A), descending; without deconv_flag
+        divided by P.neuron_sn), 'sparsity_spatial' (ascending), 'sparsity_temporal' (descending), or by an explicit permutation (0-based).  Returns srt (0-based).
+        MATLAB's sort rule is hostops.matlab_sort_order's.  'circularity', 'temporal_cluster' and 'spatial_cluster' raise NotImplementedError.
+
+        The per-trace statistics come from one kernel over the engine's C and C_raw (cnmfe_trace_order_stats); the rows of C, C_raw, S, kernel_pars and sn are
+        gathered on the device (cnmfe_merge_apply without groups, keep = srt), A's columns, ids, tags, P.kernel_pars and P.neuron_sn on the host.  A_prev and C_prev
+        stay, as in the reference.  After a deconvolving update_temporal_parallel no K x T matrix is uploaded (counters merge_trace_uploads, trace_matrix_uploads)."""
+        K = self.A.shape[1]
+        if isinstance(srt, str):
+            if K == 0:
+                return np.zeros(0, dtype=np.int64)
+            val, descend = self._order_criterion(srt)
+            srt = hostops.matlab_sort_order(val, descend=descend)
+        else:
+            srt = np.asarray(srt)
+            if srt.ndim != 1 or srt.size != K or not np.issubdtype(srt.dtype, np.integer) or not np.array_equal(np.sort(srt), np.arange(K)):
+                raise ValueError("orderROIs: srt must be a permutation of 0 .. %d" % (K - 1))
+            srt = srt.astype(np.int64)
+        if K == 0:
+            return srt
+        self._traces_SRC()
+        Cn, Rn, Sn, kp, sn = self.engine.merge_apply([], [], srt)
+        self._set_after_merge(sp.csc_matrix(self.A, dtype=np.float32)[:, srt], srt, Cn, Rn, Sn, kp, sn)
+        return srt
+
+    def _demix_traces(self, use_craw):
+        K = self.A.shape[1]
+        return (self.C_raw if (self.C_raw is not None and self.C_raw.shape[0] == K) else self.C) if use_craw else self.C
+
+    def _default_amp_ac(self, use_craw):
+        """amp_ac = median(max(obj.A, [], 1)' .* max(CC, [], 2)) * 2  (show_demixed_video.m:37); max(CC, [], 2) from the engine's statistics: nothing is uploaded"""
+        K = self.A.shape[1]
+        if K == 0:
+            return float("nan")
+        q = self._order_stats()
+        amax = np.asarray(sp.csc_matrix(self.A).max(axis=0).todense(), dtype=np.float64).ravel()
+        return float(2.0 * np.median(amax * q[:, 6 if use_craw else 3]))
+
+    def demixed_frames(self, kt=1, frame_range=None, amp_ac=None, use_craw=False, colors=None, chunk=100):
+        """The six panels of show_demixed_video (@Sources2D/show_demixed_video.m:70-81,94-127) for the displayed frames frame_range(1) : kt : frame_range(2), as a
+        generator over chunks of at most `chunk` displayed frames (the reference reloads every 100 kt frames).  Each chunk is a dict: frames (1-based), raw, bg,
+        signal (raw - bg), denoised (A CC), residual (raw - bg - A CC) as d1 x d2 x n float32 and mixed as d1 x d2 x n x 3 uint16; entries outside the owned patches
+        are zero when sharded, as in reconstruct_background.  Every panel of a frame is computed on the device from one read of the resident video and residual plus
+        the pixel's row of A (cnmfe_demix_frames[_ssub]); nothing of d x T is assembled.
+        Defaults as the reference: all frames; amp_ac = 2 median(max(A) .* max(CC)); colors (K x 3) = rows of prism(64).  Deviation: the colours are drawn once
+        for the whole call by numpy.random.default_rng(0) -- the reference draws new ones with randi at every reload.
+        Per patch the residual of (A_prev, C_prev) is requested once, as the temporal update requests it -- right after update_temporal_parallel the patch still
+        holds it and nothing is asked for, so no trace matrix moves (bg_ssub > 1: cnmfe_background_ssub before every chunk -- the context keeps one patch's
+        low-resolution background, and C_prev goes up with it); do not run an update between two chunks."""
+        self._need_data()
+        v, eng = self.video, self.engine
+        K, T = self.C.shape
+        kt, chunk = int(kt), int(chunk)
+        if kt < 1 or chunk < 1:
+            raise ValueError("kt and chunk must be at least 1")
+        f0, f1 = (1, T) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
+        if not (1 <= f0 <= f1 <= T):
+            raise ValueError("frame_range = (%d, %d) outside 1 .. %d" % (f0, f1, T))
+        CC = self._demix_traces(use_craw)
+        A = self.A if sp.isspmatrix_csc(self.A) else sp.csc_matrix(self.A)
+        amp_ac = self._default_amp_ac(use_craw) if amp_ac is None else float(amp_ac)
+        if colors is None:
+            colors = hostops.prism64()[np.random.default_rng(0).integers(0, 64, size=K)]
+        colors = np.asarray(colors, dtype=np.float32).reshape(-1, 3)
+        if colors.shape[0] != K:
+            raise ValueError("colors must be %d x 3" % K)
+        mix_scale = 2.0 / amp_ac * 65536.0 if K else 0.0
+        b0_ = self.reconstruct_b0().reshape(-1, order="F")                                           # (a collective when sharded)
+        b0_new_ = np.asarray(self.b0_new, dtype=np.float64).reshape(-1, order="F")
+        frames = np.arange(f0, f1 + 1, kt)
+        cut = {idx: self._slice(A, idx, "patch") for idx in v.owned}
+        names = ("raw", "bg", "signal", "denoised", "residual")
+        for c0 in range(0, frames.size, chunk):
+            fr = frames[c0:c0 + chunk]
+            n = fr.size
+            out = {k: np.zeros((v.d1 * v.d2, n), dtype=np.float32) for k in names}
+            mixed = np.zeros((v.d1 * v.d2, n, 3), dtype=np.uint16)
+            for idx in v.owned:
+                pp = v.patch_pix[idx]
+                if self.ssub > 1:
+                    self._background_resident(idx, b0_)
+                elif not self._temporal_residual_done(idx):                  # (right after update_temporal_parallel the patch still holds that residual: nothing to ask for)
+                    self._temporal_residual_early(idx)
+                ind, A_pp = cut[idx]
+                res = eng.demix_frames(v.pid[idx], b0_[v.block_pix[idx]] if self.ssub == 1 else None, b0_new_[pp], A_pp if ind.size else None, CC, ind,
+                                       colors[ind], mix_scale, int(fr[0]) - 1, kt, n)
+                for k in names:
+                    out[k][pp] = res[k].T
+                for m in range(3):
+                    mixed[pp, :, m] = res["mixed"][m].T
+            ch ={k: a.reshape(v.d1, v.d2, n, order="F") for k, a in out.items()}
+            ch["mixed"] = mixed.reshape(v.d1, v.d2, n, 3, order="F")
+            ch["frames"] = fr
+            yield ch
+
+    def show_demixed_video(self, path=None, kt=1, frame_range=None, amp_ac=None, range_ac=None, range_Y=None, multi_factor=None, use_craw=False, colors=None):
+        """show_demixed_video(obj, save_avi, kt, frame_range, amp_ac, range_ac, range_Y, multi_factor, use_craw)  (@Sources2D/show_demixed_video.m): the six-panel
+        video -- raw, background, raw - background, denoised, residual, demixed -- of the displayed frames, every panel mapped to 8 bits by imagesc's rule
+        (hostops.imagesc_8bit) in grey within the ranges of :36-57 (hostops.demix_ranges), tiled 2 x 3 in the reference's positions (hostops.demixed_montage).
+        path: a multi-page TIFF is written there through PIL, one page per displayed frame (RuntimeError without PIL); None: nothing is written.  Returns the
+        ranges (range_ac, range_res, range_Y, multi_factor, amp_ac).
+        Deviations: no figure, no titles, no time stamp; a TIFF in place of the AVI; the default range_Y takes the quantiles over ALL samples of the first chunk's raw
+        panel (the reference: over 10 000 random samples)."""
+        Image = Tiff = None
+        if path is not None:
+            try:
+                from PIL import Image, TiffImagePlugin as Tiff
+            except ImportError as e:
+                raise RuntimeError("show_demixed_video(path=...) writes the TIFF through PIL, which is not installed") from e
+        amp_ac = self._default_amp_ac(use_craw) if amp_ac is None else float(amp_ac)
+        ranges, writer = None, None
+        try:
+            for ch in self.demixed_frames(kt, frame_range, amp_ac, use_craw, colors):
+                if ranges is None:
+                    ranges = hostops.demix_ranges(amp_ac, ch["raw"] if range_Y is None else None, range_ac, range_Y, multi_factor)
+                    ranges["amp_ac"] = amp_ac
+                if path is None:
+                    continue
+                if writer is None:
+                    writer = Tiff.AppendingTiffWriter(path, True)
+                for j in range(ch["frames"].size):
+                    page = hostops.demixed_montage({k: ch[k][:, :, j] for k in ("raw", "bg", "signal", "denoised", "residual", "mixed")}, ranges)
+                    Image.fromarray(page).save(writer, format="TIFF")      # (h x w x 3 uint8: RGB)
+                    writer.newFrame()
+        finally:
+            if writer is not None:
+                writer.close()
+        return ranges
+
     # -- known footprints ---------------------------------------------------------------
     def initTemporal(self, frame_range=None, use_parallel=True):
         """@Sources2D/initTemporal.m:89-168,270-292 (ring model): the traces of the footprints obj.A under the background obj.W / obj.b0 (set_W / set_b0, or an

@@ -372,6 +372,11 @@ int cnmfe_trace_diff_spikes(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X
  * K must be the bound matrix'; the bit arithmetic (and nnz(A(:, k)) < min_pixel) is the host's.  64 <= T <= 147456 (WELCH_TMAX; beyond 20416 frames
  * C_raw's row is read in place). */
 int cnmfe_trace_tags(cnmfe_ctx *ctx, int32_t K, double *out /* 4 K */);
+/* orderROIs' per-trace statistics (Sources2D.m:573-653) and the max(CC, [], 2) of show_demixed_video.m:37, of the context's C and C_raw, one workgroup per trace, fp64,
+ * two passes (the means first), a fixed reduction order:
+ * out[7 k + 0] = mean(C(k, :)), [1] = var(C(k, :), 0), [2] = var(C_raw(k, :) - C(k, :), 0), [3] = max(C(k, :)), [4] = ||C_raw(k, :)||_2, [5] = ||C_raw(k, :)||_1,
+ * [6] = max(C_raw(k, :)).  K must be the bound matrix' (CNMFE_ESTATE otherwise, or without residents); K = 0 is legal.  T is a loop bound: any T >= 1. */
+int cnmfe_trace_order_stats(cnmfe_ctx *ctx, int32_t K, double *out /* 7 K */);
 /* The K-changing step of the three merges and of obj.delete, in place on the context's matrices (K rows before, nkeep after):
  *   group g = rows grp_idx[grp_ptr[g] .. grp_ptr[g + 1]) with weights w[...] (same positions): ci = w' C_raw(IDs, :) summed in fp64 in that order and rounded to fp32
  *   once is the new C_raw row of IDs(1) = its first member (:184); deconvolveCa(ci, deconv_options_0) by the AR(1) FOOPSI kernel of cnmfe_deconv_temporal with a fresh
@@ -576,6 +581,30 @@ int cnmfe_df_load(cnmfe_ctx *ctx, int32_t K, int64_t T, const double *Yf /* K x 
 int cnmfe_df_finish(cnmfe_ctx *ctx, const double *inv_norm /* K */, double df_prctile, int64_t df_window /* 0: none */, const float *C, int c_src,
                     const float *C_raw, int raw_src, float *C_df_out /* K x T */, float *C_raw_df_out /* K x T */, double *Df_out /* K, or K x T with a window */,
                     double *Yf_out /* K x T or NULL */);
+
+/* ---- (f) closing calls: the six panels of show_demixed_video   @Sources2D/show_demixed_video.m:70-81,94-127, demos/demo_large_data_1p.m:229
+ * The displayed frames t_j = frame0 + j * stride (0-based, j < nframes, stride = kt >= 1) of one patch, every panel nframes x d frame-major over the patch's d pixels:
+ *   raw       fp32   Y(p, t) = Yc + Ymean of the resident video
+ *   bg        fp32   Ybg(p, t): the bits cnmfe_reconstruct_background[_ssub] writes for that frame (same arguments b0_block / b0_new, same preconditions: CNMFE_ESTATE
+ *                    without the residual of (A_prev, C_prev) / without cnmfe_background_ssub; with bg_ssub > 1 the contiguous frames a run of displayed frames spans are
+ *                    reconstructed into the lane's chunk scratch -- at most 256 MB, as for dF/F -- and read from there)
+ *   signal    fp32   raw - bg, one fp32 subtraction (:107)
+ *   denoised  fp32   (float) sum_k (double)A(p, k) (double)CC(k, t) over the pixel's stored neurons in ascending column order, an fp64 fma chain (:113)
+ *   residual  fp32   (float)((double)raw - (double)bg - that fp64 sum) (:120)
+ *   mixed     uint16 THREE planes of nframes x d (colour m at mixed_out + m * nframes * d): uint16(mix_scale * sum_k A(p, k) (col(k, m) CC(k, t))) in fp64 (:79-81) with
+ *                    MATLAB's conversion -- round half away from zero, saturate to [0, 65535], NaN -> 0; mix_scale = 2 / amp_ac * 65536
+ * A: d x Ksel CSC over the PATCH rows (empty columns are legal).  The traces are a trace SOURCE of section (h): a host matrix Ksel x T with its order (ind ignored; one
+ * counted upload), or CNMFE_BOUND / CNMFE_RES_CRAW with ind[Ksel] = the rows of the call's neurons in the bound matrix.  col: Ksel x 3 floats, row-major.
+ * Every output may be NULL and lies in host or device memory (out_memspace).  One thread per (pixel, frame), plain stores, no atomics, fixed summation order: two calls on
+ * equal inputs are bit-identical, with any number of lanes.  nframes = 0 and Ksel = 0 are legal (Ksel = 0: denoised and mixed are zero).
+ * CNMFE_EINVAL: stride < 1, nframes < 0 or > 65535, a displayed frame outside [0, T), a row of A outside [0, d), an ind outside the bound matrix, any other source. */
+int cnmfe_demix_frames(cnmfe_ctx *ctx, int patch_id, const float *b0_block /* d_b */, const float *b0_new /* d */, int32_t Ksel, const int64_t *A_colptr,
+                       const int32_t *A_rowidx, const float *A_val, const float *CC, int c_src, const int32_t *ind /* Ksel or NULL */, const float *col /* Ksel x 3 */,
+                       double mix_scale, int64_t frame0, int64_t stride, int64_t nframes, float *raw_out, float *bg_out, float *signal_out, float *denoised_out,
+                       float *residual_out, uint16_t *mixed_out /* 3 x nframes x d */, int out_memspace);
+int cnmfe_demix_frames_ssub(cnmfe_ctx *ctx, int patch_id, const float *b0_new /* d */, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
+                            const float *CC, int c_src, const int32_t *ind, const float *col, double mix_scale, int64_t frame0, int64_t stride, int64_t nframes,
+                            float *raw_out, float *bg_out, float *signal_out, float *denoised_out, float *residual_out, uint16_t *mixed_out, int out_memspace);
 
 /* ---- S6: post_process_spatial (connected = true, circular = false)
  * @Sources2D/post_process_spatial.m:19-32 -> endoscope/connectivity_constraint.m:1-18.
