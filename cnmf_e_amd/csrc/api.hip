@@ -1081,6 +1081,38 @@ int cnmfe_peel_open(cnmfe_ctx *ctx, int patch_id, const float *psf, int32_t psf_
     return rc;
 }
 
+// ---- options.ssub / options.tsub: the seed images and the session on dsData of the block (ds.hpp) ----
+// the refusals of seed_args, plus those of the two factors
+static int ds_args(cnmfe_ctx *ctx, int patch_id, int32_t ssub, int32_t tsub, const float *psf, int32_t &psf_n, int64_t nframes, const double *Q, int32_t &M, float sig,
+                   const float *Cn_ds, const float *PNR_ds, Patch *&P) {
+    RET(seed_args(ctx, patch_id, psf, psf_n, 0, nframes, Q, M, sig, Cn_ds, PNR_ds, P));
+    if (ssub < 1 || ssub > 8 || tsub < 1) return fail(CNMFE_EINVAL, "down-sampling: ssub = %d (1 .. 8), tsub = %d (>= 1)", ssub, tsub);
+    if (nframes / tsub < 64) return fail(CNMFE_EUNSUPPORTED, "down-sampling: floor(nframes / tsub) = floor(%lld / %d) = %lld frames are left, at least 64 are needed", (long long)nframes, tsub, (long long)(nframes / tsub));
+    return 0;
+}
+
+int cnmfe_seed_images_ds(cnmfe_ctx *ctx, int patch_id, int32_t ssub, int32_t tsub, const float *psf, int32_t psf_n, int64_t nframes, const double *Q, int32_t M,
+                         float sig, float *Cn_ds, float *PNR_ds) {
+    Patch *P = nullptr;
+    RET(ds_args(ctx, patch_id, ssub, tsub, psf, psf_n, nframes, Q, M, sig, Cn_ds, PNR_ds, P));
+    CK(hipSetDevice(ctx->device));
+    RET(ensure_ymean(ctx, P));
+    return seed_images_ds_run(ctx, P, ssub, tsub, psf, psf_n, nframes, Q, M, sig, Cn_ds, PNR_ds);
+}
+
+int cnmfe_peel_open_ds(cnmfe_ctx *ctx, int patch_id, int32_t ssub, int32_t tsub, const float *psf, int32_t psf_n, int64_t nframes, const double *Qpre, int32_t Mpre,
+                       float sig, float *Cn_ds, float *PNR_ds, float *Sn_ds, float *Yds_out, int out_memspace) {
+    Patch *P = nullptr;
+    RET(ds_args(ctx, patch_id, ssub, tsub, psf, psf_n, nframes, Qpre, Mpre, sig, Cn_ds, PNR_ds, P));
+    if (P->peel) return fail(CNMFE_ESTATE, "patch %d already has an open peel session", patch_id);
+    CK(hipSetDevice(ctx->device));
+    RET(ensure_ymean(ctx, P));
+    P->peel = new PeelSession();
+    const int rc = peel_open_ds_run(ctx, P, ssub, tsub, psf, psf_n, nframes, Qpre, Mpre, sig, Cn_ds, PNR_ds, Sn_ds, Yds_out, out_memspace);
+    if (rc != 0) { (void)hipStreamSynchronize(ctx->st()); delete P->peel; P->peel = nullptr; }
+    return rc;
+}
+
 // The second pass (@Sources2D/initComponents_residual_parallel.m:186-220): the session on the PATCH, its source video Yres = Ysig - A(patch, ind) C(ind, :) built
 // off the resident residual (peel.hpp, k_peel_yres).  Ysig is only read; the residual REQUEST is the session's: cnmfe_peel_close drops it (as a fit does), so the
 // next update requests its own and finds the patch as it would have without the session

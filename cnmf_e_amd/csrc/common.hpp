@@ -149,7 +149,9 @@ constexpr int WELCH_TMAX = 147456;
 // [ceil(n / 4)][d_b] float4), GetSn of HY per block pixel (fp64), the detrend basis, ci | y_bg (fp64, n each) and the box kernels' scratch
 // The session runs on the geometry of its SOURCE video: the centred block (cnmfe_peel_open: d = d_b, nr_b x nc_b, y_bg adds the pixel mean back) or the
 // residual video of the patch (cnmfe_peel_open_residual: Yw starts as Yres = Ysig - A C, d x nr x nc of the patch, no pixel mean -- the residual carries its own)
-struct PeelSession { DevBuf hy, yw, sn, q, ci, scr; int64_t n = 0, nq = 0; int M = 0; int64_t d = 0; int nr = 0, nc = 0; bool residual = false; };
+// or the down-sampled block (cnmfe_peel_open_ds, ds.hpp: Yw starts as dsData of the block on the ceil(nr_b / ssub) x ceil(nc_b / ssub) grid with floor(n / tsub)
+// frames; y_bg adds the session's OWN pixel mean box(ymean) -- own_mean -- or none behind a pre-detrend -- no_mean)
+struct PeelSession { DevBuf hy, yw, sn, q, ci, scr, ymean; int64_t n = 0, nq = 0; int M = 0; int64_t d = 0; int nr = 0, nc = 0; bool residual = false, own_mean = false, no_mean = false; };
 // the video a seed / peel pass reads: [ceil(n / 4)][d] float4, nr x nc pixels column-major
 struct SeedSrc { const float4 *y4; int64_t d; int nr, nc; };
 
@@ -657,6 +659,10 @@ int peel_open_residual_run(cnmfe_ctx *ctx, Patch *P, int32_t Ksel, const int64_t
                            const float *psf, int32_t psf_n, float sig, float *Cn_out, float *PNR_out, float *Sn_out, float *Yres_out, int out_memspace);   // peel.hpp (deconv.hip)
 int peel_open_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, int64_t nframes, const double *Q, int32_t M, float sig,
                   float *Cn_out, float *PNR_out, float *Sn_out);   // peel.hpp (deconv.hip)
+int seed_images_ds_run(cnmfe_ctx *ctx, Patch *P, int ssub, int tsub, const float *psf, int32_t psf_n, int64_t nframes, const double *Q, int32_t M, float sig,
+                       float *Cn_out, float *PNR_out);   // ds.hpp (deconv.hip)
+int peel_open_ds_run(cnmfe_ctx *ctx, Patch *P, int ssub, int tsub, const float *psf, int32_t psf_n, int64_t nframes, const double *Qpre, int32_t Mpre, float sig,
+                     float *Cn_out, float *PNR_out, float *Sn_out, float *Yds_out, int out_memspace);   // ds.hpp (deconv.hip)
 int peel_extract_run(cnmfe_ctx *ctx, Patch *P, int r, int c, int gSiz, double *corr_box, double *ai_box, double *ci_out, double *stats);
 int peel_apply_run(cnmfe_ctx *ctx, Patch *P, int r, int c, int gSiz, const double *ai_box, const double *Hai_box2, const double *ci, double sig, double min_pnr,
                    double min_corr, float *PNR_box2, float *Cn_box2);

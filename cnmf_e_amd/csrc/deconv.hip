@@ -1097,6 +1097,7 @@ __device__ __forceinline__ double get_sn_long(const YT &y, const DeconvCfg &c, f
 }  // namespace cnmfe
 #include "seed.hpp"       // (f) seed images: Cn and PNR of the spatially filtered block (its noise is get_sn above)
 #include "peel.hpp"       // (g) greedy initialisation: the peel-off session over those images (its kernels need get_sn, select_pair and seed.hpp's)
+#include "ds.hpp"         // (g') ssub / tsub: dsData of the block as the source video of the seed pipeline and of a peel session
 namespace cnmfe {
 
 // ---- host side -------------------------------------------------------------------------------------------

@@ -46,7 +46,9 @@
 // Seed images (correlation_pnr_parallel.m:70-104 per patch):
 //   [Cn_block, PNR_block] = cnmfe_mex('seed_images', h, pid, psf, nframes, Q)   psf: odd n x n (or []), Q: nframes x M orthonormal detrend basis (or [] / omitted);
 //                                                                          nr_b x nc_b double images of the block (its size is remembered from 'patch')
+//   [Cn_ds, PNR_ds] = cnmfe_mex('seed_images_ds', h, pid, ssub, tsub, psf, nframes, Q)        the seed images of dsData(block): ceil(nr_b / ssub) x ceil(nc_b / ssub), Q: floor(nframes / tsub) x M
 // Greedy initialisation, a peel session per patch (greedyROI_endoscope.m:119-145, 287-311, 378-402; the search loop is the host's):
+//   [Cn_ds, PNR_ds, Sn_ds, Yds] = cnmfe_mex('peel_open_ds', h, pid, ssub, tsub, psf, nframes, Qpre)   the session on dsData(block); Qpre: nframes x M, the full-length basis; Yds single, d1s d2s x Ts
 //   [Cn_block, PNR_block, Sn_block] = cnmfe_mex('peel_open', h, pid, psf, nframes, Q)          the arguments and images of 'seed_images' (+ GetSn of the filtered traces)
 //   [corr, ai, ci, stats] = cnmfe_mex('peel_extract', h, pid, r, c, gSiz)                       (r, c): the seed, 1-BASED in the block; corr, ai: the clipped
 //                                                                          (2 gSiz + 1)^2 box; ci: 1 x nframes; stats: [max(diff(y0)) std(diff(y0)) norm(ci) GetSn(ci) n_hi n_lo]
@@ -774,7 +776,29 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
         CHECK(cnmfe_seed_images(c, pid, psf, pn, 0, nf, Q, M, 3.0f, cn, pnr));
         pout[0] = to_double(cn, nrb, ncb);
         if (nout > 1) pout[1] = to_double(pnr, nrb, ncb);
-    } else if (!strcmp(cmd, "peel_open") || !strcmp(cmd, "peel_open_residual") || !strcmp(cmd, "peel_extract") || !strcmp(cmd, "peel_apply") || !strcmp(cmd, "peel_close")) {
+    } else if (!strcmp(cmd, "seed_images_ds")) {               // [Cn_ds, PNR_ds] = cnmfe_mex('seed_images_ds', h, pid, ssub, tsub, psf, nframes, Q)   correlation_pnr_parallel.m:81-96
+        if (nin != 7 && nin != 8) FAIL("seed_images_ds: 7 or 8 inputs required");
+        int slot = 0;
+        while (slot < g_ndims && !(g_dims[slot].c == c && g_dims[slot].pid == pid)) ++slot;
+        if (slot == g_ndims) FAIL("seed_images_ds: patch %d was not created through this gateway", pid);
+        const int ssub = (int)mxGetScalar(pin[3]), tsub = (int)mxGetScalar(pin[4]);
+        if (ssub < 1 || ssub > 8 || tsub < 1) FAIL("seed_images_ds: ssub = %d (1 .. 8), tsub = %d (>= 1)", ssub, tsub);
+        const size_t d1s = ((size_t)g_dims[slot].nr_b + ssub - 1) / ssub, d2s = ((size_t)g_dims[slot].nc_b + ssub - 1) / ssub;
+        const mxArray *F = pin[5];
+        if (!mxIsEmpty(F) && mxGetM(F) != mxGetN(F)) FAIL("seed_images_ds: psf must be square");
+        const int32_t pn = mxIsEmpty(F) ? 0 : (int32_t)mxGetM(F);
+        const float *psf = pn ? f32_of(F, NULL) : NULL;
+        const int64_t nf = (int64_t)mxGetScalar(pin[6]);
+        const double *Q = NULL; int32_t M = 0;
+        if (nin == 8 && !mxIsEmpty(pin[7])) {
+            if (!mxIsDouble(pin[7]) || mxIsSparse(pin[7]) || (int64_t)mxGetM(pin[7]) != nf / tsub) FAIL("seed_images_ds: Q must be a full double floor(nframes / tsub) x M matrix");
+            Q = mxGetPr(pin[7]); M = (int32_t)mxGetN(pin[7]);
+        }
+        float *cn = (float *)mxMalloc((d1s * d2s + 1) * sizeof(float)), *pnr = (float *)mxMalloc((d1s * d2s + 1) * sizeof(float));
+        CHECK(cnmfe_seed_images_ds(c, pid, ssub, tsub, psf, pn, nf, Q, M, 3.0f, cn, pnr));
+        pout[0] = to_double(cn, d1s, d2s);
+        if (nout > 1) pout[1] = to_double(pnr, d1s, d2s);
+    } else if (!strcmp(cmd, "peel_open") || !strcmp(cmd, "peel_open_ds") || !strcmp(cmd, "peel_open_residual") || !strcmp(cmd, "peel_extract") || !strcmp(cmd, "peel_apply") || !strcmp(cmd, "peel_close")) {
         int slot = 0;
         while (slot < g_ndims && !(g_dims[slot].c == c && g_dims[slot].pid == pid)) ++slot;
         if (slot == g_ndims) FAIL("%s: patch %d was not created through this gateway", cmd, pid);
@@ -815,6 +839,31 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
             pout[0] = to_double(cn, (size_t)nrb, (size_t)ncb);
             if (nout > 1) pout[1] = to_double(pnr, (size_t)nrb, (size_t)ncb);
             if (nout > 2) pout[2] = to_double(sn, (size_t)nrb, (size_t)ncb);
+        } else if (!strcmp(cmd, "peel_open_ds")) {                    // [Cn_ds, PNR_ds, Sn_ds, Yds] = cnmfe_mex('peel_open_ds', h, pid, ssub, tsub, psf, nframes, Qpre)
+            if (nin != 7 && nin != 8) FAIL("peel_open_ds: 7 or 8 inputs required");
+            const int ssub = (int)mxGetScalar(pin[3]), tsub = (int)mxGetScalar(pin[4]);
+            if (ssub < 1 || ssub > 8 || tsub < 1) FAIL("peel_open_ds: ssub = %d (1 .. 8), tsub = %d (>= 1)", ssub, tsub);
+            const size_t d1s = ((size_t)nrb + ssub - 1) / ssub, d2s = ((size_t)ncb + ssub - 1) / ssub, ds = d1s * d2s;
+            const mxArray *F = pin[5];
+            if (!mxIsEmpty(F) && mxGetM(F) != mxGetN(F)) FAIL("peel_open_ds: psf must be square");
+            const int32_t pn = mxIsEmpty(F) ? 0 : (int32_t)mxGetM(F);
+            const float *psf = pn ? f32_of(F, NULL) : NULL;
+            const int64_t nf = (int64_t)mxGetScalar(pin[6]);
+            if (nf < 1 || nf > g_dims[slot].T) FAIL("peel_open_ds: nframes = %lld of %lld", (long long)nf, (long long)g_dims[slot].T);
+            const int64_t Ts = nf / tsub;
+            const double *Q = NULL; int32_t M = 0;
+            if (nin == 8 && !mxIsEmpty(pin[7])) {
+                if (!mxIsDouble(pin[7]) || mxIsSparse(pin[7]) || (int64_t)mxGetM(pin[7]) != nf) FAIL("peel_open_ds: Qpre must be a full double nframes x M matrix (the FULL-LENGTH basis)");
+                Q = mxGetPr(pin[7]); M = (int32_t)mxGetN(pin[7]);
+            }
+            float *cn = (float *)mxMalloc((ds + 1) * sizeof(float)), *pnr = (float *)mxMalloc((ds + 1) * sizeof(float)), *sn = (float *)mxMalloc((ds + 1) * sizeof(float));
+            mxArray *yds = nout > 3 ? mxCreateNumericMatrix(ds, (size_t)Ts, mxSINGLE_CLASS, mxREAL) : NULL;
+            CHECK(cnmfe_peel_open_ds(c, pid, ssub, tsub, psf, pn, nf, Q, M, 3.0f, cn, pnr, sn, yds ? (float *)mxGetData(yds) : NULL, CNMFE_HOST));
+            g_dims[slot].peel_n = Ts; g_dims[slot].peel_nr = (int32_t)d1s; g_dims[slot].peel_nc = (int32_t)d2s;
+            pout[0] = to_double(cn, d1s, d2s);
+            if (nout > 1) pout[1] = to_double(pnr, d1s, d2s);
+            if (nout > 2) pout[2] = to_double(sn, d1s, d2s);
+            if (nout > 3) pout[3] = yds;
         } else if (!strcmp(cmd, "peel_close")) {               // cnmfe_mex('peel_close', h, pid)
             if (nin != 3) FAIL("peel_close: 3 inputs required");
             CHECK(cnmfe_peel_close(c, pid));

@@ -541,7 +541,7 @@ int peel_extract_run(cnmfe_ctx *ctx, Patch *P, int r, int c, int gSiz, double *c
     LAUNCH(ctx, "peel_corr_part", k_peel_corr_part, dim3((unsigned)b.nc, (unsigned)nch), dim3(256), 0, hy4, d_b, nr_b, b, pctr, (int)n, qchunk, dPart);
     LAUNCH(ctx, "peel_corr_fin", k_peel_corr_fin, dim3(1), dim3(256), 0, dPart, npart, npix, ictr, (int)n, dCorr, dHi, dLo, dCnt);
     const size_t sh_tr = (size_t)4 * npix * sizeof(double) + 264 * sizeof(int);
-    LAUNCH(ctx, "peel_traces", k_peel_traces, dim3((unsigned)nq), dim3(256), sh_tr, hy4, yw4, (S->M > 0 || S->residual) ? (const double *)nullptr : P->ymean_d.as<double>(), d_b, nr_b, b,
+    LAUNCH(ctx, "peel_traces", k_peel_traces, dim3((unsigned)nq), dim3(256), sh_tr, hy4, yw4, (S->M > 0 || S->residual || S->no_mean) ? (const double *)nullptr : (S->own_mean ? S->ymean.as<double>() : P->ymean_d.as<double>()), d_b, nr_b, b,
            dHi, dLo, dCnt, (int)n, dCi, dBg);
     if (w.lng) {
         WELCH_LAUNCH_LONG(ctx, "peel_trace_stats", k_peel_trace_stats_long, w, 1, tabs, hy4, d_b, pctr, (const double *)dCi, (const double *)dBg, (const int *)dCnt, dMom, dSt);

@@ -328,6 +328,7 @@ class Engine:
     supports_fit_reserve = True       # fit_reserve()
     supports_synchronize = True       # synchronize()
     supports_init_temporal = True     # init_temporal() / init_temporal_job()
+    supports_init_ds = True           # seed_images_ds() / peel_open_ds(): options.ssub / options.tsub of the seed images and the first initialisation
     supports_traces_grow = True       # traces_grow(): zero rows under the bound matrix and its residents, on the device
 
     # pinned buffers of LazyHostTraces, recycled by size (page-locking 20 MB costs milliseconds)
@@ -533,6 +534,47 @@ class Engine:
                                                _p(Cn, L.f32p), _p(PNR, L.f32p), _p(Sn, L.f32p), dst, L.HOST))
         self._peel[pid] = (n, info["nr"], info["nc"])
         return Cn, PNR, Sn, out
+
+    # ---- options.ssub / options.tsub: the same two calls on dsData of the block (cnmfe_seed_images_ds / cnmfe_peel_open_ds) ----
+    def ds_dims(self, pid, ssub, tsub, nframes=None):
+        """(d1s, d2s, Ts) of dsData (utilities/dsData.m:29-31) of a patch's block over the first `nframes` frames"""
+        info = self._patch[pid]
+        n = info["T"] if nframes is None else int(nframes)
+        ssub, tsub = max(int(ssub), 1), max(int(tsub), 1)                  # (factors below 1 are the library's to refuse: only the buffers are sized here)
+        return -(-info["nr_b"] // ssub), -(-info["nc_b"] // ssub), n // tsub
+
+    def seed_images_ds(self, pid, ssub, tsub, psf, nframes=None, Q=None, sig=3.0):
+        """seed_images of Yds = dsData(block) (correlation_pnr_parallel.m:86-96): the block is down-sampled on the device (box resize to ceil(nr_b / ssub) x
+        ceil(nc_b / ssub), means of tsub frames, Ts = floor(nframes / tsub)), then filtered with `psf` (built from the SCALED gSig / gSiz) and detrended against
+        Q, Ts x M.  Two float32 arrays of d1s * d2s pixels, column-major on the low-resolution grid."""
+        d1s, d2s, Ts = self.ds_dims(pid, ssub, tsub, nframes)
+        _info, n, psf_a, psf_n, _q, _m = self._seed_args(pid, psf, nframes, None)
+        Q_a, M = None, 0
+        if Q is not None and np.size(Q):
+            Q = np.asarray(Q, dtype=np.float64)
+            if Q.ndim != 2 or Q.shape[0] != Ts:
+                raise ValueError("Q must be (%d, M) for the down-sampled series, got %s" % (Ts, Q.shape))
+            M = int(Q.shape[1]); Q_a = np.ascontiguousarray(Q.T)
+        Cn = np.empty(max(d1s * d2s, 1), dtype=np.float32); PNR = np.empty(max(d1s * d2s, 1), dtype=np.float32)
+        L.check(L.lib.cnmfe_seed_images_ds(self._ctx, pid, int(ssub), int(tsub), _p(psf_a, L.f32p), psf_n, n, _p(Q_a, L.f64p), M, float(sig),
+                                           _p(Cn, L.f32p), _p(PNR, L.f32p)))
+        return Cn[:d1s * d2s], PNR[:d1s * d2s]
+
+    def peel_open_ds(self, pid, ssub, tsub, psf, nframes=None, Qpre=None, sig=3.0, want_video=False):
+        """open the peel session of a patch on Yds = dsData(block) (greedyROI_endoscope.m:46-61).  Qpre: nframes x Mpre, the FULL-LENGTH detrend basis: the block
+        is detrended before it is down-sampled (initComponents_parallel.m:341-343), on the device and without a full-resolution copy.  Returns (Cn, PNR, Sn,
+        Yds): d1s * d2s float32 each, column-major on the low-resolution grid; Yds (want_video) is the (Ts, d1s * d2s) float32 video the session searches, else
+        None.  extract / apply then take seeds 0-based on the d1s x d2s grid and traces of Ts samples."""
+        d1s, d2s, Ts = self.ds_dims(pid, ssub, tsub, nframes)
+        _info, n, psf_a, psf_n, Q_a, M = self._seed_args(pid, psf, nframes, Qpre)
+        ds = max(d1s * d2s, 1)
+        Cn = np.empty(ds, dtype=np.float32); PNR = np.empty(ds, dtype=np.float32); Sn = np.empty(ds, dtype=np.float32)
+        out = np.empty((max(Ts, 0), d1s * d2s), dtype=np.float32) if want_video else None
+        dst = out.ctypes.data_as(L.C.c_void_p) if want_video else L.C.c_void_p(None)
+        L.check(L.lib.cnmfe_peel_open_ds(self._ctx, pid, int(ssub), int(tsub), _p(psf_a, L.f32p), psf_n, n, _p(Q_a, L.f64p), M, float(sig),
+                                         _p(Cn, L.f32p), _p(PNR, L.f32p), _p(Sn, L.f32p), dst, L.HOST))
+        self._peel[pid] = (Ts, d1s, d2s)
+        return Cn[:d1s * d2s], PNR[:d1s * d2s], Sn[:d1s * d2s], out
 
     def peel_extract(self, pid, r, c, gSiz):
         """extract_ac.m:19-58 around the 0-based block pixel (r, c): (corr, ai) as nr x nc float64 images of the box, ci (nframes float64), stats = dict of

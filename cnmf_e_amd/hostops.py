@@ -268,6 +268,50 @@ def refine_ac(ai_img, ci, sn_ci, connected=True, min_pixels=5):
     return ai, ci, bool(np.linalg.norm(ai) != 0)                           # :103-107
 
 
+# --------------------------------------------------------------------------------------
+# imresize along one dimension (options.ssub / options.tsub: greedyROI_endoscope.m:464-487, correlation_pnr_parallel.m:97-100, utilities/dsData.m:35)
+# --------------------------------------------------------------------------------------
+def _cubic_kernel(x):
+    ax = np.abs(x); ax2 = ax * ax; ax3 = ax2 * ax
+    return (1.5 * ax3 - 2.5 * ax2 + 1) * (ax <= 1) + (-0.5 * ax3 + 2.5 * ax2 - 4 * ax + 2) * ((ax > 1) & (ax <= 2))
+
+
+def _box_kernel(x):
+    return ((x >= -0.5) & (x < 0.5)).astype(np.float64)
+
+
+def imresize_matrix(n_in, n_out, method="bicubic"):
+    """The (n_out x n_in) float64 weight matrix of imresize(., [.. n_out ..], method) along one dimension of length n_in (the toolbox's documented
+    `contributions` rule): scale = n_out / n_in, output sample x sits at u = x / scale + (1 - 1 / scale) / 2, the kernel ('box': -0.5 <= x < 0.5, 'bicubic':
+    Keys, a = -0.5) is stretched by 1 / scale when shrinking (antialiasing is on), taps are mirrored at the border and every row is normalised to sum 1."""
+    kernel, kw = {"box": (_box_kernel, 1.0), "bicubic": (_cubic_kernel, 4.0)}[method]
+    n_in, n_out = int(n_in), int(n_out)
+    scale = n_out / n_in
+    if scale < 1:
+        h = lambda x: scale * kernel(scale * x)
+        kw = kw / scale
+    else:
+        h = kernel
+    x = np.arange(1, n_out + 1, dtype=np.float64)
+    u = x / scale + 0.5 * (1 - 1 / scale)
+    left = np.floor(u - kw / 2)
+    ind = left[:, None] + np.arange(int(np.ceil(kw)) + 2)[None, :]
+    w = h(u[:, None] - ind)
+    w = w / w.sum(axis=1, keepdims=True)
+    aux = np.concatenate([np.arange(n_in), np.arange(n_in - 1, -1, -1)])   # [1:n n:-1:1], 0-based
+    src = aux[np.mod(ind.astype(np.int64) - 1, aux.size)]
+    M = np.zeros((n_out, n_in))
+    np.add.at(M, (np.repeat(np.arange(n_out), src.shape[1]), src.ravel()), w.ravel())
+    return M
+
+
+def imresize_to(img, out_size, method="bicubic"):
+    """imresize(img, [nr nc], method) on the first two dimensions of a float64 array (rows, then columns)"""
+    img = np.asarray(img, dtype=np.float64)
+    out = np.tensordot(imresize_matrix(img.shape[0], out_size[0], method), img, axes=(1, 0))
+    return np.moveaxis(np.tensordot(imresize_matrix(img.shape[1], out_size[1], method), out, axes=(1, 1)), 0, 1)
+
+
 def box_of(nr, nc, r, c, reach):
     """0-based half-open (r0, r1, c0, c1) of rsub x csub (greedyROI_endoscope.m:299-300,310-311) around the 0-based pixel (r, c)"""
     return max(0, r - reach), min(nr, r + reach + 1), max(0, c - reach), min(nc, c + reach + 1)

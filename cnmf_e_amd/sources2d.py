@@ -66,8 +66,8 @@ class Options:
     center_psf: bool = True          # subtract the kernel's mean over its support (1p data)
     nk: int = 1                      # knots of the detrending spline basis; 1 = no detrending
     detrend_method: str = "spline"   # 'spline' | 'local_min' (only 'spline' is built)
-    ssub: int = 1                    # spatial / temporal downsampling of the initialisation (only 1 is built)
-    tsub: int = 1
+    ssub: int = 1                    # spatial / temporal down-sampling of the seed images and the first initialisation (dsData.m): ssub in 1..8, tsub >= 1;
+    tsub: int = 1                    # both are read where Sources2D is constructed (Sources2D._ds_factors)
     # the greedy initialisation (initComponents_parallel): CNMFSetParms.m names at :19,97-100, their defaults at :209,286-289
     min_corr: float = 0.3            # :19 / :209   minimum local correlation of a seed pixel
     min_pnr: float = 10.0            # :97 / :286   minimum peak-to-noise ratio of a seed pixel
@@ -757,6 +757,7 @@ class Sources2D:
         self._cmean_of = None           # the C whose row means _cmean holds; any other self.C voids them
         self._init_observer = None      # tests: set to a function the two initialisations call at every step; never reset
         self._bbox_cache = ()           # _bbox_of: (matrix, bounding boxes of its columns) of the last four matrices, by identity
+        self._ds_declared = (options.ssub, options.tsub)      # the down-sampling of the initialisation is declared at construction, like bg_ssub (_ds_factors)
         self._bind_C()
         self.ssub = int(options.bg_ssub)
         npatch = len(video.order)
@@ -991,11 +992,12 @@ class Sources2D:
         """[Cn, PNR] = obj.correlation_pnr_parallel(frame_range)  (@Sources2D/correlation_pnr_parallel.m:1-128): the local-correlation and peak-to-noise images
         of the spatially filtered video, d1 x d2 float64 each.  Every owned patch evaluates its block on the device (Engine.seed_images) and keeps the patch
         interior (:117-127: the interiors are disjoint, so the reference's max merge is a scatter; sharded runs sum them).  frame_range = (1, n), 1-based
-        inclusive and clipped to the recording as in :40-45."""
+        inclusive and clipped to the recording as in :40-45.
+        options.ssub / options.tsub other than 1 (:81-100): every block is down-sampled on the device first (Engine.seed_images_ds: dsData), filtered with the
+        kernel of gSig / ssub and ceil(gSiz / ssub), detrended against the basis of the Ts = floor(n / tsub) frames that are left, and with ssub > 1 both images
+        are resized back to the block (imresize, bicubic) before the patch interior is kept."""
         self._need_data()
         v, o = self.video, self.options
-        if int(o.ssub) != 1 or int(o.tsub) != 1:
-            raise NotImplementedError("correlation_pnr_parallel: ssub / tsub other than 1 are not built")
         nk = int(o.nk)
         if nk > 1 and str(o.detrend_method).lower() != "spline":
             raise NotImplementedError("correlation_pnr_parallel: detrend_method %r is not built (only 'spline')" % (o.detrend_method,))
@@ -1004,15 +1006,47 @@ class Sources2D:
         if f0 != 1:
             raise NotImplementedError("correlation_pnr_parallel reads the frames from the first one on (frame_range = [%d, %d])" % (f0, f1))
         n = f1 - f0 + 1
-        psf = seed_psf(float(o.gSig), float(o.gSiz), bool(o.center_psf))
-        Q = np.linalg.qr(bspline_basis(n, nk))[0] if nk > 1 else None     # detrend_data.m:23-29: the projection only needs the span
+        ssub, tsub = self._ds_factors(n)
+        ds = ssub != 1 or tsub != 1
+        psf = seed_psf(float(o.gSig) / ssub, float(np.ceil(float(o.gSiz) / ssub)), bool(o.center_psf))      # :81-82
+        Q = np.linalg.qr(bspline_basis(n // tsub, nk))[0] if nk > 1 else None     # detrend_data.m:23-29: the projection only needs the span
         Cn = np.zeros(v.d1 * v.d2, dtype=np.float64); PNR = np.zeros(v.d1 * v.d2, dtype=np.float64)
         for idx in v.owned:
-            cn_b, pnr_b = self.engine.seed_images(v.pid[idx], psf, n, Q, 3.0)
+            if ds:
+                bp = v.block_pos[idx]
+                nr_b, nc_b = int(bp[1] - bp[0] + 1), int(bp[3] - bp[2] + 1)
+                cn_b, pnr_b = self.engine.seed_images_ds(v.pid[idx], ssub, tsub, psf, n, Q, 3.0)
+                if ssub != 1:                                              # :97-100
+                    d1s, d2s = -(-nr_b // ssub), -(-nc_b // ssub)
+                    cn_b, pnr_b = (hostops.imresize_to(x.astype(np.float64).reshape(d1s, d2s, order="F"), (nr_b, nc_b)).reshape(-1, order="F") for x in (cn_b, pnr_b))
+            else:
+                cn_b, pnr_b = self.engine.seed_images(v.pid[idx], psf, n, Q, 3.0)
             Cn[v.patch_pix[idx]] = cn_b[v.ind_patch[idx]]
             PNR[v.patch_pix[idx]] = pnr_b[v.ind_patch[idx]]
         both = self._allreduce(np.stack([Cn, PNR]))
         return both[0].reshape(v.d1, v.d2, order="F"), both[1].reshape(v.d1, v.d2, order="F")
+
+    def _ds_factors(self, n):
+        """(ssub, tsub) of the options, checked: ssub an integer in 1..8, tsub an integer >= 1, and with either other than 1 at least 64 of the n frames left
+        (ValueError with the numbers).  Factors other than 1 are honoured where the object was CONSTRUCTED with them, as bg_ssub is read at construction: an
+        options object swapped in later with other factors is refused (NotImplementedError), and so is an engine that does not declare the down-sampled entry
+        points (Engine.supports_init_ds) -- both before the frame count is looked at."""
+        ssub, tsub = self.options.ssub, self.options.tsub
+        if isinstance(ssub, bool) or ssub != int(ssub) or not (1 <= int(ssub) <= 8):
+            raise ValueError("options.ssub must be an integer in 1..8, got %r" % (ssub,))
+        if isinstance(tsub, bool) or tsub != int(tsub) or int(tsub) < 1:
+            raise ValueError("options.tsub must be an integer >= 1, got %r" % (tsub,))
+        ssub, tsub = int(ssub), int(tsub)
+        if ssub != 1 or tsub != 1:
+            declared = getattr(self, "_ds_declared", (1, 1))
+            if (ssub, tsub) != declared:
+                raise NotImplementedError("ssub = %d, tsub = %d were set after the object was constructed with ssub = %s, tsub = %s: other factors need a new Sources2D"
+                                          % (ssub, tsub, declared[0], declared[1]))
+            if not self._can("init_ds"):
+                raise NotImplementedError("this engine does not build ssub / tsub other than 1 (supports_init_ds)")
+        if (ssub != 1 or tsub != 1) and n // tsub < 64:
+            raise ValueError("options.tsub = %d leaves floor(%d / %d) = %d frames, at least 64 are needed" % (tsub, n, tsub, n // tsub))
+        return ssub, tsub
 
     def _init_deconv(self):
         """the deconvolution of one accepted trace (greedyROI_endoscope.m:355-364) both initialisations hand to hostops.greedy_roi_block: ci_raw -> (ci, ci_raw - b,
@@ -1025,6 +1059,28 @@ class Sources2D:
             c_, r_, s_, kp_, _sn = self.engine.deconv_temporal(np.asarray(ci_raw, dtype=np.float32)[None, :], o.deconv_options)
             return c_[0].astype(np.float64), r_[0].astype(np.float64), s_[0].astype(np.float64), float(kp_[0])
         return deconv
+
+    def _init_upsample(self, res, ssub, tsub, low, full, n):
+        """greedyROI_endoscope.m:464-487: the result of hostops.greedy_roi_block on the low-resolution session brought back to the block and to n frames"""
+        k = len(res["A"])
+        out = dict(res)
+        if ssub != 1:
+            A = []
+            for (r0, r1, c0, c1), ai in res["A"]:
+                img = np.zeros(low)
+                img[r0:r1, c0:c1] = ai
+                A.append(((0, full[0], 0, full[1]), hostops.imresize_to(img, full)))       # :467 (bicubic; negative lobes kept)
+            out["A"] = A
+            out["center"] = res["center"] * ssub - 1                                       # :473
+        if tsub != 1 and k:
+            Ts = len(res["C"][0])
+            Mbox = hostops.imresize_matrix(Ts, n, "box")                                    # :481-482
+            out["C"] = [Mbox @ np.asarray(c, dtype=np.float64) for c in res["C"]]
+            out["C_raw"] = [Mbox @ np.asarray(c, dtype=np.float64) for c in res["C_raw"]]
+            if self.options.deconv_flag:
+                Mcub = hostops.imresize_matrix(Ts, n, "bicubic")                            # :484
+                out["S"] = [Mcub @ np.asarray(s, dtype=np.float64) for s in res["S"]]
+        return out
 
     def _stitch_init(self, per_patch, n):
         """the collection both initialisations share (initComponents_parallel.m:410-469, initComponents_residual_parallel.m:345-398): per_patch[idx] = (the
@@ -1075,12 +1131,15 @@ class Sources2D:
         (1-based).  K: the maximum number of neurons PER PATCH (None: options.K).  frame_range = (1, n).
         seeds: a list of 1-based FOV pixels (r, c), the counterpart of seed_method = 'manual': min_corr and min_pnr are halved (:66-69), and every patch tries
         the given pixels of its block ONCE, in the given order -- the one deviation: the reference asks for another round of clicks until none is valid.
-        Not built (NotImplementedError): ssub / tsub other than 1, detrend_method 'local_min', a frame range that does not start at 1, use_prev, save_avi /
-        debug_on."""
+        options.ssub / options.tsub other than 1 (greedyROI_endoscope.m:46-61,464-487): the session of every block runs on Yds = dsData(detrended block) on the
+        device (Engine.peel_open_ds: ceil(nr_b / ssub) x ceil(nc_b / ssub) pixels, Ts = floor(n / tsub) frames) with gSig / ssub, gSiz = round(gSiz / ssub),
+        min_pixel / ssub^2 and bd = round(bd / ssub); `seeds` land on the low-resolution pixel that holds them.  The results come back at full resolution as the
+        reference brings them back: footprints, Cn and PNR by imresize (bicubic: negative lobes are kept), center = center * ssub - 1 (the reference's rule; for
+        ssub >= 3 it may leave the block, and the patch-interior test is applied to it as it is), C and C_raw by imresize(., [k, n], 'box') along time, S
+        bicubic; P.kernel_pars stay as fitted at the LOW frame rate, which is the reference's behaviour.
+        Not built (NotImplementedError): detrend_method 'local_min', a frame range that does not start at 1, use_prev, save_avi / debug_on."""
         self._need_data()
         v, o = self.video, self.options
-        if int(o.ssub) != 1 or int(o.tsub) != 1:
-            raise NotImplementedError("initComponents_parallel: ssub / tsub other than 1 are not built")
         nk = int(o.nk)
         if str(o.detrend_method).lower() != "spline":
             raise NotImplementedError("initComponents_parallel: detrend_method %r is not built (only 'spline')" % (o.detrend_method,))
@@ -1095,11 +1154,14 @@ class Sources2D:
         if seeds is None and str(o.seed_method).lower() == "manual":
             raise ValueError("seed_method = 'manual' needs the seed pixels: initComponents_parallel(seeds=[(r, c), ...])")
         n = f1 - f0 + 1
+        ssub, tsub = self._ds_factors(n)
+        ds = ssub != 1 or tsub != 1
         K = o.K if K is None else K
-        gSiz = int(_mround(float(o.gSiz)))
-        bd = gSiz if o.bd is None else int(o.bd)                          # initComponents_parallel.m:200-203
-        psf = seed_psf(float(o.gSig), float(o.gSiz), bool(o.center_psf))
-        Q = np.linalg.qr(bspline_basis(n, nk))[0] if nk > 1 else None
+        bd = int(_mround(float(o.gSiz))) if o.bd is None else int(o.bd)   # initComponents_parallel.m:200-203
+        gSiz = int(_mround(float(o.gSiz) / ssub))                         # greedyROI_endoscope.m:56-59
+        min_pixel = float(o.min_pixel) / ssub ** 2
+        psf = seed_psf(float(o.gSig) / ssub, float(gSiz) if ds else float(o.gSiz), bool(o.center_psf))
+        Q = np.linalg.qr(bspline_basis(n, nk))[0] if nk > 1 else None     # (ssub / tsub: the FULL-LENGTH basis, the block is detrended before it is down-sampled)
         connected = bool(o.spatial_constraints.get("connected", True))
         deconv = self._init_deconv()
         d = v.d1 * v.d2
@@ -1110,21 +1172,32 @@ class Sources2D:
             pid = v.pid[idx]
             pp, bp = v.patch_pos[idx], v.block_pos[idx]
             nr_b, nc_b = int(bp[1] - bp[0] + 1), int(bp[3] - bp[2] + 1)
-            cn_b, pnr_b, _sn_b = self.engine.peel_open(pid, psf, n, Q, 3.0)
+            d1s, d2s = -(-nr_b // ssub), -(-nc_b // ssub)                # the session's grid (the block itself without down-sampling)
+            if ds:
+                cn_b, pnr_b, _sn_b, yds = self.engine.peel_open_ds(pid, ssub, tsub, psf, n, Q, 3.0, want_video=observer is not None)
+            else:
+                cn_b, pnr_b, _sn_b = self.engine.peel_open(pid, psf, n, Q, 3.0)
             try:
+                cn_s, pnr_s = cn_b.astype(np.float64).reshape(d1s, d2s, order="F"), pnr_b.astype(np.float64).reshape(d1s, d2s, order="F")
+                if ds and observer is not None:
+                    observer(idx, "open", dict(Cn=cn_b, PNR=pnr_b, Yds=yds))
+                if ssub != 1:                                              # greedyROI_endoscope.m:471-472
+                    cn_b, pnr_b = (hostops.imresize_to(x, (nr_b, nc_b)).reshape(-1, order="F") for x in (cn_s, pnr_s))
                 Cn[v.patch_pix[idx]] = cn_b[v.ind_patch[idx]]
                 PNR[v.patch_pix[idx]] = pnr_b[v.ind_patch[idx]]
                 bd4 = [bd if int(pp[j]) == int(bp[j]) else 0 for j in range(4)]      # initComponents_parallel.m:318
+                bd4 = [int(_mround(b / ssub)) for b in bd4]                # greedyROI_endoscope.m:59
                 loc = None
                 if seeds is not None:
-                    loc = [(int(r) - int(bp[0]), int(c) - int(bp[2])) for (r, c) in seeds
+                    loc = [((int(r) - int(bp[0])) // ssub, (int(c) - int(bp[2])) // ssub) for (r, c) in seeds
                            if int(bp[0]) <= int(r) <= int(bp[1]) and int(bp[2]) <= int(c) <= int(bp[3])]
                 sess = _PeelSession(self.engine, pid, gSiz)
-                res = hostops.greedy_roi_block(sess, cn_b.astype(np.float64).reshape(nr_b, nc_b, order="F"), pnr_b.astype(np.float64).reshape(nr_b, nc_b, order="F"),
-                                               gSiz, psf, float(o.min_corr), float(o.min_pnr), float(o.min_pixel), bd4, K, connected, deconv, loc, 3.0,
+                res = hostops.greedy_roi_block(sess, cn_s, pnr_s, gSiz, psf, float(o.min_corr), float(o.min_pnr), min_pixel, bd4, K, connected, deconv, loc, 3.0,
                                                None if observer is None else (lambda kind, data, idx=idx: observer(idx, kind, data)))
             finally:
                 self.engine.peel_close(pid)
+            if ds:
+                res = self._init_upsample(res, ssub, tsub, (d1s, d2s), (nr_b, nc_b), n)
             # initComponents_parallel.m:428-431: the neurons whose seed pixel lies in the patch interior
             ctr = res["center"]
             keep = [k for k in range(ctr.shape[0]) if int(pp[0]) <= ctr[k, 0] + int(bp[0]) - 1 <= int(pp[1]) and int(pp[2]) <= ctr[k, 1] + int(bp[2]) - 1 <= int(pp[3])]

@@ -197,6 +197,30 @@ int cnmfe_peel_open(cnmfe_ctx *ctx, int patch_id, const float *psf, int32_t psf_
 int cnmfe_peel_open_residual(cnmfe_ctx *ctx, int patch_id, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx /* in [0, d) */, const float *A_val,
                              const float *C, int c_order, const float *psf, int32_t psf_n, float sig, float *Cn_patch /* d */, float *PNR_patch /* d */,
                              float *Sn_patch /* d or NULL */, float *Yres_out /* d x T or NULL */, int out_memspace);
+/* options.ssub / options.tsub (greedyROI_endoscope.m:46-61, correlation_pnr_parallel.m:81-100): the same two calls on Yds = dsData(Y) of the block
+ * (utilities/dsData.m:29-43), which is built on the device from the resident centred video in one pass:
+ *   spatial   per frame imresize(., [d1s, d2s], 'box') with d1s = ceil(nr_b / ssub), d2s = ceil(nc_b / ssub): the box kernel stretched by in / out PER
+ *             DIMENSION (antialiasing), taps mirrored at the border, each row of weights normalised (a size ssub does not divide has a scale that is not 1 / ssub);
+ *   temporal  the mean of every tsub consecutive frames, Ts = floor(nframes / tsub), the rest discarded.
+ * Taps then frames are summed in fp64 in a fixed order and rounded once to fp32; two calls are bit-identical.  ssub in 1 .. 8 and tsub >= 1, else
+ * CNMFE_EINVAL; floor(nframes / tsub) < 64 and a derived (bg_ssub) patch are CNMFE_EUNSUPPORTED; otherwise the refusals of cnmfe_seed_images (frame0 = 0).
+ *
+ * cnmfe_seed_images_ds (correlation_pnr_parallel.m:86-96): down-sample first, then the seed pipeline on the SHORT series -- Q is Ts x M.  The caller scales the
+ * filter (gSig / ssub, ceil(gSiz / ssub)) and resizes the d1s x d2s images back.  Scratch of the call: the down-sampled and the filtered video, 2 x 16 *
+ * ceil(Ts / 4) * d1s d2s bytes.
+ *
+ * cnmfe_peel_open_ds: the session on the d1s x d2s grid with Ts frames.  Qpre: nframes x Mpre, the FULL-LENGTH detrend basis (initComponents_parallel.m:341-343
+ * detrends the full block before greedyROI_endoscope.m:52 down-samples it); the two maps commute in exact arithmetic, so the device projects the spatially
+ * resized pixels on Qpre (k_ds_coef) and subtracts the bin means of the trend inside the down-sampling pass: no full-resolution detrended copy exists.  The seed
+ * pipeline then runs with M = 0.  Yw starts as the down-sampled video (Yds_out, may be NULL: exactly that fp32 video, d1s d2s x Ts frame-major, to host or device
+ * memory); y_bg adds box(pixel mean), with Mpre > 0 nothing.  The session keeps 2 x 16 * ceil(Ts / 4) * d1s d2s bytes (CNMFE_ENOMEM names them).
+ * cnmfe_peel_extract / _apply / _close work in the session's geometry: seeds 0-based on the d1s x d2s grid, ci of Ts samples.  ssub = tsub = 1, Mpre = 0 is the
+ * identity: Yds_out is the centred video bit for bit and the images are cnmfe_peel_open's. */
+int cnmfe_seed_images_ds(cnmfe_ctx *ctx, int patch_id, int32_t ssub, int32_t tsub, const float *psf, int32_t psf_n, int64_t nframes,
+                         const double *Q /* Ts x M */, int32_t M, float sig, float *Cn_ds /* d1s * d2s */, float *PNR_ds /* d1s * d2s */);
+int cnmfe_peel_open_ds(cnmfe_ctx *ctx, int patch_id, int32_t ssub, int32_t tsub, const float *psf, int32_t psf_n, int64_t nframes,
+                       const double *Qpre /* nframes x Mpre */, int32_t Mpre, float sig, float *Cn_ds /* d1s * d2s */, float *PNR_ds /* d1s * d2s */,
+                       float *Sn_ds /* d1s * d2s or NULL */, float *Yds_out /* d1s * d2s x Ts or NULL */, int out_memspace);
 int cnmfe_peel_extract(cnmfe_ctx *ctx, int patch_id, int32_t r, int32_t c, int32_t gSiz, double *corr_box /* nr * nc */, double *ai_box /* nr * nc */,
                        double *ci /* nframes */, double *stats /* 6 */);
 int cnmfe_peel_apply(cnmfe_ctx *ctx, int patch_id, int32_t r, int32_t c, int32_t gSiz, const double *ai_box /* nr * nc */,
