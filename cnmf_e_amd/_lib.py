@@ -128,6 +128,10 @@ PROTOTYPES = {
     "cnmfe_deconv_temporal": (C.c_int, [c_ctx, C.c_int32, C.c_int64, f32p, C.c_int, C.POINTER(DeconvOpts), f32p, f32p, f32p, f32p]),
     "cnmfe_deconv_temporal_bound": (C.c_int, [c_ctx, C.POINTER(DeconvOpts), f32p, f32p, f32p, f32p, f32p]),
     "cnmfe_post_process_spatial": (C.c_int, [c_ctx, C.c_int32, C.c_int32, C.c_int32, i64p, i32p, f32p, u8p]),
+    "cnmfe_circular_constraints": (C.c_int, [c_ctx, C.c_int32, C.c_int32, C.c_int32, i64p, i32p, f32p, i32p, i64p, f32p, C.c_int64, u8p, C.c_int]),
+    "cnmfe_search_dilate": (C.c_int, [c_ctx, C.c_int32, C.c_int32, C.c_int32, i64p, i32p, f32p, u8p, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                      i32p, i64p, u8p, C.c_int64, u8p, C.c_int]),
+    "cnmfe_trim_spatial": (C.c_int, [c_ctx, C.c_int32, C.c_int32, C.c_int32, i64p, i32p, f32p, C.c_double, C.c_int32, C.c_int32, u8p, u8p, u8p, C.c_int]),
     "cnmfe_stitch_begin": (C.c_int, [c_ctx, C.c_int32, C.c_int64]),
     "cnmfe_stitch_dims": (C.c_int, [c_ctx, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "cnmfe_stitch_add": (C.c_int, [c_ctx, C.c_int32, i32p]),

@@ -702,7 +702,7 @@ int cnmfe_get_option(cnmfe_ctx *ctx, const char *name, int64_t *value) {
     const struct { const char *n; int64_t v; } counters[] = {{"temporal_early_hits", ctx->early_hits}, {"temporal_early_drops", ctx->early_drops}, {"temporal_early_declined", ctx->early_declined},
                                                               {"temporal_early_entries", ctx->early.nent}, {"temporal_proj_entries", ctx->last_nent}, {"temporal_nowait", ctx->sweep_nowait},
                                                               {"merge_trace_uploads", ctx->merge_uploads}, {"trace_matrix_uploads", ctx->trace_uploads}, {"init_temporal_levels", ctx->last_nlevels}, {"lanes_live", (int64_t)std::max<size_t>(1, ctx->lanes.size())},
-                                                              {"bound_K", ctx->bound_valid ? (int64_t)ctx->bound_K : 0}, {"bound_T", ctx->bound_valid ? ctx->bound_T : 0}};
+                                                              {"image_ops_host_columns", ctx->image_ops_host}, {"bound_K", ctx->bound_valid ? (int64_t)ctx->bound_K : 0}, {"bound_T", ctx->bound_valid ? ctx->bound_T : 0}};
     for (const auto &c : counters) if (!strcmp(c.n, name)) { *value = c.v; return 0; }
     auto it = ctx->opts.find(name);
     if (it == ctx->opts.end()) return fail(CNMFE_EINVAL, "option '%s' is unknown or was never set (its default holds)", name);
@@ -2173,6 +2173,53 @@ int cnmfe_post_process_spatial(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K
     CK(hipSetDevice(ctx->device));
     GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;          // (lanes: lane 0, behind the other lanes; they wait for what this queues)
     return postproc_run(ctx, d1, d2, K, A_colptr, A_rowidx, A_val, keep);
+}
+
+// footprint image operations (footprint_ops.hpp): the arguments every one of them checks, then the context's global scope like cnmfe_post_process_spatial
+static int fp_check(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const void *host_col) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    if (d1 <= 0 || d2 <= 0 || (int64_t)d1 * d2 > INT32_MAX) return fail(CNMFE_EINVAL, "bad dims");
+    RET(check_csc("A", K, (int64_t)d1 * d2, A_colptr, A_rowidx));
+    if (K > 0 && ((!A_val && A_colptr[K] > 0) || !host_col)) return fail(CNMFE_EINVAL, "null A_val / host_col");
+    return 0;
+}
+int cnmfe_circular_constraints(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, int32_t *box,
+                               int64_t *off, float *out, int64_t out_cap, uint8_t *host_col, int out_memspace) {
+    RET(fp_check(ctx, d1, d2, K, A_colptr, A_rowidx, A_val, host_col));
+    if (!box || !off) return fail(CNMFE_EINVAL, "null box / off");
+    if (out_memspace != CNMFE_HOST && out_memspace != CNMFE_DEVICE) return fail(CNMFE_EINVAL, "unknown memspace %d", out_memspace);
+    ctx->image_ops_host = 0; off[0] = 0;
+    if (K == 0) return 0;
+    CK(hipSetDevice(ctx->device));
+    GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
+    return fp_circular_run(ctx, d1, d2, K, A_colptr, A_rowidx, A_val, box, off, out, out_cap, host_col, out_memspace);
+}
+int cnmfe_search_dilate(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const uint8_t *se,
+                        int32_t se_h, int32_t se_w, int32_t nb, double nrgthr, int32_t *box, int64_t *off, uint8_t *out, int64_t out_cap, uint8_t *host_col, int out_memspace) {
+    RET(fp_check(ctx, d1, d2, K, A_colptr, A_rowidx, A_val, host_col));
+    if (!box || !off) return fail(CNMFE_EINVAL, "null box / off");
+    if (!se || se_h <= 0 || se_w <= 0 || se_h > 4096 || se_w > 4096) return fail(CNMFE_EINVAL, "se: null, or a side outside 1 .. 4096");
+    if (!(nrgthr > 0.0 && nrgthr <= 1.0)) return fail(CNMFE_EINVAL, "nrgthr = %g outside (0, 1]", nrgthr);
+    if (nb < 0) return fail(CNMFE_EINVAL, "nb = %d", nb);
+    if (out_memspace != CNMFE_HOST && out_memspace != CNMFE_DEVICE) return fail(CNMFE_EINVAL, "unknown memspace %d", out_memspace);
+    ctx->image_ops_host = 0; off[0] = 0;
+    if (K == 0) return 0;
+    CK(hipSetDevice(ctx->device));
+    GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
+    return fp_dilate_run(ctx, d1, d2, K, A_colptr, A_rowidx, A_val, se, se_h, se_w, nb, nrgthr, box, off, out, out_cap, host_col, out_memspace);
+}
+int cnmfe_trim_spatial(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, double thr, int32_t sz,
+                       int32_t min_pixel, uint8_t *keep, uint8_t *ind_small, uint8_t *host_col, int out_memspace) {
+    RET(fp_check(ctx, d1, d2, K, A_colptr, A_rowidx, A_val, host_col));
+    if (sz < 1 || sz > 9 || !(sz & 1)) return fail(CNMFE_EINVAL, "sz = %d: the square's side is odd, 1 .. 9", sz);
+    if (!(thr >= 0.0)) return fail(CNMFE_EINVAL, "thr = %g is negative", thr);
+    if (out_memspace != CNMFE_HOST && out_memspace != CNMFE_DEVICE) return fail(CNMFE_EINVAL, "unknown memspace %d", out_memspace);
+    ctx->image_ops_host = 0;
+    if (K == 0) return 0;
+    if ((!keep && A_colptr[K] > 0) || !ind_small) return fail(CNMFE_EINVAL, "null keep / ind_small");
+    CK(hipSetDevice(ctx->device));
+    GlobalScope gs_(ctx); if (gs_.rc) return gs_.rc;
+    return fp_trim_run(ctx, d1, d2, K, A_colptr, A_rowidx, A_val, thr, sz, min_pixel, keep, ind_small, host_col, out_memspace);
 }
 
 int cnmfe_profile_enable(cnmfe_ctx *ctx, int on) { if (!ctx) return fail(CNMFE_EINVAL, "null context"); ctx->prof.drain(); ctx->prof.on = on == 2 ? 2 : (on != 0); return 0; }

@@ -469,6 +469,8 @@ struct cnmfe_ctx : cnmfe::LaneState {
     int64_t residents_gen = -1; bool res_has_s = false;
     cnmfe::DevBuf mrg[23];                                 // [0] an uploaded source, [1] the result of cnmfe_trace_diff_spikes (diff_K x diff_T), [2..5] moments / K x K / sn, [6..22] cnmfe_merge_apply
     int32_t diff_K = 0; int64_t diff_T = 0;
+    cnmfe::DevBuf fpo[4];                                  // footprint image operations (footprint_ops.hpp): [0] the boxes' offsets, [1] the result, [2] the structuring element, [3] counts
+    int64_t image_ops_host = 0;                            // counter image_ops_host_columns: columns the last such call left to the caller (box above FP_MAX_CELLS)
     int64_t trace_uploads = 0;                             // counter trace_matrix_uploads: K x T matrices ANY entry point took through a pointer (upload_traces; a bound matrix or rows of it do not count)
     int64_t last_nlevels = 0;                              // counter init_temporal_levels: launches of level kernels the last cnmfe_init_temporal queued itself (the depth of its schedule)
     int64_t merge_uploads = 0;                             // counter merge_trace_uploads: K x T matrices the merge / tag entry points took from the host
@@ -651,6 +653,12 @@ int merge_apply_run(cnmfe_ctx *ctx, int32_t ng, const int32_t *gptr, const int32
                     const cnmfe_deconv_opts *opts, float *C_out, float *C_raw_out, float *S_out, float *pars_out, float *sn_out);
 int postproc_run(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx,
                  const float *A_val, uint8_t *keep);
+int fp_circular_run(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, int32_t *box_out,
+                    int64_t *off, float *out, int64_t out_cap, uint8_t *host_col, int out_memspace);                                  // factor.hip (footprint_ops.hpp)
+int fp_dilate_run(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const uint8_t *se,
+                  int32_t se_h, int32_t se_w, int32_t nb, double nrgthr, int32_t *box_out, int64_t *off, uint8_t *out, int64_t out_cap, uint8_t *host_col, int out_memspace);
+int fp_trim_run(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, double thr, int32_t sz,
+                int32_t min_pixel, uint8_t *keep, uint8_t *ind_small, uint8_t *host_col, int out_memspace);
 int ensure_ymean(cnmfe_ctx *ctx, Patch *P);
 int sn_video_run(cnmfe_ctx *ctx, Patch *P, int64_t nframes, float *sn_out);
 int seed_images_run(cnmfe_ctx *ctx, const SeedSrc &src, const float *psf, int32_t psf_n, int64_t nframes, const double *Q, int32_t M, float sig,

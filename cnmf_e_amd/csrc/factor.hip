@@ -336,6 +336,7 @@ __global__ void __launch_bounds__(1024) k_hals_temporal_jobs(const HJobDev *__re
     const HJobDev j = jobs[e.x];
     hals_temporal_one(e.y, (const int *)j.nptr, (const int *)j.nidx, (const float *)j.nval, (const float *)j.aa, (const float *)j.U, (float *)j.C, (float *)j.Craw, j.ldc, T, red);
 }
+#include "footprint_ops.hpp"       // the other image operations on one footprint's box: circular_constraints, threshold + dilate, trimSpatial
 // ---- S6: connectivity_constraint.m:1-18 on a per-neuron box -------------------------------------------
 constexpr int PP_MAX = 64;    // max box side (bbox + 2 px margin each side)
 __global__ void __launch_bounds__(256) k_connectivity(const int64_t *__restrict__ colptr, const int *__restrict__ erow, const float *__restrict__ aval,
@@ -1068,6 +1069,112 @@ int postproc_run(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_
            dBox.as<int4>(), d1, d2, dKeep.as<unsigned char>());
     CK(hipMemcpyAsync(keep, dKeep.p, (size_t)nnz, hipMemcpyDeviceToHost, ctx->st()));
     CK(hipStreamSynchronize(ctx->st()));
+    return 0;
+}
+
+// ---- footprint image operations (footprint_ops.hpp): the host side ---------------------------------------------------------------------------------
+// box[k] = the bounding box of the NON-ZEROS of column k grown by `margin` and clipped to the field of view, (r0, c0, h, w); off[k] = the cells of the boxes in
+// front of it.  A column without a non-zero has h = w = 0; so has one whose box has more than FP_MAX_CELLS cells (or every column, with host_all): host_col[k] = 1,
+// the caller computes it.  Returns the number of such columns.
+static int64_t fp_boxes(int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, int margin, bool host_all,
+                        std::vector<int4> &box, int64_t *off, uint8_t *host_col) {
+    box.assign(K, make_int4(0, 0, 0, 0));
+    int64_t nhost = 0, cells = 0;
+    for (int k = 0; k < K; ++k) {
+        int rmin = d1, rmax = -1, cmin = d2, cmax = -1;
+        for (int64_t e = A_colptr[k]; e < A_colptr[k + 1]; ++e) {
+            if (A_val[e] == 0.f) continue;
+            const int r = A_rowidx[e] % d1, c = A_rowidx[e] / d1;
+            rmin = std::min(rmin, r); rmax = std::max(rmax, r); cmin = std::min(cmin, c); cmax = std::max(cmax, c);
+        }
+        off[k] = cells; host_col[k] = 0;
+        if (rmax < 0) continue;
+        const int r0 = std::max(0, rmin - margin), r1 = std::min(d1 - 1, rmax + margin), c0 = std::max(0, cmin - margin), c1 = std::min(d2 - 1, cmax + margin);
+        const int64_t n = (int64_t)(r1 - r0 + 1) * (c1 - c0 + 1);
+        if (host_all || n > FP_MAX_CELLS) { host_col[k] = 1; ++nhost; continue; }
+        box[k] = make_int4(r0, c0, r1 - r0 + 1, c1 - c0 + 1);
+        cells += n;
+    }
+    off[K] = cells;
+    return nhost;
+}
+static void fp_boxes_out(const std::vector<int4> &box, int32_t *out) {
+    for (size_t k = 0; k < box.size(); ++k) { out[4 * k] = box[k].x; out[4 * k + 1] = box[k].y; out[4 * k + 2] = box[k].z; out[4 * k + 3] = box[k].w; }
+}
+// the call's A and its boxes on the device, in the slots the connectivity step uses (a kept spatial result of this lane ends here)
+static int fp_upload(cnmfe_ctx *ctx, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const std::vector<int4> &box) {
+    DevBuf *S_ = ctx->scr;
+    const int64_t nnz = A_colptr[K];
+    ctx->kept.drop();
+    RET(to_dev(ctx, S_[kept::SCR_COLPTR], A_colptr, (size_t)K + 1));
+    RET(to_dev(ctx, S_[kept::SCR_EROW], A_rowidx, (size_t)nnz));
+    RET(to_dev(ctx, S_[kept::SCR_AVAL], A_val, (size_t)nnz));
+    RET(to_dev(ctx, S_[13], box.data(), box.size()));
+    return 0;
+}
+template <class T> static int fp_result(cnmfe_ctx *ctx, T *out, const T *dev, size_t n, int out_memspace) {
+    if (n) CK(hipMemcpyAsync(out, dev, n * sizeof(T), out_memspace == CNMFE_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->st()));
+    CK(hipStreamSynchronize(ctx->st()));
+    return ctx_check_errflag(ctx);
+}
+
+int fp_circular_run(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, int32_t *box_out,
+                    int64_t *off, float *out, int64_t out_cap, uint8_t *host_col, int out_memspace) {
+    std::vector<int4> box;
+    ctx->image_ops_host = fp_boxes(d1, d2, K, A_colptr, A_rowidx, A_val, 0, false, box, off, host_col);
+    fp_boxes_out(box, box_out);
+    if (!out || off[K] == 0) return 0;
+    if (out_cap < off[K]) return fail(CNMFE_EINVAL, "out holds %lld cells, the boxes have %lld (call with out = NULL for the sizes)", (long long)out_cap, (long long)off[K]);
+    RET(fp_upload(ctx, K, A_colptr, A_rowidx, A_val, box));
+    RET(to_dev(ctx, ctx->fpo[0], off, (size_t)K + 1));
+    RET(ctx->fpo[1].ensure((size_t)off[K] * sizeof(float)));
+    DevBuf *S_ = ctx->scr;
+    LAUNCH(ctx, "fp_circular", k_fp_circular, dim3(K), dim3(FP_NT), 0, S_[kept::SCR_COLPTR].as<int64_t>(), S_[kept::SCR_EROW].as<int>(), S_[kept::SCR_AVAL].as<float>(),
+           S_[13].as<int4>(), ctx->fpo[0].as<int64_t>(), d1, d2, ctx->fpo[1].as<float>());
+    return fp_result(ctx, out, ctx->fpo[1].as<float>(), (size_t)off[K], out_memspace);
+}
+
+int fp_dilate_run(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const uint8_t *se,
+                  int32_t se_h, int32_t se_w, int32_t nb, double nrgthr, int32_t *box_out, int64_t *off, uint8_t *out, int64_t out_cap, uint8_t *host_col, int out_memspace) {
+    std::vector<int4> box;
+    // an element with an even side (its origin is a convention of its own) or a side above FP_MAX_SE: every column is the caller's
+    const bool host_all = !(se_h & 1) || !(se_w & 1) || se_h > FP_MAX_SE || se_w > FP_MAX_SE;
+    const int margin = FP_CLOSE_MARGIN + std::max(se_h, se_w) / 2;
+    ctx->image_ops_host = fp_boxes(d1, d2, K, A_colptr, A_rowidx, A_val, margin, host_all, box, off, host_col);
+    fp_boxes_out(box, box_out);
+    if (!out || off[K] == 0) return 0;
+    if (out_cap < off[K]) return fail(CNMFE_EINVAL, "out holds %lld cells, the boxes have %lld (call with out = NULL for the sizes)", (long long)out_cap, (long long)off[K]);
+    RET(fp_upload(ctx, K, A_colptr, A_rowidx, A_val, box));
+    RET(to_dev(ctx, ctx->fpo[0], off, (size_t)K + 1));
+    RET(ctx->fpo[1].ensure((size_t)off[K]));
+    RET(to_dev(ctx, ctx->fpo[2], se, (size_t)se_h * se_w));
+    DevBuf *S_ = ctx->scr;
+    LAUNCH(ctx, "fp_threshold_dilate", k_fp_threshold_dilate, dim3(K), dim3(FP_NT), 0, S_[kept::SCR_COLPTR].as<int64_t>(), S_[kept::SCR_EROW].as<int>(),
+           S_[kept::SCR_AVAL].as<float>(), S_[13].as<int4>(), ctx->fpo[0].as<int64_t>(), d1, d2, K, nb, 1.0 - nrgthr, ctx->fpo[2].as<unsigned char>(), se_h, se_w,
+           ctx->fpo[1].as<unsigned char>());
+    return fp_result(ctx, out, ctx->fpo[1].as<unsigned char>(), (size_t)off[K], out_memspace);
+}
+
+int fp_trim_run(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, double thr, int32_t sz,
+                int32_t min_pixel, uint8_t *keep, uint8_t *ind_small, uint8_t *host_col, int out_memspace) {
+    std::vector<int4> box; std::vector<int64_t> off((size_t)K + 1);
+    ctx->image_ops_host = fp_boxes(d1, d2, K, A_colptr, A_rowidx, A_val, 0, false, box, off.data(), host_col);
+    const int64_t nnz = A_colptr[K];
+    // a column without a non-zero keeps its (zero) entries and is small when min_pixel > 0; a host column's flags are the caller's
+    for (int k = 0; k < K; ++k) ind_small[k] = !host_col[k] && 0 < min_pixel;
+    if (nnz == 0) return 0;
+    RET(fp_upload(ctx, K, A_colptr, A_rowidx, A_val, box));
+    RET(ctx->fpo[1].ensure((size_t)nnz));
+    RET(ctx->fpo[3].ensure((size_t)K * sizeof(int)));
+    CK(hipMemsetAsync(ctx->fpo[1].p, 1, (size_t)nnz, ctx->st()));
+    CK(hipMemsetAsync(ctx->fpo[3].p, 0, (size_t)K * sizeof(int), ctx->st()));
+    DevBuf *S_ = ctx->scr;
+    LAUNCH(ctx, "fp_trim", k_fp_trim, dim3(K), dim3(FP_NT), 0, S_[kept::SCR_COLPTR].as<int64_t>(), S_[kept::SCR_EROW].as<int>(), S_[kept::SCR_AVAL].as<float>(),
+           S_[13].as<int4>(), d1, d2, thr, sz / 2, ctx->fpo[1].as<unsigned char>(), ctx->fpo[3].as<int>());
+    std::vector<int> cnt((size_t)K);
+    CK(hipMemcpyAsync(cnt.data(), ctx->fpo[3].p, (size_t)K * sizeof(int), hipMemcpyDeviceToHost, ctx->st()));
+    RET(fp_result(ctx, keep, ctx->fpo[1].as<unsigned char>(), (size_t)nnz, out_memspace));
+    for (int k = 0; k < K; ++k) if (!host_col[k]) ind_small[k] = cnt[k] < min_pixel;                  // :958
     return 0;
 }
 

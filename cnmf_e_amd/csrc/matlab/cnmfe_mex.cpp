@@ -35,6 +35,9 @@
 //   rss = cnmfe_mex('compute_rss', h, pid, A_patch, C_or_rows, b0_block, b0_new_patch)
 //   Ybg = cnmfe_mex('reconstruct_background', h, pid, b0_block, b0_new_patch, frame0, nframes)
 //   keep = cnmfe_mex('postprocess', h, A, d1, d2)                          post_process_spatial.m:19-32 (connected)
+//   [box, off, out, host_col] = cnmfe_mex('circular_constraints', h, A, d1, d2)                  circular_constraints.m:8-55 per column (compactSpatial)
+//   [box, off, out, host_col] = cnmfe_mex('search_dilate', h, A, d1, d2, se, nb, nrgthr)         determine_search_location(A, 'dilate', ...) with the element se
+//   [keep, ind_small, host_col] = cnmfe_mex('trim_spatial', h, A, d1, d2, thr, sz, min_pixel)    Sources2D.m:942-965 (trimSpatial)
 // Round 6 -- the calls the measured host (cnmf_e_amd/sources2d.py, bench.py) makes and this gateway lacked; the .m twins use them:
 //   cnmfe_mex('set_option', h, name, value)                                cnmfe_set_option (the tunables of include/cnmfe.h; the defaults ARE the fast path)
 //   cnmfe_mex('synchronize', h)                                            wait for the context's stream; reports what its kernels raised
@@ -458,6 +461,56 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
         pout[0] = mxCreateLogicalMatrix((size_t)A.nnz, 1);
         mxLogical *k = mxGetLogicals(pout[0]);
         for (int64_t i = 0; i < A.nnz; ++i) k[i] = keep[i] != 0;
+        return;
+    }
+    // footprint image operations (include/cnmfe.h): both calls of a boxed operation -- the sizes, then the result -- are made here.  box: 4 x K, rows (r0, c0, h, w)
+    // with r0, c0 1-BASED; off: (K + 1) x 1, 0-based cell offsets into out; out: the cells of the boxes, column-major box after box; host_col: the columns left to the caller
+    if (!strcmp(cmd, "circular_constraints") || !strcmp(cmd, "search_dilate")) {
+        const bool dil = cmd[0] == 's';
+        if (nin != (dil ? 8 : 5)) FAIL("%s: %d inputs required", cmd, dil ? 8 : 5);
+        Csc A = csc_of(pin[2]);
+        const int32_t d1 = (int32_t)mxGetScalar(pin[3]), d2 = (int32_t)mxGetScalar(pin[4]);
+        const size_t K = (size_t)A.K;
+        int32_t *box = (int32_t *)mxCalloc(4 * K + 4, sizeof(int32_t));
+        int64_t *off = (int64_t *)mxCalloc(K + 1, sizeof(int64_t));
+        uint8_t *hc = (uint8_t *)mxCalloc(K + 1, 1), *se = NULL;
+        int32_t sh = 0, sw = 0, nb = 0; double nrgthr = 0;
+        if (dil) {
+            sh = (int32_t)mxGetM(pin[5]); sw = (int32_t)mxGetN(pin[5]); nb = (int32_t)mxGetScalar(pin[6]); nrgthr = mxGetScalar(pin[7]);
+            if (!mxIsLogical(pin[5]) && !mxIsDouble(pin[5])) FAIL("search_dilate: se is a logical or double matrix");
+            se = (uint8_t *)mxCalloc((size_t)sh * sw + 1, 1);
+            for (int32_t i = 0; i < sh; ++i) for (int32_t j = 0; j < sw; ++j)                                  // column-major -> row-major
+                se[(size_t)i * sw + j] = mxIsLogical(pin[5]) ? mxGetLogicals(pin[5])[i + (size_t)j * sh] != 0 : mxGetPr(pin[5])[i + (size_t)j * sh] != 0;
+        }
+        void *out = NULL;
+        for (int pass = 0; pass < 2; ++pass) {
+            const int64_t cap = pass ? off[K] : 0;
+            if (pass) { if (cap == 0) break; out = mxCalloc((size_t)cap, dil ? 1 : sizeof(float)); }
+            if (dil) CHECK(cnmfe_search_dilate(c, d1, d2, A.K, A.cp, A.ri, A.v, se, sh, sw, nb, nrgthr, box, off, (uint8_t *)out, cap, hc, CNMFE_HOST));
+            else CHECK(cnmfe_circular_constraints(c, d1, d2, A.K, A.cp, A.ri, A.v, box, off, (float *)out, cap, hc, CNMFE_HOST));
+        }
+        pout[0] = mxCreateDoubleMatrix(4, K, mxREAL);
+        for (size_t k = 0; k < K; ++k) for (int j = 0; j < 4; ++j) mxGetPr(pout[0])[4 * k + j] = (double)box[4 * k + j] + (j < 2 && box[4 * k + 2] > 0 ? 1.0 : 0.0);
+        if (nout > 1) { pout[1] = mxCreateDoubleMatrix(K + 1, 1, mxREAL); for (size_t k = 0; k <= K; ++k) mxGetPr(pout[1])[k] = (double)off[k]; }
+        if (nout > 2) {
+            const size_t n = (size_t)off[K];
+            if (dil) { pout[2] = mxCreateLogicalMatrix(n, 1); for (size_t i = 0; i < n; ++i) mxGetLogicals(pout[2])[i] = ((uint8_t *)out)[i] != 0; }
+            else { pout[2] = mxCreateNumericMatrix(n, 1, mxSINGLE_CLASS, mxREAL); if (n) memcpy(mxGetData(pout[2]), out, n * sizeof(float)); }
+        }
+        if (nout > 3) { pout[3] = mxCreateLogicalMatrix(K, 1); for (size_t k = 0; k < K; ++k) mxGetLogicals(pout[3])[k] = hc[k] != 0; }
+        return;
+    }
+    if (!strcmp(cmd, "trim_spatial")) {                         // [keep, ind_small, host_col] = cnmfe_mex('trim_spatial', h, A, d1, d2, thr, sz, min_pixel)
+        if (nin != 8) FAIL("trim_spatial: 8 inputs required");
+        Csc A = csc_of(pin[2]);
+        const size_t K = (size_t)A.K;
+        uint8_t *keep = (uint8_t *)mxCalloc((size_t)A.nnz + 1, 1), *small = (uint8_t *)mxCalloc(K + 1, 1), *hc = (uint8_t *)mxCalloc(K + 1, 1);
+        CHECK(cnmfe_trim_spatial(c, (int32_t)mxGetScalar(pin[3]), (int32_t)mxGetScalar(pin[4]), A.K, A.cp, A.ri, A.v, mxGetScalar(pin[5]), (int32_t)mxGetScalar(pin[6]),
+                                 (int32_t)mxGetScalar(pin[7]), keep, small, hc, CNMFE_HOST));
+        pout[0] = mxCreateLogicalMatrix((size_t)A.nnz, 1);
+        for (int64_t i = 0; i < A.nnz; ++i) mxGetLogicals(pout[0])[i] = keep[i] != 0;
+        if (nout > 1) { pout[1] = mxCreateLogicalMatrix(K, 1); for (size_t k = 0; k < K; ++k) mxGetLogicals(pout[1])[k] = small[k] != 0; }
+        if (nout > 2) { pout[2] = mxCreateLogicalMatrix(K, 1); for (size_t k = 0; k < K; ++k) mxGetLogicals(pout[2])[k] = hc[k] != 0; }
         return;
     }
     if (!strcmp(cmd, "set_option")) {                           // cnmfe_mex('set_option', h, name, value)

@@ -330,6 +330,8 @@ class Engine:
     supports_init_temporal = True     # init_temporal() / init_temporal_job()
     supports_init_ds = True           # seed_images_ds() / peel_open_ds(): options.ssub / options.tsub of the seed images and the first initialisation
     supports_traces_grow = True       # traces_grow(): zero rows under the bound matrix and its residents, on the device
+    supports_image_ops = True         # circular_constraints() / search_dilate() / trim_spatial(): the image operations on single footprints (footprint_ops.hpp)
+    IMAGE_OPS_MAX_BOX = 4096          # cells of the largest box those kernels take (FP_MAX_CELLS); a column above it is computed by hostops and spliced in
 
     # pinned buffers of LazyHostTraces, recycled by size (page-locking 20 MB costs milliseconds)
     def _pinned_take(self, nbytes):
@@ -1231,6 +1233,88 @@ class Engine:
         out = sp.csc_matrix((va * keep, ri.copy(), cp.copy()), shape=(d1 * d2, K))
         out.eliminate_zeros()
         return out
+
+    # ---- image operations on single footprints (include/cnmfe.h, "footprint image operations") -----------------------
+    @staticmethod
+    def _box_cells(box, off, K, d1):
+        """(column, pixel) of every cell of the boxes, in the order of the device's result: column after column, column-major inside a box"""
+        h = box[:, 2].astype(np.int64)
+        col = np.repeat(np.arange(K), (off[1:] - off[:-1]))
+        loc = np.arange(int(off[K]), dtype=np.int64) - off[col]
+        hc = h[col]
+        return col, (box[col, 1] + loc // hc) * d1 + box[col, 0] + loc % hc
+
+    @staticmethod
+    def _splice(out, host, sel, shape, dtype):
+        """`out` with the columns `sel`, empty so far, taken from `host` (the same columns computed by hostops)"""
+        host = sp.coo_matrix(host)
+        add = sp.csc_matrix((host.data.astype(dtype), (host.row, sel[host.col])), shape=shape)
+        out = sp.csc_matrix(out + add, dtype=dtype)
+        out.sort_indices()
+        return out
+
+    def _boxed(self, fn, head, tail, K, d1, out_dtype, out_ptr):
+        """the two calls of a boxed operation: the sizes, then the result"""
+        box = np.zeros((max(K, 1), 4), dtype=np.int32); off = np.zeros(K + 1, dtype=np.int64); host_col = np.zeros(max(K, 1), dtype=np.uint8)
+        none = C.cast(None, out_ptr)
+        L.check(fn(*head, *tail, _p(box, L.i32p), _p(off, L.i64p), none, 0, _p(host_col, L.u8p), L.HOST))
+        out = np.zeros(int(off[K]), dtype=out_dtype)
+        if out.size:
+            L.check(fn(*head, *tail, _p(box, L.i32p), _p(off, L.i64p), _p(out, out_ptr), out.size, _p(host_col, L.u8p), L.HOST))
+        col, pix = self._box_cells(box[:K], off, K, d1)
+        nz = np.flatnonzero(out)
+        return col[nz], pix[nz], out[nz], np.flatnonzero(host_col[:K])
+
+    def circular_constraints(self, A_full, d1, d2):
+        """circular_constraints (endoscope/circular_constraints.m:8-55) of every column of the d1*d2 x K matrix: what hostops.circular_constraints_columns
+        returns, as float32.  A column whose bounding box has more than IMAGE_OPS_MAX_BOX cells is computed there (counter image_ops_host_columns)."""
+        from . import hostops
+        A_full = sp.csc_matrix(A_full)
+        K, cp, ri, va = _csc(A_full, d1 * d2)
+        col, pix, val, sel = self._boxed(L.lib.cnmfe_circular_constraints, (self._ctx, d1, d2, K, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p)), (), K, d1,
+                                         np.float32, L.f32p)
+        out = sp.csc_matrix((val, pix, np.concatenate([[0], np.cumsum(np.bincount(col, minlength=K))])), shape=(d1 * d2, K))
+        if sel.size:
+            out = self._splice(out, hostops.circular_constraints_columns(A_full[:, sel].astype(np.float32), d1, d2), sel, out.shape, np.float32)
+        return out
+
+    def search_dilate(self, A_full, d1, d2, se, nb=1, nrgthr=0.99):
+        """IND = determine_search_location(A, 'dilate', ...) with the structuring element `se`: what hostops.search_location_dilate returns"""
+        from . import hostops
+        A_full = sp.csc_matrix(A_full)
+        K, cp, ri, va = _csc(A_full, d1 * d2)
+        se8 = np.ascontiguousarray(np.atleast_2d(np.asarray(se, dtype=bool)), dtype=np.uint8)
+        col, pix, val, sel = self._boxed(L.lib.cnmfe_search_dilate, (self._ctx, d1, d2, K, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p)),
+                                         (_p(se8, L.u8p), se8.shape[0], se8.shape[1], int(nb), float(nrgthr)), K, d1, np.uint8, L.u8p)
+        out = sp.csc_matrix((np.ones(pix.size, dtype=bool), pix, np.concatenate([[0], np.cumsum(np.bincount(col, minlength=K))])), shape=(d1 * d2, K))
+        if sel.size:
+            # (the rule for the last nb columns counts from the end of the WHOLE matrix)
+            host = sp.hstack([hostops.search_location_dilate(A_full[:, [k]].astype(np.float32), d1, d2, se, 1 if k >= K - nb else 0, nrgthr) for k in sel], format="csc")
+            out = self._splice(out, host, sel, out.shape, bool)
+        return out
+
+    def trim_spatial(self, A_full, d1, d2, thr=0.01, sz=5, min_pixel=0):
+        """trimSpatial (@Sources2D/Sources2D.m:942-965): (the trimmed matrix as float32, ind_small) -- what hostops.trim_spatial returns"""
+        from . import hostops
+        sz = int(sz)
+        if sz < 1 or sz > 9 or sz % 2 == 0:
+            raise ValueError("trim_spatial: sz = %d; the square's side is odd, 1 .. 9" % sz)
+        A_full = sp.csc_matrix(A_full)
+        K, cp, ri, va = _csc(A_full, d1 * d2)
+        keep = np.ones(cp[-1], dtype=np.uint8); small = np.zeros(max(K, 1), dtype=np.uint8); host_col = np.zeros(max(K, 1), dtype=np.uint8)
+        L.check(L.lib.cnmfe_trim_spatial(self._ctx, d1, d2, K, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p), float(thr), sz, int(min_pixel), _p(keep, L.u8p),
+                                         _p(small, L.u8p), _p(host_col, L.u8p), L.HOST))
+        out = sp.csc_matrix((va * keep, ri.copy(), cp.copy()), shape=(d1 * d2, K))
+        out.eliminate_zeros()
+        small = small[:K].astype(bool)
+        sel = np.flatnonzero(host_col[:K])
+        if sel.size:
+            hA, hs = hostops.trim_spatial(A_full[:, sel].astype(np.float32), d1, d2, thr, sz, min_pixel)
+            keep_cols = np.ones(K, dtype=np.float32); keep_cols[sel] = 0
+            out = self._splice(out @ sp.diags(keep_cols), hA, sel, out.shape, np.float32)
+            out.eliminate_zeros()
+            small[sel] = hs
+        return out, small
 
     # ---- measurement ---------------------------------------------------------------
     def profile(self, on=True):

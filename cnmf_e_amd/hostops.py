@@ -1,10 +1,14 @@
 """Host-side image operations on single footprints: the optional branches around the spatial update.
 
   search_method = 'dilate'        utilities/determine_search_location.m:89-94  (threshold_components.m:1-63 + imdilate)
-  spatial_constraints.circular    endoscope/circular_constraints.m:1-55
+  spatial_constraints.circular    endoscope/circular_constraints.m:1-55   (also Sources2D.compactSpatial)
+  trimSpatial                     @Sources2D/Sources2D.m:942-965
 
-Both are off in every demo (CNMFSetParms.m: search_method 'ellipse', circular false) and work on one d1 x d2 image per neuron, so they
-stay on the host next to determine_search_location's ellipse branch ("host-side prerequisite; tiny").  The Image
+CNMFSetParms.m sets search_method 'ellipse' and circular false, but the demos do not all leave them there: demo_batch_1p.m:19 and demo_sfn_2018.m:19 set
+with_dendrites = true, which selects search_method = 'dilate', and demo_large_data_1p.m:132 / demo_sfn_2018.m:130 / demo_endoscope.m:135-136 call
+compactSpatial (circular_constraints per column) and trimSpatial.  An engine that declares supports_image_ops runs these on the device (csrc/footprint_ops.hpp) and
+EQUALS the functions here, which remain the statement of the arithmetic, the path of every other engine, and the path of a column whose box exceeds
+Engine.IMAGE_OPS_MAX_BOX.  Each works on one d1 x d2 image per neuron.  The Image
 Processing Toolbox calls are written with scipy.ndimage under the toolbox's documented border rules: medfilt2 pads with zeros, imdilate
 with -Inf, imerode with +Inf; bwlabel(., 4) / bwlabeln(., 8) are 4- / 8-connected; strel('disk', R, 0) is the exact disc x^2 + y^2 <= R^2.
 
@@ -138,6 +142,34 @@ def circular_constraints_columns(A, d1, d2):
     out = sp.csc_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=A.shape)
     out.sort_indices()
     return out
+
+
+def trim_spatial(A, d1, d2, thr=0.01, sz=5, min_pixel=0):
+    """ind_small = obj.trimSpatial(thr, sz) (@Sources2D/Sources2D.m:942-965) for every column of a sparse d x K matrix: open with a sz x sz square, threshold at
+    thr * max(ai), keep the 4-connected component that holds the maximum of the OPENED image (nothing is zeroed when the opening removed everything: l is all
+    zero); ind_small(m) = sum(ai > 0) < min_pixel.  Returns (the trimmed matrix, ind_small).  An even sz is refused: the toolbox's origin of an even element is a
+    rule of its own that nothing here needs."""
+    sz = int(sz)
+    if sz < 1 or sz > 9 or sz % 2 == 0:
+        raise ValueError("trim_spatial: sz = %d; the square's side is odd, 1 .. 9" % sz)
+    A = sp.csc_matrix(A)
+    K = A.shape[1]
+    ind_small = np.zeros(K, dtype=bool)
+    rows, cols, vals = [], [], []
+    for k in range(K):
+        col = A.getcol(k)
+        img = np.asarray(col.todense(), dtype=np.float64).reshape(d1, d2, order="F")
+        if col.nnz:
+            ai_open = ndi.maximum_filter(ndi.minimum_filter(img, size=sz, mode="constant", cval=np.inf), size=sz, mode="constant", cval=-np.inf)   # :951
+            lab, _ = ndi.label(ai_open > img.max() * thr, structure=CROSS4)                                                                     # :953-954
+            ind_max = int(np.argmax(ai_open.reshape(-1, order="F")))                                                                            # :955
+            img[lab != lab[ind_max % d1, ind_max // d1]] = 0                                                                                    # :957
+        ind_small[k] = np.count_nonzero(img > 0) < min_pixel                                                                                    # :958
+        nz = np.nonzero(img.reshape(-1, order="F"))[0]
+        rows.append(nz); cols.append(np.full(nz.size, k)); vals.append(img.reshape(-1, order="F")[nz].astype(A.dtype))
+    out = sp.csc_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=A.shape) if K else sp.csc_matrix(A.shape, dtype=A.dtype)
+    out.sort_indices()
+    return out, ind_small
 
 
 # --------------------------------------------------------------------------------------

@@ -753,6 +753,7 @@ class Sources2D:
         self._prefetch_wanted = False   # _spatial_finish: the next search masks are to start under the temporal update's sweep call; _start_wanted_prefetch clears it
         self._ind_future = None         # (A, future of A's search masks) of _prefetch_search_location; taken by _search_location_csc, ignored unless A is self.A
         self._pool = None               # the mask thread's executor, made on first use
+        self.image_ops_on_device = True # the 'dilate' masks, the circular tail, compactSpatial and trimSpatial on the engine when it declares supports_image_ops; False: hostops (same results)
         self._gather_cap = 0            # _gather_sparse: entries per rank its padded block holds; grows with the gathered counts
         self._cmean_of = None           # the C whose row means _cmean holds; any other self.C voids them
         self._init_observer = None      # tests: set to a function the two initialisations call at every step; never reset
@@ -1937,7 +1938,7 @@ class Sources2D:
             A_pp = self._post_process(A_raw) if o.spatial_constraints.get("connected", True) else A_raw      # :341, :24-26
         self.A = A_pp                                                                                # :341 (A_pp given: done with the fetch)
         if o.spatial_constraints.get("circular", False):                                            # post_process_spatial.m:28-30
-            self.A = hostops.circular_constraints_columns(self.A, v.d1, v.d2)
+            self.A = self._circular_columns(self.A)
         self._update_b0_new()                                                                        # :347-351
         # the NEXT spatial update's masks depend on this A only: their thread starts under the temporal update's blocking (GIL-free) sweep call (or the next fit call), not
         # here, where its Python would share the GIL with the temporal set-up the device waits for (0.4 ms of a rank's 4.3 at c4).  CNMFE_PREFETCH_EARLY=1, one patch: at once
@@ -1953,6 +1954,38 @@ class Sources2D:
         the spatial -> temporal hand-over where the device idles)"""
         v = self.video
         return self.engine.post_process_spatial(A_, v.d1, v.d2)
+
+    def _image_ops_device(self, A):
+        """the image operations on single footprints run on the engine: asked for (image_ops_on_device), offered (supports_image_ops), and A holds the fp32 values
+        the kernels read (any other type goes through hostops, whose float64 sees every bit of it)"""
+        return bool(self.image_ops_on_device) and self._can("image_ops") and A.dtype == np.float32
+
+    def _circular_columns(self, A):
+        v = self.video
+        if self._image_ops_device(A):
+            return self.engine.circular_constraints(A, v.d1, v.d2)
+        return hostops.circular_constraints_columns(A, v.d1, v.d2)
+
+    def compactSpatial(self):
+        """obj.compactSpatial() (@Sources2D/Sources2D.m:968-974): circular_constraints on every footprint.  Replaces obj.A and nothing else: A_prev, the bound
+        traces, W and b0 stay, and a search mask prefetched for the old A is not used (_search_location_csc takes a prefetch only for the A it was made from)."""
+        self.A = self._circular_columns(sp.csc_matrix(self.A))
+
+    def trimSpatial(self, thr=0.01, sz=5):
+        """ind_small = obj.trimSpatial(thr, sz) (@Sources2D/Sources2D.m:942-965): every footprint keeps the 4-connected component, above thr * max, of its
+        opening by a sz x sz square that holds the opening's maximum.  Replaces obj.A; returns the boolean ind_small (fewer than options.min_pixel positive
+        pixels are left) and deletes nothing, as the reference (:963-964 are comments there).  sz is odd, 1 .. 9 (ValueError otherwise)."""
+        v = self.video
+        sz = int(sz)
+        if sz < 1 or sz > 9 or sz % 2 == 0:
+            raise ValueError("trimSpatial: sz = %d; the square's side is odd, 1 .. 9" % sz)
+        A = sp.csc_matrix(self.A)
+        min_pixel = int(np.ceil(self.options.min_pixel))                   # (a count below a fractional bound is a count below its ceiling)
+        if self._image_ops_device(A):
+            self.A, ind_small = self.engine.trim_spatial(A, v.d1, v.d2, thr, sz, min_pixel)
+        else:
+            self.A, ind_small = hostops.trim_spatial(A, v.d1, v.d2, thr, sz, min_pixel)
+        return ind_small
 
     def _start_wanted_prefetch(self):
         if self._prefetch_wanted:
@@ -1995,9 +2028,12 @@ class Sources2D:
         if o.search_method == "dilate":
             # update_spatial_parallel.m:56 copies the options BEFORE :63-65 clears obj.options.se: an update uses the element it finds and the
             # next one strel('disk', bSiz, 0) (determine_search_location.m:42-44).  The element is only READ here (prefetches and measurement
-            # helpers call this too); update_spatial_parallel clears it once per update.  Host work on every rank (off in every demo).
+            # helpers call this too); update_spatial_parallel clears it once per update.  Every rank computes all columns (demo_batch_1p.m:19 and
+            # demo_sfn_2018.m:19 turn 'dilate' on through with_dendrites): on the engine (footprint_ops.hpp), or with hostops -- the same index sets.
             se = o.se if se is _UNSET else se
             se = hostops.strel_disk(4) if isinstance(se, str) else hostops.strel_disk(o.bSiz) if se is None else se
+            if self._image_ops_device(A):
+                return self.engine.search_dilate(A, v.d1, v.d2, se, o.nb, o.nrgthr)
             return hostops.search_location_dilate(A, v.d1, v.d2, se, o.nb, o.nrgthr)
         if v.world_size == 1:
             return determine_search_location(A, v.d1, v.d2, o.min_size, o.max_size, o.dist)

@@ -637,6 +637,39 @@ int cnmfe_post_process_spatial(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K
                                const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
                                uint8_t *keep);
 
+/* ---- footprint image operations: compactSpatial / spatial_constraints.circular, search_method = 'dilate', trimSpatial
+ * Small morphological operations on one footprint's bounding box, one workgroup per neuron, the box in LDS (cnmf_e_amd/csrc/footprint_ops.hpp).  A is the
+ * whole-FOV d1*d2 x K CSC (rows ascending inside a column, inside [0, d1*d2): CNMFE_EINVAL otherwise), non-negative like every footprint; the calls run in the
+ * context's global scope like cnmfe_post_process_spatial.
+ * Arithmetic: everything that decides -- a comparison, the first maximum, a sum that is compared -- is fp64 on the fp32 values of A, each product and sum
+ * rounded on its own (no fused multiply-add), in the order of the NumPy statements in cnmf_e_amd/hostops.py, whose results these calls EQUAL.  The cumulative
+ * sum of the energy threshold is sequential, in the order of MATLAB's stable sort (squared value, then column-major pixel).  The first maximum is the first in
+ * column-major order.  Iterations (component labels) are bounded by the cells of the box.  No atomics: two calls give the same bits.
+ * Boxes: box[4 k ..] = (r0, c0, h, w), 0-based, of the non-zeros of column k grown by what the operation can reach and clipped to the field of view; off[k] = the
+ * cells of the boxes in front of it, off[K] = all of them.  The result of column k lies at out + off[k], column-major over its box.  A box of more than 4096 cells
+ * (64 x 64; with strel('disk', 4, 0): a 52 x 52 footprint, or a 10-pixel-wide dendrite 174 pixels long) is not computed: h = w = 0, host_col[k] = 1, and the caller
+ * computes THAT column (the Python engine: with hostops); the read-only counter image_ops_host_columns (cnmfe_get_option) says how many columns of the last call
+ * that was.  out = NULL: box, off and host_col only -- how a caller sizes out (out_cap cells; too small: CNMFE_EINVAL).  box, off, host_col are host memory; out
+ * (keep) is host or device memory (out_memspace).
+ *
+ * cnmfe_circular_constraints: endoscope/circular_constraints.m:8-55 per column (Sources2D.compactSpatial, post_process_spatial.m:28-30).  The box is the bounding
+ *   box of the non-zeros, whose edges are the image's edges for gradient(), the dilation and medfilt2 (the reference recurses on the crop).  out: the new values of
+ *   the box (the support may grow inside it); an empty column has no cells, a box under 2 x 2 comes back unchanged.
+ * cnmfe_search_dilate: utilities/threshold_components.m:20-62 + determine_search_location.m:89-98: medfilt2, the pixels holding nrgthr (in (0, 1]) of the energy,
+ *   imclose by the 3 x 3 square (the dilation sees false outside the FOV, the erosion true), the 8-connected component with the most energy of the filtered
+ *   image, imdilate by se (se_h x se_w bytes, row-major, origin at the centre) clipped at the FOV.  The last nb columns are dilated from > 0 without thresholding.
+ *   out: one byte per cell, 1 = in the index set.  An se with an even side or a side above 15 leaves every non-empty column to the caller.
+ * cnmfe_trim_spatial: @Sources2D/Sources2D.m:942-965: imopen by the sz x sz square (sz odd, 1 .. 9: CNMFE_EINVAL otherwise; erosion pads with +Inf, dilation with
+ *   -Inf), temp = ai_open > max(ai) * thr (thr >= 0), 4-connected labels, keep[e] = 1 where l == l(argmax ai_open) -- all of the column when the opening removed
+ *   everything --, ind_small[k] = sum(ai > 0) < min_pixel afterwards.  keep has one byte per stored entry like cnmfe_post_process_spatial's. */
+int cnmfe_circular_constraints(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
+                               int32_t *box /* 4 K */, int64_t *off /* K + 1 */, float *out, int64_t out_cap, uint8_t *host_col /* K */, int out_memspace);
+int cnmfe_search_dilate(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
+                        const uint8_t *se, int32_t se_h, int32_t se_w, int32_t nb, double nrgthr,
+                        int32_t *box /* 4 K */, int64_t *off /* K + 1 */, uint8_t *out, int64_t out_cap, uint8_t *host_col /* K */, int out_memspace);
+int cnmfe_trim_spatial(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
+                       double thr, int32_t sz, int32_t min_pixel, uint8_t *keep /* nnz */, uint8_t *ind_small /* K */, uint8_t *host_col /* K */, int out_memspace);
+
 /* ---- measurement: per-kernel HIP-event timing on the engine's stream ---------
  * on = 1: every launch is bracketed by a pair of events; on = 2: only the kernels a roofline is quoted for (residual sweep, ring solve, window
  * projection / table correction, the two residual projections) -- the pairs cost host and device time per launch, which a run that wants its
@@ -722,7 +755,7 @@ int cnmfe_set_option(cnmfe_ctx *ctx, const char *name, int64_t value);
  * (requests the projection could not serve), temporal_early_entries / temporal_proj_entries ((block, neuron) entries of the last early / of the last projection),
  * temporal_nowait (temporal updates whose levels were queued without the host wait), and merge_trace_uploads (K x T matrices the merge / tag entry points and
  * cnmfe_traces_load took from the host: 0 while they work on the context's own matrices), and bound_K / bound_T (the shape of the bound trace matrix, 0 without
- * one: what a gateway sizes the outputs of cnmfe_merge_apply with), and lanes_live (the execution lanes in force, 1 without option lanes). */
+ * one: what a gateway sizes the outputs of cnmfe_merge_apply with), and lanes_live (the execution lanes in force, 1 without option lanes), and image_ops_host_columns (columns the last footprint image operation left to the caller). */
 int cnmfe_get_option(cnmfe_ctx *ctx, const char *name, int64_t *value);
 
 /* The hand-over between the spatial and the temporal update (option temporal_early).  After cnmfe_update_spatial_fetch_connected[_async] of a patch that is the
