@@ -83,6 +83,8 @@ PROTOTYPES = {
     "cnmfe_peel_open_residual": (C.c_int, [c_ctx, C.c_int, C.c_int32, i64p, i32p, f32p, f32p, C.c_int, f32p, C.c_int32, C.c_float, f32p, f32p, f32p, C.c_void_p, C.c_int]),
     "cnmfe_seed_images_ds": (C.c_int, [c_ctx, C.c_int, C.c_int32, C.c_int32, f32p, C.c_int32, C.c_int64, f64p, C.c_int32, C.c_float, f32p, f32p]),
     "cnmfe_peel_open_ds": (C.c_int, [c_ctx, C.c_int, C.c_int32, C.c_int32, f32p, C.c_int32, C.c_int64, f64p, C.c_int32, C.c_float, f32p, f32p, f32p, C.c_void_p, C.c_int]),
+    "cnmfe_peel_open_residual_ds": (C.c_int, [c_ctx, C.c_int, C.c_int32, C.c_int32, C.c_int32, i64p, i32p, f32p, f32p, C.c_int, f32p, C.c_int32, C.c_float, f32p, f32p, f32p,
+                                              C.c_void_p, C.c_int]),
     "cnmfe_peel_extract": (C.c_int, [c_ctx, C.c_int, C.c_int32, C.c_int32, C.c_int32, f64p, f64p, f64p, f64p]),
     "cnmfe_peel_apply": (C.c_int, [c_ctx, C.c_int, C.c_int32, C.c_int32, C.c_int32, f64p, f64p, f64p, C.c_double, C.c_double, C.c_double, f32p, f32p]),
     "cnmfe_peel_close": (C.c_int, [c_ctx, C.c_int]),

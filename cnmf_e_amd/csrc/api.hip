@@ -1113,14 +1113,12 @@ int cnmfe_peel_open_ds(cnmfe_ctx *ctx, int patch_id, int32_t ssub, int32_t tsub,
     return rc;
 }
 
-// The second pass (@Sources2D/initComponents_residual_parallel.m:186-220): the session on the PATCH, its source video Yres = Ysig - A(patch, ind) C(ind, :) built
-// off the resident residual (peel.hpp, k_peel_yres).  Ysig is only read; the residual REQUEST is the session's: cnmfe_peel_close drops it (as a fit does), so the
-// next update requests its own and finds the patch as it would have without the session
-int cnmfe_peel_open_residual(cnmfe_ctx *ctx, int patch_id, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const float *C,
-                             int c_order, const float *psf, int32_t psf_n, float sig, float *Cn_patch, float *PNR_patch, float *Sn_patch, float *Yres_out,
-                             int out_memspace) {
+// the refusals the two residual opens share; psf_n comes back normalised.  ssub = tsub = 1 for cnmfe_peel_open_residual itself
+static int residual_open_args(cnmfe_ctx *ctx, int patch_id, int32_t ssub, int32_t tsub, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx,
+                              const float *A_val, const float *C, int c_order, const float *psf, int32_t &psf_n, float sig, const float *Cn_patch,
+                              const float *PNR_patch, Patch *&P) {
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
-    Patch *P = get_patch(ctx, patch_id);
+    P = get_patch(ctx, patch_id);
     if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
     if (!Cn_patch || !PNR_patch) return fail(CNMFE_EINVAL, "null Cn_patch / PNR_patch");
     if (psf_n < 0 || Ksel < 0 || !(sig == sig) || std::isinf(sig)) return fail(CNMFE_EINVAL, "residual peel session: psf_n = %d, Ksel = %d, sig = %g", psf_n, Ksel, (double)sig);
@@ -1128,15 +1126,45 @@ int cnmfe_peel_open_residual(cnmfe_ctx *ctx, int patch_id, int32_t Ksel, const i
     if (P->derived) return fail(CNMFE_EUNSUPPORTED, "a peel session of a derived (bg_ssub) patch is not built: patch %d", patch_id);
     if (psf_n > 0 && (psf_n % 2 == 0 || psf_n > 25)) return fail(CNMFE_EUNSUPPORTED, "seed images: the filter must be odd-sized and at most 25 x 25 (got %d; pad an even kernel)", psf_n);
     if (P->T < 64 || P->T > WELCH_TMAX) return fail(CNMFE_EUNSUPPORTED, "seed images support 64 <= nframes <= WELCH_TMAX = %d (the residual session reads all %lld frames)", WELCH_TMAX, (long long)P->T);
+    if (ssub < 1 || ssub > 8 || tsub < 1) return fail(CNMFE_EINVAL, "down-sampling: ssub = %d (1 .. 8), tsub = %d (>= 1)", ssub, tsub);
+    if (P->T / tsub < 64) return fail(CNMFE_EUNSUPPORTED, "down-sampling: floor(T / tsub) = floor(%lld / %d) = %lld frames are left, at least 64 are needed", (long long)P->T, tsub, (long long)(P->T / tsub));
     RET(require_residual(P, patch_id));
     if (P->peel) return fail(CNMFE_ESTATE, "patch %d already has an open peel session", patch_id);
     RET(check_csc("A", Ksel, P->d, A_colptr, A_rowidx));
     if (Ksel > 0 && ((!A_val && A_colptr[Ksel] > 0) || (!C && c_order != CNMFE_BOUND))) return fail(CNMFE_EINVAL, "null A_val / C");
+    return 0;
+}
+
+// The second pass (@Sources2D/initComponents_residual_parallel.m:186-220): the session on the PATCH, its source video Yres = Ysig - A(patch, ind) C(ind, :) built
+// off the resident residual (peel.hpp, k_peel_yres).  Ysig is only read; the residual REQUEST is the session's: cnmfe_peel_close drops it (as a fit does), so the
+// next update requests its own and finds the patch as it would have without the session
+int cnmfe_peel_open_residual(cnmfe_ctx *ctx, int patch_id, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const float *C,
+                             int c_order, const float *psf, int32_t psf_n, float sig, float *Cn_patch, float *PNR_patch, float *Sn_patch, float *Yres_out,
+                             int out_memspace) {
+    Patch *P = nullptr;
+    RET(residual_open_args(ctx, patch_id, 1, 1, Ksel, A_colptr, A_rowidx, A_val, C, c_order, psf, psf_n, sig, Cn_patch, PNR_patch, P));
     CK(hipSetDevice(ctx->device));
     RET(residual_materialize(ctx, P));                       // a virtual or pending residual: Ysig itself is about to be read
     P->peel = new PeelSession();
     const int rc = peel_open_residual_run(ctx, P, Ksel, A_colptr, A_rowidx, A_val, C, c_order, psf, psf_n, sig, Cn_patch, PNR_patch, Sn_patch, Yres_out, out_memspace);
     // a failed open (CNMFE_ENOMEM ...) has realised the residual all the same: it is dropped as a close would drop it, so that the next update requests its own
+    if (rc != 0) { (void)hipStreamSynchronize(ctx->st()); delete P->peel; P->peel = nullptr; P->residual.invalidate(); }
+    return rc;
+}
+
+// options.ssub / options.tsub of the second pass (greedyROI_endoscope.m:46-61 on the patch residual): the session on dsData(Yres), built off the resident
+// residual as dsData(Ysig) - A_ds C_ds (ds.hpp, k_ds_video_res) -- no full-resolution Yres.  ssub = tsub = 1 IS cnmfe_peel_open_residual.
+int cnmfe_peel_open_residual_ds(cnmfe_ctx *ctx, int patch_id, int32_t ssub, int32_t tsub, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx,
+                                const float *A_val, const float *C, int c_order, const float *psf, int32_t psf_n, float sig, float *Cn_ds, float *PNR_ds,
+                                float *Sn_ds, float *Yds_out, int out_memspace) {
+    Patch *P = nullptr;
+    RET(residual_open_args(ctx, patch_id, ssub, tsub, Ksel, A_colptr, A_rowidx, A_val, C, c_order, psf, psf_n, sig, Cn_ds, PNR_ds, P));
+    CK(hipSetDevice(ctx->device));
+    RET(residual_materialize(ctx, P));
+    P->peel = new PeelSession();
+    const int rc = (ssub == 1 && tsub == 1)
+        ? peel_open_residual_run(ctx, P, Ksel, A_colptr, A_rowidx, A_val, C, c_order, psf, psf_n, sig, Cn_ds, PNR_ds, Sn_ds, Yds_out, out_memspace)
+        : peel_open_residual_ds_run(ctx, P, ssub, tsub, Ksel, A_colptr, A_rowidx, A_val, C, c_order, psf, psf_n, sig, Cn_ds, PNR_ds, Sn_ds, Yds_out, out_memspace);
     if (rc != 0) { (void)hipStreamSynchronize(ctx->st()); delete P->peel; P->peel = nullptr; P->residual.invalidate(); }
     return rc;
 }

@@ -671,6 +671,9 @@ int seed_images_ds_run(cnmfe_ctx *ctx, Patch *P, int ssub, int tsub, const float
                        float *Cn_out, float *PNR_out);   // ds.hpp (deconv.hip)
 int peel_open_ds_run(cnmfe_ctx *ctx, Patch *P, int ssub, int tsub, const float *psf, int32_t psf_n, int64_t nframes, const double *Qpre, int32_t Mpre, float sig,
                      float *Cn_out, float *PNR_out, float *Sn_out, float *Yds_out, int out_memspace);   // ds.hpp (deconv.hip)
+int peel_open_residual_ds_run(cnmfe_ctx *ctx, Patch *P, int ssub, int tsub, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
+                              const float *C, int c_order, const float *psf, int32_t psf_n, float sig, float *Cn_out, float *PNR_out, float *Sn_out,
+                              float *Yds_out, int out_memspace);   // ds.hpp (deconv.hip)
 int peel_extract_run(cnmfe_ctx *ctx, Patch *P, int r, int c, int gSiz, double *corr_box, double *ai_box, double *ci_out, double *stats);
 int peel_apply_run(cnmfe_ctx *ctx, Patch *P, int r, int c, int gSiz, const double *ai_box, const double *Hai_box2, const double *ci, double sig, double min_pnr,
                    double min_corr, float *PNR_box2, float *Cn_box2);

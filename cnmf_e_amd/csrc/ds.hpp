@@ -11,44 +11,14 @@
 //                dsData(Y - (Y Q) Q') = dsData(Y) - sum_m mean_bin(Q(:, m)) G[m]: both maps are linear, one acts in space and one in time, so no full-resolution
 //                detrended copy exists; k_ds_video subtracts the correction in fp64 before its single rounding.
 // Because the box weights sum to 1, dsData(raw) = dsData(Yc) + box(ymean): k_ds_mean resizes the patch's fp64 pixel mean for the session.
+// The second pass (cnmfe_peel_open_residual_ds) opens its session on dsData(Yres), Yres = Ysig - A C of the PATCH, by the same linearity:
+//   k_ds_video_res     dsData(Ysig) - A_ds C_ds off the resident residual: k_ds_video's layout and bins (DsPix::bins), then the pixel's CSR row of A_ds times the bin means
+//                      of the traces in fp64, ONE rounding.  No full-resolution Yres exists.
+//   k_trace_bin_mean   C_ds, K x Ts fp64, on the device so that a bound C never comes down.  A_ds is formed on the host in float64: ds_fold.hpp.
 #pragma once
+#include "ds_fold.hpp"   // the host rules: ds_box_taps, A_ds (ds_fold_csc), the bin mean
 
 namespace cnmfe {
-
-constexpr int DS_SSUB_MAX = 8;
-constexpr int DS_NT_MAX = DS_SSUB_MAX + 1;            // non-zero box taps of one output sample: at most ceil(in / out) + 1 <= ssub + 1
-
-// the non-zero taps of every output sample in ascending (virtual) order, padded to `nt` per sample with weight 0 on a valid index
-struct DsTaps { int n_in = 0, n_out = 0, nt = 0; std::vector<int> idx; std::vector<double> w; };
-
-static DsTaps ds_box_taps(int n_in, int n_out) {
-    DsTaps t; t.n_in = n_in; t.n_out = n_out;
-    const double scale = (double)n_out / (double)n_in;
-    const double kw = scale < 1.0 ? 1.0 / scale : 1.0;
-    const int P = (int)std::ceil(kw) + 2;
-    std::vector<int> ii((size_t)n_out * P); std::vector<double> ww((size_t)n_out * P);
-    std::vector<int> cnt((size_t)n_out, 0);
-    for (int o = 0; o < n_out; ++o) {
-        const double x = o + 1.0, u = x / scale + 0.5 * (1.0 - 1.0 / scale);
-        const double left = std::floor(u - kw / 2);
-        double sum = 0;
-        int c = 0;
-        for (int i = 0; i < P; ++i) {
-            double d = u - (left + i);
-            if (scale < 1.0) d = scale * d;
-            if (!(d >= -0.5 && d < 0.5)) continue;
-            const long v = (long)left + i - 1, per = 2L * n_in;   // 0-based virtual index, aux = [1:n n:-1:1]
-            const long mth = ((v % per) + per) % per;
-            ii[(size_t)o * P + c] = (int)(mth < n_in ? mth : per - 1 - mth); ww[(size_t)o * P + c] = 1.0; sum += 1.0; ++c;
-        }
-        for (int i = 0; i < c; ++i) ww[(size_t)o * P + i] /= sum;
-        cnt[(size_t)o] = c; t.nt = std::max(t.nt, c);
-    }
-    t.idx.assign((size_t)n_out * t.nt, 0); t.w.assign((size_t)n_out * t.nt, 0.0);
-    for (int o = 0; o < n_out; ++o)
-        for (int i = 0; i < cnt[(size_t)o]; ++i) { t.idx[(size_t)o * t.nt + i] = ii[(size_t)o * P + i]; t.w[(size_t)o * t.nt + i] = ww[(size_t)o * P + i]; }
-    return t;
-}
 
 // geometry and tap tables of one call, as the kernels take them
 struct DsGeo {
@@ -83,6 +53,22 @@ template <int NT> struct DsPix {
             }
         }
     }
+    // the SUMS of the four bins of output quad Q: it consumes exactly the input quads [Q tsub, (Q + 1) tsub), the frames of a bin added in ascending order
+    __device__ __forceinline__ void bins(const DsGeo &g, const float4 *__restrict__ src4, int nq_in, int Q, int tsub, double acc[4]) const {
+        acc[0] = acc[1] = acc[2] = acc[3] = 0.0;
+        for (int lq = 0; lq < tsub; ++lq) {
+            const int64_t iq = (int64_t)Q * tsub + lq;
+            if (iq >= nq_in) break;                          // (only behind the last output frame: t < Ts reads input frames below Ts tsub <= n)
+            double s[4];
+            quad(g, src4 + iq * g.d_in, s);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int j = (4 * lq + e) / tsub;           // the output frame of the quad this input frame belongs to
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) if (j == jj) acc[jj] += s[e];
+            }
+        }
+    }
 };
 
 // grid (ceil(ds / 256), output quads).  G: [M][ds] (k_ds_coef_fin), bm: [M][Ts] the bin means of Qpre's columns; M = 0: no correction.
@@ -93,19 +79,8 @@ __global__ void __launch_bounds__(256) k_ds_video(const float4 *__restrict__ yc4
     if (p >= g.ds) return;
     const int Q = (int)blockIdx.y;
     DsPix<NT> px; px.load(g, p);
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int lq = 0; lq < tsub; ++lq) {
-        const int64_t iq = (int64_t)Q * tsub + lq;
-        if (iq >= nq_in) break;                              // (only behind the last output frame: t < Ts reads input frames below Ts tsub <= n)
-        double s[4];
-        px.quad(g, yc4 + iq * g.d_in, s);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int j = (4 * lq + e) / tsub;               // the output frame of the quad this input frame belongs to
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) if (j == jj) acc[jj] += s[e];
-        }
-    }
+    double acc[4];
+    px.bins(g, yc4, nq_in, Q, tsub, acc);
     float o[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -118,6 +93,42 @@ __global__ void __launch_bounds__(256) k_ds_video(const float4 *__restrict__ yc4
         o[j] = (float)v;                                     // the padding frames of the last quad: 0
     }
     out4[(int64_t)Q * g.ds + p] = make_float4(o[0], o[1], o[2], o[3]);
+}
+
+// The source video of the SECOND pass (cnmfe_peel_open_residual_ds): dsData(Ysig - A C) = dsData(Ysig) - A_ds C_ds off the resident residual of the PATCH
+// (g: d_in = d, nr_in = nr of the patch).  k_ds_video's thread layout and bins; then the pixel's stored low-resolution footprints (CSR row of A_ds, columns
+// ascending; fp64) times the bin means of their traces (cds: [K][Ts] fp64, k_trace_bin_mean) leave in fp64, and the difference is rounded ONCE.  Every
+// (pixel, quad) is written by one thread and every sum has one order: no atomics, equal bits between runs.  16 tsub ntr ntc bytes read per thread through whole
+// cache lines (the lanes run along the output rows), 16 written; the trace values of a wave's few neurons come from L2 as in k_peel_yres.
+// rowptr == nullptr: no footprint in the patch, plain dsData(Ysig).
+template <int NT>
+__global__ void __launch_bounds__(256) k_ds_video_res(const float4 *__restrict__ ysig4, int nq_in, DsGeo g, int tsub, int Ts, const int *__restrict__ rowptr,
+                                                      const int *__restrict__ col, const double *__restrict__ val, const double *__restrict__ cds,
+                                                      float4 *__restrict__ out4) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= g.ds) return;
+    const int Q = (int)blockIdx.y;
+    DsPix<NT> px; px.load(g, p);
+    double acc[4];
+    px.bins(g, ysig4, nq_in, Q, tsub, acc);
+    double v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = 4 * Q + j < Ts ? acc[j] / (double)tsub : 0.0;      // the padding frames of the last quad: 0
+    const int e0 = rowptr ? rowptr[p] : 0, e1 = rowptr ? rowptr[p + 1] : 0;
+    for (int e = e0; e < e1; ++e) {
+        const double a = -val[e];
+        const double *c = cds + (int64_t)col[e] * Ts + 4 * (int64_t)Q;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (4 * Q + j < Ts) v[j] = fma(a, c[j], v[j]);
+    }
+    out4[(int64_t)Q * g.ds + p] = make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+}
+
+// C_ds: the bin means of K traces (rows of stride ldc floats, upload_traces' layout), [K][Ts] fp64.  One thread per (bin, trace): ds_bin_mean (ds_fold.hpp).
+__global__ void __launch_bounds__(256) k_trace_bin_mean(const float *__restrict__ C, int64_t ldc, int tsub, int Ts, double *__restrict__ cds) {
+    const int t = (int)blockIdx.x * 256 + threadIdx.x, k = (int)blockIdx.y;
+    if (t >= Ts) return;
+    cds[(int64_t)k * Ts + t] = ds_bin_mean(C + (int64_t)k * ldc + (int64_t)t * tsub, tsub);
 }
 
 // grid (ceil(ds / 256), frame chunks): part[(chunk * M + m) * ds + p] = sum over the chunk's frames t < n of Q[m * n + t] Ys(p, t), frames ascending
@@ -195,15 +206,18 @@ struct DsCall {
     else                LAUNCH(ctx, name, (kern<DS_NT_MAX>), grid, dim3(256), 0, __VA_ARGS__); \
 } while (0)
 
-static int ds_plan(cnmfe_ctx *ctx, Patch *P, int ssub, int tsub, int64_t nframes, DsCall &c) {
+// the plan of one call on a source video of nr x nc pixels (d = nr nc float4s per frame quad): the BLOCK for the first pass, the PATCH for the second
+static int ds_plan(cnmfe_ctx *ctx, int nr, int nc, int64_t d, int ssub, int tsub, int64_t nframes, DsCall &c, DsTaps *tr_out = nullptr, DsTaps *tc_out = nullptr) {
     c.ssub = ssub; c.tsub = tsub;
-    c.d1s = (P->nr_b + ssub - 1) / ssub; c.d2s = (P->nc_b + ssub - 1) / ssub; c.ds = (int64_t)c.d1s * c.d2s;
+    c.d1s = (nr + ssub - 1) / ssub; c.d2s = (nc + ssub - 1) / ssub; c.ds = (int64_t)c.d1s * c.d2s;
     c.Ts = nframes / tsub; c.nq = (c.Ts + 3) / 4;
-    const DsTaps tr = ds_box_taps(P->nr_b, c.d1s), tc = ds_box_taps(P->nc_b, c.d2s);
+    const DsTaps tr = ds_box_taps(nr, c.d1s), tc = ds_box_taps(nc, c.d2s);
     if (tr.nt > DS_NT_MAX || tc.nt > DS_NT_MAX) return fail(CNMFE_EUNSUPPORTED, "down-sampling: %d / %d box taps per sample (at most %d)", tr.nt, tc.nt, DS_NT_MAX);
     RET(to_dev(ctx, c.ri, tr.idx)); RET(to_dev(ctx, c.rw, tr.w)); RET(to_dev(ctx, c.ci, tc.idx)); RET(to_dev(ctx, c.cw, tc.w));
-    c.g.d_in = P->d_b; c.g.ds = c.ds; c.g.nr_in = P->nr_b; c.g.d1s = c.d1s; c.g.ntr = tr.nt; c.g.ntc = tc.nt;
+    c.g.d_in = d; c.g.ds = c.ds; c.g.nr_in = nr; c.g.d1s = c.d1s; c.g.ntr = tr.nt; c.g.ntc = tc.nt;
     c.g.ri = c.ri.as<int>(); c.g.ci = c.ci.as<int>(); c.g.rw = c.rw.as<double>(); c.g.cw = c.cw.as<double>();
+    if (tr_out) *tr_out = tr;
+    if (tc_out) *tc_out = tc;
     return 0;
 }
 
@@ -251,7 +265,7 @@ static int ds_export(cnmfe_ctx *ctx, const DsCall &c, const float4 *y4, float *o
 int seed_images_ds_run(cnmfe_ctx *ctx, Patch *P, int ssub, int tsub, const float *psf, int32_t psf_n, int64_t nframes, const double *Q, int32_t M, float sig,
                        float *Cn_out, float *PNR_out) {
     DsCall c;
-    RET(ds_plan(ctx, P, ssub, tsub, nframes, c));
+    RET(ds_plan(ctx, P->nr_b, P->nc_b, P->d_b, ssub, tsub, nframes, c));
     DevBuf yds;
     const size_t vid = (size_t)c.nq * (size_t)c.ds * sizeof(float4);
     if (yds.ensure(vid) != 0) {
@@ -271,7 +285,7 @@ int peel_open_ds_run(cnmfe_ctx *ctx, Patch *P, int ssub, int tsub, const float *
                      float *Cn_out, float *PNR_out, float *Sn_out, float *Yds_out, int out_memspace) {
     PeelSession *S = P->peel;
     DsCall c;
-    RET(ds_plan(ctx, P, ssub, tsub, nframes, c));
+    RET(ds_plan(ctx, P->nr_b, P->nc_b, P->d_b, ssub, tsub, nframes, c));
     S->n = c.Ts; S->nq = c.nq; S->M = 0; S->d = c.ds; S->nr = c.d1s; S->nc = c.d2s; S->residual = false; S->own_mean = Mpre == 0; S->no_mean = Mpre > 0;
     const size_t vid = (size_t)c.nq * (size_t)c.ds * sizeof(float4);
     if (S->hy.ensure(vid) != 0 || S->yw.ensure(vid) != 0) {
@@ -298,6 +312,54 @@ int peel_open_ds_run(cnmfe_ctx *ctx, Patch *P, int ssub, int tsub, const float *
     }
     if (Yds_out) RET(ds_export(ctx, c, S->yw.as<float4>(), Yds_out, out_memspace));      // (nothing has been peeled yet) exactly the fp32 video the session searches
     CK(hipStreamSynchronize(ctx->st()));                     // (Qpre is the caller's pageable memory; the tables of `c` go with this frame)
+    return 0;
+}
+
+// cnmfe_peel_open_residual_ds: the session of the second pass on dsData(Yres) of the PATCH (@Sources2D/initComponents_residual_parallel.m:171-177,232 ->
+// greedyROI_endoscope.m:46-61), Yres = Ysig - A(patch, ind) C(ind, :).  The caller has made sure that P->ysig holds the residual itself (residual_materialize).
+// A_ds is formed here in float64 (ds_fold_csc), C_ds on the device (k_trace_bin_mean: a bound C never comes down), and k_ds_video_res writes the down-sampled
+// difference straight into Yw: no full-resolution Yres exists.  The residual carries its own mean: no ymean, no k_ds_mean.
+int peel_open_residual_ds_run(cnmfe_ctx *ctx, Patch *P, int ssub, int tsub, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
+                              const float *C, int c_order, const float *psf, int32_t psf_n, float sig, float *Cn_out, float *PNR_out, float *Sn_out,
+                              float *Yds_out, int out_memspace) {
+    PeelSession *S = P->peel;
+    const int64_t n = P->T, nq_in = (n + 3) / 4;
+    DsCall c;
+    DsTaps tr, tc;
+    RET(ds_plan(ctx, P->nr, P->nc, P->d, ssub, tsub, n, c, &tr, &tc));
+    S->n = c.Ts; S->nq = c.nq; S->M = 0; S->d = c.ds; S->nr = c.d1s; S->nc = c.d2s; S->residual = true;
+    const size_t vid = (size_t)c.nq * (size_t)c.ds * sizeof(float4);
+    if (S->hy.ensure(vid) != 0 || S->yw.ensure(vid) != 0) {
+        (void)hipGetLastError();
+        return fail(CNMFE_ENOMEM, "down-sampled residual peel session: no room for the filtered video and the working copy, 2 x %zu bytes (16 x ceil(Ts / 4) x d1s d2s = 16 x %lld x %lld)",
+                    vid, (long long)c.nq, (long long)c.ds);
+    }
+    RET(S->sn.ensure((size_t)c.ds * sizeof(double)));
+    RET(S->ci.ensure(peel_al((size_t)c.Ts * sizeof(double)) * 2));
+    // (buffers of this call: released when it returns, behind the stream's last wait)
+    DevBuf dC, dCds, dRow, dCol, dVal;
+    const bool has_ac = Ksel > 0 && A_colptr[Ksel] > 0;
+    if (has_ac) {
+        DsCSR fold;
+        if (!ds_fold_csc(P->nr, P->nc, tr, tc, Ksel, A_colptr, A_rowidx, A_val, fold))
+            return fail(CNMFE_EUNSUPPORTED, "down-sampled residual peel session: the low-resolution footprints hold 2^31 entries or more");
+        int64_t ldc = 4;
+        RET(upload_traces(ctx, dC, C, Ksel, n, c_order, &ldc));
+        RET(dCds.ensure((size_t)Ksel * (size_t)c.Ts * sizeof(double)));
+        LAUNCH(ctx, "trace_bin_mean", k_trace_bin_mean, dim3((unsigned)((c.Ts + 255) / 256), (unsigned)Ksel), dim3(256), 0, dC.as<float>(), ldc, tsub, (int)c.Ts, dCds.as<double>());
+        RET(to_dev(ctx, dRow, fold.rowptr)); RET(to_dev(ctx, dCol, fold.col)); RET(to_dev(ctx, dVal, fold.val));
+    }
+    DS_LAUNCH_NT(ctx, "ds_video_res", k_ds_video_res, std::max(c.g.ntr, c.g.ntc), dim3((unsigned)((c.ds + 255) / 256), (unsigned)c.nq), P->ysig.as<float4>(), (int)nq_in, c.g,
+                 tsub, (int)c.Ts, has_ac ? dRow.as<int>() : (const int *)nullptr, dCol.as<int>(), dVal.as<double>(), dCds.as<double>(), S->yw.as<float4>());
+    RET(seed_images_run(ctx, SeedSrc{S->yw.as<float4>(), c.ds, c.d1s, c.d2s}, psf, psf_n, c.Ts, nullptr, 0, sig, Cn_out, PNR_out, S));
+    if (Sn_out) {
+        std::vector<double> sn((size_t)c.ds);
+        CK(hipMemcpyAsync(sn.data(), S->sn.p, (size_t)c.ds * sizeof(double), hipMemcpyDeviceToHost, ctx->st()));
+        CK(hipStreamSynchronize(ctx->st()));
+        for (int64_t i = 0; i < c.ds; ++i) Sn_out[i] = (float)sn[(size_t)i];
+    }
+    if (Yds_out) RET(ds_export(ctx, c, S->yw.as<float4>(), Yds_out, out_memspace));      // (nothing has been peeled yet) exactly the fp32 video the session searches
+    CK(hipStreamSynchronize(ctx->st()));                     // (the tables of `c` and the buffers of this frame are read until here)
     return 0;
 }
 

@@ -60,6 +60,9 @@
 //   [Cn_patch, PNR_patch, Sn_patch, Yres] = cnmfe_mex('peel_open_residual', h, pid, A_patch, C_or_rows, psf)   the second pass (initComponents_residual_parallel.m:186-220):
 //                                                                          the session on the PATCH and on Ysig - A_patch C, after 'residual' / 'residual_ssub'; the images are
 //                                                                          nr x nc of the patch, Yres (asked for as 4th output) d x T single; extract / apply then take the seed in the patch
+//   [Cn_ds, PNR_ds, Sn_ds, Yds] = cnmfe_mex('peel_open_residual_ds', h, pid, ssub, tsub, A_patch, C_or_rows, psf)   the second pass with options.ssub / options.tsub: the session on
+//                                                                          dsData(Ysig - A_patch C) of the PATCH, ceil(nr / ssub) x ceil(nc / ssub) pixels, Ts = floor(T / tsub) frames; A_patch
+//                                                                          at full resolution; Yds (asked for as 4th output) d1s d2s x Ts single; extract / apply then take the seed on that grid
 // Known footprints (@Sources2D/initTemporal.m:156-168 per patch; the loop over the patches, the stitch and deconvTemporal are the caller's, as in cnmf_e_amd/sources2d.py -- no .m twin is written):
 //   [C, C_raw, AA, S, pars, sn] = cnmfe_mex('init_temporal', h, pid, A_block, iters_plain, iters_last, smin, max_tau)   A_block: sparse, BLOCK rows x K; without smin and
 //                                                                          max_tau the last sweeps are plain too (three outputs).  C_raw and AA also stay on the device:
@@ -851,7 +854,7 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
         CHECK(cnmfe_seed_images_ds(c, pid, ssub, tsub, psf, pn, nf, Q, M, 3.0f, cn, pnr));
         pout[0] = to_double(cn, d1s, d2s);
         if (nout > 1) pout[1] = to_double(pnr, d1s, d2s);
-    } else if (!strcmp(cmd, "peel_open") || !strcmp(cmd, "peel_open_ds") || !strcmp(cmd, "peel_open_residual") || !strcmp(cmd, "peel_extract") || !strcmp(cmd, "peel_apply") || !strcmp(cmd, "peel_close")) {
+    } else if (!strcmp(cmd, "peel_open") || !strcmp(cmd, "peel_open_ds") || !strcmp(cmd, "peel_open_residual") || !strcmp(cmd, "peel_open_residual_ds") || !strcmp(cmd, "peel_extract") || !strcmp(cmd, "peel_apply") || !strcmp(cmd, "peel_close")) {
         int slot = 0;
         while (slot < g_ndims && !(g_dims[slot].c == c && g_dims[slot].pid == pid)) ++slot;
         if (slot == g_ndims) FAIL("%s: patch %d was not created through this gateway", cmd, pid);
@@ -873,6 +876,26 @@ void mexFunction(int nout, mxArray *pout[], int nin, const mxArray *pin[]) {
             if (nout > 1) pout[1] = to_double(pnr, nrp, ncp);
             if (nout > 2) pout[2] = to_double(sn, nrp, ncp);
             if (nout > 3) pout[3] = yres;
+        } else if (!strcmp(cmd, "peel_open_residual_ds")) {           // [Cn_ds, PNR_ds, Sn_ds, Yds] = cnmfe_mex('peel_open_residual_ds', h, pid, ssub, tsub, A_patch, C_or_rows, psf)
+            if (nin != 8) FAIL("peel_open_residual_ds: 8 inputs required");
+            const int ssub = (int)mxGetScalar(pin[3]), tsub = (int)mxGetScalar(pin[4]);
+            if (ssub < 1 || ssub > 8 || tsub < 1) FAIL("peel_open_residual_ds: ssub = %d (1 .. 8), tsub = %d (>= 1)", ssub, tsub);
+            const mxArray *F = pin[7];
+            if (!mxIsEmpty(F) && mxGetM(F) != mxGetN(F)) FAIL("peel_open_residual_ds: psf must be square");
+            const int32_t pn = mxIsEmpty(F) ? 0 : (int32_t)mxGetM(F);
+            const float *psf = pn ? f32_of(F, NULL) : NULL;
+            Csc A = csc_of(pin[5]);
+            Traces Cm = traces_of(pin[6], A.K);
+            const size_t d1s = ((size_t)g_dims[slot].nr_p + ssub - 1) / ssub, d2s = ((size_t)g_dims[slot].nc_p + ssub - 1) / ssub, ds = d1s * d2s;
+            const int64_t Ts = g_dims[slot].T / tsub;
+            float *cn = (float *)mxMalloc((ds + 1) * sizeof(float)), *pnr = (float *)mxMalloc((ds + 1) * sizeof(float)), *sn = (float *)mxMalloc((ds + 1) * sizeof(float));
+            mxArray *yds = nout > 3 ? mxCreateNumericMatrix(ds, (size_t)Ts, mxSINGLE_CLASS, mxREAL) : NULL;
+            CHECK(cnmfe_peel_open_residual_ds(c, pid, ssub, tsub, A.K, A.cp, A.ri, A.v, Cm.ptr, Cm.order, psf, pn, 3.0f, cn, pnr, sn, yds ? (float *)mxGetData(yds) : NULL, CNMFE_HOST));
+            g_dims[slot].peel_n = Ts; g_dims[slot].peel_nr = (int32_t)d1s; g_dims[slot].peel_nc = (int32_t)d2s;
+            pout[0] = to_double(cn, d1s, d2s);
+            if (nout > 1) pout[1] = to_double(pnr, d1s, d2s);
+            if (nout > 2) pout[2] = to_double(sn, d1s, d2s);
+            if (nout > 3) pout[3] = yds;
         } else if (!strcmp(cmd, "peel_open")) {                       // [Cn_block, PNR_block, Sn_block] = cnmfe_mex('peel_open', h, pid, psf, nframes, Q)
             if (nin != 5 && nin != 6) FAIL("peel_open: 5 or 6 inputs required");
             const mxArray *F = pin[3];

@@ -329,6 +329,7 @@ class Engine:
     supports_synchronize = True       # synchronize()
     supports_init_temporal = True     # init_temporal() / init_temporal_job()
     supports_init_ds = True           # seed_images_ds() / peel_open_ds(): options.ssub / options.tsub of the seed images and the first initialisation
+    supports_init_residual_ds = True  # peel_open_residual_ds(): options.ssub / options.tsub of the second pass (initComponents_residual_parallel)
     supports_traces_grow = True       # traces_grow(): zero rows under the bound matrix and its residents, on the device
     supports_image_ops = True         # circular_constraints() / search_dilate() / trim_spatial(): the image operations on single footprints (footprint_ops.hpp)
     IMAGE_OPS_MAX_BOX = 4096          # cells of the largest box those kernels take (FP_MAX_CELLS); a column above it is computed by hostops and spliced in
@@ -536,6 +537,27 @@ class Engine:
                                                _p(Cn, L.f32p), _p(PNR, L.f32p), _p(Sn, L.f32p), dst, L.HOST))
         self._peel[pid] = (n, info["nr"], info["nc"])
         return Cn, PNR, Sn, out
+
+    def peel_open_residual_ds(self, pid, ssub, tsub, A_patch, C, psf, sig=3.0, want_video=False):
+        """peel_open_residual on dsData(Yres) of the PATCH (options.ssub / options.tsub of the second pass, greedyROI_endoscope.m:46-61): the device forms
+        dsData(Ysig) - A_ds C_ds off the resident residual, so no full-resolution Yres exists.  A_patch, C as for peel_open_residual (FULL resolution; the
+        library down-samples both).  Returns (Cn, PNR, Sn, Yds): d1s * d2s float32 each, column-major on the ceil(nr / ssub) x ceil(nc / ssub) grid; Yds
+        (want_video) is the (Ts, d1s * d2s) float32 video the session searches, Ts = floor(T / tsub), else None.  extract / apply then take seeds 0-based on that
+        grid and traces of Ts samples.  ssub = tsub = 1 is peel_open_residual bit for bit.  Closing the session drops the residual."""
+        info = self._patch[pid]
+        _i, n, psf_a, psf_n, _q, _m = self._seed_args(pid, psf, None, None)
+        fs, ft = max(int(ssub), 1), max(int(tsub), 1)                      # (factors below 1 are the library's to refuse: only the buffers are sized here)
+        d1s, d2s, Ts = -(-info["nr"] // fs), -(-info["nc"] // fs), n // ft
+        K, cp, ri, va = _csc(A_patch, info["d"]) if A_patch is not None and A_patch.shape[1] else (0, None, None, None)
+        cptr, cord, _keep = self._targs(C, K, info["T"])
+        ds = max(d1s * d2s, 1)
+        Cn = np.empty(ds, dtype=np.float32); PNR = np.empty(ds, dtype=np.float32); Sn = np.empty(ds, dtype=np.float32)
+        out = np.empty((max(Ts, 0), d1s * d2s), dtype=np.float32) if want_video else None
+        dst = out.ctypes.data_as(L.C.c_void_p) if want_video else L.C.c_void_p(None)
+        L.check(L.lib.cnmfe_peel_open_residual_ds(self._ctx, pid, int(ssub), int(tsub), K, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p), cptr, cord,
+                                                  _p(psf_a, L.f32p), psf_n, float(sig), _p(Cn, L.f32p), _p(PNR, L.f32p), _p(Sn, L.f32p), dst, L.HOST))
+        self._peel[pid] = (Ts, d1s, d2s)
+        return Cn[:d1s * d2s], PNR[:d1s * d2s], Sn[:d1s * d2s], out
 
     # ---- options.ssub / options.tsub: the same two calls on dsData of the block (cnmfe_seed_images_ds / cnmfe_peel_open_ds) ----
     def ds_dims(self, pid, ssub, tsub, nframes=None):

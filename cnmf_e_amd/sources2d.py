@@ -1057,7 +1057,7 @@ class Sources2D:
             return None
 
         def deconv(ci_raw):
-            c_, r_, s_, kp_, _sn = self.engine.deconv_temporal(np.asarray(ci_raw, dtype=np.float32)[None, :], o.deconv_options)
+            c_, r_, s_, kp_, _sn = self.engine.deconv_temporal(np.asarray(ci_raw, dtype=np.float64)[None, :], o.deconv_options)      # (the engine rounds to fp32 at the ABI)
             return c_[0].astype(np.float64), r_[0].astype(np.float64), s_[0].astype(np.float64), float(kp_[0])
         return deconv
 
@@ -1233,11 +1233,28 @@ class Sources2D:
         being the sessions' opening images placed by patch.  K: the maximum number of new neurons PER PATCH (None: the patch's pixel count, :61-64).
         min_corr, min_pnr, seed_method: when given they overwrite the options and stay overwritten (:47-55) -- first of all, as in the reference, so a call that is
         then refused (seed_method = 'manual' without seeds) has changed them all the same.  seeds: as in initComponents_parallel, tried by the
-        patch that holds them.  Not built (NotImplementedError): ssub / tsub other than 1, save_avi."""
+        patch that holds them.
+        options.ssub / options.tsub other than 1 (:171-177,232 hand greedyROI_endoscope the patch residual and the options; greedyROI_endoscope.m:46-61,464-487):
+        the session of every patch runs on dsData(Yres) (Engine.peel_open_residual_ds: ceil(nr / ssub) x ceil(nc / ssub) pixels of the PATCH, Ts = floor(T / tsub)
+        frames; the device forms dsData(Ysig) - A_ds C_ds, no full-resolution Yres exists) with gSig / ssub, gSiz = round(gSiz / ssub), min_pixel / ssub^2, the
+        filter built from the scaled values and bd = round(bd * [edge flags] / ssub) (:173, then greedyROI_endoscope.m:59); `seeds` land on the low-resolution
+        cell ((r - r0) // ssub, (c - c0) // ssub) of the patch that holds them.  The results come back as in initComponents_parallel (_init_upsample): footprints,
+        Cn and PNR by bicubic imresize to the patch (negative lobes kept), center = center * ssub - 1, C and C_raw by imresize(., [k, T], 'box') along time, S
+        bicubic, P.kernel_pars as fitted at the LOW frame rate; a neuron is kept when its up-sampled footprint has any non-zero pixel (:362-363).  The factors are
+        those the object was constructed with (_ds_factors); an engine without supports_init_residual_ds is refused, and so is a call with factors other than 1
+        before any background was fitted (_first_run: the reference's second pass reads the fitted W, b0 of every patch, :186-217; on the ring's initial indicator
+        the residual is no background-free video, and the down-sampled session is built for the fitted one only -- NotImplementedError).  An observer's "open" record then carries
+        Yds, the (Ts, d1s d2s) video the session searches, instead of Yres.
+        Not built (NotImplementedError): save_avi."""
         self._need_data()
         v, o = self.video, self.options
-        if int(o.ssub) != 1 or int(o.tsub) != 1:
-            raise NotImplementedError("initComponents_residual_parallel: ssub / tsub other than 1 are not built")
+        ssub, tsub = self._ds_factors(v.T)
+        ds = ssub != 1 or tsub != 1
+        if ds and not self._can("init_residual_ds"):
+            raise NotImplementedError("this engine does not build ssub / tsub other than 1 in the second pass (supports_init_residual_ds)")
+        if ds and self._first_run():                                      # W{1} is still the ring's indicator (update_background_parallel.m:143): nothing was fitted
+            raise NotImplementedError("initComponents_residual_parallel with ssub / tsub other than 1 before the first update_background_parallel is not built: "
+                                      "the down-sampled session needs the residual of a fitted background")
         if save_avi:
             raise NotImplementedError("initComponents_residual_parallel: save_avi is not built")
         if min_corr is not None:                                          # :47-55
@@ -1249,9 +1266,10 @@ class Sources2D:
         if seeds is None and str(o.seed_method).lower() == "manual":
             raise ValueError("seed_method = 'manual' needs the seed pixels: initComponents_residual_parallel(seeds=[(r, c), ...])")
         n = v.T
-        gSiz = int(_mround(float(o.gSiz)))
-        bd = gSiz if o.bd is None else int(o.bd)                          # :80-83
-        psf = seed_psf(float(o.gSig), float(o.gSiz), bool(o.center_psf))
+        bd = int(_mround(float(o.gSiz))) if o.bd is None else int(o.bd)   # :80-83
+        gSiz = int(_mround(float(o.gSiz) / ssub))                         # greedyROI_endoscope.m:56-59
+        min_pixel = float(o.min_pixel) / ssub ** 2
+        psf = seed_psf(float(o.gSig) / ssub, float(gSiz) if ds else float(o.gSiz), bool(o.center_psf))
         connected = bool(o.spatial_constraints.get("connected", True))
         deconv = self._init_deconv()
         d = v.d1 * v.d2
@@ -1263,26 +1281,35 @@ class Sources2D:
             pid = v.pid[idx]
             pp = [int(x) for x in v.patch_pos[idx]]
             nr, nc = pp[1] - pp[0] + 1, pp[3] - pp[2] + 1
+            d1s, d2s = -(-nr // ssub), -(-nc // ssub)                     # the session's grid (the patch itself without down-sampling)
             ind, A_blk = self._slice(self.A, idx, "block")                # :116-117
             C_blk = self._rows(self.C, ind) if ind.size else None         # :120
             self._residual(idx, A_blk if ind.size else None, C_blk)       # :199-217 without A(patch, ind) C: the resident Ysig (it goes with the session: tag None)
             A_pp = self._slice(self.A, idx, "patch", cols=ind)[1] if ind.size else None
-            cn_p, pnr_p, _sn_p, yres = self.engine.peel_open_residual(pid, A_pp, C_blk, psf, 3.0, want_video=want_video)
+            if ds:
+                cn_p, pnr_p, _sn_p, yvid = self.engine.peel_open_residual_ds(pid, ssub, tsub, A_pp, C_blk, psf, 3.0, want_video=want_video)
+            else:
+                cn_p, pnr_p, _sn_p, yvid = self.engine.peel_open_residual(pid, A_pp, C_blk, psf, 3.0, want_video=want_video)
             try:
                 if observer is not None:
-                    observer(idx, "open", dict(Cn=cn_p, PNR=pnr_p, Yres=yres))
+                    observer(idx, "open", dict(Cn=cn_p, PNR=pnr_p, **({"Yds": yvid} if ds else {"Yres": yvid})))
+                cn_s, pnr_s = cn_p.astype(np.float64).reshape(d1s, d2s, order="F"), pnr_p.astype(np.float64).reshape(d1s, d2s, order="F")
+                if ssub != 1:                                              # greedyROI_endoscope.m:471-472
+                    cn_p, pnr_p = (hostops.imresize_to(x, (nr, nc)).reshape(-1, order="F") for x in (cn_s, pnr_s))
                 Cn[v.patch_pix[idx]] = cn_p
                 PNR[v.patch_pix[idx]] = pnr_p
                 bd4 = [bd * int(f) for f in (idx[0] == 0, idx[0] == v.nr_patch - 1, idx[1] == 0, idx[1] == v.nc_patch - 1)]      # :173
+                bd4 = [int(_mround(b / ssub)) for b in bd4]                # greedyROI_endoscope.m:59
                 loc = None
                 if seeds is not None:
-                    loc = [(int(r) - pp[0], int(c) - pp[2]) for (r, c) in seeds if pp[0] <= int(r) <= pp[1] and pp[2] <= int(c) <= pp[3]]
+                    loc = [((int(r) - pp[0]) // ssub, (int(c) - pp[2]) // ssub) for (r, c) in seeds if pp[0] <= int(r) <= pp[1] and pp[2] <= int(c) <= pp[3]]
                 sess = _PeelSession(self.engine, pid, gSiz)
-                res = hostops.greedy_roi_block(sess, cn_p.astype(np.float64).reshape(nr, nc, order="F"), pnr_p.astype(np.float64).reshape(nr, nc, order="F"),
-                                               gSiz, psf, float(o.min_corr), float(o.min_pnr), float(o.min_pixel), bd4, nr * nc if K is None else K, connected,
-                                               deconv, loc, 3.0, None if observer is None else (lambda kind, data, idx=idx: observer(idx, kind, data)))
+                res = hostops.greedy_roi_block(sess, cn_s, pnr_s, gSiz, psf, float(o.min_corr), float(o.min_pnr), min_pixel, bd4, nr * nc if K is None else K,
+                                               connected, deconv, loc, 3.0, None if observer is None else (lambda kind, data, idx=idx: observer(idx, kind, data)))
             finally:
                 self.engine.peel_close(pid)
+            if ds:
+                res = self._init_upsample(res, ssub, tsub, (d1s, d2s), (nr, nc), n)
             keep = [k for k in range(res["center"].shape[0]) if np.any(res["A"][k][1])]      # :362-363
             per_patch[idx] = (res, keep, (pp[0], pp[2]))
         A_new, Cm, Craw, Sm, kp, center = self._stitch_init(per_patch, n)

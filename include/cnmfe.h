@@ -215,12 +215,30 @@ int cnmfe_peel_open_residual(cnmfe_ctx *ctx, int patch_id, int32_t Ksel, const i
  * pipeline then runs with M = 0.  Yw starts as the down-sampled video (Yds_out, may be NULL: exactly that fp32 video, d1s d2s x Ts frame-major, to host or device
  * memory); y_bg adds box(pixel mean), with Mpre > 0 nothing.  The session keeps 2 x 16 * ceil(Ts / 4) * d1s d2s bytes (CNMFE_ENOMEM names them).
  * cnmfe_peel_extract / _apply / _close work in the session's geometry: seeds 0-based on the d1s x d2s grid, ci of Ts samples.  ssub = tsub = 1, Mpre = 0 is the
- * identity: Yds_out is the centred video bit for bit and the images are cnmfe_peel_open's. */
+ * identity: Yds_out is the centred video bit for bit and the images are cnmfe_peel_open's.
+ *
+ * cnmfe_peel_open_residual_ds: options.ssub / options.tsub of the SECOND pass (initComponents_residual_parallel.m:171-177,232 hands greedyROI_endoscope the
+ * patch residual, which :46-61 down-samples): the session on dsData(Yres) of the PATCH, d1s = ceil(nr / ssub), d2s = ceil(nc / ssub), Ts = floor(T / tsub).
+ * dsData is linear, so the device forms
+ *   dsData(Ysig - A C) = dsData(Ysig) - A_ds C_ds
+ * off the resident residual: A_ds = every footprint column box-resized on the patch grid (the library does it in float64 with the tap tables of the kernel,
+ * exact zeros dropped), C_ds = the mean of every tsub consecutive samples of each trace (on the device in fp64: a bound C never comes down).  Per low-resolution
+ * pixel and frame: taps, then the frames of the bin in ascending order, one division by tsub, then the pixel's footprints in ascending column order by fma, ONE
+ * rounding to fp32 -- no full-resolution difference video exists and two calls are bit-identical.  Arguments and refusals are those of cnmfe_peel_open_residual
+ * (A over the PATCH rows at FULL resolution, the resident residual, no open session, no derived patch) plus the factors': ssub in 1 .. 8 and tsub >= 1, else
+ * CNMFE_EINVAL; floor(T / tsub) < 64 is CNMFE_EUNSUPPORTED.  Cn_ds / PNR_ds / Sn_ds: d1s d2s floats; Yds_out (may be NULL): exactly the fp32 video the
+ * session searches, d1s d2s x Ts frame-major.  The session keeps 2 x 16 * ceil(Ts / 4) * d1s d2s bytes (CNMFE_ENOMEM names them); extract / apply take seeds
+ * 0-based on the d1s x d2s grid and ci of Ts samples; y_bg takes no pixel mean.  The residual request belongs to the session exactly as for
+ * cnmfe_peel_open_residual (cnmfe_peel_close and a failed open drop it).  ssub = tsub = 1 IS cnmfe_peel_open_residual: images, Sn and video bit for bit. */
 int cnmfe_seed_images_ds(cnmfe_ctx *ctx, int patch_id, int32_t ssub, int32_t tsub, const float *psf, int32_t psf_n, int64_t nframes,
                          const double *Q /* Ts x M */, int32_t M, float sig, float *Cn_ds /* d1s * d2s */, float *PNR_ds /* d1s * d2s */);
 int cnmfe_peel_open_ds(cnmfe_ctx *ctx, int patch_id, int32_t ssub, int32_t tsub, const float *psf, int32_t psf_n, int64_t nframes,
                        const double *Qpre /* nframes x Mpre */, int32_t Mpre, float sig, float *Cn_ds /* d1s * d2s */, float *PNR_ds /* d1s * d2s */,
                        float *Sn_ds /* d1s * d2s or NULL */, float *Yds_out /* d1s * d2s x Ts or NULL */, int out_memspace);
+int cnmfe_peel_open_residual_ds(cnmfe_ctx *ctx, int patch_id, int32_t ssub, int32_t tsub, int32_t Ksel, const int64_t *A_colptr,
+                                const int32_t *A_rowidx /* in [0, d) */, const float *A_val, const float *C, int c_order, const float *psf, int32_t psf_n, float sig,
+                                float *Cn_ds /* d1s * d2s */, float *PNR_ds /* d1s * d2s */, float *Sn_ds /* d1s * d2s or NULL */,
+                                float *Yds_out /* d1s * d2s x Ts or NULL */, int out_memspace);
 int cnmfe_peel_extract(cnmfe_ctx *ctx, int patch_id, int32_t r, int32_t c, int32_t gSiz, double *corr_box /* nr * nc */, double *ai_box /* nr * nc */,
                        double *ci /* nframes */, double *stats /* 6 */);
 int cnmfe_peel_apply(cnmfe_ctx *ctx, int patch_id, int32_t r, int32_t c, int32_t gSiz, const double *ai_box /* nr * nc */,
