@@ -58,6 +58,8 @@ class Sources2DBatch:
         if not batches:
             raise ValueError("Sources2DBatch needs at least one batch")
         v0 = batches[0].video
+        if str(options.background_model).lower() == "svd" or any(getattr(s, "bg_model", "ring") == "svd" for s in batches):
+            raise NotImplementedError("Sources2DBatch is not built for background_model = 'svd'")
         for m, s in enumerate(batches):
             v = s.video
             if getattr(s, "dist", None) is not None:

@@ -614,7 +614,7 @@ static int require_residual(const Patch *P, int patch_id) {
 }
 static int require_residual_full(const Patch *P, int patch_id, const char *what) {
     RET(require_residual(P, patch_id));
-    if (P->residual.source != rplan::SRC_FULL) return fail(CNMFE_EUNSUPPORTED, "%s needs the residual of cnmfe_residual (bg_ssub = 1)", what);
+    if (!rplan::serves_ring_readers(P->residual.source)) return fail(CNMFE_EUNSUPPORTED, "%s needs the residual of cnmfe_residual (bg_ssub = 1)", what);
     return 0;
 }
 
@@ -689,7 +689,7 @@ int cnmfe_synchronize(cnmfe_ctx *ctx) {
 int cnmfe_set_option(cnmfe_ctx *ctx, const char *name, int64_t value) {
     if (!ctx || !name) return fail(CNMFE_EINVAL, "null argument");
     // behaviour switches (include/cnmfe.h) and, behind them, the probes of scripts/ (diagnostics: solve_probe, r1_probe, deconv_trace, trace_long, host_trace, debug)
-    static const char *known[] = {"r1_variant", "r1_delta", "r1_lazy", "r1_defer", "r1_virtual", "gram_incremental", "prealloc", "solve_packed", "sweep_dag", "win_i8_planes", "solve_staged", "solve_inv", "solve_inv_terms", "gram_i8", "win_i8", "proj_tiled", "proj_i8", "proj_i8_planes", "ssub_virtual", "temporal_early", "fit_side", "ring_side",
+    static const char *known[] = {"r1_variant", "r1_delta", "r1_lazy", "r1_defer", "r1_virtual", "gram_incremental", "prealloc", "solve_packed", "sweep_dag", "win_i8_planes", "solve_staged", "solve_inv", "solve_inv_terms", "gram_i8", "win_i8", "proj_tiled", "proj_i8", "proj_i8_planes", "ssub_virtual", "temporal_early", "fit_side", "ring_side", "bg_svd_tol_exp", "bg_svd_max_iter",
                                   "solve_probe", "r1_probe", "deconv_trace", "trace_long", "host_trace", "debug", nullptr};
     if (!strcmp(name, "lanes")) { RET(lanes_set(ctx, value)); ctx->opts[name] = value; return 0; }
     for (int i = 0; known[i]; ++i) if (!strcmp(known[i], name)) { ctx->opts[name] = value; if (!strcmp(name, "host_trace")) ctx->trace_level = (int)value; return 0; }
@@ -1016,6 +1016,59 @@ int cnmfe_residual(cnmfe_ctx *ctx, int patch_id, int32_t Ksel, const int64_t *A_
     CK(hipSetDevice(ctx->device));
     RET(ensure_ymean(ctx, P));
     return residual_run(ctx, P, patch_id, Ksel, A_colptr, A_rowidx, A_val, C, c_order, Ysig_out, out_memspace);
+}
+
+// ---- background_model = 'svd' (bg_svd.hpp) ----
+int cnmfe_bg_svd_fit(cnmfe_ctx *ctx, int patch_id, int32_t nb, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const float *C, int c_order) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    Patch *P = get_patch(ctx, patch_id);
+    if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
+    if (nb < 0 || nb > 8) return fail(CNMFE_EUNSUPPORTED, "nb = %d; the low-rank background holds 0 .. 8 components", nb);
+    if (nb > std::min<int64_t>(P->d_b, P->T)) return fail(CNMFE_EUNSUPPORTED, "nb = %d exceeds min(d_b, T) = %lld", nb, (long long)std::min<int64_t>(P->d_b, P->T));
+    RET(check_csc("A", K, P->d_b, A_colptr, A_rowidx));
+    if (K > 0 && A_colptr[K] > 0 && (!A_val || (!C && c_order != CNMFE_BOUND))) return fail(CNMFE_EINVAL, "null A_val / C");
+    CK(hipSetDevice(ctx->device));
+    RET(ensure_ymean(ctx, P));
+    return bg_svd_fit_run(ctx, P, nb, K, A_colptr, A_rowidx, A_val, C, c_order);
+}
+
+int cnmfe_bg_svd_get(cnmfe_ctx *ctx, int patch_id, double *b, double *f, double *b0) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    Patch *P = get_patch(ctx, patch_id);
+    if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
+    if (P->svd_nb < 0) return fail(CNMFE_ESTATE, "patch %d has no low-rank background (cnmfe_bg_svd_fit / cnmfe_bg_svd_set)", patch_id);
+    CK(hipSetDevice(ctx->device));
+    return bg_svd_get_run(ctx, P, b, f, b0);
+}
+
+int cnmfe_bg_svd_set(cnmfe_ctx *ctx, int patch_id, int32_t nb, const double *b, const double *f, const double *b0) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    Patch *P = get_patch(ctx, patch_id);
+    if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
+    if (nb < 0 || nb > 8) return fail(CNMFE_EUNSUPPORTED, "nb = %d; the low-rank background holds 0 .. 8 components", nb);
+    if (!b0 || (nb > 0 && (!b || !f))) return fail(CNMFE_EINVAL, "null b / f / b0");
+    CK(hipSetDevice(ctx->device));
+    return bg_svd_set_run(ctx, P, nb, b, f, b0);
+}
+
+int cnmfe_bg_svd_stats(cnmfe_ctx *ctx, int patch_id, double out[20]) {
+    if (!ctx || !out) return fail(CNMFE_EINVAL, "null argument");
+    Patch *P = get_patch(ctx, patch_id);
+    if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
+    const SvdStats &s = P->svd_stats;
+    out[0] = (double)s.passes; out[1] = (double)s.iters; out[2] = s.converged; out[3] = s.nb;
+    for (int i = 0; i < 8; ++i) { out[4 + i] = s.resid[i]; out[12 + i] = s.sv[i]; }
+    return 0;
+}
+
+int cnmfe_residual_lowrank(cnmfe_ctx *ctx, int patch_id, float *Ysig_out, int out_memspace) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    Patch *P = get_patch(ctx, patch_id);
+    if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
+    if (P->svd_nb < 0) return fail(CNMFE_ESTATE, "patch %d has no low-rank background (cnmfe_bg_svd_fit / cnmfe_bg_svd_set)", patch_id);
+    CK(hipSetDevice(ctx->device));
+    RET(ensure_ymean(ctx, P));
+    return bg_svd_resid_run(ctx, P, Ysig_out, out_memspace);
 }
 
 int cnmfe_get_sn(cnmfe_ctx *ctx, int patch_id, float *sn_out) {

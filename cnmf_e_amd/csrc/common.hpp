@@ -189,6 +189,10 @@ struct ResidualState {
     rplan::TermsView terms() const { return {has_pending, applied.view(), pending.view()}; }
 };
 
+// what the last low-rank background fit of a patch did (bg_svd.hpp; cnmfe_bg_svd_stats): video passes, iterations, the relative residual
+// |M u_i - theta_i u_i| / theta_1 and the singular value of every component, and whether every residual met the tolerance before the iteration cap
+struct SvdStats { int64_t passes = 0, iters = 0; int converged = 0; int nb = 0; double resid[8] = {}, sv[8] = {}; };
+
 // ---- per-patch resident state ----------------------------------------------------
 struct Patch {
     int32_t prect[4], brect[4];        // 1-based inclusive [r0 r1 c0 c1]
@@ -213,6 +217,8 @@ struct Patch {
     bool ring_ready = false;
     DevBuf sn_b;                       // d_b fp32 noise levels of the block pixels (cnmfe_set_noise): only the outlier branch of the ring fit reads them
     bool sn_ready = false;
+    // background_model = 'svd' (bg_svd.hpp): b (nb columns of d), f (nb rows of T), b0 (d), all fp64; svd_nb = -1: none yet (cnmfe_bg_svd_fit / cnmfe_bg_svd_set)
+    DevBuf svd_b, svd_f, svd_b0; int svd_nb = -1; SvdStats svd_stats;
     DevBuf ysig;                       // Ysig4[ceil(T/4)][d] float4, the background-subtracted video of this patch where it is resident; `residual` says what it holds
     ResidualState residual;
     // P(j,k) = sum_t Yc_j(t) Cc_k(t) in fp64 per 16x16 block of the block region and list slot: pt_tab[(pt_lp[b] + slot) * 256 + lp_of(pixel)], pt_slot[b * pt_K + k]
@@ -385,6 +391,7 @@ struct LaneState {
     // per-call device scratch of the factor updates (factor.hip, deconv.hip): grown on demand, NEVER freed between calls -- a hipMalloc /
     // hipFree pair per buffer and call cost more than the small kernels they serve, and hipFree drains the device
     DevBuf scr[24];
+    DevBuf svd[19];           // bg_svd.hpp: the panels Q, Z, G, D, the passes' partial sums, the small products, the call's A as CSC and CSR
     DevBuf itp[30];           // init_temporal.hpp: the block's footprints, the ring-filtered footprints and their rough-start selection (fp64), their lists, U | C0 of the projection
     DeconvScratch dscr;
     kept::KeptSpatial kept;   // what the last deferred spatial update of this lane left in scr[SCR_COLPTR | SCR_EROW | SCR_AVAL | SCR_KEEP] (kept_results.hpp)
@@ -660,6 +667,11 @@ int fp_dilate_run(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64
 int fp_trim_run(cnmfe_ctx *ctx, int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, double thr, int32_t sz,
                 int32_t min_pixel, uint8_t *keep, uint8_t *ind_small, uint8_t *host_col, int out_memspace);
 int ensure_ymean(cnmfe_ctx *ctx, Patch *P);
+// bg_svd.hpp (vproj.hip): the low-rank background model
+int bg_svd_fit_run(cnmfe_ctx *ctx, Patch *P, int nb, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const float *C, int c_order);
+int bg_svd_set_run(cnmfe_ctx *ctx, Patch *P, int nb, const double *b, const double *f, const double *b0);
+int bg_svd_get_run(cnmfe_ctx *ctx, Patch *P, double *b, double *f, double *b0);
+int bg_svd_resid_run(cnmfe_ctx *ctx, Patch *P, float *Ysig_out, int out_memspace);
 int sn_video_run(cnmfe_ctx *ctx, Patch *P, int64_t nframes, float *sn_out);
 int seed_images_run(cnmfe_ctx *ctx, const SeedSrc &src, const float *psf, int32_t psf_n, int64_t nframes, const double *Q, int32_t M, float sig,
                     float *Cn_out, float *PNR_out, PeelSession *keep = nullptr);   // seed.hpp (deconv.hip)

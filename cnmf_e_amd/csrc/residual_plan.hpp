@@ -9,7 +9,7 @@ namespace rplan {
 
 // ---- the state beside Ysig, as the rules see it -----------------------------------------------------------------------------------------------------------
 enum Form { NONE = 0, VIRTUAL = 1, RESIDENT = 2 };        // no residual | a recorded request (no sweep has run) | Ysig itself lies in the patch's buffer
-enum Source { SRC_NONE = 0, SRC_FULL = 1, SRC_SSUB = 2 }; // who wrote it: cnmfe_residual | cnmfe_residual_ssub
+enum Source { SRC_NONE = 0, SRC_FULL = 1, SRC_SSUB = 2, SRC_LOWRANK = 3 }; // who wrote it: cnmfe_residual | cnmfe_residual_ssub | cnmfe_residual_lowrank
 struct TermView { bool ac; int64_t ldc; int32_t K; };     // a footprint term: has footprints at all, row stride of its centred traces, number of traces
 struct TermsView { bool has_pending; TermView applied, pending; };
 struct View { Form form; int source; bool buffer; };      // buffer: the patch's Ysig buffer is allocated
@@ -43,6 +43,15 @@ inline Plan residual_plan(const View &v, const Request &q, const ResidualOpts &o
     else if (p.virt_new) p.action = Record;
     return p;
 }
+
+// ---- the low-rank background (background_model = 'svd', bg_svd.hpp) ------------------------------------------------------------------------------------------
+// Its residual Yc + (Ymean - b0) - b f is always RESIDENT, carries no footprint term (nothing applied, nothing pending) and is never recorded: the sweep-free form
+// would be a rank-nb correction of the projections and is not built.  A fit, a transplant of b, f, b0 and an upload of the video invalidate it; a request that finds
+// it still valid has nothing to do.  A ring request (SRC_FULL / SRC_SSUB) never reuses it and it never reuses theirs: residual_plan's `kept` compares the sources.
+struct LowrankPlan { bool sweep; };
+inline LowrankPlan lowrank_plan(const View &v) { return {!(v.form == RESIDENT && v.source == SRC_LOWRANK && v.buffer)}; }
+// compute_RSS and reconstruct_background are built on the ring's W: they serve the residual of cnmfe_residual only
+inline bool serves_ring_readers(int source) { return source == SRC_FULL; }
 
 // ---- the kernel of the sweep --------------------------------------------------------------------------------------------------------------------------------
 // variant: 14 duo-role kernel (radius 15, no footprint term inside the sweep), 11 arc kernel (radius 15), 10 LDS-DMA kernel (radius 15 / 18 and the low-resolution

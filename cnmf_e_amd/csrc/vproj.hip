@@ -18,6 +18,7 @@
 #include "common.hpp"
 #include "win_proj.hpp"
 #include "vproj_i8.hpp"
+#include "bg_svd.hpp"
 #include <climits>
 
 namespace cnmfe {

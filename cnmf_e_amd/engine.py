@@ -332,6 +332,7 @@ class Engine:
     supports_init_residual_ds = True  # peel_open_residual_ds(): options.ssub / options.tsub of the second pass (initComponents_residual_parallel)
     supports_traces_grow = True       # traces_grow(): zero rows under the bound matrix and its residents, on the device
     supports_image_ops = True         # circular_constraints() / search_dilate() / trim_spatial(): the image operations on single footprints (footprint_ops.hpp)
+    supports_bg_svd = True            # bg_svd_fit() / bg_svd_get() / bg_svd_set() / bg_svd_stats() / residual_lowrank(): options.background_model = 'svd'
     IMAGE_OPS_MAX_BOX = 4096          # cells of the largest box those kernels take (FP_MAX_CELLS); a column above it is computed by hostops and spliced in
 
     # pinned buffers of LazyHostTraces, recycled by size (page-locking 20 MB costs milliseconds)
@@ -699,6 +700,51 @@ class Engine:
         else:
             dst, space = (out.ctypes.data_as(C.c_void_p) if want else C.c_void_p(None)), L.HOST
         L.check(L.lib.cnmfe_residual(self._ctx, pid, K, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p), cptr, cord, dst, space))
+        return out
+
+    # -- background_model = 'svd' (cnmfe_bg_svd_*, cnmfe_residual_lowrank) ---------------------------------------
+    def bg_svd_fit(self, pid, nb, A_block=None, C_block=None):
+        """[b, f, b0] = fit_svd_model(Y, nb, A, C, ...) of one patch (update_background_parallel.m:238-242); the factors stay resident.  Returns bg_svd_stats(pid);
+        a fit that stopped at the iteration cap is no error: it raises a RuntimeWarning."""
+        info = self._patch[pid]
+        K, cp, ri, va = _csc(A_block, info["d_b"]) if A_block is not None and A_block.shape[1] else (0, None, None, None)
+        cptr, cord, _keep = self._targs(C_block, K, info["T"])
+        L.check(L.lib.cnmfe_bg_svd_fit(self._ctx, pid, int(nb), K, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p), cptr, cord))
+        st = self.bg_svd_stats(pid)
+        if not st["converged"]:
+            import warnings
+            warnings.warn("low-rank background of patch %d: %d iterations did not reach the tolerance (residuals %s)"
+                          % (pid, st["iterations"], np.array2string(st["residual"], precision=2)), RuntimeWarning, stacklevel=2)
+        return st
+
+    def bg_svd_stats(self, pid):
+        out = np.zeros(20, dtype=np.float64)
+        L.check(L.lib.cnmfe_bg_svd_stats(self._ctx, pid, _p(out, L.f64p)))
+        nb = int(out[3])
+        return dict(passes=int(out[0]), iterations=int(out[1]), converged=bool(out[2]), nb=nb, residual=out[4:4 + nb].copy(), s=out[12:12 + nb].copy())
+
+    def bg_svd_get(self, pid):
+        """(b (d, nb), f (nb, T), b0 (d,)) of one patch, float64"""
+        info = self._patch[pid]
+        nb = self.bg_svd_stats(pid)["nb"]
+        b = np.zeros((nb, info["d"]), dtype=np.float64); f = np.zeros((nb, info["T"]), dtype=np.float64); b0 = np.zeros(info["d"], dtype=np.float64)
+        L.check(L.lib.cnmfe_bg_svd_get(self._ctx, pid, _p(b, L.f64p), _p(f, L.f64p), _p(b0, L.f64p)))
+        return np.ascontiguousarray(b.T), f, b0
+
+    def bg_svd_set(self, pid, b, f, b0):
+        """transplant a saved background: b (d, nb), f (nb, T), b0 (d,)"""
+        info = self._patch[pid]
+        b = np.asarray(b, dtype=np.float64).reshape(info["d"], -1); nb = b.shape[1]
+        f = np.ascontiguousarray(np.asarray(f, dtype=np.float64).reshape(nb, info["T"]))
+        b0 = np.ascontiguousarray(np.asarray(b0, dtype=np.float64).reshape(info["d"]))
+        bt = np.ascontiguousarray(b.T)                        # nb columns of d, one after the other
+        L.check(L.lib.cnmfe_bg_svd_set(self._ctx, pid, nb, _p(bt, L.f64p), _p(f, L.f64p), _p(b0, L.f64p)))
+
+    def residual_lowrank(self, pid, want=False):
+        """Ysig = Y(patch) - (b f + b0), resident for the updates (update_spatial_parallel.m:184-187); want=True returns it as a (T, d) host array"""
+        info = self._patch[pid]
+        out = np.empty((info["T"], info["d"]), dtype=np.float32) if want else None
+        L.check(L.lib.cnmfe_residual_lowrank(self._ctx, pid, out.ctypes.data_as(C.c_void_p) if want else C.c_void_p(None), L.HOST))
         return out
 
     def get_sn(self, pid):

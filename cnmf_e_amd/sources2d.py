@@ -721,10 +721,13 @@ class Sources2D:
     fetch with ``get_W`` / ``get_b0``), b0_new, options, P (sn, Ymean)."""
 
     def __init__(self, video: PatchedVideo, options: Options, A, C, sn, dist_group=None):
-        if options.background_model != "ring":
-            raise ValueError("only the ring background model is built (north star); got %r" % options.background_model)
+        self.bg_model = str(options.background_model).lower()             # (the reference compares with strcmpi)
+        if self.bg_model not in ("ring", "svd"):
+            raise ValueError("only the ring and the svd background models are built; got %r" % options.background_model)
         if not (1 <= int(options.bg_ssub) <= 8):
             raise ValueError("bg_ssub must be in 1..8")
+        if self.bg_model == "svd":
+            self._svd_check(video.engine, options, dist_group)
         self.video = video
         self.options = options
         options.d1, options.d2 = video.d1, video.d2
@@ -760,11 +763,19 @@ class Sources2D:
         self._bbox_cache = ()           # _bbox_of: (matrix, bounding boxes of its columns) of the last four matrices, by identity
         self._ds_declared = (options.ssub, options.tsub)      # the down-sampling of the initialisation is declared at construction, like bg_ssub (_ds_factors)
         self._bind_C()
-        self.ssub = int(options.bg_ssub)
+        self.ssub = int(options.bg_ssub) if self.bg_model == "ring" else 1      # (the svd model ignores bg_ssub, as the reference does)
         npatch = len(video.order)
         # bg_ssub > 1: every patch gets two low-resolution companions on the device (cnmfe.h, cnmfe_patch_derive)
         self.pid_fit = {idx: npatch + 2 * video.pid[idx] for idx in video.order}
         self.pid_res = {idx: npatch + 2 * video.pid[idx] + 1 for idx in video.order}
+        self._ymean_full = None
+        if self.bg_model == "svd":
+            # initComponents_parallel.m:265-281: b{m} = zeros(nr*nc, nb), f{m} = zeros(nb, T) (and b0{m} zero); no ring, no low-resolution companions, no fit buffers
+            for idx in video.owned:
+                n = video.patch_pix[idx].size
+                self.engine.bg_svd_set(video.pid[idx], np.zeros((n, int(options.nb))), np.zeros((int(options.nb), video.T)), np.zeros(n))
+                self.P["Ymean"][idx] = self.engine.ymean(video.pid[idx])[video.ind_patch[idx]]
+            return
         for idx in video.owned:                                           # initComponents_parallel.m:213-236
             self.engine.ring_init(video.pid[idx], options.ring_radius, options.num_neighbors)
             if self.ssub > 1:                                             # :214,237-251: rr = ceil(r/bg_ssub), W on the low-resolution block
@@ -778,6 +789,24 @@ class Sources2D:
             self.P["Ymean"][idx] = self.engine.ymean(video.pid[idx])[video.ind_patch[idx]]      # :338-339, patch part
         self._ymean_full = None
 
+    @staticmethod
+    def _svd_check(engine, options, dist_group):
+        """background_model = 'svd': what the constructor refuses"""
+        if not getattr(engine, "supports_bg_svd", False):
+            raise NotImplementedError("this engine does not build background_model = 'svd' (supports_bg_svd)")
+        if not (0 <= int(options.nb) <= 8):
+            raise ValueError("background_model = 'svd' takes nb in 0..8, got %r" % (options.nb,))
+        if dist_group is not None:
+            raise NotImplementedError("background_model = 'svd' is not built for a dist_group (one rank only)")
+        get = getattr(engine, "get_option", None)
+        if get is not None and int(get("lanes", 1)) > 1:
+            raise NotImplementedError("background_model = 'svd' is not built for lanes > 1")
+
+    def _svd_refuse(self, what):
+        """the methods that read the ring background (W, b0 on the block) are not built for the svd model"""
+        if self.bg_model == "svd":
+            raise NotImplementedError("%s is not built for background_model = 'svd'" % what)
+
     def _can(self, what):
         """the engine's class-level flag supports_<what> (engine.Engine lists them), read where the decision is made; an engine that does not declare it does not offer it"""
         return getattr(self.engine, "supports_" + what, False)
@@ -789,6 +818,7 @@ class Sources2D:
 
     # -- accessors ------------------------------------------------------------------
     def get_W(self, idx):
+        self._svd_refuse("get_W")
         return self.engine.ring_csr(self.video.pid[idx] if self.ssub == 1 else self.pid_fit[idx])
 
     def _slice(self, A, idx, kind, cols=None):
@@ -903,6 +933,7 @@ class Sources2D:
         (T, d_patch) float32 array (frame-major == the reference's d x T in MATLAB order).  greedyROI_endoscope itself is host code
         outside this engine (initialisation is out of scope)."""
         self._need_data()
+        self._svd_refuse("init_residual")
         ind, A_blk = self._slice(self.A, idx, "block")                                               # :116-117
         C_blk = self._rows(self.C, ind) if ind.size else None                                        # :120
         out = self._residual(idx, A_blk if ind.size else None, C_blk, want=True)
@@ -914,7 +945,33 @@ class Sources2D:
         return out
 
     def get_b0(self, idx):
+        if self.bg_model == "svd":
+            return self.engine.bg_svd_get(self.video.pid[idx])[2]
         return self.engine.b0(self.video.pid[idx])
+
+    # -- background_model = 'svd': obj.b{m} (d x nb), obj.f{m} (nb x T), obj.b0{m} (d) of a patch, float64; they live on the engine --
+    def get_b(self, idx):
+        self._svd_only("get_b")
+        return self.engine.bg_svd_get(self.video.pid[idx])[0]
+
+    def get_f(self, idx):
+        self._svd_only("get_f")
+        return self.engine.bg_svd_get(self.video.pid[idx])[1]
+
+    def set_bg_svd(self, idx, b, f, b0):
+        """obj.b{idx}, obj.f{idx}, obj.b0{idx} = a saved background (another session of the same recording).  The patch's resident residual goes with the old one.
+        A b{1} that is not all zero makes the next update_background_parallel a later run (its flag_first reads mean2(b{1}))."""
+        self._svd_only("set_bg_svd")
+        n = self.video.patch_pix[idx].size
+        b = np.asarray(b, dtype=np.float64).reshape(n, -1)
+        if b.shape[1] > 8:
+            raise ValueError("b{%s} has %d columns; at most 8" % (idx, b.shape[1]))
+        self.engine.bg_svd_set(self.video.pid[idx], b, np.asarray(f, dtype=np.float64).reshape(b.shape[1], self.video.T), np.asarray(b0, dtype=np.float64).reshape(n))
+        self._b0_new_src = "b0"
+
+    def _svd_only(self, what):
+        if self.bg_model != "svd":
+            raise NotImplementedError("%s belongs to background_model = 'svd'" % what)
 
     # -- a known background on a fresh object: W{m}, b0{m} of another recording of the same field of view (there is get_W / get_b0; these are the way in) --
     def set_W(self, idx, values):
@@ -922,7 +979,7 @@ class Sources2D:
         CSR order.  The patch's resident residual goes with the old W.  The reference's first-run test (fit_ring_model.m:25: two distinct values in row 1 of
         W{m}, also update_background_parallel.m:143) then sees a FITTED W: the next update_background_parallel of this object refits from it as a later run
         and takes the "nothing changed here" skip of :188-199 for patches without neurons."""
-        pat = self.get_W(idx)
+        pat = self.get_W(idx)                                              # (refuses the svd model)
         if sp.issparse(values):
             V = sp.csr_matrix(values)
             if V.shape != pat.shape:
@@ -942,6 +999,7 @@ class Sources2D:
     def set_b0(self, idx, b0):
         """obj.b0{idx} = b0 (the patch's pixels, column-major).  Beside a W from set_W this completes a transplanted background: the first-run test of
         fit_ring_model.m:25 looks at W alone and then sees a fitted one.  The patch's resident residual goes with the old b0; b0_new is re-read from b0."""
+        self._svd_refuse("set_b0 (use set_bg_svd)")
         b0 = np.ascontiguousarray(b0, dtype=np.float32).ravel()
         if b0.size != self.video.patch_pix[idx].size:
             raise ValueError("b0{%s} has %d pixels, got %d" % (idx, self.video.patch_pix[idx].size, b0.size))
@@ -1247,6 +1305,7 @@ class Sources2D:
         Yds, the (Ts, d1s d2s) video the session searches, instead of Yres.
         Not built (NotImplementedError): save_avi."""
         self._need_data()
+        self._svd_refuse("initComponents_residual_parallel")
         v, o = self.video, self.options
         ssub, tsub = self._ds_factors(v.T)
         ds = ssub != 1 or tsub != 1
@@ -1738,8 +1797,10 @@ class Sources2D:
 
     # -- background -------------------------------------------------------------------
     def update_background_parallel(self, use_parallel=True):
-        """@Sources2D/update_background_parallel.m:121-146,176-230,311-317 (ring model, bg_ssub = 1)."""
+        """@Sources2D/update_background_parallel.m:121-146,176-230,311-317 (ring model, bg_ssub = 1; :238-242 for the svd model: _svd_update_background)."""
         self._need_data()
+        if self.bg_model == "svd":
+            return self._svd_update_background()
         v, o = self.video, self.options
         # the block slices of the current A: prepared by the temporal update under its GPU work when A has not changed since
         cached = self._cur_blocks_src is self.A
@@ -1778,6 +1839,93 @@ class Sources2D:
         self._prev_csr_src = self.A
         self.C_prev = self.C                                               # :317
         return infos
+
+    # -- background_model = 'svd' -------------------------------------------------------------------------------------
+    def _svd_update_background(self):
+        """update_background_parallel.m:121-130,145,188-199,238-242,316-317.  flag_first = (mean2(b{1}) == 0) reads patch 1 ONLY and decides for every patch, like the
+        ring model's test on W{1}: a patch without a neuron in its block is skipped on every later run and keeps its b, f, b0.  nb = 0 leaves b{1} = 0 after a fit,
+        so every run is then a first run, as in the reference.  DEVIATION, nb = 0 only: the reference's very FIRST call sees b{1} = zeros(nr*nc, 0), whose mean2 is NaN, so
+        its flag_first is false there and patches without neurons keep b0 = 0 until a later call; here an empty b{1} counts as a first run from the start, and every
+        patch gets its b0 = Ymean on the first call.  thresh_outlier and sn are dead for this model (fit_svd_model.m:29 tests a misspelt variable): not passed."""
+        v, o, eng = self.video, self.options, self.engine
+        b1 = eng.bg_svd_get(v.pid[v.order[0]])[0]
+        flag_first = b1.size == 0 or float(np.mean(b1)) == 0.0                                       # :145
+        stats = {}
+        for idx in v.owned:
+            ind_nz, A_block = self._slice(self.A, idx, "block")                                      # :128-129
+            if A_block.shape[1] == 0 and not flag_first:                                             # :188-199
+                continue
+            stats[idx] = eng.bg_svd_fit(v.pid[idx], int(o.nb), A_block if A_block.shape[1] else None, self._rows(self.C, ind_nz) if ind_nz.size else None)   # :242
+        self._b0_new_src = "b0"
+        self.A_prev = self.A                                                                         # :316
+        self._prev_csr_src = self.A
+        self._prev_blocks = {}
+        self.C_prev = self.C                                                                         # :317
+        return stats
+
+    def _svd_update_spatial(self):
+        """update_spatial_parallel.m:61-100,116-216 with tmp_block = patch_pos (:131): the neurons whose search mask meets the PATCH, the data of the patch without halo,
+        Ysig = Y - (b f + b0) (:184-187), the same HALS / NNLS calls; the stitch (:320-341) is the ring model's.  No b0_new tail (:347-351 is ring-only)."""
+        v, o, eng = self.video, self.options, self.engine
+        if o.search_method not in ("ellipse", "dilate"):
+            raise NotImplementedError("search_method must be 'ellipse' or 'dilate'")
+        d, K = v.d1 * v.d2, self.A.shape[1]
+        se_now = o.se
+        if o.search_method == "dilate":
+            o.se = None
+        IND = self._search_location_csc(se_now)                                                      # :66
+        trip = ([], [], [])
+        for idx in v.owned:
+            ind, IND_patch, A_patch, C_patch = self._spatial_masks(idx, IND)                         # :87-91
+            if ind.size == 0:
+                continue                                                                             # :121-124
+            pp = v.patch_pix[idx]
+            eng.residual_lowrank(v.pid[idx])                                                         # :184-187
+            r = eng.update_spatial(v.pid[idx], o.spatial_algorithm, A_patch, C_patch, IND_patch, self.P["sn"][pp] if o.spatial_algorithm == "hals_thresh" else None,
+                                   20 if o.spatial_algorithm == "nnls" else 3)                       # :203,205,211
+            self._spatial_collect(trip, r, pp, ind)
+        A_raw = (_csc_from_triplets(np.concatenate(trip[0]), np.concatenate(trip[1]), np.concatenate(trip[2]), (d, K)) if trip[0]
+                 else sp.csc_matrix((d, K), dtype=np.float32))
+        A_raw.eliminate_zeros(); A_raw.sort_indices()
+        self.A_raw = A_raw
+        self.A = self._post_process(A_raw) if o.spatial_constraints.get("connected", True) else A_raw   # :341
+        if o.spatial_constraints.get("circular", False):
+            self.A = self._circular_columns(self.A)
+        self._early_u = None
+
+    def _svd_update_temporal(self, use_c_hat):
+        """update_temporal_parallel.m:74-87,112-186,264-286 with tmp_block = patch_pos (:78): the neurons that touch the PATCH, Ysig = Y - (b f + b0) (:170-173); the
+        stitch over the patches (AA, :264-280) is the ring model's.  No b0_new tail (:291-295 is ring-only)."""
+        v, o, eng = self.video, self.options, self.engine
+        K, T = self.C.shape
+        eng.stitch_begin(K, T)
+        self._cur_blocks, self._cur_blocks_src = {}, None
+        for idx in v.owned:
+            ind, A_pp = self._slice(self.A, idx, "patch")                                            # :83-84
+            if ind.size == 0:
+                continue                                                                             # :123
+            eng.residual_lowrank(v.pid[idx])                                                         # :170-173
+            C_patch = self._rows(self.C, ind)                                                        # :86
+            if not use_c_hat:
+                eng.fast_temporal(v.pid[idx], A_pp, want_raw=False)                                  # :178
+            elif o.deconv_flag:
+                eng.hals_temporal_deconv(v.pid[idx], A_pp, C_patch, o.maxIter, o.deconv_options, want_all=None)   # :180
+            else:
+                eng.hals_temporal(v.pid[idx], A_pp, C_patch, o.maxIter, want_C=False, want_raw=False)
+            eng.stitch_add(ind)                                                                      # :274-275
+        lazy = (not o.deconv_flag) and self._can("lazy_traces")
+        bound_deconv = o.deconv_flag and self._can("bound_deconv") and self._can("lazy_traces")
+        self.C_raw = eng.stitch_finish(subtract_min=not o.deconv_flag, want="lazy" if lazy else ("bound" if bound_deconv else True))   # :279-280, :285
+        self.C = self.deconvTemporal() if o.deconv_flag else self.C_raw                              # :282-283 / :286
+
+    def _svd_reconstruct_background(self, f0, f1):
+        """Sources2D.m:1346-1350: b f(:, frames) + b0 per patch, on the host in float64 from the fetched factors (the result is a host array anyway)"""
+        v = self.video
+        Ybg = np.zeros((v.d1 * v.d2, f1 - f0 + 1), dtype=np.float32)
+        for idx in v.owned:
+            b, f, b0 = self.engine.bg_svd_get(v.pid[idx])
+            Ybg[v.patch_pix[idx]] = b @ f[:, f0 - 1:f1] + b0[:, None]
+        return Ybg.reshape(v.d1, v.d2, -1, order="F")
 
     def _temporal_residual_early(self, idx):
         """update_temporal_parallel.m:149-152 asks for the residual of (A_prev, C_prev) on the block -- both known since the background update.
@@ -1820,6 +1968,10 @@ class Sources2D:
         sweeps of the patch before), _spatial_launch queues it, its values are collected at once or, from an engine that queues downloads, `spatial_lag` patches
         late (_spatial_drain); _spatial_finish stitches them into obj.A."""
         self._need_data()
+        if self.bg_model == "svd":
+            if update_sn:
+                self._svd_refuse("update_spatial_parallel(update_sn=True)")
+            return self._svd_update_spatial()
         v, o, eng = self.video, self.options, self.engine
         sn_new = np.zeros(v.d1 * v.d2, dtype=np.float64) if update_sn else None                  # :101-102
         if o.search_method not in ("ellipse", "dilate"):
@@ -2129,6 +2281,7 @@ class Sources2D:
         Per patch the engine needs the residual of (A_prev, C_prev) on the block (:1427-1429, :1475) -- the one the temporal update asks for, so
         right after update_temporal_parallel it is still resident (or pending) and this costs one read of Ysig per patch."""
         self._need_data()
+        self._svd_refuse("compute_RSS")
         v = self.video
         b0_ = self.reconstruct_b0().reshape(-1, order="F")                                           # :1398 (a collective when sharded)
         b0_new_ = np.asarray(self.b0_new, dtype=np.float64).reshape(-1, order="F")                   # :1399
@@ -2149,6 +2302,8 @@ class Sources2D:
         v = self.video
         T = self.C.shape[1]
         f0, f1 = (1, T) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
+        if self.bg_model == "svd":
+            return self._svd_reconstruct_background(f0, f1)                                          # :1346-1350
         b0_ = self.reconstruct_b0().reshape(-1, order="F")                                           # :1292
         b0_new_ = np.asarray(self.b0_new, dtype=np.float64).reshape(-1, order="F")                   # :1293
         Ybg = np.zeros((v.d1 * v.d2, f1 - f0 + 1), dtype=np.float32)                                 # :1297
@@ -2175,6 +2330,7 @@ class Sources2D:
         each other on NaN; Df is float64, C_df and C_raw_df are (float)((double)C / Df).  medfilt1 and prctile are MathWorks functions restated from their
         documentation (parity unpinned).  want_Yf = True appends Yf (K x T float64) to the result."""
         self._need_data()
+        self._svd_refuse("extract_DF_F_endoscope")
         v, o, eng = self.video, self.options, self.engine
         K, T = self.C.shape
         p = float(o.df_prctile)
@@ -2303,6 +2459,7 @@ class Sources2D:
         holds it and nothing is asked for, so no trace matrix moves (bg_ssub > 1: cnmfe_background_ssub before every chunk -- the context keeps one patch's
         low-resolution background, and C_prev goes up with it); do not run an update between two chunks."""
         self._need_data()
+        self._svd_refuse("demixed_frames")
         v, eng = self.video, self.engine
         K, T = self.C.shape
         kt, chunk = int(kt), int(chunk)
@@ -2356,6 +2513,7 @@ class Sources2D:
         ranges (range_ac, range_res, range_Y, multi_factor, amp_ac).
         Deviations: no figure, no titles, no time stamp; a TIFF in place of the AVI; the default range_Y takes the quantiles over ALL samples of the first chunk's raw
         panel (the reference: over 10 000 random samples)."""
+        self._svd_refuse("show_demixed_video")
         Image = Tiff = None
         if path is not None:
             try:
@@ -2393,6 +2551,7 @@ class Sources2D:
         W and b0 stay as they are (:270).  frame_range: the frames that were uploaded, None or (1, T).
         Not built (NotImplementedError): bg_ssub > 1 (the reference's ring branch multiplies W with the full-resolution block), other frame ranges."""
         self._need_data()
+        self._svd_refuse("initTemporal")
         v, o, eng = self.video, self.options, self.engine
         if self.ssub > 1:
             raise NotImplementedError("initTemporal: bg_ssub > 1 is not built (initTemporal.m:165-166 multiplies W with the full-resolution block)")
@@ -2438,6 +2597,8 @@ class Sources2D:
         aa .* C_raw is added to the engine's stitch accumulator (:269-278), sharded runs all-reduce that buffer in place (the
         overlap-region stitch, ONE collective), and :279-286 run on the device; one K x T copy comes back for obj.C_raw / obj.C."""
         self._need_data()
+        if self.bg_model == "svd":
+            return self._svd_update_temporal(use_c_hat)
         v, o, eng = self.video, self.options, self.engine
         K, T = self.C.shape
         launched_any = False

@@ -759,6 +759,8 @@ int cnmfe_synchronize(cnmfe_ctx *ctx);
  *                     with more than one patch in the context, in a fit with thresh_outlier and for cnmfe_residual_ssub.  Results are bit-equal
  *                     (tests/test_gpu_trace_ahead.py)
  *   prealloc          default 1: cnmfe_fit_reserve may allocate the fit's large buffers ahead of the first fit
+ *   bg_svd_tol_exp    default 12: cnmfe_bg_svd_fit stops when every wanted component's residual |M u_i - theta_i u_i| is at most 10^-value theta_1 (1 .. 16)
+ *   bg_svd_max_iter   default 40: ... or after this many iterations (two reads of the video each); the fit then reports converged = 0
  * A deployment short of HBM sets win_i8 = proj_tiled = 0 (and solve_packed = 0) or leaves it to the engine, which falls back by itself.
  * Diagnostics (scripts/): solve_probe, r1_probe (phase probes: results are NOT the product's), deconv_trace, host_trace (1: host-side phase times of every call on
  * stderr, 2: + slow launch calls), debug (1: NaN-poison never-computed table entries), trace_long (default 0: the seed-statistics, peel-trace, trace-difference and
@@ -784,6 +786,33 @@ int cnmfe_get_option(cnmfe_ctx *ctx, const char *name, int64_t *value);
  * early result is dropped and the update projects as before: the values are the same either way. */
 int cnmfe_temporal_early_project(cnmfe_ctx *ctx, int32_t K, const int64_t *IND_colptr, const int32_t *IND_rowidx, int64_t *token);
 int cnmfe_temporal_early_claim(cnmfe_ctx *ctx, int64_t token);
+
+/* ---- background_model = 'svd': the low-rank background of a patch         update_background_parallel.m:238-242 -> endoscope/fit_svd_model.m, svdsecon.m
+ * On the BLOCK (d_b x T):  Bf = (Y - mean(Y,2)) - A (C - mean(C,2));  [u,s,v] = the top nb singular triplets of Bf - mean(Bf,2);
+ *   b = u(ind_patch,:) s,  f = v',  b0 = Ymean(ind_patch) - A(ind_patch,:) Cmean - b mean(f,2);   nb = 0: b = f = 0, b0 = Ymean(ind_patch) - A(ind_patch,:) Cmean.
+ * The engine never forms Bf or a Gram matrix of it: block subspace iteration with a Rayleigh-Ritz step on 16 columns, two reads of the resident video per
+ * iteration, every sum in fp64 and in a fixed order (two fits of the same input give the same bits; a bound C and the same C uploaded give the same bits).
+ * Each u_i is scaled so that its entry of largest magnitude is positive.  thresh_outlier and sn play no part: the reference's outlier branch tests a misspelt
+ * variable and never runs.
+ *   cnmfe_bg_svd_fit      A: d_b x K CSC over BLOCK rows, C: K x T or (NULL, CNMFE_BOUND) / (rows, CNMFE_BOUND_ROWS).  K = 0 (or an empty A) is the reference's
+ *                         A = ones, C = zeros branch.  The iteration stops when |M u_i - theta_i u_i| <= tol theta_1 for every i <= nb (M = Bf Bf', measured, not
+ *                         estimated) or at the iteration cap: options bg_svd_tol_exp (tol = 10^-value, default 12) and bg_svd_max_iter (default 40).  A fit that
+ *                         hits the cap is NOT an error: it keeps what it has and says so in cnmfe_bg_svd_stats.  CNMFE_EUNSUPPORTED for nb outside 0 .. 8 or
+ *                         nb > min(d_b, T).  The factors stay with the patch on the device in fp64.
+ *   cnmfe_bg_svd_get      b: d x nb (column-major: nb columns of d), f: nb x T (row-major), b0: d; any may be NULL.  CNMFE_ESTATE before a fit or a set.
+ *   cnmfe_bg_svd_set      transplants a saved background (the same layouts; nb = 0: b and f are ignored).
+ *   cnmfe_bg_svd_stats    out[20]: [0] reads of the video, [1] iterations, [2] converged (1 / 0), [3] nb, [4 .. 11] the residual of each component relative to
+ *                         theta_1 as the last iteration measured it, [12 .. 19] the singular values.
+ *   cnmfe_residual_lowrank  Ysig = Y(ind_patch,:) - (b f + b0) of the patch, computed in fp64 and rounded once to fp32, resident for cnmfe_update_spatial,
+ *                         cnmfe_hals_temporal[_deconv / _job] and cnmfe_fast_temporal exactly as the residual of cnmfe_residual is (Ysig_out as there).  A fit, a set
+ *                         and an upload of the video invalidate it: an update without it is CNMFE_ESTATE.  cnmfe_compute_rss, cnmfe_reconstruct_background and what
+ *                         is built on them serve the ring model only (CNMFE_EUNSUPPORTED on this residual). */
+int cnmfe_bg_svd_fit(cnmfe_ctx *ctx, int patch_id, int32_t nb, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx /* BLOCK rows */, const float *A_val,
+                     const float *C, int c_order);
+int cnmfe_bg_svd_get(cnmfe_ctx *ctx, int patch_id, double *b, double *f, double *b0);
+int cnmfe_bg_svd_set(cnmfe_ctx *ctx, int patch_id, int32_t nb, const double *b, const double *f, const double *b0);
+int cnmfe_bg_svd_stats(cnmfe_ctx *ctx, int patch_id, double out[20]);
+int cnmfe_residual_lowrank(cnmfe_ctx *ctx, int patch_id, float *Ysig_out, int out_memspace);
 
 #ifdef __cplusplus
 }
