@@ -179,6 +179,10 @@ PROTOTYPES = {
                                      f32p, f32p, f32p, f32p, f32p, u16p, C.c_int]),
     "cnmfe_demix_frames_ssub": (C.c_int, [c_ctx, C.c_int, f32p, C.c_int32, i64p, i32p, f32p, f32p, C.c_int, i32p, f32p, C.c_double, C.c_int64, C.c_int64, C.c_int64,
                                           f32p, f32p, f32p, f32p, f32p, u16p, C.c_int]),
+    "cnmfe_peel_open_lowrank": (C.c_int, [c_ctx, C.c_int, C.c_int32, C.c_int32, C.c_int32, i64p, i32p, f32p, f32p, C.c_int, f32p, C.c_int32, C.c_float, f32p, f32p, f32p,
+                                          C.c_void_p, C.c_int]),
+    "cnmfe_demix_frames_lowrank": (C.c_int, [c_ctx, C.c_int, C.c_int32, i64p, i32p, f32p, f32p, C.c_int, i32p, f32p, C.c_double, C.c_int64, C.c_int64, C.c_int64,
+                                             f32p, f32p, f32p, f32p, f32p, u16p, C.c_int]),
 }
 # exports younger than the oldest build CNMFE_LIB is used with (A/B runs against the parent commit's library)
 OPTIONAL = {"cnmfe_get_option", "cnmfe_temporal_early_project", "cnmfe_temporal_early_claim"}

@@ -1169,7 +1169,7 @@ int cnmfe_peel_open_ds(cnmfe_ctx *ctx, int patch_id, int32_t ssub, int32_t tsub,
 // the refusals the two residual opens share; psf_n comes back normalised.  ssub = tsub = 1 for cnmfe_peel_open_residual itself
 static int residual_open_args(cnmfe_ctx *ctx, int patch_id, int32_t ssub, int32_t tsub, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx,
                               const float *A_val, const float *C, int c_order, const float *psf, int32_t &psf_n, float sig, const float *Cn_patch,
-                              const float *PNR_patch, Patch *&P) {
+                              const float *PNR_patch, Patch *&P, bool need_residual = true) {
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
     P = get_patch(ctx, patch_id);
     if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
@@ -1181,7 +1181,7 @@ static int residual_open_args(cnmfe_ctx *ctx, int patch_id, int32_t ssub, int32_
     if (P->T < 64 || P->T > WELCH_TMAX) return fail(CNMFE_EUNSUPPORTED, "seed images support 64 <= nframes <= WELCH_TMAX = %d (the residual session reads all %lld frames)", WELCH_TMAX, (long long)P->T);
     if (ssub < 1 || ssub > 8 || tsub < 1) return fail(CNMFE_EINVAL, "down-sampling: ssub = %d (1 .. 8), tsub = %d (>= 1)", ssub, tsub);
     if (P->T / tsub < 64) return fail(CNMFE_EUNSUPPORTED, "down-sampling: floor(T / tsub) = floor(%lld / %d) = %lld frames are left, at least 64 are needed", (long long)P->T, tsub, (long long)(P->T / tsub));
-    RET(require_residual(P, patch_id));
+    if (need_residual) RET(require_residual(P, patch_id));
     if (P->peel) return fail(CNMFE_ESTATE, "patch %d already has an open peel session", patch_id);
     RET(check_csc("A", Ksel, P->d, A_colptr, A_rowidx));
     if (Ksel > 0 && ((!A_val && A_colptr[Ksel] > 0) || (!C && c_order != CNMFE_BOUND))) return fail(CNMFE_EINVAL, "null A_val / C");
@@ -1222,6 +1222,27 @@ int cnmfe_peel_open_residual_ds(cnmfe_ctx *ctx, int patch_id, int32_t ssub, int3
     return rc;
 }
 
+// The second pass under background_model = 'svd' (@Sources2D/initComponents_residual_parallel.m:107-122,195-199,224-227): the session on the PATCH and on
+// Yres = Y(patch) - A(patch, ind) C(ind, :) - (b f + b0), formed from the centred video and the patch's fp64 factors in one pass (peel.hpp, k_peel_yres_lowrank).
+// No residual is required, read or changed at full resolution.  ssub / tsub other than 1: Ysig = Y - (b f + b0) is realised (cnmfe_residual_lowrank's sweep) and
+// the down-sampled residual session runs on it; that residual belongs to the session as for cnmfe_peel_open_residual_ds.
+int cnmfe_peel_open_lowrank(cnmfe_ctx *ctx, int patch_id, int32_t ssub, int32_t tsub, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx,
+                            const float *A_val, const float *C, int c_order, const float *psf, int32_t psf_n, float sig, float *Cn_out, float *PNR_out,
+                            float *Sn_out, float *Y_out, int out_memspace) {
+    Patch *P = nullptr;
+    RET(residual_open_args(ctx, patch_id, ssub, tsub, Ksel, A_colptr, A_rowidx, A_val, C, c_order, psf, psf_n, sig, Cn_out, PNR_out, P, false));
+    if (P->svd_nb < 0) return fail(CNMFE_ESTATE, "patch %d has no low-rank background (cnmfe_bg_svd_fit / cnmfe_bg_svd_set)", patch_id);
+    CK(hipSetDevice(ctx->device));
+    RET(ensure_ymean(ctx, P));
+    const bool ds = ssub != 1 || tsub != 1;
+    if (ds) RET(bg_svd_resid_run(ctx, P, nullptr, CNMFE_HOST));
+    P->peel = new PeelSession();
+    const int rc = ds ? peel_open_residual_ds_run(ctx, P, ssub, tsub, Ksel, A_colptr, A_rowidx, A_val, C, c_order, psf, psf_n, sig, Cn_out, PNR_out, Sn_out, Y_out, out_memspace)
+                      : peel_open_lowrank_run(ctx, P, Ksel, A_colptr, A_rowidx, A_val, C, c_order, psf, psf_n, sig, Cn_out, PNR_out, Sn_out, Y_out, out_memspace);
+    if (rc != 0) { (void)hipStreamSynchronize(ctx->st()); delete P->peel; P->peel = nullptr; if (ds) P->residual.invalidate(); }
+    return rc;
+}
+
 static int peel_args(cnmfe_ctx *ctx, int patch_id, int32_t r, int32_t c, int32_t gSiz, Patch *&P) {
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
     P = get_patch(ctx, patch_id);
@@ -1259,7 +1280,7 @@ int cnmfe_peel_close(cnmfe_ctx *ctx, int patch_id) {
     if (!P->peel) return fail(CNMFE_ESTATE, "patch %d has no open peel session", patch_id);
     CK(hipSetDevice(ctx->device));
     CK(hipStreamSynchronize(ctx->st()));
-    if (P->peel->residual) P->residual.invalidate();            // the residual was requested for the session and goes with it
+    if (P->peel->residual && !P->peel->keep_resid) P->residual.invalidate();      // the residual was requested for the session and goes with it (a full-resolution low-rank session never read it)
     delete P->peel; P->peel = nullptr;
     return 0;
 }
@@ -2153,7 +2174,7 @@ int cnmfe_df_finish(cnmfe_ctx *ctx, const double *inv_norm, double df_prctile, i
 
 // ---- the demixed panels (demix.hpp) ----
 // Everything k_demix_panels indexes with is checked here: the frames in [0, T), A's rows in [0, d) (check_csc), the trace rows in [0, K of the source).
-static int demix_patch(cnmfe_ctx *ctx, int patch_id, const float *b0_block /* nullptr: bg_ssub > 1 */, const float *b0_new, int32_t Ksel, const int64_t *cp, const int32_t *ri,
+static int demix_patch(cnmfe_ctx *ctx, int patch_id, bool lowrank /* the svd model: neither b0 */, const float *b0_block /* nullptr: bg_ssub > 1 */, const float *b0_new, int32_t Ksel, const int64_t *cp, const int32_t *ri,
                        const float *va, const float *CC, int c_src, const int32_t *ind, const float *col, double mix_scale, int64_t frame0, int64_t stride, int64_t nframes,
                        float *raw, float *bg, float *signal, float *denoised, float *residual, uint16_t *mixed, int out_memspace) {
     Patch *P = get_patch(ctx, patch_id);                     // (the patch's lane from here on)
@@ -2162,8 +2183,10 @@ static int demix_patch(cnmfe_ctx *ctx, int patch_id, const float *b0_block /* nu
     if (nframes > 0 && (frame0 >= P->T || (nframes > 1 && stride > (P->T - 1 - frame0) / (nframes - 1))))      // (no product that could overflow)
         return fail(CNMFE_EINVAL, "displayed frames %lld + j * %lld, j < %lld, reach beyond the %lld frames of the patch", (long long)frame0, (long long)stride, (long long)nframes, (long long)P->T);
     if (out_memspace != CNMFE_HOST && out_memspace != CNMFE_DEVICE) return fail(CNMFE_EINVAL, "bad out_memspace");
-    if (!b0_new) return fail(CNMFE_EINVAL, "null b0_new");
-    if (b0_block) RET(require_residual_full(P, patch_id, "cnmfe_demix_frames"));
+    if (lowrank) {
+        if (P->svd_nb < 0) return fail(CNMFE_ESTATE, "patch %d has no low-rank background (cnmfe_bg_svd_fit / cnmfe_bg_svd_set)", patch_id);
+    } else if (!b0_new) return fail(CNMFE_EINVAL, "null b0_new");
+    else if (b0_block) RET(require_residual_full(P, patch_id, "cnmfe_demix_frames"));
     else if (ctx->bgs_patch != patch_id) return fail(CNMFE_ESTATE, "cnmfe_background_ssub has not been run for patch %d", patch_id);
     if (Ksel < 0) return fail(CNMFE_EINVAL, "Ksel=%d", Ksel);
     const bool host_src = c_src == CNMFE_COLMAJOR || c_src == CNMFE_ROWMAJOR;
@@ -2205,7 +2228,9 @@ static int demix_patch(cnmfe_ctx *ctx, int patch_id, const float *b0_block /* nu
         devm = mixed ? reinterpret_cast<unsigned short *>(base + 5 * np * 4) : nullptr;
     }
     const DemixOut out{devf[0], devf[1], devf[2], devf[3], devf[4], devm};
-    if (b0_block) {
+    if (lowrank) {
+        RET(demix_launch_lowrank(ctx, P, Ksel, dCC, ldc, mix_scale, frame0, stride, nframes, out));
+    } else if (b0_block) {
         RET(demix_kappa(ctx, P, b0_block, b0_new));
         RET(demix_launch(ctx, P, Ksel, dCC, ldc, mix_scale, frame0, stride, nframes, 0, nframes, nullptr, 0, out));
     } else {
@@ -2233,14 +2258,22 @@ int cnmfe_demix_frames(cnmfe_ctx *ctx, int patch_id, const float *b0_block, cons
                        int64_t nframes, float *raw_out, float *bg_out, float *signal_out, float *denoised_out, float *residual_out, uint16_t *mixed_out, int out_memspace) {
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
     if (!b0_block) return fail(CNMFE_EINVAL, "null b0_block");
-    return demix_patch(ctx, patch_id, b0_block, b0_new, Ksel, A_colptr, A_rowidx, A_val, CC, c_src, ind, col, mix_scale, frame0, stride, nframes, raw_out, bg_out, signal_out,
+    return demix_patch(ctx, patch_id, false, b0_block, b0_new, Ksel, A_colptr, A_rowidx, A_val, CC, c_src, ind, col, mix_scale, frame0, stride, nframes, raw_out, bg_out, signal_out,
                        denoised_out, residual_out, mixed_out, out_memspace);
 }
 int cnmfe_demix_frames_ssub(cnmfe_ctx *ctx, int patch_id, const float *b0_new, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val,
                             const float *CC, int c_src, const int32_t *ind, const float *col, double mix_scale, int64_t frame0, int64_t stride, int64_t nframes,
                             float *raw_out, float *bg_out, float *signal_out, float *denoised_out, float *residual_out, uint16_t *mixed_out, int out_memspace) {
     if (!ctx) return fail(CNMFE_EINVAL, "null context");
-    return demix_patch(ctx, patch_id, nullptr, b0_new, Ksel, A_colptr, A_rowidx, A_val, CC, c_src, ind, col, mix_scale, frame0, stride, nframes, raw_out, bg_out, signal_out,
+    return demix_patch(ctx, patch_id, false, nullptr, b0_new, Ksel, A_colptr, A_rowidx, A_val, CC, c_src, ind, col, mix_scale, frame0, stride, nframes, raw_out, bg_out, signal_out,
+                       denoised_out, residual_out, mixed_out, out_memspace);
+}
+// background_model = 'svd': bg from the patch's resident b, f, b0 (k_demix_panels_lowrank); no residual is read, requested or changed
+int cnmfe_demix_frames_lowrank(cnmfe_ctx *ctx, int patch_id, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const float *CC, int c_src,
+                               const int32_t *ind, const float *col, double mix_scale, int64_t frame0, int64_t stride, int64_t nframes, float *raw_out, float *bg_out,
+                               float *signal_out, float *denoised_out, float *residual_out, uint16_t *mixed_out, int out_memspace) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    return demix_patch(ctx, patch_id, true, nullptr, nullptr, Ksel, A_colptr, A_rowidx, A_val, CC, c_src, ind, col, mix_scale, frame0, stride, nframes, raw_out, bg_out, signal_out,
                        denoised_out, residual_out, mixed_out, out_memspace);
 }
 

@@ -150,8 +150,9 @@ constexpr int WELCH_TMAX = 147456;
 // The session runs on the geometry of its SOURCE video: the centred block (cnmfe_peel_open: d = d_b, nr_b x nc_b, y_bg adds the pixel mean back) or the
 // residual video of the patch (cnmfe_peel_open_residual: Yw starts as Yres = Ysig - A C, d x nr x nc of the patch, no pixel mean -- the residual carries its own)
 // or the down-sampled block (cnmfe_peel_open_ds, ds.hpp: Yw starts as dsData of the block on the ceil(nr_b / ssub) x ceil(nc_b / ssub) grid with floor(n / tsub)
-// frames; y_bg adds the session's OWN pixel mean box(ymean) -- own_mean -- or none behind a pre-detrend -- no_mean)
-struct PeelSession { DevBuf hy, yw, sn, q, ci, scr, ymean; int64_t n = 0, nq = 0; int M = 0; int64_t d = 0; int nr = 0, nc = 0; bool residual = false, own_mean = false, no_mean = false; };
+// frames; y_bg adds the session's OWN pixel mean box(ymean) -- own_mean -- or none behind a pre-detrend -- no_mean).  keep_resid: a residual session that never
+// read P->ysig (cnmfe_peel_open_lowrank at full resolution): closing it leaves the patch's residual state as it is
+struct PeelSession { DevBuf hy, yw, sn, q, ci, scr, ymean; int64_t n = 0, nq = 0; int M = 0; int64_t d = 0; int nr = 0, nc = 0; bool residual = false, own_mean = false, no_mean = false, keep_resid = false; };
 // the video a seed / peel pass reads: [ceil(n / 4)][d] float4, nr x nc pixels column-major
 struct SeedSrc { const float4 *y4; int64_t d; int nr, nc; };
 
@@ -647,6 +648,8 @@ int demix_stage(cnmfe_ctx *ctx, Patch *P, int32_t Ksel, const int64_t *cp, const
 int demix_kappa(cnmfe_ctx *ctx, Patch *P, const float *b0_block, const float *b0_new);
 int demix_launch(cnmfe_ctx *ctx, Patch *P, int32_t Ksel, const float *dCC, int64_t ldc, double mix_scale, int64_t frame0, int64_t stride, int64_t nframes, int64_t j0,
                  int64_t nj, const float *slab, int64_t slab0, const DemixOut &out);
+int demix_launch_lowrank(cnmfe_ctx *ctx, Patch *P, int32_t Ksel, const float *dCC, int64_t ldc, double mix_scale, int64_t frame0, int64_t stride, int64_t nframes,
+                         const DemixOut &out);
 // merge.hpp (deconv.hip)
 int trace_source_dev(cnmfe_ctx *ctx, int32_t K, int64_t T, const float *X, int src, const float **dX);   // the K x ceil4(T) device matrix a trace SOURCE names (a host matrix: one counted upload)
 int trace_order_stats_run(cnmfe_ctx *ctx, int32_t K, double *out);
@@ -677,6 +680,8 @@ int seed_images_run(cnmfe_ctx *ctx, const SeedSrc &src, const float *psf, int32_
                     float *Cn_out, float *PNR_out, PeelSession *keep = nullptr);   // seed.hpp (deconv.hip)
 int peel_open_residual_run(cnmfe_ctx *ctx, Patch *P, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const float *C, int c_order,
                            const float *psf, int32_t psf_n, float sig, float *Cn_out, float *PNR_out, float *Sn_out, float *Yres_out, int out_memspace);   // peel.hpp (deconv.hip)
+int peel_open_lowrank_run(cnmfe_ctx *ctx, Patch *P, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const float *C, int c_order,
+                          const float *psf, int32_t psf_n, float sig, float *Cn_out, float *PNR_out, float *Sn_out, float *Yres_out, int out_memspace);    // peel.hpp (deconv.hip)
 int peel_open_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, int64_t nframes, const double *Q, int32_t M, float sig,
                   float *Cn_out, float *PNR_out, float *Sn_out);   // peel.hpp (deconv.hip)
 int seed_images_ds_run(cnmfe_ctx *ctx, Patch *P, int ssub, int tsub, const float *psf, int32_t psf_n, int64_t nframes, const double *Q, int32_t M, float sig,

@@ -65,6 +65,48 @@ __global__ void __launch_bounds__(256) k_demix_panels(const float4 *__restrict__
     }
 }
 
+// background_model = 'svd': the same panels on bg = (float)(b0(m) + sum_i b(m, i) f(i, t)), an fp64 fma chain over ascending i rounded once -- the patch's fp64
+// factors (bg_svd.hpp), no Ysig and no kappa, so no residual is asked for.  A sibling of k_demix_panels rather than a third flavour: the two instantiations above keep
+// their code.  The workgroup shares t (blockIdx.y): f(i, t) is one address for all lanes; b's columns b[i d + m] coalesce along pixels.
+__global__ void __launch_bounds__(256) k_demix_panels_lowrank(const float4 *__restrict__ yc4, int64_t d_b, int nr, int nr_b, int roff, int coff, int64_t d,
+                                                              const float *__restrict__ ymean_f, const double *__restrict__ b0, const double *__restrict__ b,
+                                                              const double *__restrict__ f, int nb, int64_t T, const int *__restrict__ arow, const int *__restrict__ acol,
+                                                              const float *__restrict__ aval, const int *__restrict__ trow, const float *__restrict__ CC, int64_t ldc,
+                                                              const float *__restrict__ col, double mix_scale, int64_t frame0, int64_t stride, int64_t nframes, DemixOut out) {
+    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (m >= d) return;
+    const int64_t j = blockIdx.y;
+    const int64_t q = (int64_t)((int)(m / nr) + coff) * nr_b + (int)(m % nr) + roff;
+    const int64_t t = frame0 + j * stride, c = t >> 2; const int u = (int)(t & 3);
+    const float y = reinterpret_cast<const float *>(yc4 + c * d_b + q)[u];
+    const float raw = y + ymean_f[q];
+    double bf = b0[m];
+    for (int i = 0; i < nb; ++i) bf = fma(b[(int64_t)i * d + m], f[(int64_t)i * T + t], bf);
+    const float bg = (float)bf;
+    double acc = 0.0, mx0 = 0.0, mx1 = 0.0, mx2 = 0.0;
+    if (arow)
+        for (int e = arow[m]; e < arow[m + 1]; ++e) {
+            const int k = acol[e];
+            const double a = (double)aval[e], cv = (double)CC[(int64_t)trow[k] * ldc + t];
+            acc = fma(a, cv, acc);
+            mx0 = fma(a, (double)col[3 * k] * cv, mx0);
+            mx1 = fma(a, (double)col[3 * k + 1] * cv, mx1);
+            mx2 = fma(a, (double)col[3 * k + 2] * cv, mx2);
+        }
+    const int64_t o = j * d + m;
+    if (out.raw) out.raw[o] = raw;
+    if (out.bg) out.bg[o] = bg;
+    if (out.signal) out.signal[o] = raw - bg;
+    if (out.denoised) out.denoised[o] = (float)acc;
+    if (out.residual) out.residual[o] = (float)((double)raw - (double)bg - acc);
+    if (out.mixed) {
+        const int64_t plane = nframes * d;
+        out.mixed[o] = demix_u16(mix_scale * mx0);
+        out.mixed[plane + o] = demix_u16(mix_scale * mx1);
+        out.mixed[2 * plane + o] = demix_u16(mix_scale * mx2);
+    }
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------
 
 // the call's A (CSR over the patch pixels), trace rows and colours on the active lane (every index was checked by the caller)
@@ -103,6 +145,18 @@ int demix_launch(cnmfe_ctx *ctx, Patch *P, int32_t Ksel, const float *dCC, int64
         LAUNCH(ctx, "demix_panels", k_demix_panels<false>, grid, dim3(256), 0, P->Yc4.as<float4>(), P->d_b, P->nr, P->nr_b, P->roff, P->coff, P->ysig.as<float4>(), P->d,
                P->ymean_f.as<float>(), ctx->tmp[12].as<float>(), (const float *)nullptr, int64_t(0), arow, ctx->dmx[1].as<int>(), ctx->dmx[2].as<float>(),
                ctx->dmx[3].as<int>(), dCC, ldc, ctx->dmx[4].as<float>(), mix_scale, f0, stride, nframes, o);
+    return 0;
+}
+
+// all nframes displayed frames of the call under the patch's low-rank factors (the caller has checked P->svd_nb >= 0 and the frames)
+int demix_launch_lowrank(cnmfe_ctx *ctx, Patch *P, int32_t Ksel, const float *dCC, int64_t ldc, double mix_scale, int64_t frame0, int64_t stride, int64_t nframes,
+                         const DemixOut &out) {
+    if (nframes <= 0) return 0;
+    const int *arow = Ksel > 0 ? ctx->dmx[0].as<int>() : (const int *)nullptr;
+    const dim3 grid((unsigned)((P->d + 255) / 256), (unsigned)nframes);
+    LAUNCH(ctx, "demix_panels_lowrank", k_demix_panels_lowrank, grid, dim3(256), 0, P->Yc4.as<float4>(), P->d_b, P->nr, P->nr_b, P->roff, P->coff, P->d,
+           P->ymean_f.as<float>(), P->svd_b0.as<double>(), P->svd_b.as<double>(), P->svd_f.as<double>(), P->svd_nb, P->T, arow, ctx->dmx[1].as<int>(),
+           ctx->dmx[2].as<float>(), ctx->dmx[3].as<int>(), dCC, ldc, ctx->dmx[4].as<float>(), mix_scale, frame0, stride, nframes, out);
     return 0;
 }
 

@@ -12,7 +12,8 @@
 // <= 36864 for k_peel_traces).  The two that hold a whole trace -- k_seed_stats (seed.hpp) and k_peel_trace_stats -- have a long flavour beyond 20416 frames whose
 // trace stays in global memory (welch_cfg, deconv.hip); k_peel_trace_stats_long needs no scratch: ci already lies there as doubles.
 // A session runs on the geometry of its source video (PeelSession::d / nr / nc): the block for cnmfe_peel_open, the PATCH and its residual video
-// Yres = Ysig - A C (k_peel_yres) for cnmfe_peel_open_residual, the second pass of @Sources2D/initComponents_residual_parallel.m:186-220.
+// Yres = Ysig - A C (k_peel_yres) for cnmfe_peel_open_residual, the second pass of @Sources2D/initComponents_residual_parallel.m:186-220; under
+// background_model = 'svd' the same geometry and Yres = Y - A C - (b f + b0) straight from the centred video (k_peel_yres_lowrank) for cnmfe_peel_open_lowrank.
 #pragma once
 
 namespace cnmfe {
@@ -77,6 +78,52 @@ __global__ void __launch_bounds__(256) k_peel_yres(const float4 *__restrict__ ys
         float v[4] = {(float)((double)y4.x - s[0]), (float)((double)y4.y - s[1]), (float)((double)y4.z - s[2]), (float)((double)y4.w - s[3])};
 #pragma unroll
         for (int j = 0; j < 4; ++j) if (4 * q + j >= n) v[j] = 0.f;
+        yw4[(int64_t)q * d + p] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+
+// The same video under background_model = 'svd' (@Sources2D/initComponents_residual_parallel.m:107-122,195-199,224-227): Yres = Y(patch) - A(patch, ind) C(ind, :)
+// - (b f + b0), written straight from the centred BLOCK video -- no Ysig is realised.  Per (patch pixel, frame quad)
+//     Yc + (ymean_f - b0) - [sum_i b(m, i) f(i, t) + sum_e a_e C(col_e, t)]
+// in fp64: one fma chain, i ascending, then the pixel's CSR row ascending, ONE rounding to fp32; the padding frames of the last quad become 0.  16 bytes read
+// (block-indexed through roff / coff / nr_b, as k_lowrank_resid reads them), 16 written; the pixel's row of b (at most PEEL_LR_NB doubles) stays in registers over
+// the quads of its chunk; f(i, 4q ..) is the same address for every lane of the workgroup and comes from L2 like the trace quads.  f's rows are T doubles apart, so
+// they are read as scalars with k_lowrank_resid's guards on the last quad.  rowptr == nullptr: no footprint in the patch; nb = 0: no b f.
+constexpr int PEEL_LR_NB = 8;                         // = SVD_NB_MAX (bg_svd.hpp lives in another translation unit)
+__global__ void __launch_bounds__(256) k_peel_yres_lowrank(const float4 *__restrict__ yc4, const float *__restrict__ ymean_f, const double *__restrict__ b0,
+                                                           const double *__restrict__ b, const double *__restrict__ f, int nb, int64_t d, int64_t d_b, int n, int nr,
+                                                           int nr_b, int roff, int coff, int qchunk, const int *__restrict__ rowptr, const int *__restrict__ col,
+                                                           const float *__restrict__ val, const float *__restrict__ C, int64_t ldc, float4 *__restrict__ yw4) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= d) return;
+    const int64_t pb = (int64_t)((int)(p / nr) + coff) * nr_b + (int)(p % nr) + roff;
+    const int nq = (n + 3) / 4, q0 = (int)blockIdx.y * qchunk, q1 = min(nq, q0 + qchunk);
+    const int e0 = rowptr ? rowptr[p] : 0, e1 = rowptr ? rowptr[p + 1] : 0;
+    const double dl = (double)ymean_f[pb] - b0[p];
+    double bm[PEEL_LR_NB];
+#pragma unroll
+    for (int i = 0; i < PEEL_LR_NB; ++i) bm[i] = i < nb ? b[(int64_t)i * d + p] : 0.0;
+    for (int q = q0; q < q1; ++q) {
+        const float4 y4 = yc4[(int64_t)q * d_b + pb];
+        const int t = 4 * q;
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int i = 0; i < PEEL_LR_NB; ++i)
+            if (i < nb) {
+                const double *fr = f + (int64_t)i * n + t;
+                s[0] = fma(bm[i], fr[0], s[0]);
+                if (t + 1 < n) s[1] = fma(bm[i], fr[1], s[1]);
+                if (t + 2 < n) s[2] = fma(bm[i], fr[2], s[2]);
+                if (t + 3 < n) s[3] = fma(bm[i], fr[3], s[3]);
+            }
+        for (int e = e0; e < e1; ++e) {
+            const double a = (double)val[e];
+            const float4 c4 = *reinterpret_cast<const float4 *>(C + (int64_t)col[e] * ldc + 4 * (int64_t)q);
+            s[0] = fma(a, (double)c4.x, s[0]); s[1] = fma(a, (double)c4.y, s[1]); s[2] = fma(a, (double)c4.z, s[2]); s[3] = fma(a, (double)c4.w, s[3]);
+        }
+        float v[4] = {(float)(((double)y4.x + dl) - s[0]), (float)(((double)y4.y + dl) - s[1]), (float)(((double)y4.z + dl) - s[2]), (float)(((double)y4.w + dl) - s[3])};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (t + j >= n) v[j] = 0.f;
         yw4[(int64_t)q * d + p] = make_float4(v[0], v[1], v[2], v[3]);
     }
 }
@@ -470,13 +517,15 @@ int peel_open_run(cnmfe_ctx *ctx, Patch *P, const float *psf, int32_t psf_n, int
     return 0;
 }
 
-// cnmfe_peel_open_residual: the session on the PATCH and its residual video (all frames, no detrending: initComponents_residual_parallel.m:176-177,220).
-// The caller has made sure that P->ysig holds the residual itself (residual_materialize).
-int peel_open_residual_run(cnmfe_ctx *ctx, Patch *P, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const float *C, int c_order,
-                           const float *psf, int32_t psf_n, float sig, float *Cn_out, float *PNR_out, float *Sn_out, float *Yres_out, int out_memspace) {
+// The session of the second pass on the PATCH and its residual video (all frames, no detrending: initComponents_residual_parallel.m:176-177,220).
+// lowrank = false (cnmfe_peel_open_residual): Yres = Ysig - A C; the caller has made sure that P->ysig holds the residual itself (residual_materialize).
+// lowrank = true  (cnmfe_peel_open_lowrank): Yres = Yc + (ymean - b0) - b f - A C from the centred block video and the patch's fp64 factors; P->ysig and the
+// residual state are neither read nor written, so the session keeps the state as it found it (PeelSession::keep_resid).
+static int peel_open_patch_run(cnmfe_ctx *ctx, Patch *P, bool lowrank, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const float *C,
+                               int c_order, const float *psf, int32_t psf_n, float sig, float *Cn_out, float *PNR_out, float *Sn_out, float *Yres_out, int out_memspace) {
     PeelSession *S = P->peel;
     const int64_t n = P->T, d = P->d, nq = (n + 3) / 4;
-    S->n = n; S->nq = nq; S->M = 0; S->d = d; S->nr = P->nr; S->nc = P->nc; S->residual = true;
+    S->n = n; S->nq = nq; S->M = 0; S->d = d; S->nr = P->nr; S->nc = P->nc; S->residual = true; S->keep_resid = lowrank;
     const size_t vid = (size_t)nq * (size_t)d * sizeof(float4);
     if (S->hy.ensure(vid) != 0 || S->yw.ensure(vid) != 0) {
         (void)hipGetLastError();
@@ -500,8 +549,13 @@ int peel_open_residual_run(cnmfe_ctx *ctx, Patch *P, int32_t Ksel, const int64_t
     int64_t nseg = std::max<int64_t>(1, std::min<int64_t>(nq, (4096 + nblk - 1) / nblk));
     const int qchunk = (int)((nq + nseg - 1) / nseg);
     nseg = (nq + qchunk - 1) / qchunk;
-    LAUNCH(ctx, "peel_yres", k_peel_yres, dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, P->ysig.as<float4>(), d, (int)n, qchunk,
-           has_ac ? dRow.as<int>() : (const int *)nullptr, dCol.as<int>(), dVal.as<float>(), dC.as<float>(), ldc, S->yw.as<float4>());
+    if (lowrank)
+        LAUNCH(ctx, "peel_yres_lowrank", k_peel_yres_lowrank, dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, P->Yc4.as<float4>(), P->ymean_f.as<float>(),
+               P->svd_b0.as<double>(), P->svd_b.as<double>(), P->svd_f.as<double>(), P->svd_nb, d, P->d_b, (int)n, P->nr, P->nr_b, P->roff, P->coff, qchunk,
+               has_ac ? dRow.as<int>() : (const int *)nullptr, dCol.as<int>(), dVal.as<float>(), dC.as<float>(), ldc, S->yw.as<float4>());
+    else
+        LAUNCH(ctx, "peel_yres", k_peel_yres, dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, P->ysig.as<float4>(), d, (int)n, qchunk,
+               has_ac ? dRow.as<int>() : (const int *)nullptr, dCol.as<int>(), dVal.as<float>(), dC.as<float>(), ldc, S->yw.as<float4>());
     RET(seed_images_run(ctx, SeedSrc{S->yw.as<float4>(), d, P->nr, P->nc}, psf, psf_n, n, nullptr, 0, sig, Cn_out, PNR_out, S));
     if (Sn_out) {
         std::vector<double> sn((size_t)d);
@@ -512,6 +566,14 @@ int peel_open_residual_run(cnmfe_ctx *ctx, Patch *P, int32_t Ksel, const int64_t
     if (Yres_out) RET(ysig_export(ctx, P, S->yw, Yres_out, out_memspace));      // (nothing has been peeled yet: Yw is Yres) exactly the fp32 video the session searches, frame-major like cnmfe_residual's output
     CK(hipStreamSynchronize(ctx->st()));
     return 0;
+}
+int peel_open_residual_run(cnmfe_ctx *ctx, Patch *P, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const float *C, int c_order,
+                           const float *psf, int32_t psf_n, float sig, float *Cn_out, float *PNR_out, float *Sn_out, float *Yres_out, int out_memspace) {
+    return peel_open_patch_run(ctx, P, false, Ksel, A_colptr, A_rowidx, A_val, C, c_order, psf, psf_n, sig, Cn_out, PNR_out, Sn_out, Yres_out, out_memspace);
+}
+int peel_open_lowrank_run(cnmfe_ctx *ctx, Patch *P, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const float *C, int c_order,
+                          const float *psf, int32_t psf_n, float sig, float *Cn_out, float *PNR_out, float *Sn_out, float *Yres_out, int out_memspace) {
+    return peel_open_patch_run(ctx, P, true, Ksel, A_colptr, A_rowidx, A_val, C, c_order, psf, psf_n, sig, Cn_out, PNR_out, Sn_out, Yres_out, out_memspace);
 }
 
 int peel_extract_run(cnmfe_ctx *ctx, Patch *P, int r, int c, int gSiz, double *corr_box, double *ai_box, double *ci_out, double *stats) {

@@ -333,6 +333,8 @@ class Engine:
     supports_traces_grow = True       # traces_grow(): zero rows under the bound matrix and its residents, on the device
     supports_image_ops = True         # circular_constraints() / search_dilate() / trim_spatial(): the image operations on single footprints (footprint_ops.hpp)
     supports_bg_svd = True            # bg_svd_fit() / bg_svd_get() / bg_svd_set() / bg_svd_stats() / residual_lowrank(): options.background_model = 'svd'
+    supports_bg_svd_init_residual = True  # peel_open_lowrank(): the second pass (initComponents_residual_parallel) under the svd model
+    supports_bg_svd_demix = True      # demix_frames_lowrank(): demixed_frames / show_demixed_video under the svd model
     IMAGE_OPS_MAX_BOX = 4096          # cells of the largest box those kernels take (FP_MAX_CELLS); a column above it is computed by hostops and spliced in
 
     # pinned buffers of LazyHostTraces, recycled by size (page-locking 20 MB costs milliseconds)
@@ -746,6 +748,26 @@ class Engine:
         out = np.empty((info["T"], info["d"]), dtype=np.float32) if want else None
         L.check(L.lib.cnmfe_residual_lowrank(self._ctx, pid, out.ctypes.data_as(C.c_void_p) if want else C.c_void_p(None), L.HOST))
         return out
+
+    def peel_open_lowrank(self, pid, ssub, tsub, A_patch, C, psf, sig=3.0, want_video=False):
+        """open the peel session of the SECOND pass under the svd model (initComponents_residual_parallel.m:107-122,195-199,224-227): the session runs on the PATCH
+        and on Yres = Y(patch) - A_patch C - (b f + b0), written in one pass from the resident video and the patch's factors (no residual_lowrank() is needed, none
+        is made, and the patch's residual is as valid after peel_close as it was before).  ssub / tsub other than 1: dsData(Yres), through the realised Ysig and
+        peel_open_residual_ds' session (closing that one drops the residual).  Arguments and returns as peel_open_residual_ds."""
+        info = self._patch[pid]
+        _i, n, psf_a, psf_n, _q, _m = self._seed_args(pid, psf, None, None)
+        fs, ft = max(int(ssub), 1), max(int(tsub), 1)                      # (factors below 1 are the library's to refuse: only the buffers are sized here)
+        d1s, d2s, Ts = -(-info["nr"] // fs), -(-info["nc"] // fs), n // ft
+        K, cp, ri, va = _csc(A_patch, info["d"]) if A_patch is not None and A_patch.shape[1] else (0, None, None, None)
+        cptr, cord, _keep = self._targs(C, K, info["T"])
+        ds = max(d1s * d2s, 1)
+        Cn = np.empty(ds, dtype=np.float32); PNR = np.empty(ds, dtype=np.float32); Sn = np.empty(ds, dtype=np.float32)
+        out = np.empty((max(Ts, 0), d1s * d2s), dtype=np.float32) if want_video else None
+        dst = out.ctypes.data_as(L.C.c_void_p) if want_video else L.C.c_void_p(None)
+        L.check(L.lib.cnmfe_peel_open_lowrank(self._ctx, pid, int(ssub), int(tsub), K, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p), cptr, cord,
+                                              _p(psf_a, L.f32p), psf_n, float(sig), _p(Cn, L.f32p), _p(PNR, L.f32p), _p(Sn, L.f32p), dst, L.HOST))
+        self._peel[pid] = (Ts, d1s, d2s)
+        return Cn[:d1s * d2s], PNR[:d1s * d2s], Sn[:d1s * d2s], out
 
     def get_sn(self, pid):
         """sn = GetSn(Ysig) per patch pixel (update_spatial_parallel.m:191-194); needs residual() first"""
@@ -1252,7 +1274,7 @@ class Engine:
         a = _traces(np.asarray(CC)[ind], Ksel, T)
         return _p(a, L.f32p), L.ROWMAJOR, None, a
 
-    def demix_frames(self, pid, b0_block, b0_new_patch, A_patch, CC, ind, col, mix_scale, frame0, stride, nframes, want=None):
+    def demix_frames(self, pid, b0_block, b0_new_patch, A_patch, CC, ind, col, mix_scale, frame0, stride, nframes, want=None, _lowrank=False):
         """the six panels of show_demixed_video for the displayed frames frame0 + j stride (0-based), j < nframes, of one patch (cnmfe_demix_frames; b0_block = None:
         cnmfe_demix_frames_ssub, after background_ssub).  A_patch: d x Ksel over the patch rows, ind: its columns' rows in CC (K x T; the bound matrix and the resident
         C_raw are read where they lie), col: Ksel x 3.  Returns a dict of (nframes, d) float32 arrays raw, bg, signal, denoised, residual and mixed (3, nframes, d)
@@ -1267,10 +1289,15 @@ class Engine:
         if col.shape[0] != Ksel:
             raise ValueError("col is %s, expected (%d, 3)" % (col.shape, Ksel))
         cptr, csrc, rows, _keep = self._demix_traces(CC, ind, Ksel, T)
-        bn = np.ascontiguousarray(b0_new_patch, dtype=np.float32).ravel()
-        bb = None if b0_block is None else np.ascontiguousarray(b0_block, dtype=np.float32).ravel()
-        if bn.size != d or (bb is not None and bb.size != info["d_b"]):
-            raise ValueError("b0_block / b0_new do not have the block's / the patch's size")
+        if _lowrank:
+            head, fn = (self._ctx, pid), L.lib.cnmfe_demix_frames_lowrank
+        else:
+            bn = np.ascontiguousarray(b0_new_patch, dtype=np.float32).ravel()
+            bb = None if b0_block is None else np.ascontiguousarray(b0_block, dtype=np.float32).ravel()
+            if bn.size != d or (bb is not None and bb.size != info["d_b"]):
+                raise ValueError("b0_block / b0_new do not have the block's / the patch's size")
+            head = (self._ctx, pid) + (() if bb is None else (_p(bb, L.f32p),)) + (_p(bn, L.f32p),)
+            fn = L.lib.cnmfe_demix_frames_ssub if bb is None else L.lib.cnmfe_demix_frames
         nframes = int(nframes)
         names = ("raw", "bg", "signal", "denoised", "residual", "mixed") if want is None else tuple(want)
         n = max(nframes, 0)
@@ -1279,11 +1306,13 @@ class Engine:
             out["mixed"] = np.zeros((3, n, d), dtype=np.uint16)
         ptr = lambda k: _p(out[k], L.f32p) if k in out and out[k].size else None       # (zero frames: NULL, nothing is written)
         mix = out["mixed"].ctypes.data_as(L.u16p) if "mixed" in out and out["mixed"].size else None
-        head = (self._ctx, pid) + (() if bb is None else (_p(bb, L.f32p),))
-        fn = L.lib.cnmfe_demix_frames_ssub if bb is None else L.lib.cnmfe_demix_frames
-        L.check(fn(*head, _p(bn, L.f32p), Ksel, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p), cptr, csrc, _p(rows, L.i32p) if rows is not None else None,
+        L.check(fn(*head, Ksel, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p), cptr, csrc, _p(rows, L.i32p) if rows is not None else None,
                    _p(col, L.f32p), float(mix_scale), int(frame0), int(stride), nframes, ptr("raw"), ptr("bg"), ptr("signal"), ptr("denoised"), ptr("residual"), mix, L.HOST))
         return out
+
+    def demix_frames_lowrank(self, pid, A_patch, CC, ind, col, mix_scale, frame0, stride, nframes, want=None):
+        """demix_frames under the svd model (cnmfe_demix_frames_lowrank): bg = b0 + b f from the patch's resident factors, no b0 argument and no residual"""
+        return self.demix_frames(pid, None, None, A_patch, CC, ind, col, mix_scale, frame0, stride, nframes, want, _lowrank=True)
 
     def _mark_batch(self, *lazies):
         """the asynchronous call just made queued one batch of downloads: its generation number goes to the buffers it fills"""

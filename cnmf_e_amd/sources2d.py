@@ -1303,15 +1303,21 @@ class Sources2D:
         before any background was fitted (_first_run: the reference's second pass reads the fitted W, b0 of every patch, :186-217; on the ring's initial indicator
         the residual is no background-free video, and the down-sampled session is built for the fitted one only -- NotImplementedError).  An observer's "open" record then carries
         Yds, the (Ts, d1s d2s) video the session searches, instead of Yres.
+        background_model = 'svd' (:107-122,195-199,224-227; an engine with supports_bg_svd_init_residual, else NotImplementedError): the session's block IS the patch,
+        its neurons are those with any weight in the patch rectangle, and Yres = Y(patch) - A(patch, ind) C(ind, :) - (b f + b0) comes out of one pass over the
+        resident video (Engine.peel_open_lowrank): no residual is requested and the updates that follow find the engine as they would have without the call.  There is
+        no first-run refusal: before any fit b = f = b0 = 0 (the constructor set them) and Yres = Y - A C, as in the reference; ssub / tsub are honoured as above.
         Not built (NotImplementedError): save_avi."""
         self._need_data()
-        self._svd_refuse("initComponents_residual_parallel")
+        svd = self.bg_model == "svd"
+        if svd and not self._can("bg_svd_init_residual"):
+            self._svd_refuse("initComponents_residual_parallel")
         v, o = self.video, self.options
         ssub, tsub = self._ds_factors(v.T)
         ds = ssub != 1 or tsub != 1
         if ds and not self._can("init_residual_ds"):
             raise NotImplementedError("this engine does not build ssub / tsub other than 1 in the second pass (supports_init_residual_ds)")
-        if ds and self._first_run():                                      # W{1} is still the ring's indicator (update_background_parallel.m:143): nothing was fitted
+        if ds and not svd and self._first_run():                                    # W{1} is still the ring's indicator (update_background_parallel.m:143): nothing was fitted
             raise NotImplementedError("initComponents_residual_parallel with ssub / tsub other than 1 before the first update_background_parallel is not built: "
                                       "the down-sampled session needs the residual of a fitted background")
         if save_avi:
@@ -1341,11 +1347,19 @@ class Sources2D:
             pp = [int(x) for x in v.patch_pos[idx]]
             nr, nc = pp[1] - pp[0] + 1, pp[3] - pp[2] + 1
             d1s, d2s = -(-nr // ssub), -(-nc // ssub)                     # the session's grid (the patch itself without down-sampling)
-            ind, A_blk = self._slice(self.A, idx, "block")                # :116-117
-            C_blk = self._rows(self.C, ind) if ind.size else None         # :120
-            self._residual(idx, A_blk if ind.size else None, C_blk)       # :199-217 without A(patch, ind) C: the resident Ysig (it goes with the session: tag None)
-            A_pp = self._slice(self.A, idx, "patch", cols=ind)[1] if ind.size else None
-            if ds:
+            if svd:                                                       # :107-117 with block = patch: the neurons with any weight in the PATCH rectangle
+                ind, A_pp = self._slice(self.A, idx, "patch")
+                C_blk = self._rows(self.C, ind) if ind.size else None     # :120
+                if not ind.size:
+                    A_pp = None
+            else:
+                ind, A_blk = self._slice(self.A, idx, "block")            # :116-117
+                C_blk = self._rows(self.C, ind) if ind.size else None     # :120
+                self._residual(idx, A_blk if ind.size else None, C_blk)   # :199-217 without A(patch, ind) C: the resident Ysig (it goes with the session: tag None)
+                A_pp = self._slice(self.A, idx, "patch", cols=ind)[1] if ind.size else None
+            if svd:                                                       # :195-199,224-227: Y - A C - (b f + b0) in one pass, no Ysig (Engine.peel_open_lowrank)
+                cn_p, pnr_p, _sn_p, yvid = self.engine.peel_open_lowrank(pid, ssub, tsub, A_pp, C_blk, psf, 3.0, want_video=want_video)
+            elif ds:
                 cn_p, pnr_p, _sn_p, yvid = self.engine.peel_open_residual_ds(pid, ssub, tsub, A_pp, C_blk, psf, 3.0, want_video=want_video)
             else:
                 cn_p, pnr_p, _sn_p, yvid = self.engine.peel_open_residual(pid, A_pp, C_blk, psf, 3.0, want_video=want_video)
@@ -2457,9 +2471,13 @@ class Sources2D:
         for the whole call by numpy.random.default_rng(0) -- the reference draws new ones with randi at every reload.
         Per patch the residual of (A_prev, C_prev) is requested once, as the temporal update requests it -- right after update_temporal_parallel the patch still
         holds it and nothing is asked for, so no trace matrix moves (bg_ssub > 1: cnmfe_background_ssub before every chunk -- the context keeps one patch's
-        low-resolution background, and C_prev goes up with it); do not run an update between two chunks."""
+        low-resolution background, and C_prev goes up with it); do not run an update between two chunks.
+        background_model = 'svd' (an engine with supports_bg_svd_demix, else NotImplementedError): bg = b f + b0 of each patch's resident factors, in fp64 and rounded
+        once (Engine.demix_frames_lowrank); no b0 image, no b0_new and no residual are formed or requested."""
         self._need_data()
-        self._svd_refuse("demixed_frames")
+        svd = self.bg_model == "svd"
+        if svd and not self._can("bg_svd_demix"):
+            self._svd_refuse("demixed_frames")
         v, eng = self.video, self.engine
         K, T = self.C.shape
         kt, chunk = int(kt), int(chunk)
@@ -2477,8 +2495,9 @@ class Sources2D:
         if colors.shape[0] != K:
             raise ValueError("colors must be %d x 3" % K)
         mix_scale = 2.0 / amp_ac * 65536.0 if K else 0.0
-        b0_ = self.reconstruct_b0().reshape(-1, order="F")                                           # (a collective when sharded)
-        b0_new_ = np.asarray(self.b0_new, dtype=np.float64).reshape(-1, order="F")
+        if not svd:
+            b0_ = self.reconstruct_b0().reshape(-1, order="F")                                       # (a collective when sharded)
+            b0_new_ = np.asarray(self.b0_new, dtype=np.float64).reshape(-1, order="F")
         frames = np.arange(f0, f1 + 1, kt)
         cut = {idx: self._slice(A, idx, "patch") for idx in v.owned}
         names = ("raw", "bg", "signal", "denoised", "residual")
@@ -2489,13 +2508,16 @@ class Sources2D:
             mixed = np.zeros((v.d1 * v.d2, n, 3), dtype=np.uint16)
             for idx in v.owned:
                 pp = v.patch_pix[idx]
-                if self.ssub > 1:
-                    self._background_resident(idx, b0_)
-                elif not self._temporal_residual_done(idx):                  # (right after update_temporal_parallel the patch still holds that residual: nothing to ask for)
-                    self._temporal_residual_early(idx)
                 ind, A_pp = cut[idx]
-                res = eng.demix_frames(v.pid[idx], b0_[v.block_pix[idx]] if self.ssub == 1 else None, b0_new_[pp], A_pp if ind.size else None, CC, ind,
-                                       colors[ind], mix_scale, int(fr[0]) - 1, kt, n)
+                if svd:
+                    res = eng.demix_frames_lowrank(v.pid[idx], A_pp if ind.size else None, CC, ind, colors[ind], mix_scale, int(fr[0]) - 1, kt, n)
+                else:
+                    if self.ssub > 1:
+                        self._background_resident(idx, b0_)
+                    elif not self._temporal_residual_done(idx):              # (right after update_temporal_parallel the patch still holds that residual: nothing to ask for)
+                        self._temporal_residual_early(idx)
+                    res = eng.demix_frames(v.pid[idx], b0_[v.block_pix[idx]] if self.ssub == 1 else None, b0_new_[pp], A_pp if ind.size else None, CC, ind,
+                                           colors[ind], mix_scale, int(fr[0]) - 1, kt, n)
                 for k in names:
                     out[k][pp] = res[k].T
                 for m in range(3):
@@ -2513,7 +2535,8 @@ class Sources2D:
         ranges (range_ac, range_res, range_Y, multi_factor, amp_ac).
         Deviations: no figure, no titles, no time stamp; a TIFF in place of the AVI; the default range_Y takes the quantiles over ALL samples of the first chunk's raw
         panel (the reference: over 10 000 random samples)."""
-        self._svd_refuse("show_demixed_video")
+        if not self._can("bg_svd_demix"):
+            self._svd_refuse("show_demixed_video")
         Image = Tiff = None
         if path is not None:
             try:

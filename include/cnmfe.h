@@ -806,13 +806,31 @@ int cnmfe_temporal_early_claim(cnmfe_ctx *ctx, int64_t token);
  *   cnmfe_residual_lowrank  Ysig = Y(ind_patch,:) - (b f + b0) of the patch, computed in fp64 and rounded once to fp32, resident for cnmfe_update_spatial,
  *                         cnmfe_hals_temporal[_deconv / _job] and cnmfe_fast_temporal exactly as the residual of cnmfe_residual is (Ysig_out as there).  A fit, a set
  *                         and an upload of the video invalidate it: an update without it is CNMFE_ESTATE.  cnmfe_compute_rss, cnmfe_reconstruct_background and what
- *                         is built on them serve the ring model only (CNMFE_EUNSUPPORTED on this residual). */
+ *                         is built on them serve the ring model only (CNMFE_EUNSUPPORTED on this residual).
+ *   cnmfe_peel_open_lowrank  the SECOND pass under this model (@Sources2D/initComponents_residual_parallel.m:107-122,195-199,224-227): the session on the PATCH and on
+ *                         Yres = Y(patch) - A(patch, ind) C(ind, :) - (b f + b0).  With ssub = tsub = 1 the video is written in ONE pass from the centred video and
+ *                         the fp64 factors (fp64 fma chain: b f over ascending i, then the pixel's footprints in ascending column order; one rounding to fp32; 16
+ *                         bytes read and 16 written per pixel and frame quad): no Ysig is realised, no residual is required, and the patch's residual state is the
+ *                         same before the open and after cnmfe_peel_close.  Arguments, outputs and refusals are those of cnmfe_peel_open_residual_ds (A over the
+ *                         PATCH rows, no open session, no derived patch, the factors' ranges) except that no residual is asked for; CNMFE_ESTATE before a fit or a
+ *                         set.  A failed open leaves no session.  With other factors Ysig is realised as cnmfe_residual_lowrank realises it and the session is
+ *                         cnmfe_peel_open_residual_ds' on it: that residual goes with the session.  extract / apply / close are the session's as ever.
+ *   cnmfe_demix_frames_lowrank  cnmfe_demix_frames under this model: bg = (float)(b0(p) + sum_i b(p, i) f(i, t)), an fp64 fma chain over ascending i; raw, signal,
+ *                         denoised, residual and mixed keep their expressions on that bg.  No b0 argument, no residual read, requested or changed; CNMFE_ESTATE
+ *                         before a fit or a set. */
 int cnmfe_bg_svd_fit(cnmfe_ctx *ctx, int patch_id, int32_t nb, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx /* BLOCK rows */, const float *A_val,
                      const float *C, int c_order);
 int cnmfe_bg_svd_get(cnmfe_ctx *ctx, int patch_id, double *b, double *f, double *b0);
 int cnmfe_bg_svd_set(cnmfe_ctx *ctx, int patch_id, int32_t nb, const double *b, const double *f, const double *b0);
 int cnmfe_bg_svd_stats(cnmfe_ctx *ctx, int patch_id, double out[20]);
 int cnmfe_residual_lowrank(cnmfe_ctx *ctx, int patch_id, float *Ysig_out, int out_memspace);
+int cnmfe_peel_open_lowrank(cnmfe_ctx *ctx, int patch_id, int32_t ssub, int32_t tsub, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx /* in [0, d) */,
+                            const float *A_val, const float *C, int c_order, const float *psf, int32_t psf_n, float sig, float *Cn_out /* d1s * d2s */,
+                            float *PNR_out /* d1s * d2s */, float *Sn_out /* d1s * d2s or NULL */, float *Y_out /* d1s * d2s x Ts or NULL */, int out_memspace);
+int cnmfe_demix_frames_lowrank(cnmfe_ctx *ctx, int patch_id, int32_t Ksel, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, const float *CC,
+                               int c_src, const int32_t *ind /* Ksel or NULL */, const float *col /* Ksel x 3 */, double mix_scale, int64_t frame0, int64_t stride,
+                               int64_t nframes, float *raw_out, float *bg_out, float *signal_out, float *denoised_out, float *residual_out,
+                               uint16_t *mixed_out /* 3 x nframes x d */, int out_memspace);
 
 #ifdef __cplusplus
 }
