@@ -116,6 +116,7 @@ PROTOTYPES = {
                                             C.c_double, C.c_int, i64p]),
     "cnmfe_residual_ssub": (C.c_int, [c_ctx, C.c_int, C.c_int, C.c_int32, C.c_int32, i64p, i32p, f32p, f32p, C.c_int, C.c_void_p, C.c_int]),
     "cnmfe_residual": (C.c_int, [c_ctx, C.c_int, C.c_int32, i64p, i32p, f32p, f32p, C.c_int, C.c_void_p, C.c_int]),
+    "cnmfe_init_temporal_lowrank": (C.c_int, [c_ctx, C.c_int, C.c_int32, i64p, i32p, f32p, C.c_int32, C.c_int32, C.POINTER(DeconvOpts), f32p, f32p, f32p, f32p, f32p, f32p, f64p, f64p, C.c_int]),
     "cnmfe_bg_svd_fit": (C.c_int, [c_ctx, C.c_int, C.c_int32, C.c_int32, i64p, i32p, f32p, f32p, C.c_int]),
     "cnmfe_bg_svd_get": (C.c_int, [c_ctx, C.c_int, f64p, f64p, f64p]),
     "cnmfe_bg_svd_set": (C.c_int, [c_ctx, C.c_int, C.c_int32, f64p, f64p, f64p]),

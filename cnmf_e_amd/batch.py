@@ -58,8 +58,12 @@ class Sources2DBatch:
         if not batches:
             raise ValueError("Sources2DBatch needs at least one batch")
         v0 = batches[0].video
-        if str(options.background_model).lower() == "svd" or any(getattr(s, "bg_model", "ring") == "svd" for s in batches):
-            raise NotImplementedError("Sources2DBatch is not built for background_model = 'svd'")
+        self.svd = str(options.background_model).lower() == "svd" or any(getattr(s, "bg_model", "ring") == "svd" for s in batches)
+        if self.svd:
+            if any(getattr(s, "bg_model", "ring") != "svd" for s in batches) or str(options.background_model).lower() != "svd":
+                raise ValueError("background_model = 'svd' must be the model of the shared options and of every batch")
+            if not all(getattr(s.engine, "supports_bg_svd_init_temporal", False) for s in batches):
+                raise NotImplementedError("Sources2DBatch under background_model = 'svd' needs engines with init_temporal_lowrank (supports_bg_svd_init_temporal)")
         for m, s in enumerate(batches):
             v = s.video
             if getattr(s, "dist", None) is not None:
@@ -148,24 +152,37 @@ class Sources2DBatch:
         The reference hands W_init, b0_init of batch 1 to the later batches (:47-50,60-63): what initComponents_parallel left BEFORE any fit, the uniform ring mean
         and zeros (initComponents_parallel.m:213-236) -- exactly what a fresh Sources2D of the same geometry holds.  That equality is asserted once per batch (get_W,
         bit for bit) and nothing is transplanted: set_W would mark the ring as fitted, and the first-run test of update_background_parallel.m:143 must still say
-        "first run".  save_avi is not built."""
+        "first run".  save_avi is not built.
+        background_model = 'svd': there is no W and nothing is asserted.  Every batch after the first receives, per owned patch,
+        set_bg_svd(idx, b_prev, zeros((nb, T_k)), zeros(d_patch)) with b_prev = get_b(idx) of the batch BEFORE it, taken after that batch's
+        update_background_parallel and second pass; its initTemporal then fits the footprints and b_prev jointly and replaces f and b0.  This is a deviation:
+        initComponents_batch.m:55-56 assigns exactly that b (neuron_k.b = obj.b), but :61 overwrites it with b_init, the zeros(nr*nc, nb) of
+        initComponents_parallel.m:272, which makes tmp_A'*tmp_A of initTemporal.m:182 singular for every nb >= 1 -- the reference's own demo yields non-finite
+        traces from its second batch on.  Everything else is literal, with its consequences: update_background_parallel's first-run test sees a non-zero b{1}
+        in the later batches, so a patch without neurons keeps f = 0, b0 = 0 there until it has one."""
         if save_avi:
             raise NotImplementedError("initComponents_batch: save_avi is not built")
-        W_init = None
+        W_init = b_prev = None
         for m, s in enumerate(self.batches):
             s.options = self.options                                       # :40
             if m == 0:
                 s.initComponents_parallel(K)                               # :45 (the batch's recording is its frame range)
-                W_init = {idx: s.get_W(idx) for idx in s.video.owned}      # :47-50: before its first fit
+                if not self.svd:
+                    W_init = {idx: s.get_W(idx) for idx in s.video.owned}  # :47-50: before its first fit
             else:
                 self._hand_down(s)                                         # :53-58
-                for idx in s.video.owned:                                  # :60-63, as an assertion
-                    if not self._same_W(W_init[idx], s.get_W(idx)):
+                for idx in s.video.owned:
+                    if self.svd:                                           # :55-56 (and NOT :61, see above)
+                        b = np.asarray(b_prev[idx], dtype=np.float64)
+                        s.set_bg_svd(idx, b, np.zeros((b.shape[1], s.video.T)), np.zeros(b.shape[0]))
+                    elif not self._same_W(W_init[idx], s.get_W(idx)):      # :60-63, as an assertion
                         raise RuntimeError("batch %d: W{%s} is not the unfitted ring of batch 1 (a batch must come fresh to initComponents_batch)" % (m + 1, idx))
                 if self.A.shape[1]:                                        # (no neuron so far: no trace to initialise, the residual pass below may find the first)
                     s.initTemporal()                                       # :65
             s.update_background_parallel()                                 # :68
             s.initComponents_residual_parallel()                           # :71
+            if self.svd:
+                b_prev = {idx: s.get_b(idx) for idx in s.video.owned}      # obj.b of :75-83: what the next batch starts from
             self._collect(s)                                               # :75-83
         K_all = self.A.shape[1]                                            # :87
         for s in self.batches:

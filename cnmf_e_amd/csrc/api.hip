@@ -689,7 +689,7 @@ int cnmfe_synchronize(cnmfe_ctx *ctx) {
 int cnmfe_set_option(cnmfe_ctx *ctx, const char *name, int64_t value) {
     if (!ctx || !name) return fail(CNMFE_EINVAL, "null argument");
     // behaviour switches (include/cnmfe.h) and, behind them, the probes of scripts/ (diagnostics: solve_probe, r1_probe, deconv_trace, trace_long, host_trace, debug)
-    static const char *known[] = {"r1_variant", "r1_delta", "r1_lazy", "r1_defer", "r1_virtual", "gram_incremental", "prealloc", "solve_packed", "sweep_dag", "win_i8_planes", "solve_staged", "solve_inv", "solve_inv_terms", "gram_i8", "win_i8", "proj_tiled", "proj_i8", "proj_i8_planes", "ssub_virtual", "temporal_early", "fit_side", "ring_side", "bg_svd_tol_exp", "bg_svd_max_iter",
+    static const char *known[] = {"r1_variant", "r1_delta", "r1_lazy", "r1_defer", "r1_virtual", "gram_incremental", "prealloc", "solve_packed", "sweep_dag", "win_i8_planes", "solve_staged", "solve_inv", "solve_inv_terms", "gram_i8", "win_i8", "proj_tiled", "proj_i8", "proj_i8_planes", "ssub_virtual", "temporal_early", "fit_side", "ring_side", "bg_svd_tol_exp", "bg_svd_max_iter", "init_temporal_lowrank_nmax",
                                   "solve_probe", "r1_probe", "deconv_trace", "trace_long", "host_trace", "debug", nullptr};
     if (!strcmp(name, "lanes")) { RET(lanes_set(ctx, value)); ctx->opts[name] = value; return 0; }
     for (int i = 0; known[i]; ++i) if (!strcmp(known[i], name)) { ctx->opts[name] = value; if (!strcmp(name, "host_trace")) ctx->trace_level = (int)value; return 0; }
@@ -701,7 +701,7 @@ int cnmfe_get_option(cnmfe_ctx *ctx, const char *name, int64_t *value) {
     if (!ctx || !name || !value) return fail(CNMFE_EINVAL, "null argument");
     const struct { const char *n; int64_t v; } counters[] = {{"temporal_early_hits", ctx->early_hits}, {"temporal_early_drops", ctx->early_drops}, {"temporal_early_declined", ctx->early_declined},
                                                               {"temporal_early_entries", ctx->early.nent}, {"temporal_proj_entries", ctx->last_nent}, {"temporal_nowait", ctx->sweep_nowait},
-                                                              {"merge_trace_uploads", ctx->merge_uploads}, {"trace_matrix_uploads", ctx->trace_uploads}, {"init_temporal_levels", ctx->last_nlevels}, {"lanes_live", (int64_t)std::max<size_t>(1, ctx->lanes.size())},
+                                                              {"merge_trace_uploads", ctx->merge_uploads}, {"trace_matrix_uploads", ctx->trace_uploads}, {"init_temporal_levels", ctx->last_nlevels}, {"init_temporal_lowrank_video_reads", ctx->itl_reads}, {"init_temporal_lowrank_factor_us", ctx->itl_factor_us}, {"lanes_live", (int64_t)std::max<size_t>(1, ctx->lanes.size())},
                                                               {"image_ops_host_columns", ctx->image_ops_host}, {"bound_K", ctx->bound_valid ? (int64_t)ctx->bound_K : 0}, {"bound_T", ctx->bound_valid ? ctx->bound_T : 0}};
     for (const auto &c : counters) if (!strcmp(c.n, name)) { *value = c.v; return 0; }
     auto it = ctx->opts.find(name);
@@ -1550,6 +1550,28 @@ int cnmfe_init_temporal_job(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64
     RET(init_temporal_run(ctx, P, K, A_colptr, A_rowidx, A_val, iters_plain, iters_last, opts, nullptr, nullptr, nullptr, nullptr, nullptr, AA_out, CNMFE_ROWMAJOR, job));
     *job_out = ctx->tjobs_used++;
     return 0;
+}
+
+// ... under background_model = 'svd': initTemporal.m:180-192 of one patch (init_temporal_lowrank.hpp)
+int cnmfe_init_temporal_lowrank(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, int32_t iters_plain, int32_t iters_last,
+                                const cnmfe_deconv_opts *opts, float *C_out, float *C_raw_out, float *S_out, float *kernel_pars_out, float *sn_out, float *AA_out, double *f_out,
+                                double *b0_out, int c_order) {
+    if (!ctx) return fail(CNMFE_EINVAL, "null context");
+    Patch *P = get_patch(ctx, patch_id);
+    if (!P) return fail(CNMFE_ESTATE, "patch %d not created", patch_id);
+    if (P->derived) return fail(CNMFE_EUNSUPPORTED, "init_temporal_lowrank: patch %d is a low-resolution (bg_ssub) patch", patch_id);
+    if (P->svd_nb < 0) return fail(CNMFE_ESTATE, "patch %d has no low-rank background (cnmfe_bg_svd_fit / cnmfe_bg_svd_set)", patch_id);
+    if (K <= 0) return fail(CNMFE_EINVAL, "K=%d", K);
+    if (!A_colptr || !A_rowidx) return fail(CNMFE_EINVAL, "null A");
+    RET(check_csc("A", K, P->d_b, A_colptr, A_rowidx));
+    if (!A_val && A_colptr[K] > 0) return fail(CNMFE_EINVAL, "null A_val");
+    if (iters_plain < 0 || iters_last < 0 || iters_plain + iters_last <= 0) return fail(CNMFE_EINVAL, "iters_plain = %d, iters_last = %d", iters_plain, iters_last);
+    if (opts && iters_last <= 0) return fail(CNMFE_EINVAL, "deconvolution options need iters_last > 0");
+    if (opts && (opts->type != 1 || opts->method != 1)) return fail(CNMFE_EUNSUPPORTED, "only deconvolution type 'ar1' with method 'foopsi' is built");
+    if (c_order != CNMFE_COLMAJOR && c_order != CNMFE_ROWMAJOR) return fail(CNMFE_EINVAL, "c_order must be CNMFE_COLMAJOR or CNMFE_ROWMAJOR (there is no input matrix to be bound)");
+    CK(hipSetDevice(ctx->device));
+    return init_temporal_lowrank_run(ctx, P, patch_id, K, A_colptr, A_rowidx, A_val, iters_plain, iters_last, opts, C_out, C_raw_out, S_out, kernel_pars_out, sn_out, AA_out,
+                                     f_out, b0_out, c_order);
 }
 
 int cnmfe_temporal_jobs_sweep(cnmfe_ctx *ctx) {

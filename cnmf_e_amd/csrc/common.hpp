@@ -393,6 +393,7 @@ struct LaneState {
     // hipFree pair per buffer and call cost more than the small kernels they serve, and hipFree drains the device
     DevBuf scr[24];
     DevBuf svd[19];           // bg_svd.hpp: the panels Q, Z, G, D, the passes' partial sums, the small products, the call's A as CSC and CSR
+    DevBuf itl[16];           // init_temporal_lowrank.hpp: M = [A_p, b] as CSC (fp64), the pair list, G, the Cholesky tiles, R | Y | X of the solve
     DevBuf itp[30];           // init_temporal.hpp: the block's footprints, the ring-filtered footprints and their rough-start selection (fp64), their lists, U | C0 of the projection
     DeconvScratch dscr;
     kept::KeptSpatial kept;   // what the last deferred spatial update of this lane left in scr[SCR_COLPTR | SCR_EROW | SCR_AVAL | SCR_KEEP] (kept_results.hpp)
@@ -480,6 +481,7 @@ struct cnmfe_ctx : cnmfe::LaneState {
     cnmfe::DevBuf fpo[4];                                  // footprint image operations (footprint_ops.hpp): [0] the boxes' offsets, [1] the result, [2] the structuring element, [3] counts
     int64_t image_ops_host = 0;                            // counter image_ops_host_columns: columns the last such call left to the caller (box above FP_MAX_CELLS)
     int64_t trace_uploads = 0;                             // counter trace_matrix_uploads: K x T matrices ANY entry point took through a pointer (upload_traces; a bound matrix or rows of it do not count)
+    int64_t itl_reads = 0, itl_factor_us = 0;             // counters init_temporal_lowrank_video_reads / _factor_us: projection passes and the host factorisation's time of the last cnmfe_init_temporal_lowrank
     int64_t last_nlevels = 0;                              // counter init_temporal_levels: launches of level kernels the last cnmfe_init_temporal queued itself (the depth of its schedule)
     int64_t merge_uploads = 0;                             // counter merge_trace_uploads: K x T matrices the merge / tag entry points took from the host
     // dF/F (dff.hpp): the K x T fp64 accumulator of cnmfe_df_begin .. cnmfe_df_finish (row stride df_T), and [0] 1 / sum(A.^2), [1] the rows that are not finite, [2] Df,
@@ -611,7 +613,14 @@ int temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, c
 // init_temporal.hpp (factor.hip): initTemporal.m:156-168 of one patch -- A: d_b x K CSC over BLOCK rows
 int init_temporal_run(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, int32_t iters_plain, int32_t iters_last,
                       const cnmfe_deconv_opts *dopts, float *C_out, float *C_raw_out, float *S_out, float *pars_out, float *sn_out, float *AA_out, int c_order, TemporalJob *job = nullptr);
-int vproj_pass_plan(Patch *P, int32_t K, const int64_t *colptr, const int32_t *rowidx, int per, std::vector<int> &pass_of);   // vproj.hip
+int vproj_pass_plan(Patch *P, int32_t K, const int64_t *colptr, const int32_t *rowidx, int per, std::vector<int> &pass_of, int reach = -1);   // vproj.hip
+// init_temporal_lowrank.hpp (factor.hip): initTemporal.m:180-192 of one patch under background_model = 'svd' -- A: d_b x K CSC over BLOCK rows
+int init_temporal_lowrank_run(cnmfe_ctx *ctx, Patch *P, int patch_id, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, const float *A_val, int32_t iters_plain,
+                              int32_t iters_last, const cnmfe_deconv_opts *dopts, float *C_out, float *C_raw_out, float *S_out, float *pars_out, float *sn_out, float *AA_out,
+                              double *f_out, double *b0_out, int c_order);
+// vproj.hip: R(row_of[j], :) = M(:, j)' Yc - cst[row_of[j]] in fp64 for ncol columns of a CSC matrix over PATCH rows with fp64 values; 1: a block meets more columns than its list holds
+int vproj_columns64(cnmfe_ctx *ctx, Patch *P, int32_t ncol, const int64_t *colptr, const int32_t *rowidx, const int64_t *dColptr, const int *dErow, const double *dVal,
+                    const int *dRowOf, const double *dCst, double *dR, int64_t ldr);
 int temporal_sweep_jobs(cnmfe_ctx *ctx);                  // factor.hip: the level sweeps of every job set up since cnmfe_stitch_begin, level by level across the jobs
 #ifdef __HIPCC__
 // LDS-DMA: 64 lanes x 16 B, global (uniform base + per-lane 32-bit byte offset) -> LDS [lds_dst + lane*16].  Invisible to

@@ -974,6 +974,7 @@ int temporal_sweep_jobs(cnmfe_ctx *ctx) {
 }
 
 #include "init_temporal.hpp"      // (f) known footprints: initTemporal's per-patch regression (its sweeps are the level kernels and the schedule above)
+#include "init_temporal_lowrank.hpp"   // ... under background_model = 'svd': the joint least-squares fit of the footprints and the background's spatial factors
 
 static int postproc_boxes(int32_t d1, int32_t d2, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx, std::vector<int4> &box);
 

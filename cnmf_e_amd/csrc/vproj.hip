@@ -538,9 +538,10 @@ int vproj_temporal(cnmfe_ctx *ctx, Patch *P, int32_t K, const int64_t *A_colptr,
 // dealt into PASSES, each a projection of its own: a neuron goes into the first pass in which every block it meets still has `per` free slots (first fit, in
 // ascending k: a fixed assignment).  pass_of[k] = its pass; returns the number of passes (1 unless a block is that crowded), 0 when the ring is wider than the
 // panel builder's window.
-int vproj_pass_plan(Patch *P, int32_t K, const int64_t *colptr, const int32_t *rowidx, int per, std::vector<int> &pass_of) {
+// (reach >= 0: the columns are grown by `reach` pixels instead of the ring radius -- 0 for the columns of init_temporal_lowrank.hpp, which no ring filters)
+int vproj_pass_plan(Patch *P, int32_t K, const int64_t *colptr, const int32_t *rowidx, int per, std::vector<int> &pass_of, int reach) {
     const BgGeom g = bg_geom(P);
-    const int nblk = g.nbr * g.nbc, R = g.p_radius;
+    const int nblk = g.nbr * g.nbc, R = reach >= 0 ? reach : g.p_radius;
     pass_of.assign((size_t)K, 0);
     if (16 + 2 * R > VP_WS || per > WIN_NLB) return 0;
     std::vector<int> lo(g.nbc, 0), hi(g.nbc, -1), need;
@@ -559,6 +560,72 @@ int vproj_pass_plan(Patch *P, int32_t K, const int64_t *colptr, const int32_t *r
         pass_of[k] = (int)p;
     }
     return (int)std::max<size_t>(1, fill.size());
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------------
+// known footprints under the low-rank background (init_temporal_lowrank.hpp):  R(row_of[j], :) = M(:, j)' Yc  in fp64, NEVER rounded to fp32 -- the rows are the
+// right-hand side of a linear system -- minus cst[row_of[j]] per row (the caller's correction of the video's centring).  M: CSC over PATCH rows with fp64 values (the footprints on the patch, then the dense columns of b); no ring, so the
+// panels are the columns themselves (k_vp_build_b<double> with an empty ring) and the projection is k_vp_proj_b as the temporal update runs it on the fp64 pipe.
+// ------------------------------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_vp_reduce64(const double *__restrict__ part, int64_t ldp, const int *__restrict__ nptr, const int *__restrict__ nent,
+                                                     const int *__restrict__ row_of, const double *__restrict__ cst, int64_t T, double *__restrict__ R, int64_t ldr) {
+    const int j = blockIdx.y;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= ldr) return;
+    double s = 0.0;
+    if (t < T) {
+        for (int i = nptr[j]; i < nptr[j + 1]; ++i) s += part[(int64_t)nent[i] * ldp + t];              // (ascending block order: one fixed sum)
+        s -= cst[row_of[j]];                                                                           // what the fp32 centring left of the pixel means (see the caller)
+    }
+    R[(int64_t)row_of[j] * ldr + t] = s;
+}
+
+int vproj_columns64(cnmfe_ctx *ctx, Patch *P, int32_t ncol, const int64_t *colptr, const int32_t *rowidx, const int64_t *dColptr, const int *dErow, const double *dVal,
+                    const int *dRowOf, const double *dCst, double *dR, int64_t ldr) {
+    HostTrace ht(ctx, "vproj_columns64");
+    BgGeom g = bg_geom(P);
+    g.p = 0; g.p_radius = 0;                                // no ring: k_vp_build_b reads neither W nor the offsets
+    const int nblk = g.nbr * g.nbc;
+    std::vector<int> lo(g.nbc, 0), hi(g.nbc, -1), need_ptr((size_t)ncol + 1, 0), need;
+    for (int32_t k = 0; k < ncol; ++k) {
+        reach_blocks(P, g, 0, rowidx, colptr[k], colptr[k + 1], lo, hi, need);
+        need_ptr[k + 1] = (int)need.size();
+    }
+    VpLists L;
+    if (vp_make_lists(need_ptr, need, nblk, ncol, false, L)) return 1;
+    const int64_t nent = L.nent, ldp = ldr;
+    if (nent * ldp * 8 > (int64_t(24) << 30)) return 1;
+    DevBuf *V = ctx->vp;
+    DevBuf &dEb = V[1], &dEk = V[2], &dEs = V[3], &dG16 = V[4], &dBt = V[6], &dPart = V[8], &dNptr = V[9], &dNent = V[10];
+    RET(vp_upload_lists(ctx, L));
+    const size_t bt_bytes = (size_t)std::max(1, L.g16[nblk]) * BLKPX * 16 * sizeof(double);
+    RET(dBt.ensure_hw(bt_bytes, ctx->hw_vp[6]));
+    RET(dPart.ensure_hw((size_t)std::max<int64_t>(1, nent) * ldp * sizeof(double), ctx->hw_vp[8]));
+    CK(hipMemsetAsync(dBt.p, 0, bt_bytes, ctx->st()));
+    if (nent > 0) {
+        LAUNCH(ctx, "temporal_build_B", k_vp_build_b<double>, dim3((unsigned)nent), dim3(256), 0, dEb.as<int>(), dEk.as<int>(), dEs.as<int>(), dG16.as<int>(), g, 0, dColptr, dErow, dVal,
+               (const int *)nullptr, (const int *)nullptr, (const float *)nullptr, dBt.as<double>());
+        bool tiled = false;
+        if (!P->derived && proj_opts(ctx).tiled != 0) {
+            const int64_t ncg_t = (P->Tc + 15) >> 4;
+            const size_t ybytes = (size_t)nblk * ncg_t * 64 * 64 * sizeof(float4);
+            if (!P->yt4_valid) {
+                bool ok = true;
+                RET(fits_leaving(P->yt4, ybytes, &ok));
+                if (ok) {
+                    RET(P->yt4.ensure(ybytes));
+                    LAUNCH(ctx, "temporal_tile_video", k_tile_video, dim3((unsigned)nblk, (unsigned)ncg_t), dim3(256), 0, P->Yc4.as<float4>(), g, P->Tc, ncg_t, P->yt4.as<float4>());
+                    P->yt4_valid = true;
+                }
+            }
+            tiled = P->yt4_valid;
+        }
+        RET(vp_launch_proj(ctx, P, g, L, tiled, ldp));
+    }
+    LAUNCH(ctx, "itl_reduce_R", k_vp_reduce64, dim3((unsigned)((ldr + 255) / 256), (unsigned)ncol), dim3(256), 0, dPart.as<double>(), ldp, dNptr.as<int>(), dNent.as<int>(), dRowOf,
+           dCst, P->T, dR, ldr);
+    ht.mark("launches");
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------

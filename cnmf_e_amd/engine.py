@@ -334,6 +334,7 @@ class Engine:
     supports_image_ops = True         # circular_constraints() / search_dilate() / trim_spatial(): the image operations on single footprints (footprint_ops.hpp)
     supports_bg_svd = True            # bg_svd_fit() / bg_svd_get() / bg_svd_set() / bg_svd_stats() / residual_lowrank(): options.background_model = 'svd'
     supports_bg_svd_init_residual = True  # peel_open_lowrank(): the second pass (initComponents_residual_parallel) under the svd model
+    supports_bg_svd_init_temporal = True  # init_temporal_lowrank(): initTemporal (and with it batch mode) under the svd model
     supports_bg_svd_demix = True      # demix_frames_lowrank(): demixed_frames / show_demixed_video under the svd model
     IMAGE_OPS_MAX_BOX = 4096          # cells of the largest box those kernels take (FP_MAX_CELLS); a column above it is computed by hostops and spliced in
 
@@ -919,6 +920,30 @@ class Engine:
                                           None if opts is None else C.byref(opts), _p(Cout, L.f32p), _p(Craw, L.f32p), _p(S, L.f32p), _p(pars, L.f32p),
                                           _p(sn, L.f32p), _p(AA, L.f32p), L.ROWMAJOR))
         return Cout, Craw, S, pars, sn, AA
+
+    def init_temporal_lowrank(self, pid, A_block, iters_plain=10, iters_last=2, deconv_options=None, want=True):
+        """init_temporal under background_model = 'svd' (initTemporal.m:180-192): the joint least-squares fit of the footprints A_block (d_b x K, BLOCK rows; the
+        rows outside the patch are dropped) and the patch's resident b to every frame, then the sweeps from that C on Y - (b f + b0).  The patch's f and b0 are
+        replaced (b0 = the pixel mean).  Returns (C, C_raw, S, kernel_pars, sn, AA, f, b0); want=False downloads nothing but AA (C_raw and AA stay on the device
+        for stitch_add).  counter('init_temporal_lowrank_video_reads'): the projection passes of the last call (1 unless a 16 x 16 block meets more than 64 columns)."""
+        info = self._patch[pid]
+        K, cp, ri, va = _csc(A_block, info["d_b"])
+        T = info["T"]
+        opts = None if deconv_options is None else self._dopts(deconv_options)
+        Cout = np.empty((K, T), dtype=np.float32) if want else None
+        Craw = np.empty((K, T), dtype=np.float32) if want else None
+        dec = want and opts is not None
+        S = np.empty((K, T), dtype=np.float32) if dec else None
+        pars = np.zeros(K, dtype=np.float32) if dec else None
+        sn = np.zeros(K, dtype=np.float32) if dec else None
+        AA = np.empty(K, dtype=np.float32)
+        nb = self.bg_svd_stats(pid)["nb"] if want else 0
+        f = np.zeros((nb, T), dtype=np.float64) if want else None
+        b0 = np.zeros(info["d"], dtype=np.float64) if want else None
+        L.check(L.lib.cnmfe_init_temporal_lowrank(self._ctx, pid, K, _p(cp, L.i64p), _p(ri, L.i32p), _p(va, L.f32p), int(iters_plain), int(iters_last),
+                                                  None if opts is None else C.byref(opts), _p(Cout, L.f32p), _p(Craw, L.f32p), _p(S, L.f32p), _p(pars, L.f32p),
+                                                  _p(sn, L.f32p), _p(AA, L.f32p), _p(f, L.f64p), _p(b0, L.f64p), L.ROWMAJOR))
+        return Cout, Craw, S, pars, sn, AA, f, b0
 
     def init_temporal_job(self, pid, A_block, iters_plain=10, iters_last=2, deconv_options=None):
         """init_temporal for several patches per engine: the plain sweeps run at once, the last ones with the other jobs' in temporal_jobs_sweep; returns

@@ -742,6 +742,7 @@ class Sources2D:
         self.C_prev = self.C
         self.P = {"sn": np.asarray(sn, dtype=np.float32).reshape(-1).copy(), "Ymean": {}}
         self._b0_new_val = None; self._b0_new_src = None
+        self._svd_bg_fitted = False     # background_model = 'svd': b, f, b0 come from this object's own update_background_parallel (initTemporal then keeps its refusal)
         self.dist = dist_group
         # test hook: take the collective (sharded) branches even with one rank, so that a single-GPU box can run the all-gather of A, the
         # device-side stitch of C_raw and the lazy all-reduces over RCCL exactly as an N-rank job does (scripts/nccl_smoke.py)
@@ -962,6 +963,7 @@ class Sources2D:
         """obj.b{idx}, obj.f{idx}, obj.b0{idx} = a saved background (another session of the same recording).  The patch's resident residual goes with the old one.
         A b{1} that is not all zero makes the next update_background_parallel a later run (its flag_first reads mean2(b{1}))."""
         self._svd_only("set_bg_svd")
+        self._svd_bg_fitted = False
         n = self.video.patch_pix[idx].size
         b = np.asarray(b, dtype=np.float64).reshape(n, -1)
         if b.shape[1] > 8:
@@ -1870,6 +1872,7 @@ class Sources2D:
             if A_block.shape[1] == 0 and not flag_first:                                             # :188-199
                 continue
             stats[idx] = eng.bg_svd_fit(v.pid[idx], int(o.nb), A_block if A_block.shape[1] else None, self._rows(self.C, ind_nz) if ind_nz.size else None)   # :242
+        self._svd_bg_fitted = True
         self._b0_new_src = "b0"
         self.A_prev = self.A                                                                         # :316
         self._prev_csr_src = self.A
@@ -2572,10 +2575,24 @@ class Sources2D:
         all-reduce when sharded); then obj.deconvTemporal() under deconv_flag (:292), else C = C_raw as :290 leaves it.  Sets C, C_raw (and S, P.kernel_pars,
         P.neuron_sn under deconv_flag); the new traces are the engine's bound matrix, so the update_background_parallel that follows uploads no K x T matrix.
         W and b0 stay as they are (:270).  frame_range: the frames that were uploaded, None or (1, T).
-        Not built (NotImplementedError): bg_ssub > 1 (the reference's ring branch multiplies W with the full-resolution block), other frame ranges."""
+        Not built (NotImplementedError): bg_ssub > 1 (the reference's ring branch multiplies W with the full-resolution block), other frame ranges.
+        background_model = 'svd' (:180-192,250-262; an engine with supports_bg_svd_init_temporal, else NotImplementedError): per owned patch the neurons with any
+        weight in the PATCH (tmp_block = patch_pos, :103-109) and Engine.init_temporal_lowrank -- the footprints and the patch's b (set_bg_svd, or an earlier
+        fit) fitted JOINTLY to every frame, f and b0 of the patch replaced (b0 = the pixel mean), then the same sweeps on Y - (b f + b0).  A patch without
+        neurons keeps its b, f and b0 (:156-159).  bg_ssub is ignored, as everywhere in this model.  One deviation: a column of b that is identically zero is
+        left out of the joint system and its row of f is 0 (the reference divides by a singular matrix).
+        What the svd branch serves is a background that was HANDED to this object -- set_bg_svd: the second session of an animal, the next temporal batch -- or the
+        zeros of a fresh object.  Once this object's own update_background_parallel has fitted b, f, b0 to the uploaded recording the call keeps the refusal it had
+        before the branch was built (NotImplementedError); set_bg_svd(idx, get_b(idx), get_f(idx), get_b0(idx)) says that the fitted b is the one to extract under."""
         self._need_data()
-        self._svd_refuse("initTemporal")
+        if self.bg_model == "svd" and not self._can("bg_svd_init_temporal"):
+            self._svd_refuse("initTemporal")
+        if self.bg_model == "svd" and self._svd_bg_fitted:
+            raise NotImplementedError("initTemporal under background_model = 'svd' extracts traces under a background handed in with set_bg_svd; after this object's own "
+                                      "update_background_parallel it is not built (hand the fitted factors back with set_bg_svd to extract under them)")
         v, o, eng = self.video, self.options, self.engine
+        if self.bg_model == "svd":
+            return self._svd_init_temporal(frame_range)
         if self.ssub > 1:
             raise NotImplementedError("initTemporal: bg_ssub > 1 is not built (initTemporal.m:165-166 multiplies W with the full-resolution block)")
         if frame_range is not None and len(frame_range) and (int(frame_range[0]) != 1 or int(frame_range[1]) != v.T):
@@ -2610,6 +2627,32 @@ class Sources2D:
         self._ymean_full = None
         lazy = (not o.deconv_flag) and self._can("lazy_traces")
         bound_deconv = o.deconv_flag and not sharded and self._can("bound_deconv") and self._can("lazy_traces")
+        self.C_raw = eng.stitch_finish(subtract_min=False, want="lazy" if lazy else ("bound" if bound_deconv else True))      # :289-290
+        self.C = self.deconvTemporal() if o.deconv_flag else self.C_raw                               # :292
+        return self.C
+
+    def _svd_init_temporal(self, frame_range):
+        """initTemporal under background_model = 'svd' (initTemporal.m:103-109,150-159,180-192,270-292); the stitch and the deconvTemporal tail are the ring model's"""
+        v, o, eng = self.video, self.options, self.engine
+        if frame_range is not None and len(frame_range) and (int(frame_range[0]) != 1 or int(frame_range[1]) != v.T):
+            raise NotImplementedError("initTemporal works on the frames that were uploaded, [1, %d] (frame_range = [%d, %d])" % (v.T, int(frame_range[0]), int(frame_range[1])))
+        K, T = self.A.shape[1], v.T
+        if K == 0:
+            raise ValueError("initTemporal needs footprints: obj.A has no columns")
+        dopt = o.deconv_options if o.deconv_flag else None
+        eng.stitch_begin(K, T)
+        for idx in v.owned:
+            self.P["Ymean"][idx] = eng.ymean(v.pid[idx])[v.ind_patch[idx]]                           # :152-153
+            ind = self._slice(self.A, idx, "patch")[0]                                               # :103-109 with tmp_block = patch_pos
+            if ind.size == 0:
+                continue                                                                              # :156-159: b, f, b0 of this patch stay
+            A_blk = self._slice(self.A, idx, "block", cols=ind)[1]                                   # (the engine takes BLOCK rows and drops those outside the patch)
+            self._resid_tag.pop(idx, None)
+            eng.init_temporal_lowrank(v.pid[idx], A_blk, 10, 2, dopt, want=False)                    # :180-192
+            eng.stitch_add(ind)                                                                       # :285-286
+        self._ymean_full = None
+        lazy = (not o.deconv_flag) and self._can("lazy_traces")
+        bound_deconv = o.deconv_flag and self._can("bound_deconv") and self._can("lazy_traces")
         self.C_raw = eng.stitch_finish(subtract_min=False, want="lazy" if lazy else ("bound" if bound_deconv else True))      # :289-290
         self.C = self.deconvTemporal() if o.deconv_flag else self.C_raw                               # :292
         return self.C

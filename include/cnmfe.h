@@ -817,7 +817,24 @@ int cnmfe_temporal_early_claim(cnmfe_ctx *ctx, int64_t token);
  *                         cnmfe_peel_open_residual_ds' on it: that residual goes with the session.  extract / apply / close are the session's as ever.
  *   cnmfe_demix_frames_lowrank  cnmfe_demix_frames under this model: bg = (float)(b0(p) + sum_i b(p, i) f(i, t)), an fp64 fma chain over ascending i; raw, signal,
  *                         denoised, residual and mixed keep their expressions on that bg.  No b0 argument, no residual read, requested or changed; CNMFE_ESTATE
- *                         before a fit or a set. */
+ *                         before a fit or a set.
+ *   cnmfe_init_temporal_lowrank  known footprints under this model (@Sources2D/initTemporal.m:180-192): the traces of the footprints A AND the temporal factors of
+ *                         the patch's resident b on its resident video.  A: d_b x K CSC over BLOCK rows; the rows outside the PATCH are dropped (:103-109).  With
+ *                         M = [A(patch, :), b] the call solves (M'M) X = M'(Y - mean(Y,2)) for all frames -- M'M and M'Y accumulated in fp64 in a fixed order, the
+ *                         video read once per projection pass (counter init_temporal_lowrank_video_reads: 1 unless a 16 x 16 block meets more than 64 columns),
+ *                         M'M Cholesky-factored on the host in float64, the two triangular solves on the device in fp64 -- and then runs HALS_temporal's sweeps
+ *                         from C = X(1:K, :) on Y - (b f + b0): iters_plain plain sweeps and iters_last more (with opts: the in-sweep AR(1) FOOPSI, kernel
+ *                         parameters estimated fresh), as cnmfe_init_temporal does.  Outputs as there (C, C_raw, S, kernel_pars, sn, AA: any may be NULL; C_raw and
+ *                         AA stay on the device for cnmfe_stitch_add) plus f_out (nb x T, row-major) and b0_out (d), float64, either may be NULL.  Afterwards the
+ *                         patch's f is X(K+1:end, :), its b0 the pixel mean of the patch, b is unchanged, and the patch is in the state cnmfe_bg_svd_set leaves:
+ *                         a resident Ysig is invalid.  A column of b that is identically zero is left out of the system; its row of f is 0 (the reference
+ *                         divides by a singular matrix).  CNMFE_ESTATE before a fit or a set, and when a Cholesky pivot is <= n eps max(diag M'M) (the message
+ *                         names the patch and the pivot); CNMFE_EUNSUPPORTED for more than 2048 unknowns (option init_temporal_lowrank_nmax lowers the cap), for
+ *                         a derived patch and for deconvolution other than 'ar1' / 'foopsi'.  A failed call changes nothing of the patch.  Two calls give the
+ *                         same bits.  Counter init_temporal_lowrank_factor_us: the host factorisation's time of the last call. */
+int cnmfe_init_temporal_lowrank(cnmfe_ctx *ctx, int patch_id, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx /* BLOCK rows */, const float *A_val,
+                                int32_t iters_plain, int32_t iters_last, const cnmfe_deconv_opts *opts, float *C_out, float *C_raw_out, float *S_out,
+                                float *kernel_pars_out, float *sn_out, float *AA_out, double *f_out, double *b0_out, int c_order);
 int cnmfe_bg_svd_fit(cnmfe_ctx *ctx, int patch_id, int32_t nb, int32_t K, const int64_t *A_colptr, const int32_t *A_rowidx /* BLOCK rows */, const float *A_val,
                      const float *C, int c_order);
 int cnmfe_bg_svd_get(cnmfe_ctx *ctx, int patch_id, double *b, double *f, double *b0);
