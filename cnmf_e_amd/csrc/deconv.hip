@@ -779,9 +779,10 @@ __global__ void __launch_bounds__(DECONV_NT) k_deconv(DeconvCfg c, DeconvIO io) 
         if (trc) printf("DT it %d b %.17g\n", it, b);
         if (!optimize_g) break;                      // :113-115
         const double g0 = g;
-        if (g > c.gmax) {                            // :104-108
-            // (foopsi_oasisAR1.m:105 sees the row AFTER HALS_temporal.m:88 took b off: with io.off that is y - bsub; without, y is the residual-based row and stays as it was)
-            const double sn2 = get_sn<RowAdd, 17, SPLIT>(RowAdd{y, io.off ? -bsub : 0.0}, c, scr, red, true, tabs);
+        if (c.optimize_b && g > c.gmax) {            // :104-108, the optimize_b arm alone: :82-90 (no b) runs update_g whatever g is
+            // (foopsi_oasisAR1.m:105 sees the row AFTER HALS_temporal.m:88 took b off, y - bsub with or without io.off: Welch's side lobes leak a baseline left in
+            //  the row into the band, and gamma moved by 1e-3 on a row of the fused sweep; deconvTemporal subtracts nothing, bsub = 0)
+            const double sn2 = get_sn<RowAdd, 17, SPLIT>(RowAdd{y, -bsub}, c, scr, red, true, tabs);
             const double g2 = est_g(y, bsub, T, sn2, red);
             if (g2 >= -1.0) g = g2;
             if (tid < 64) { oasis_first(y, bsub + b, T, g, lam, smin, P, scr, nc_pools); const int nt = build_tasks(P, io, base2); if (tid == 0) { sh_i[0] = P.n; sh_i[1] = nt; } }
@@ -891,7 +892,8 @@ __global__ void __launch_bounds__(DECONV_NT) k_deconv(DeconvCfg c, DeconvIO io) 
     const double btot = bsub + b;                     // HALS: ck_raw - b - tmp_options.b ; deconvTemporal: ck_raw - options.b
     for (int t = tid; t < T; t += NTH) {
         const float raw = (float)((double)y[t] - btot);
-        ck[t] = sabs == 0.0 ? raw : ostage[t];
+        // "if sum(abs(ck))==0, ck = ck_raw": HALS_temporal.m:94-97 has taken both baselines off ck_raw by then, deconvTemporal.m:53-55 none (b leaves C_raw alone, :59)
+        ck[t] = sabs == 0.0 ? (c.hals ? raw : y[t]) : ostage[t];
         if (wr) { so[t] = 0.f; io.Craw[(int64_t)k * io.ldc + t] = raw; }
     }
     __syncthreads();

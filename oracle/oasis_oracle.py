@@ -292,8 +292,10 @@ def HALS_temporal_deconv(Y, A, C, maxIter, **opt):
 
 
 def deconvTemporal(C_raw, **opt):
-    """@Sources2D/deconvTemporal.m:29-105 (method_noise='psd').  Returns (C, C_raw, S, kernel_pars, sn)."""
+    """@Sources2D/deconvTemporal.m:29-105 (method_noise='psd').  Returns (C, C_raw, S, kernel_pars, sn).
+    opt['maxIter']: the deconv_options field deconvolveCa.m reads (default 10)."""
     C_raw = np.array(C_raw, dtype=np.float64, copy=True)
+    opt = dict(opt); maxIter = int(opt.pop("maxIter", 10))
     K, T = C_raw.shape
     C = np.zeros((K, T)); S = np.zeros((K, T)); kp = np.zeros(K); sn = np.zeros(K)
     for k in range(K):
@@ -302,7 +304,7 @@ def deconvTemporal(C_raw, **opt):
             C_raw[k] = 0
             continue
         sn[k] = GetSn(ck_raw)                                              # :45
-        ck, sk, b, g = deconvolveCa_ar1_foopsi(ck_raw, sn[k], None, maxIter=10, **opt)             # :51
+        ck, sk, b, g = deconvolveCa_ar1_foopsi(ck_raw, sn[k], None, maxIter=maxIter, **opt)        # :51
         if np.abs(ck).sum() == 0:
             ck = ck_raw                                                    # :53-55
         C[k] = ck; S[k] = sk; kp[k] = g
